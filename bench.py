@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's measurement contract for the AQLM QuantizedLinear matvec path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: re-executes itself under torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,12 +16,16 @@ all-reduce is an extra ("sharded_70b"), never the headline value.
 
 Output protocol (benchlib/emit.py): the process prints ONE line to stdout -- the JSON result, written by rank 0 as the last
 thing it ever writes there (fd 1 is pointed at stderr for everything else, C libraries and exit handlers included).  The same
-document is written to bench_result.json.  This file is the headline path; the untimed extras live in benchlib/ (`detail`:
-benchlib/detail.py, budgeted so the default run stays near a minute -- `--full-detail` runs every section; `sharded_70b`:
-benchlib/sharded.py; `cpu_baseline` / `gpu_reference_baseline`: benchlib/cpu.py, the only importers of oracle/).
+document is written to bench_result.json.
+
+A plain run sets up the 64 layers, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given
+(DIR/layerNN_<in>x<out>.npy, float32, rank 0; the layers are seeded, so the same arguments give the same inputs) and prints the line.
+Everything else is behind --full (benchlib/full.py): `roofline`, the step's outputs against the generic kernel and the CPU oracle, and
+the untimed extras -- `cpu_baseline` / `gpu_reference_baseline` (benchlib/cpu.py, the only importers of oracle/), `sharded_70b`
+(benchlib/sharded.py) and `detail` (benchlib/detail.py, budgeted so that a --full run stays near a minute; `--full-detail` runs every
+section).
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -77,17 +81,30 @@ def emit_probe():
                0, os.environ.get("AQLM_BENCH_RESULT_FILE"))
 
 
+def dump_outputs(layers, outdir):
+    """What the timed path hands its caller: each layer's output [1, out] of the last timed step, as float32 (64 files, 1.9 MB)."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for i, L in enumerate(layers):
+        np.save(os.path.join(outdir, f"layer{i:02d}_{L.fin}x{L.fout}.npy"), L.y.float().cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-detail", action="store_true", help="skip the untimed per-shape / other-scheme breakdown and the sharded figures")
-    ap.add_argument("--full-detail", action="store_true", help="run every section of the breakdown (minutes) instead of the time-budgeted default")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline and gpu_reference_baseline legs")
+    ap.add_argument("--full", action="store_true", help="after the headline: roofline, parity checks, cpu / reference baselines, breakdown")
+    ap.add_argument("--no-detail", action="store_true", help="with --full: skip the untimed per-shape / other-scheme breakdown and the sharded figures")
+    ap.add_argument("--full-detail", action="store_true", help="--full, running every section of the breakdown (minutes) instead of the time-budgeted default")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline and gpu_reference_baseline legs")
     ap.add_argument("--no-packed", action="store_true", help="direct L2-gather kernel for every layer (no prepacked path)")
-    ap.add_argument("--soft-exit", action="store_true", help="exit through the interpreter after the line (profilers write in exit handlers)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write every layer's output of the last timed step to DIR/<layer>.npy (float32)")
     args = ap.parse_args()
+    args.full = args.full or args.full_detail
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (one process per GPU over RCCL); the driver's
@@ -100,8 +117,6 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world} (launched by torch.distributed.run with another --nproc-per-node?)")
-    if args.soft_exit:
-        os.environ["AQLM_BENCH_SOFT_EXIT"] = "1"
     StdoutGuard.install()  # from here on fd 1 is stderr for everybody; the result line goes out through emit_final
     os.environ.setdefault("NCCL_DEBUG", "WARN")  # (the librccl banner is harmless now; this only keeps stderr short)
     if os.environ.get("AQLM_BENCH_EMIT_PROBE") == "1":
@@ -109,7 +124,6 @@ def main():
     if os.environ.get("AQLM_BENCH_LAUNCH_PROBE") == "1":
         return launch_probe(world, rank)
 
-    import numpy as np
     import torch
 
     if not torch.cuda.is_available():
@@ -125,7 +139,7 @@ def main():
 
     from aqlm_amd import _native  # raises if libaqlm_hip.so is missing
     from benchlib import layers as LY
-    from benchlib.layers import CEILING_BOTH, CEILING_GATHER, CEILING_LAUNCH, HBM_PEAK_GBPS, GraphedPass, Layer
+    from benchlib.layers import GraphedPass, Layer
 
     lib = _native.lib
     if args.no_packed:
@@ -169,33 +183,6 @@ def main():
     ms_per_step = wall * 1e3 / args.steps
     value = world * step.bytes / (ms_per_step * 1e-3) * 1e-9
 
-    # ---- roofline of the dominant kernel (1x16 gemv): HIP events on the launch stream over the timed region.  HBM traffic needs
-    # the PMC counters, i.e. a rocprofv3 run of this very command: it cannot be measured from inside; the value is read from the
-    # committed summary of that run (tools/gpu/final_evidence.sh -> profiles/pmc_traffic.json) and labelled as such
-    launches = args.steps * step.n
-    avg_launch_us = ev_ms * 1e3 / launches
-    bytes_per_launch = step.bytes / step.n
-    achieved = bytes_per_launch / avg_launch_us * 1e-3  # GB/s
-    traffic, traffic_source = None, None
-    try:
-        pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-        traffic = pm.get("gemv_1x16_hbm_bytes_per_launch")
-        traffic_source = "profiles/pmc_traffic.json: " + pm.get("how", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over bench.py")
-    except Exception:  # noqa: BLE001
-        pass
-    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                "traffic": traffic, "traffic_source": traffic_source,
-                "kernel": ("aqlm::gemv_1x16_packed_kernel<F16,1,3,65520,4> (prepacked codes, finalize inside the kernel; both shapes)"
-                           if LY.PACK_MIN_OUT else "aqlm::gemv_kernel<F16,1x16,g8,NB=1>"),
-                "avg_launch_us": avg_launch_us, "algorithmic_bytes_per_launch": bytes_per_launch, "launches_timed": launches,
-                # what bounds this metric for a one-launch-per-layer operator: the 1.45 us launch boundary
-                # (43 % for the mix), two LDS gathers per code (32 %), both at once (22.5 %)
-                "ceiling": {"launch_bound_frac": CEILING_LAUNCH, "lds_gather_bound_frac": CEILING_GATHER, "both_frac": CEILING_BOTH,
-                            "boundary_us": 1.45, "what": "fraction of the 8 TB/s roofline a one-launch-per-layer 1x16 matvec can reach on the headline mix"},
-                "frac_of_ceiling": achieved / HBM_PEAK_GBPS / min(CEILING_LAUNCH, CEILING_GATHER),
-                "frac_of_ceiling_both": achieved / HBM_PEAK_GBPS / CEILING_BOTH,
-                "note": "one launch = one matvec = one kernel; duration = HIP-event time of the timed region / matvecs; achieved uses "
-                        "ALGORITHMIC bytes (2 B per code) even where the prepacked path reads ~4.8 B per code; rocprofv3 durations: profiles/"}
     bits = None
     if prepack["layers"]:
         w = max(1, prepack["weights"])
@@ -218,61 +205,18 @@ def main():
                    # share of the packed entry slots that hold no code (buckets padded to lane-steps of 4 entries), per shape
                    "packed_padding_fraction": {f"{L.fin}->{L.fout}": round(L.packed.padding_fraction(), 4) for L in layers[:2] if L.packed is not None}},
         "tokens_per_s_this_stack": world * 1e3 / ms_per_step,
-        "roofline": roofline,
         "cpu_baseline": None,
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(layers, args.dump_outputs)
+    if args.full:  # everything else the benchmark reports, outside the timed region (benchlib/full.py)
+        from benchlib import full as FULL
 
-    # ---- outside the timed region: the step's outputs against the CPU ORACLE (oracle/aqlm_oracle.c, the restated reference path --
-    # checker only, rank 0) on one layer of each shape, and against the generic HIP kernel (a different code path) on every rank
-    from aqlm_amd.inference_kernels import hip_kernel as hk
-    from benchlib import cpu as CPU
-
-    parity, parity_oracle = {}, {}
-    for L in (layers[0], layers[1]):
-        ref = hk.generic_matmat(L.x[:1], L.codes, L.codebooks, L.scales.reshape(-1, 1, 1, 1), None).float()
-        got = L.y[:1].float()
-        parity[f"{L.fin}x{L.fout}"] = float((got - ref).abs().mean() / ref.abs().mean())
-        if rank == 0:
-            parity_oracle[f"{L.fin}x{L.fout}"] = CPU.oracle_parity(L, got)
-    result["parity_mean_rel_vs_generic_kernel"] = parity
-    result["parity_mean_rel_vs_cpu_oracle"] = parity_oracle
-    assert all(v < 1e-3 for v in parity.values()), f"bench outputs are off: {parity}"
-    assert all(v < 1e-3 for v in parity_oracle.values()), f"bench outputs differ from the CPU oracle: {parity_oracle}"
-
-    # ---- everything below is OUTSIDE the timed region and must never cost the headline line: a watchdog emits what there is and
-    # ends the process if the extras are not done within their budget
-    extras = ExtrasWatchdog(result, rank, float(os.environ.get("AQLM_BENCH_EXTRAS_TIMEOUT_S", "480")), side_file)
-    try:
-        if rank == 0 and not args.no_cpu:  # the CPU leg first: the contract's `cpu_baseline` must not depend on the budgeted extras
-            extras.section = "cpu_baseline"
-            try:  # (guarded on its own: rank 0 must reach the collectives of `sharded_70b` like every other rank)
-                result["cpu_baseline"] = CPU.cpu_baseline(float(os.environ.get("AQLM_BENCH_CPU_SAMPLE_S", "12")))
-            except Exception as e:  # noqa: BLE001
-                result["cpu_baseline_error"] = f"{type(e).__name__}: {e}"
-        if not args.no_detail:
-            from benchlib import detail as DT
-            from benchlib import sharded as SH
-
-            extras.section = "sharded_70b"
-            try:
-                result["sharded_70b"] = SH.sharded_70b(lib, dev, rank, world, args.steps)
-            except Exception as e:  # noqa: BLE001 - an extra never costs the headline line
-                result["sharded_70b"] = {"error": f"{type(e).__name__}: {e}"}
-            result["detail"] = {}  # filled in place: a timed-out run still reports what it had
-            budget = 0.0 if args.full_detail else float(os.environ.get("AQLM_BENCH_DETAIL_BUDGET_S", "42"))
-            ctx = DT.Ctx(lib, dev, rank, world, max(4, args.steps // 5), layers, NBLOCKS, value)
-            DT.run_detail(ctx, result["detail"], T_PROCESS, budget, args.full_detail, extras)
-        if rank == 0 and not args.no_cpu:
-            extras.section = "gpu_reference_baseline"
-            result["gpu_reference_baseline"] = CPU.gpu_reference_baseline()
-    except Exception as e:  # noqa: BLE001 - whatever an extra does (an import error included), the line goes out
-        import traceback
-
-        result["extras_error"] = {"section": extras.section, "error": f"{type(e).__name__}: {e}", "traceback": traceback.format_exc()[-1500:]}
-    result["bench_wall_s"] = round(time.perf_counter() - T_PROCESS, 1)
-
-    if not extras.finish():
-        return  # the watchdog is emitting the line and ending the process
+        result["roofline"] = FULL.roofline(step, ev_ms, args.steps, LY.PACK_MIN_OUT)
+        if not FULL.run(args, result, lib, dev, rank, world, layers, NBLOCKS, side_file, T_PROCESS):
+            return  # the watchdog is emitting the line and ending the process
+    else:
+        result["bench_wall_s"] = round(time.perf_counter() - T_PROCESS, 1)
 
     def teardown():  # ranks meet and the process groups go BEFORE the line (librccl may talk on the way out) -- but never cost it
         try:

@@ -497,7 +497,7 @@ SECTIONS = [
 
 def run_detail(c, detail, t_start, budget_s, full, watchdog=None):
     """Run the sections in priority order; a section is only STARTED while the process is younger than `budget_s` (0 = no limit),
-    so the default `python bench.py` stays within about a minute of driver time and `--full-detail` measures everything.  Sections
+    so `python bench.py --full` stays within about a minute and `--full-detail` measures everything.  Sections
     that did not run are listed in detail["skipped"]; seconds per section in detail["section_seconds"]."""
     detail["section_seconds"], detail["skipped"] = {}, []
     for name, fn in SECTIONS:

@@ -1,11 +1,11 @@
 #!/bin/bash
-# The driver's own bench command + the assertion the driver makes on it (last stdout line parses, carries roofline + cpu_baseline).
+# The driver's bench command with --full + the assertion made on it (last stdout line parses, carries roofline + cpu_baseline).
 #   bash tools/gpu/r6_bench_check.sh <tag> [extra bench args]
 set +e
 TAG=${1:-r6bench}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 t0=$(date +%s)
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? wall=$(( $(date +%s) - t0 )) s"
+timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? wall=$(( $(date +%s) - t0 )) s"
 python3 - $OUT/bench.json <<'PY'
 import json, sys
 lines = open(sys.argv[1]).read().splitlines()
