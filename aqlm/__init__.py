@@ -43,9 +43,11 @@ if not any(isinstance(f, _AliasFinder) for f in sys.meta_path):
 from aqlm_amd import QuantizedLinear, __version__, optimize_for_training  # noqa: E402,F401
 from aqlm_amd import get_backward_pass_kernel, get_forward_pass_kernel  # noqa: E402,F401
 from aqlm_amd import SharedInputGroup, fuse_shared_input_linears, unfuse_shared_input_linears  # noqa: E402,F401
+from aqlm_amd import QuantizedMixtralExperts, quantized_experts, replace_moe_experts  # noqa: E402,F401
 
 inference = importlib.import_module(__name__ + ".inference")
 utils = importlib.import_module(__name__ + ".utils")
 inference_kernels = importlib.import_module(__name__ + ".inference_kernels")
 checkpoint = importlib.import_module(__name__ + ".checkpoint")
 fusion = importlib.import_module(__name__ + ".fusion")
+moe = importlib.import_module(__name__ + ".moe")

@@ -7,6 +7,7 @@ from . import checkpoint, inference_kernels
 from .fusion import SharedInputGroup, fuse_shared_input_linears, unfuse_shared_input_linears
 from .inference import QuantizedLinear
 from .inference_kernels import get_backward_pass_kernel, get_forward_pass_kernel, optimize_for_training
+from .moe import QuantizedMixtralExperts, quantized_experts, replace_moe_experts
 
 __version__ = "1.1.7"
 
@@ -20,4 +21,7 @@ __all__ = [
     "SharedInputGroup",
     "fuse_shared_input_linears",
     "unfuse_shared_input_linears",
+    "QuantizedMixtralExperts",
+    "quantized_experts",
+    "replace_moe_experts",
 ]

@@ -24,6 +24,9 @@ OP_GEMM_KX8_MFMA = 6
 OP_GEMV_1X16_G16_PACKED = 5
 
 MAX_SEGMENTS = 4
+MAX_ROUTED_PAIRS = 64     # aqlm_hip_gemv_1x16_routed: (token, expert) pairs per call
+MAX_ROUTED_EXPERTS = 256
+ROUTED_ENTRY_WORDS = 4    # aqlm_hip_routed_entry: codes, codebook, scales, bias (device pointers)
 
 _vp, _ci, _cl, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
 
@@ -99,6 +102,7 @@ SIGNATURES = {
     "aqlm_hip_last_error": (ctypes.c_char_p, []),
     "aqlm_hip_gemv_1x16": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_gemv_1x16_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _cl, _ci, _vp]),
+    "aqlm_hip_gemv_1x16_routed": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _ci, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi_cells": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),

@@ -169,7 +169,8 @@ def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_
     t0 = time.perf_counter()
     try:
         for m in model.modules():
-            if isinstance(m, QuantizedLinear):
+            if isinstance(m, QuantizedLinear) and not getattr(m, "_moe_expert", False):
+                # (experts of a QuantizedMixtralExperts are left alone: the routed kernel reads their canonical codes)
                 if not m.codes.is_cuda:
                     raise NotImplementedError("prepack_model needs the model on an MI355X (`model.to('cuda')` first)")
                 m.prepare_matmul_op(m.codebooks)

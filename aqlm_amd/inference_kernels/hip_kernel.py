@@ -535,6 +535,71 @@ def code1x16_matmat_multi(input, codes, codebooks, scales, bias):
     return _gemv_multi(input, codes, codebooks, scales, bias, "1x16")
 
 
+# ------------------------------------------------------------------------------------------------------
+# expert-routed 1x16 matvec (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed)
+# ------------------------------------------------------------------------------------------------------
+def routed_table(layers, device) -> torch.Tensor:
+    """The device-resident table of aqlm_hip_gemv_1x16_routed: ``layers[e][s] = (codes, codebooks, scales, bias or None)``
+    -> int64 [E * S * 4] of device pointers, entry [e * S + s].  The table holds raw addresses: the caller keeps the tensors
+    alive and rebuilds it when one of them moves (``aqlm_amd.moe.QuantizedMixtralExperts`` keys it on data_ptr + version).
+    A host-to-device copy: never while a hipGraph is being captured."""
+    words = []
+    for per_expert in layers:
+        for codes, codebooks, scales, bias in per_expert:
+            for t in (codes, codebooks, scales):
+                if not t.is_contiguous() or t.data_ptr() % 16:
+                    raise ValueError("routed table: codes / codebooks / scales must be contiguous and 16-byte aligned")
+            if bias is not None and not bias.is_contiguous():
+                raise ValueError("routed table: bias must be contiguous")
+            words += [codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), 0 if bias is None else bias.data_ptr()]
+    return torch.tensor(words, dtype=torch.int64).to(device)
+
+
+def routed_chunks(tokens: int, top_k: int):
+    """Token ranges [t0, t1) of the routed launches that serve ``tokens`` tokens: at most MAX_ROUTED_PAIRS (token, expert) pairs
+    per launch, whole tokens only."""
+    per = max(1, _native.MAX_ROUTED_PAIRS // max(1, top_k))
+    return [(t0, min(tokens, t0 + per)) for t0 in range(0, tokens, per)]
+
+
+def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
+    """Every (token, expert) pair of one or two 1x16 projections of a mixture-of-experts block in one launch per 64 pairs.
+    geometry = [num_experts, num_segments, out_features, in_features, in_group_size, top_k]; ``expert_ids`` [T, top_k] int64 /
+    int32 on the device (what the router's topk returns; read on the device only, any values are safe: ids outside
+    [0, num_experts) give zero rows); ``input`` [T, in] (token rows, ``x_per_pair`` False) or [T * top_k, in] (pair rows);
+    ``table`` from ``routed_table``.  -> [T * top_k, num_segments, out_features]; row (t * top_k + j, s) is projection s of
+    expert expert_ids[t, j] applied to its x row, bit-identical to code1x16_matmat of that expert on that row."""
+    E, S, out_features, in_features, g, top_k = (int(v) for v in geometry)
+    dt = _dtype_id(input)
+    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
+    T = expert_ids.shape[0]
+    rows = T * top_k if x_per_pair else T
+    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
+        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
+    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != input.device:
+        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {input.device}")
+    if expert_ids.device != input.device:
+        raise ValueError("expert_ids must be on the input's device")
+    x = _flat_rows(input)
+    ids = _c(expert_ids)
+    y = torch.empty((T * top_k, S, out_features), dtype=input.dtype, device=input.device)
+    if T == 0:
+        return y
+    stream = _stream_ptr(input.device)
+    esz = ids.element_size()
+    with _device_guard(input.device):
+        for t0, t1 in routed_chunks(T, top_k):
+            p0, npairs = t0 * top_k, (t1 - t0) * top_k
+            xp = x.data_ptr() + (p0 if x_per_pair else t0) * x.stride(0) * 2
+            rc = _lib.aqlm_hip_gemv_1x16_routed(table.data_ptr(), E, S, ids.data_ptr() + p0 * esz, int(esz == 8), npairs, top_k,
+                                                xp, x.stride(0), int(bool(x_per_pair)), y.data_ptr() + p0 * S * out_features * 2,
+                                                out_features, in_features, g, dt, stream)
+            if rc:
+                _native.check(rc, "aqlm routed gemv")
+    return y
+
+
 # Zero-at-rest accumulator cells of the single-kernel look-up-table matvec (aqlm_hip_gemv_8x8_lut_fused): one persistent
 # int64 buffer per (device, stream) -- launches on one stream are ordered, so consecutive layers can share it; every launch
 # leaves it zero.  Never allocated while a hipGraph is being captured (a captured torch.zeros would replay a memset per
@@ -1502,6 +1567,16 @@ for _name, _impl in (("code1x16_matmat_multi", code1x16_matmat_multi), ("codekx8
     _LIB.define(f"{_name}(Tensor input, Tensor[] codes, Tensor[] codebooks, Tensor[] scales, Tensor?[] bias) -> Tensor[]")
     _LIB.impl(_name, _impl, "CUDA")
     torch.library.register_fake(f"aqlm::{_name}")(_fake_multi)
+
+
+# expert-routed matvec (mixture-of-experts decode; no reference counterpart)
+def _fake_moe(input, expert_ids, table, geometry, x_per_pair):
+    return input.new_empty((expert_ids.shape[0] * expert_ids.shape[1], int(geometry[1]), int(geometry[2])))
+
+
+_LIB.define("code1x16_moe_matmat(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
+_LIB.impl("code1x16_moe_matmat", code1x16_moe_matmat, "CUDA")
+torch.library.register_fake("aqlm::code1x16_moe_matmat")(_fake_moe)
 
 
 # the prepacked op as a dispatcher op, so that a QuantizedLinear on the packed path traces under torch.compile

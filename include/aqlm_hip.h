@@ -92,6 +92,37 @@ int aqlm_hip_gemv_1x16_multi(const aqlm_hip_segment* segments, int num_segments,
                              int in_group_size, int batch, long x_row_stride, int dtype, void* stream);
 
 /*
+ * Expert-routed 1x16 matvec of a mixture-of-experts block (Mixtral decode).  `table` is a DEVICE array of
+ * num_experts * num_segments entries, entry [e * num_segments + s] = projection s of expert e (w1, w3 for the
+ * gate/up launch: num_segments 2; w2: num_segments 1).  All entries share out_features, in_features, in_group_size
+ * (8 or 16) and dtype; codes and codebook 16-byte aligned.  expert_ids: DEVICE [num_pairs] (= [T, top_k] row-major)
+ * int64 (ids_int64 != 0, what torch.topk returns) or int32.  For every pair p < num_pairs and segment s:
+ *     y[(p * num_segments + s) * out_features + o] = (W[e_p, s] x_row(p))[o] * scales[o] + bias[o]
+ * with x_row(p) = x + (x_per_pair ? p : p / top_k) * x_row_stride: fp32 sums, one rounding -- bit-identical to
+ * aqlm_hip_gemv_1x16 of that expert on that row.  Ids are only ever compared for equality with an expert index: a
+ * pair whose id lies outside [0, num_experts) gets a zero row, whatever the ids hold (duplicates, one expert for
+ * every pair, garbage).  The grid (row blocks x segments x experts) depends on the shapes only, so a captured launch
+ * stays valid when the routing changes; a workgroup whose expert has no pair exits at once.  num_pairs <=
+ * AQLM_HIP_MAX_ROUTED_PAIRS; more than AQLM_HIP_MAX_GEMV_BATCH pairs on one expert are taken in passes.
+ * AQLM_HIP_E_UNSUPPORTED for shapes outside the direct kernel (in_features / in_group_size % 8 != 0, x row > 64 KiB,
+ * unaligned x): the caller runs those per expert.
+ */
+typedef struct aqlm_hip_routed_entry {
+  const void* codes;     /* [out_features][in_features/in_group_size] int16 */
+  const void* codebook;  /* [65536][in_group_size] */
+  const void* scales;    /* [out_features] */
+  const void* bias;      /* [out_features] or NULL */
+} aqlm_hip_routed_entry;
+
+#define AQLM_HIP_MAX_ROUTED_PAIRS 64
+#define AQLM_HIP_MAX_ROUTED_EXPERTS 256
+
+int aqlm_hip_gemv_1x16_routed(const aqlm_hip_routed_entry* table, int num_experts, int num_segments,
+                              const void* expert_ids, int ids_int64, int num_pairs, int top_k, const void* x,
+                              long x_row_stride, int x_per_pair, void* y, int out_features, int in_features,
+                              int in_group_size, int dtype, void* stream);
+
+/*
  * Same contract for K x 8-bit schemes (256-entry codebooks held in LDS): num_codebooks in 1..16, any
  * in_group_size that is a multiple of 8 (tuned instances: 1x8 g8, 2x8 g8, 8x8 g32; other shapes run a generic kernel).
  *

@@ -1,0 +1,134 @@
+#!/usr/bin/env python
+"""One Mixtral-8x7B-shaped MoE expert block (hidden 4096, intermediate 14336, 8 experts, top-2, 1x16 g8, random codes, fp16) at
+T in {1, 2, 4, 8, 16} tokens:
+  (a) routed  -- QuantizedMixtralExperts.forward on the routed launches (aqlm_hip_gemv_1x16_routed), eager;
+  (b) graph   -- the same forward captured in a hipGraph and replayed;
+  (c) loop    -- a per-expert loop on the existing ops through each expert's QuantizedLinear.forward (prepacked experts for
+                 T <= 6 rows per expert, as a dense-MLP model would run them; the expert ids go to the host);
+  (d) dense   -- transformers' MixtralExperts in fp16, eager.
+Median wall time per call over --iters calls (CUDA events), in microseconds.  Writes --out (default profiles/moe_block.json).
+
+    python tools/moe_benchmark.py [--only graph] [--tokens 1,2,4,8,16]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+H, I, E, K = 4096, 14336, 8, 2
+# the direct 1x16 kernel gathers about 1 M codes per 3.8 us across the chip
+ESTIMATE = {"routed_t1_kernel_us": 2 * 3 * (I * H / 8) / 1e6 * 3.8, "packed_t1_us": 75.0, "dense_t1_us": 140.0,
+            "basis": "DESIGN.md 4.1: 3.8 us per million codes (direct kernel), 2 experts x 3 layers x 7.3 M codes; packed per-expert "
+                     "matvecs at 1.2 TB/s; dense reads 704 MB"}
+
+
+def build(dev, dense_too):
+    from transformers import MixtralConfig
+    from transformers.models.mixtral.modeling_mixtral import MixtralExperts
+
+    from aqlm_amd.moe import QuantizedMixtralExperts
+
+    cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=K)
+    q = QuantizedMixtralExperts(cfg, dict(in_group_size=8, out_group_size=1, num_codebooks=1, nbits_per_codebook=16), device=dev,
+                                dtype=torch.float16)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    with torch.no_grad():
+        for e in range(E):
+            for s in ("w1", "w3", "w2"):
+                lin = getattr(q.expert(e), s)
+                lin.codes.copy_(torch.randint(-32768, 32768, lin.codes.shape, generator=gen, device=dev, dtype=torch.int32))
+                lin.codebooks.copy_(torch.randn(lin.codebooks.shape, generator=gen, device=dev) * 0.05)
+                lin.scales.copy_(torch.rand(lin.scales.shape, generator=gen, device=dev) * 0.2 + 0.05)
+    dense = None
+    if dense_too:
+        dense = MixtralExperts(cfg).to(dev, torch.float16)
+        with torch.no_grad():
+            dense.gate_up_proj.normal_(0, 0.02)
+            dense.down_proj.normal_(0, 0.02)
+    return q, dense
+
+
+def loop_forward(q, x, ids, w):
+    """(c): tokens grouped per expert on the host, each expert's QuantizedLinears called through their own forward."""
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for e in torch.unique(ids).tolist():
+        tok, pos = torch.where(ids == e)
+        ex = q.expert(e)
+        xe = x[tok]
+        h = q.act_fn(ex.w1(xe)) * ex.w3(xe)
+        out.index_add_(0, tok, ex.w2(h).float() * w[tok, pos, None])
+    return out.to(x.dtype)
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    times.sort()
+    return round(times[len(times) // 2], 2)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tokens", default="1,2,4,8,16")
+    ap.add_argument("--only", choices=["routed", "graph", "loop", "dense"], default=None)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join("profiles", "moe_block.json"))
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    modes = [args.only] if args.only else ["routed", "graph", "loop", "dense"]
+    q, dense = build(dev, "dense" in modes)
+    rows = []
+    gen = torch.Generator(device=dev).manual_seed(1)
+    with torch.no_grad():
+        for T in [int(t) for t in args.tokens.split(",")]:
+            x = torch.randn((T, H), generator=gen, device=dev).half()
+            logits = torch.randn((T, E), generator=gen, device=dev)
+            w, ids = torch.topk(torch.softmax(logits, -1), K, dim=-1)
+            w = w / w.sum(-1, keepdim=True)
+            row = {"tokens": T, "experts_hit": len(set(ids.view(-1).tolist()))}
+            if "routed" in modes:
+                row["routed_eager_us"] = timed(lambda: q(x, ids, w), args.iters, args.warmup)
+            if "graph" in modes:
+                q(x, ids, w)
+                torch.cuda.synchronize()
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    q(x, ids, w)
+                torch.cuda.current_stream().wait_stream(s)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    q(x, ids, w)
+                row["routed_graph_us"] = timed(g.replay, args.iters, args.warmup)
+                del g
+            if "loop" in modes:
+                row["loop_eager_us"] = timed(lambda: loop_forward(q, x, ids, w), args.iters, args.warmup)
+            if "dense" in modes:
+                row["dense_fp16_eager_us"] = timed(lambda: dense(x, ids, w), args.iters, args.warmup)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    result = {"block": {"hidden": H, "intermediate": I, "experts": E, "top_k": K, "scheme": "1x16g8", "dtype": "float16"},
+              "device": torch.cuda.get_device_name(dev), "estimate": ESTIMATE, "rows": rows}
+    if not args.only:
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
