@@ -27,6 +27,8 @@ MAX_SEGMENTS = 4
 MAX_ROUTED_PAIRS = 64     # aqlm_hip_gemv_1x16_routed: (token, expert) pairs per call
 MAX_ROUTED_EXPERTS = 256
 ROUTED_ENTRY_WORDS = 4    # aqlm_hip_routed_entry: codes, codebook, scales, bias (device pointers)
+MAX_GROUPED_PAIRS = 1 << 18  # aqlm_hip_gemm_1x16_grouped / aqlm_hip_moe_bucket: (token, expert) pairs per call
+GROUPED_TILE_PAIRS = (16, 32, 64, 128)
 
 _vp, _ci, _cl, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
 
@@ -103,6 +105,10 @@ SIGNATURES = {
     "aqlm_hip_gemv_1x16": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_gemv_1x16_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_1x16_routed": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "aqlm_hip_moe_bucket_bytes": (_sz, [_ci, _ci, _ci]),
+    "aqlm_hip_moe_bucket": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "aqlm_hip_gemm_1x16_grouped_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_gemm_1x16_grouped": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _ci, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi_cells": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),

@@ -600,6 +600,78 @@ def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
     return y
 
 
+# ------------------------------------------------------------------------------------------------------
+# expert-grouped 1x16 GEMM (mixture-of-experts prefill / training; aqlm_hip_moe_bucket + aqlm_hip_gemm_1x16_grouped)
+# ------------------------------------------------------------------------------------------------------
+def grouped_tile_pairs(num_pairs: int, num_experts: int) -> int:
+    """Pairs per tile of the grouped launches: the mean pairs per expert rounded up to a power of two, 16 .. 128.  A function of
+    the sizes only, never of the routing, so a captured graph serves every routing."""
+    mean = -(-int(num_pairs) // max(1, int(num_experts)))
+    t = _native.GROUPED_TILE_PAIRS[0]
+    while t < mean and t < _native.GROUPED_TILE_PAIRS[-1]:
+        t *= 2
+    return t
+
+
+def grouped_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
+    """Whether aqlm_hip_gemm_1x16_grouped takes a layer of this shape (a host query: decide before a capture)."""
+    return bool(_lib.aqlm_hip_gemm_1x16_grouped_supported(int(out_features), int(in_features), int(in_group_size)))
+
+
+def _bucket_words(num_pairs: int, num_experts: int, tile_pairs: int) -> int:
+    n = _lib.aqlm_hip_moe_bucket_bytes(int(num_pairs), int(num_experts), int(tile_pairs))
+    if n == 0:
+        raise ValueError(f"moe_bucket: {num_pairs} pairs, {num_experts} experts, tiles of {tile_pairs} are outside the entry "
+                         f"(1..{_native.MAX_GROUPED_PAIRS} pairs, 1..{_native.MAX_ROUTED_EXPERTS} experts, tiles of "
+                         f"{'/'.join(map(str, _native.GROUPED_TILE_PAIRS))})")
+    return n // 4
+
+
+def moe_bucket(expert_ids, num_experts, tile_pairs):
+    """The router's ids [T, top_k] (int64 / int32, device) grouped by expert on the device (aqlm_hip_moe_bucket): an int32
+    buffer whose size depends on T * top_k, num_experts and tile_pairs only.  No host synchronisation."""
+    if expert_ids.dim() != 2 or expert_ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"expert_ids must be [T, top_k] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
+    ids = _c(expert_ids)
+    bucket = torch.empty((_bucket_words(ids.numel(), num_experts, tile_pairs),), dtype=torch.int32, device=ids.device)
+    with _device_guard(ids.device):
+        rc = _lib.aqlm_hip_moe_bucket(ids.data_ptr(), int(ids.element_size() == 8), ids.numel(), int(num_experts), int(tile_pairs),
+                                      bucket.data_ptr(), _stream_ptr(ids.device))
+    if rc:
+        _native.check(rc, "aqlm moe bucket")
+    return bucket
+
+
+def code1x16_moe_matmat_grouped(input, bucket, table, geometry, x_per_pair):
+    """``code1x16_moe_matmat`` for any number of pairs, on the expert-grouped 16-row MFMA kernel.  geometry = [num_experts,
+    num_segments, out_features, in_features, in_group_size, top_k, tile_pairs, num_pairs]; ``bucket`` from ``moe_bucket`` with
+    the same num_pairs / num_experts / tile_pairs; ``table`` from ``routed_table``; ``input`` [num_pairs / top_k, in] (token rows)
+    or [num_pairs, in] (``x_per_pair``).  -> [num_pairs, num_segments, out_features]; pairs whose id lies outside [0,
+    num_experts) get zero rows.  No host synchronisation."""
+    E, S, out_features, in_features, g, top_k, tile_pairs, P = (int(v) for v in geometry)
+    dt = _dtype_id(input)
+    if top_k < 1 or P % top_k != 0:
+        raise ValueError(f"{P} pairs is not a multiple of top_k {top_k}")
+    rows = P if x_per_pair else P // top_k
+    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
+        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
+    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != input.device:
+        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {input.device}")
+    if bucket.dtype != torch.int32 or bucket.numel() != _bucket_words(P, E, tile_pairs) or bucket.device != input.device:
+        raise ValueError("bucket must come from moe_bucket with the same pairs, experts and tile size")
+    y = torch.empty((P, S, out_features), dtype=input.dtype, device=input.device)
+    if P == 0:
+        return y
+    x = _flat_rows(input)
+    with _device_guard(input.device):
+        rc = _lib.aqlm_hip_gemm_1x16_grouped(table.data_ptr(), E, S, bucket.data_ptr(), tile_pairs, P, top_k, x.data_ptr(), x.stride(0),
+                                             int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, g, dt,
+                                             _stream_ptr(input.device))
+    if rc:
+        _native.check(rc, "aqlm grouped gemm")
+    return y
+
+
 # Zero-at-rest accumulator cells of the single-kernel look-up-table matvec (aqlm_hip_gemv_8x8_lut_fused): one persistent
 # int64 buffer per (device, stream) -- launches on one stream are ordered, so consecutive layers can share it; every launch
 # leaves it zero.  Never allocated while a hipGraph is being captured (a captured torch.zeros would replay a memset per
@@ -1577,6 +1649,24 @@ def _fake_moe(input, expert_ids, table, geometry, x_per_pair):
 _LIB.define("code1x16_moe_matmat(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
 _LIB.impl("code1x16_moe_matmat", code1x16_moe_matmat, "CUDA")
 torch.library.register_fake("aqlm::code1x16_moe_matmat")(_fake_moe)
+
+
+# expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)
+def _fake_bucket(expert_ids, num_experts, tile_pairs):
+    return expert_ids.new_empty((_bucket_words(expert_ids.shape[0] * expert_ids.shape[1], num_experts, tile_pairs),),
+                                dtype=torch.int32)
+
+
+def _fake_grouped(input, bucket, table, geometry, x_per_pair):
+    return input.new_empty((int(geometry[7]), int(geometry[1]), int(geometry[2])))
+
+
+_LIB.define("moe_bucket(Tensor expert_ids, int num_experts, int tile_pairs) -> Tensor")
+_LIB.impl("moe_bucket", moe_bucket, "CUDA")
+torch.library.register_fake("aqlm::moe_bucket")(_fake_bucket)
+_LIB.define("code1x16_moe_matmat_grouped(Tensor input, Tensor bucket, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
+_LIB.impl("code1x16_moe_matmat_grouped", code1x16_moe_matmat_grouped, "CUDA")
+torch.library.register_fake("aqlm::code1x16_moe_matmat_grouped")(_fake_grouped)
 
 
 # the prepacked op as a dispatcher op, so that a QuantizedLinear on the packed path traces under torch.compile

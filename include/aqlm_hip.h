@@ -123,6 +123,40 @@ int aqlm_hip_gemv_1x16_routed(const aqlm_hip_routed_entry* table, int num_expert
                               int in_group_size, int dtype, void* stream);
 
 /*
+ * Expert-grouped 1x16 GEMM of a mixture-of-experts block (Mixtral prefill, batched decode, training): the same
+ * projection as aqlm_hip_gemv_1x16_routed for any number of pairs, in two launches whose grids depend on the shapes only.
+ *
+ * aqlm_hip_moe_bucket groups the pairs by expert on the device, in ONE workgroup: expert_ids DEVICE [num_pairs]
+ * (= [T, top_k] row-major) int64 (ids_int64 != 0) or int32, as for the routed entry.  `bucket` is a 16-byte aligned DEVICE
+ * buffer of aqlm_hip_moe_bucket_bytes(num_pairs, num_experts, tile_pairs) bytes (a size that depends on these three only)
+ * that receives each expert's pairs in ascending pair order and a table of tiles (expert, first pair, <= tile_pairs
+ * pairs).  Ids outside [0, num_experts) join no expert: they are only compared, never used to form an address.
+ * aqlm_hip_moe_bucket_bytes returns 0 for arguments the entries refuse.
+ *
+ * aqlm_hip_gemm_1x16_grouped reads a bucket made with the same num_pairs, num_experts and tile_pairs and the routed
+ * entries' table, and writes, like aqlm_hip_gemv_1x16_routed, for every pair p < num_pairs and segment s:
+ *     y[(p * num_segments + s) * out_features + o] = (W[e_p, s] x_row(p))[o] * scales[o] + bias[o]
+ * with x_row(p) = x + (x_per_pair ? p : p / top_k) * x_row_stride; fp32 sums, one rounding; pairs with an id outside
+ * [0, num_experts) get zero rows.  A block owns 16 output rows of one tile over all of K (the 16-row kernel of
+ * aqlm_hip_gemm_1x16_mfma): each expert's rows are bit-identical to aqlm_hip_gemm_1x16_mfma on that expert's rows where
+ * that op runs its 16-row kernel (tuning key gemm_variant = 2), and a pair's bits depend neither on the other pairs nor on
+ * their number.  Grid: out_features / 16 x (ceil(num_pairs / tile_pairs) + min(num_experts, num_pairs)) tile slots x
+ * num_segments; a captured launch stays valid when the routing changes.  tile_pairs is 16, 32, 64 or 128 (the caller
+ * picks it from num_pairs and num_experts, never from the routing).  AQLM_HIP_E_UNSUPPORTED outside the 16-row kernel:
+ * aqlm_hip_gemm_1x16_grouped_supported(out_features, in_features, in_group_size) says beforehand (out_features % 16,
+ * in_features % 64, in_group_size 8 / 16, K long enough for the kernel's rings).
+ */
+#define AQLM_HIP_MAX_GROUPED_PAIRS (1 << 18)
+
+size_t aqlm_hip_moe_bucket_bytes(int num_pairs, int num_experts, int tile_pairs);
+int aqlm_hip_moe_bucket(const void* expert_ids, int ids_int64, int num_pairs, int num_experts, int tile_pairs, void* bucket,
+                        void* stream);
+int aqlm_hip_gemm_1x16_grouped_supported(int out_features, int in_features, int in_group_size);
+int aqlm_hip_gemm_1x16_grouped(const aqlm_hip_routed_entry* table, int num_experts, int num_segments, const void* bucket,
+                               int tile_pairs, int num_pairs, int top_k, const void* x, long x_row_stride, int x_per_pair,
+                               void* y, int out_features, int in_features, int in_group_size, int dtype, void* stream);
+
+/*
  * Same contract for K x 8-bit schemes (256-entry codebooks held in LDS): num_codebooks in 1..16, any
  * in_group_size that is a multiple of 8 (tuned instances: 1x8 g8, 2x8 g8, 8x8 g32; other shapes run a generic kernel).
  *

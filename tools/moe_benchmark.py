@@ -8,7 +8,14 @@ T in {1, 2, 4, 8, 16} tokens:
   (d) dense   -- transformers' MixtralExperts in fp16, eager.
 Median wall time per call over --iters calls (CUDA events), in microseconds.  Writes --out (default profiles/moe_block.json).
 
+--grouped: the expert-grouped launches (aqlm_hip_moe_bucket + aqlm_hip_gemm_1x16_grouped) against the module's own per-expert loop
+(QuantizedMixtralExperts._forward_loop, the route of more than 64 pairs before them) and, up to 64 pairs, the routed launches, at
+T up to 512; eager calls of the old and the new route alternate within one process (one pair of device events each).  Adds
+grouped_graph_us (captured and replayed) and one forward + backward row at the largest T for the grouped path and the
+differentiable loop.  Writes --out (default profiles/moe_grouped.json).
+
     python tools/moe_benchmark.py [--only graph] [--tokens 1,2,4,8,16]
+    python tools/moe_benchmark.py --grouped [--tokens 1,2,4,8,16,32,40,64,128,256,512]
 """
 import argparse
 import json
@@ -80,14 +87,99 @@ def timed(fn, iters, warmup):
     return round(times[len(times) // 2], 2)
 
 
+def timed_alternating(fns, iters, warmup):
+    """median per call of each of `fns`, their calls interleaved (a, b, a, b, ...) so that clocks and caches drift alike"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(iters):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[i].append(a.elapsed_time(b) * 1e3)
+    return [round(sorted(t)[len(t) // 2], 2) for t in times]
+
+
+def captured(fn):
+    fn()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g
+
+
+def grouped_main(args):
+    dev = torch.device("cuda:0")
+    q, _ = build(dev, False)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    tokens = [int(t) for t in args.tokens.split(",")]
+    rows = []
+    for T in tokens:
+        x = torch.randn((T, H), generator=gen, device=dev).half()
+        logits = torch.randn((T, E), generator=gen, device=dev)
+        w, ids = torch.topk(torch.softmax(logits, -1), K, dim=-1)
+        w = w / w.sum(-1, keepdim=True)
+        row = {"tokens": T, "pairs": T * K, "experts_hit": len(set(ids.view(-1).tolist()))}
+        with torch.no_grad():
+            fns = [lambda: q._forward_grouped(x, ids, w), lambda: q._forward_loop(x, ids, w)]
+            names = ["grouped_eager_us", "loop_eager_us"]
+            if T * K <= 64:
+                fns.append(lambda: q._forward_routed(x, ids, w))
+                names.append("routed_eager_us")
+            row.update(zip(names, timed_alternating(fns, args.iters, args.warmup)))
+            g = captured(lambda: q._forward_grouped(x, ids, w))
+            row["grouped_graph_us"] = timed(g.replay, args.iters, args.warmup)
+            del g
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    T = tokens[-1]
+    x0 = torch.randn((T, H), generator=gen, device=dev).half()
+    logits = torch.randn((T, E), generator=gen, device=dev)
+    w0, ids = torch.topk(torch.softmax(logits, -1), K, dim=-1)
+    x, w = x0.clone().requires_grad_(), w0.clone().requires_grad_()
+    bwd = {"tokens": T, "what": "forward + backward of (y * 1).sum(), x and top_k_weights requiring grad"}
+
+    def step(fwd):
+        x.grad = w.grad = None
+        fwd(x, ids, w).float().sum().backward()
+
+    bwd["grouped_fwd_bwd_us"], bwd["loop_fwd_bwd_us"] = timed_alternating([lambda: step(q._forward_grouped), lambda: step(q._forward_loop)],
+                                                                          max(3, args.iters // 5), 2)
+    print(json.dumps(bwd), flush=True)
+    result = {"block": {"hidden": H, "intermediate": I, "experts": E, "top_k": K, "scheme": "1x16g8", "dtype": "float16"},
+              "device": torch.cuda.get_device_name(dev), "iters": args.iters, "rows": rows, "forward_backward": bwd}
+    out = args.out or os.path.join("profiles", "moe_grouped.json")
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tokens", default="1,2,4,8,16")
+    ap.add_argument("--tokens", default=None)
+    ap.add_argument("--grouped", action="store_true")
     ap.add_argument("--only", choices=["routed", "graph", "loop", "dense"], default=None)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join("profiles", "moe_block.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.grouped:
+        args.tokens = args.tokens or "1,2,4,8,16,32,40,64,128,256,512"
+        return grouped_main(args)
+    args.tokens = args.tokens or "1,2,4,8,16"
+    args.out = args.out or os.path.join("profiles", "moe_block.json")
     dev = torch.device("cuda:0")
     modes = [args.only] if args.only else ["routed", "graph", "loop", "dense"]
     q, dense = build(dev, "dense" in modes)
