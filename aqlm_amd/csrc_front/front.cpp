@@ -332,7 +332,7 @@ struct RawEntry {
   const void* cb_data = nullptr;
   uint32_t cb_version = 0;
   bool cb_versioned = false;
-  int64_t hits_since_check = 0;
+  int64_t hits_since_check = 0;  // calls served since Python last took the count (raw_take_hits)
   at::Tensor packed;
   aqlm_hip_packed_desc desc{};
 };
@@ -347,7 +347,7 @@ static std::atomic<int64_t> g_raw_gemm_rows{7};     // mirror of hip_kernel.MATM
 static std::atomic<int64_t> g_raw_check_every{256};  // mirror of hip_kernel.RAW_OP_CHECK_EVERY: hits of a registered layer between two visits to Python, which re-checks the checksums of its codes / codebook (writes through `.data` change neither identity nor version)
 static PyObject* g_raw_py[3] = {nullptr, nullptr, nullptr};  // Python implementations (leaked on purpose: they outlive the interpreter's teardown order)
 static std::atomic<uint64_t> g_raw_served{0};
-static std::atomic<uint64_t> g_raw_hits{0};  // calls served from a registered (prepacked) layer: the Python cache reads this as its hit count
+static std::atomic<uint64_t> g_raw_hits{0};  // calls served from any registered (prepacked) layer: the Python cache reads it to see that its packs are used
 
 static bool versioned(const at::Tensor& t) { return !t.is_inference(); }
 
@@ -430,11 +430,11 @@ static at::Tensor raw_code1x16_matmat(const at::Tensor& input, const at::Tensor&
             e.cb_data == codebooks.data_ptr() && e.cb_versioned == versioned(codebooks) &&
             (!e.cb_versioned || e.cb_version == codebooks._version());
       const int64_t every = g_raw_check_every.load(std::memory_order_relaxed);
-      if (hit && every > 0 && ++e.hits_since_check >= every && c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None) {
-        e.hits_since_check = 0;
-        hit = false;  // this call goes to Python, which verifies the layer's checksums (and re-registers it if it had to repack)
+      if (hit && every > 0 && e.hits_since_check + 1 >= every && c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None) {
+        hit = false;  // this call completes a period: Python takes the count, verifies the layer's checksums (and re-registers it if it had to repack)
       }
       if (hit) {
+        ++e.hits_since_check;
         packed = e.packed;
         desc = e.desc;
       }
@@ -524,6 +524,17 @@ static void raw_forget(int64_t key) {
   }
 }
 
+// The calls served from the entry `key` since the last call of this function (0 for an unknown key); Python adds them to the
+// calls it served itself and verifies the layer once per `check_every` of the sum.
+static int64_t raw_take_hits(int64_t key) {
+  std::lock_guard<std::mutex> lock(g_raw_mu);
+  auto it = g_raw.find((const void*)(intptr_t)key);
+  if (it == g_raw.end()) return 0;
+  const int64_t n = it->second.hits_since_check;
+  it->second.hits_since_check = 0;
+  return n;
+}
+
 static void raw_clear() {
   std::unordered_map<const void*, RawEntry> old;
   std::lock_guard<std::mutex> lock(g_raw_mu);
@@ -569,6 +580,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("raw_install", &raw_install, "register the compiled kernels of aqlm::code1x16_matmat / code2x8_matmat / code1x8_matmat (CUDA key)");
   m.def("raw_register", &raw_register, "a packed layer of the raw op's cache -> key");
   m.def("raw_forget", &raw_forget);
+  m.def("raw_take_hits", &raw_take_hits, "calls served from one registered layer since the last take (and reset the count)");
   m.def("raw_clear", &raw_clear);
   m.def("raw_config", &raw_config, py::arg("on"), py::arg("prepack"), py::arg("min_codes"), py::arg("gemm_rows"), py::arg("check_every") = 256);
   m.def("raw_served", []() { return g_raw_served.load(); }, "calls launched by the compiled raw ops so far");

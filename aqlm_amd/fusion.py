@@ -20,17 +20,11 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
+from .derived import tensor_version
 from .inference import GEMV_MAX_ROWS, QuantizedLinear
 
 DEFAULT_PATTERNS: Tuple[Tuple[str, ...], ...] = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))
 MAX_MEMBERS = 4  # AQLM_HIP_MAX_SEGMENTS
-
-
-def _version(t: torch.Tensor) -> int:
-    try:
-        return t._version
-    except RuntimeError:  # inference tensors carry no version counter (and cannot be modified in place outside
-        return 0          # inference mode anyway)
 
 
 class SharedInputGroup:
@@ -88,14 +82,14 @@ class SharedInputGroup:
 
     def forward(self, member: QuantizedLinear, input: torch.Tensor) -> torch.Tensor:
         idx = next(i for i, m in enumerate(self.members) if m is member)
-        if self._input is input and self._version == _version(input) and idx in self._pending:
+        if self._input is input and self._version == tensor_version(input) and idx in self._pending:
             out = self._pending.pop(idx)
             if not self._pending:
                 self._input = None
             self.served += 1
             return out
         outs = self._launch(input)
-        self._input, self._version = input, _version(input)  # the reference keeps `input` alive while outputs are parked
+        self._input, self._version = input, tensor_version(input)  # the reference keeps `input` alive while outputs are parked
         self._pending = {i: o for i, o in enumerate(outs) if i != idx}
         self.launches += 1
         return outs[idx]

@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
+from .derived import codes_fingerprint, tensor_checksum, tensor_version
 from .inference_kernels import get_backward_pass_kernel, get_forward_pass_kernel
 from .utils import get_int_dtype
 
@@ -74,18 +75,10 @@ class QuantizedLinear(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-        self.gemv_op = None
-        self.gemm_op = None
-        self.use_gemv_rule = None
-        self._packed_codes = None  # derived, never saved: rebuilt from `codes` at first use
-        self._packed_fingerprint = None
         self._codes_dropped = False
         self._codes_drop_strict = True  # False: the first call that needs the canonical codes restores them for good (prepack_model's default)
         self._codes_shape = None
-        self._cpu_codes_alt = None  # host modules with 8-bit codebooks: codes permuted for the LUT kernel (derived)
-        self._prepack_deferred = False
         self._shared_input_group = None  # set by aqlm_amd.fusion.fuse_shared_input_linears
-        self._fast = None  # compiled fast lane of the decode call (aqlm_amd/_front.py); derived, rebuilt with the kernel choice
         # Escape hatch for mid-size batches (7 .. N - 1 rows: prefill chunks, speculative verification): run them as a dense GEMM
         # on a cached fp16 / bf16 copy of W instead of the fused dequant -> MFMA op.  Measured on MI355X at 4096 x 4096
         # (BENCH detail `bs128_1x16g8_4096x4096`): dense 12.1 / 12.6 / 14.5 us at 16 / 32 / 64 rows against 15.6 / 16.7 / 18.1 us
@@ -93,17 +86,29 @@ class QuantizedLinear(nn.Module):
         # format exists to save (2 bytes per weight for every layer that uses it), so it is off (0) unless asked for:
         # `module.prefer_dense_below_rows = 129`, or `aqlm.checkpoint.enable_dense_below_rows(model, 129)`.
         self.prefer_dense_below_rows = 0
-        self._dense = None  # (fingerprint, W) -- derived, never saved
-        self._derived_checks = None  # checksums of the parameters the derived state was built from (DERIVED_CHECK_EVERY)
-        self._calls_since_check = 0
+        self._reset_derived()
 
-    # Everything the module derives from its parameters (kernel choice, autograd ops, prepacked / permuted codes, the compiled
-    # fast lane -- a pybind11 object that cannot be pickled) is left out of copies and pickles: `copy.deepcopy(model)`,
-    # `torch.save(model)` and `pickle` work at any time (EMA copies, PEFT `modules_to_save`, draft-model clones), and the copy
-    # rebuilds its derived state at its first forward.  A module whose canonical codes were dropped hands them back to the copy.
+    # Everything the module derives from its parameters, in the state "not built yet": the kernel choice and autograd ops, the
+    # prepacked / planar codes of the GPU decode kernels (`_packed_codes`, keyed on `_packed_fingerprint`) with their codebook
+    # range, the permuted codes of the host LUT kernel, the dense W (`_dense`: (fingerprint, W)), the compiled fast lane of the
+    # decode call (`_fast`, aqlm_amd/_front.py: a pybind11 object that cannot be pickled) and the checksums of the parameters it
+    # was all built from (`_derived_checks`, see DERIVED_CHECK_EVERY).  `_prepack_deferred`: a transition inside a hipGraph
+    # capture or a trace left its last step (`_settle`, and the repack if that waited too) to the first eager forward.  None of it is saved, copied or pickled:
+    # `copy.deepcopy(model)`, `torch.save(model)` and `pickle` work at any time (EMA copies, PEFT `modules_to_save`, draft-model
+    # clones), and the copy rebuilds its derived state at its first forward.  A module whose canonical codes were dropped hands
+    # them back to the copy.
     _DERIVED_DEFAULTS = {"gemv_op": None, "gemm_op": None, "use_gemv_rule": None, "_fast": None, "_packed_codes": None,
                          "_packed_fingerprint": None, "_cpu_codes_alt": None, "_prepack_deferred": False, "_dense": None,
                          "_derived_checks": None, "_calls_since_check": 0}
+
+    def _reset_derived(self) -> None:
+        """Forget everything derived from the parameters.  With the canonical codes dropped the packed buffer IS the weights: it
+        stays and forgets only its codebook range."""
+        packed = self._packed_codes if self._codes_dropped else None
+        self.__dict__.update(self._DERIVED_DEFAULTS)
+        if packed is not None:
+            packed.forget_range()
+            self._packed_codes = packed
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -125,34 +130,36 @@ class QuantizedLinear(nn.Module):
         a path PyTorch does not version (``m.codes.data.copy_(...)``) when the periodic check (DERIVED_CHECK_EVERY) is too late
         or switched off.  A module whose canonical codes were dropped keeps its packed buffer (it IS the weights) and forgets only
         what came from the codebooks."""
-        self.gemv_op = self.gemm_op = self.use_gemv_rule = None
-        self._fast = None
-        self._dense = None
-        self._cpu_codes_alt = None
-        self._prepack_deferred = False
-        self._derived_checks = None
-        self._calls_since_check = 0
-        if self._codes_dropped:
-            if self._packed_codes is not None:
-                self._packed_codes._range_of = None
-        else:
-            self._packed_codes = None
+        self._reset_derived()
         group = self._shared_input_group
         if group is not None and hasattr(group, "invalidate"):
             group.invalidate()
 
+    def _settle(self) -> None:
+        """The last step of every transition that creates, drops or restores derived state: bring the packed buffer's codebook
+        range up to date, build the fast lane the state allows, and record the checks of exactly the state that now exists.  The
+        range and the checksums are read back, which a hipGraph capture or a trace does not allow: there the step waits for the
+        first eager forward (`_prepack_deferred`)."""
+        self._derived_checks = None
+        if torch.compiler.is_compiling() or (self.codebooks.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self._prepack_deferred = True
+            return
+        self._prepack_deferred = False
+        if self._packed_codes is not None:
+            from .inference_kernels.hip_kernel import refresh_range
+
+            refresh_range(self._packed_codes, self.codebooks)
+        if self._fast is None:
+            self._build_fast_lane()
+        self._record_derived_checks()
+
     def _record_derived_checks(self) -> None:
         """Checksums of the parameters the derived state was just built from (see DERIVED_CHECK_EVERY)."""
-        self._derived_checks = None
         # staggered start: the modules of a model were all built at the same forward; without an offset every 256th decode step would
         # verify all of them at once (one multi-millisecond spike per 256 tokens instead of one module's ~40 us now and then)
         self._calls_since_check = (id(self) >> 4) % DERIVED_CHECK_EVERY if DERIVED_CHECK_EVERY else 0
         if not DERIVED_CHECK_EVERY or (self._packed_codes is None and self._cpu_codes_alt is None and self._dense is None):
             return
-        if torch.cuda.is_available() and self.codes.is_cuda and torch.cuda.is_current_stream_capturing():
-            return
-        from .inference_kernels.hip_kernel import tensor_checksum
-
         checks = {}
         if not self._codes_dropped:
             checks["codes"] = tensor_checksum(self.codes)
@@ -168,8 +175,6 @@ class QuantizedLinear(nn.Module):
         checks = self._derived_checks
         if not checks:
             return True
-        from .inference_kernels.hip_kernel import tensor_checksum
-
         ok = all(tensor_checksum(getattr(self, name)) == value for name, value in checks.items())
         if not ok:
             self.invalidate_derived_state()
@@ -178,12 +183,19 @@ class QuantizedLinear(nn.Module):
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         # (is_compiling() FIRST: Dynamo specialises int attributes of a module, so a counter touched while tracing installs a guard
         # `_calls_since_check == k` that fails on the next call and recompiles until the limit -- ADVICE r05)
-        if not torch.compiler.is_compiling() and self._derived_checks is not None:
-            n = self._calls_since_check + 1
-            if n >= DERIVED_CHECK_EVERY > 0 and not (input.is_cuda and torch.cuda.is_current_stream_capturing()):
-                n = 0
-                self.verify_derived_state()
-            self._calls_since_check = n
+        if not torch.compiler.is_compiling():
+            if self._derived_checks is not None:
+                n = self._calls_since_check + 1
+                if n >= DERIVED_CHECK_EVERY > 0 and not (input.is_cuda and torch.cuda.is_current_stream_capturing()):
+                    n = 0
+                    self.verify_derived_state()
+                self._calls_since_check = n
+            elif self._prepack_deferred and not (input.is_cuda and torch.cuda.is_current_stream_capturing()):
+                # the first eager forward after a transition inside a capture / trace: finish it (and the repack, if that waited too)
+                if self._packed_codes is None:
+                    self.prepare_matmul_op(input)
+                else:
+                    self._settle()
         group = self._shared_input_group
         if group is not None and group.applicable(input):
             return group.forward(self, input)  # one launch for all projections of this input (fusion.py)
@@ -245,39 +257,26 @@ class QuantizedLinear(nn.Module):
         dequantises unscaled and scales y after the GEMM (cuda_kernel.cpp:249-301, 294-300), and than the fused ops here
         (fp32 accumulate, scale, one rounding); the price of running the opt-in dense route as ONE library GEMM with the bias
         fused."""
-        def ver(t):
-            try:
-                return t._version
-            except RuntimeError:
-                return 0
-
-        fp = (self._codes_fingerprint(), self.codebooks.data_ptr(), ver(self.codebooks), self.scales.data_ptr(), ver(self.scales))
+        fp = (codes_fingerprint(self.codes), self.codebooks.data_ptr(), tensor_version(self.codebooks), self.scales.data_ptr(),
+              tensor_version(self.scales))
         if self._dense is None or self._dense[0] != fp:
             from .utils import _dequantize_weight, unpack_int_data
 
             with torch.no_grad():
                 w = _dequantize_weight(unpack_int_data(self._canonical_codes(), self.nbits_per_codebook), self.codebooks, self.scales)
             self._dense = (fp, w.to(self.codebooks.dtype).contiguous())
-            self._record_derived_checks()
+            self._settle()
         return self._dense[1]
-
-    def _codes_fingerprint(self):
-        c = self.codes
-        try:
-            v = c._version
-        except RuntimeError:  # inference tensors carry no version counter
-            v = 0
-        return (id(c), c.data_ptr() if c.numel() else 0, tuple(c.shape), v)
 
     def _derived_state_is_stale(self) -> bool:
         """The prepacked buffer is derived from ``codes``: rebuild it when ``codes`` was written in place
         (``load_state_dict`` / ``copy_`` after the first forward), rebound (``module.codes = ...``, accelerate's
         ``set_module_tensor_to_device``) or when a repack was postponed during graph capture."""
-        if self._prepack_deferred:
-            return not torch.cuda.is_current_stream_capturing()
-        if (self._packed_codes is None and self._cpu_codes_alt is None) or self._codes_dropped:
+        if self._codes_dropped:
             return False
-        return self._codes_fingerprint() != self._packed_fingerprint
+        if self._packed_codes is None and self._cpu_codes_alt is None:
+            return self._prepack_deferred and not torch.cuda.is_current_stream_capturing()
+        return codes_fingerprint(self.codes) != self._packed_fingerprint
 
     def _canonical_codes(self) -> torch.Tensor:
         """``codes`` in the checkpoint layout; rebuilt from the prepacked buffer (lossless) when they were dropped."""
@@ -307,7 +306,8 @@ class QuantizedLinear(nn.Module):
         self._codes_shape = tuple(self.codes.shape)
         self.codes = nn.Parameter(torch.empty((0,), dtype=self.codes.dtype, device=self.codes.device), requires_grad=False)
         self._codes_dropped = True
-        self._build_fast_lane()
+        self._fast = None  # the lane watched the codes it no longer reads
+        self._settle()
         return True
 
     def restore_canonical_codes(self) -> None:
@@ -315,8 +315,9 @@ class QuantizedLinear(nn.Module):
             codes = self._canonical_codes()
             self._codes_dropped = False
             self.codes = nn.Parameter(codes, requires_grad=False)
-            self._packed_fingerprint = self._codes_fingerprint()
-            self._build_fast_lane()
+            self._packed_fingerprint = codes_fingerprint(self.codes)
+            self._fast = None
+            self._settle()
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         super()._save_to_state_dict(destination, prefix, keep_vars)
@@ -326,11 +327,9 @@ class QuantizedLinear(nn.Module):
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         if self._codes_dropped and prefix + "codes" in state_dict:  # new codes arrive: give them a parameter to land in
             self._codes_dropped = False
-            self._packed_codes = None
-            self._fast = None
+            self._reset_derived()
             self.codes = nn.Parameter(torch.empty(self._codes_shape, dtype=self.codes.dtype, device=self.codes.device),
                                       requires_grad=False)
-            self.gemv_op = None
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def _apply(self, fn, *args, **kwargs):
@@ -338,22 +337,14 @@ class QuantizedLinear(nn.Module):
         choice, prepacked codes); it is rebuilt at the next forward."""
         self.restore_canonical_codes()  # the derived buffer does not survive a conversion; the codes must
         out = super()._apply(fn, *args, **kwargs)
-        self.gemv_op = self.gemm_op = self.use_gemv_rule = None
-        self._fast = None
-        self._packed_codes = None
-        self._cpu_codes_alt = None
-        self._prepack_deferred = False
-        self._dense = None
+        self._reset_derived()
         return out
 
     def prepare_matmul_op(self, input: torch.Tensor):
-        self._prepare_matmul_op(input)
-        self._record_derived_checks()
-
-    def _prepare_matmul_op(self, input: torch.Tensor):
         """Resolve the decode (gemv) and batch (gemm) operators once (reference inference.py:77-96).  For host modules
         with 8-bit codebooks the reference permutes ``codes`` IN PLACE to the LUT kernel's layout (inference.py:78-83,
-        "TODO: fix this thing"); here the permuted copy is a derived buffer and ``codes`` keeps the checkpoint layout."""
+        "TODO: fix this thing"); here the permuted copy is a derived buffer and ``codes`` keeps the checkpoint layout.  Then the
+        packed copy of the codes (``_repack``) and the settle step."""
         from .inference_kernels.kernel_selector import cpu_kernel_takes_permuted_codes
 
         self._fast = None
@@ -362,7 +353,7 @@ class QuantizedLinear(nn.Module):
             from .inference_kernels.cpu_kernel import permute_codes_for_lut
 
             self._cpu_codes_alt = permute_codes_for_lut(self.codes)
-            self._packed_fingerprint = self._codes_fingerprint()
+            self._packed_fingerprint = codes_fingerprint(self.codes)
         fwd_gemv, fwd_gemm = get_forward_pass_kernel(self.codebooks, False), get_forward_pass_kernel(self.codebooks, True)
         if self._cpu_codes_alt is not None:
             # the LUT kernel reads the permuted copy; the op still receives (and saves for backward) the canonical codes
@@ -374,35 +365,34 @@ class QuantizedLinear(nn.Module):
         self.use_gemv_rule = lambda x: math.prod(x.shape[:-1]) <= GEMV_MAX_ROWS
         # load-time re-layout of the codes for the decode kernel (the reference does the analogous thing for its CPU
         # kernel here, inference.py:78-83 -- but in place; we keep `codes` untouched and add a derived buffer)
-        if self._codes_dropped:
-            self._build_fast_lane()
-            return  # the packed buffer IS the weights now
+        if not self._codes_dropped:  # (dropped: the packed buffer IS the weights now)
+            self._repack()
+        self._settle()
+
+    def _repack(self) -> None:
+        """The prepacked / planar copy of ``codes`` for the decode kernels, when the layer takes one."""
         self._packed_codes = None
-        self._prepack_deferred = False
         if (PREPACK_MIN_CODES and self.out_features * (self.in_features // self.in_group_size) >= PREPACK_MIN_CODES
                 and self.num_codebooks == 1 and self.nbits_per_codebook == 16 and self.in_group_size in (8, 16) and self.out_group_size == 1
                 and self.codes.is_cuda and self.codebooks.dtype in (torch.float16, torch.bfloat16)):
             if torch.cuda.is_current_stream_capturing():
                 # the repack synchronises its stream: not allowed inside a hipGraph capture.  This call runs on the
-                # direct kernel; the repack happens at the first forward outside a capture.
-                self._prepack_deferred = True
+                # direct kernel; the repack happens at the first forward outside a capture (with the deferred settle step).
                 return
             from .inference_kernels import hip_kernel
 
             self._packed_codes = hip_kernel.prepack_1x16(self.codes, self.in_group_size, codebooks=self.codebooks)
-            self._packed_fingerprint = self._codes_fingerprint()
+            self._packed_fingerprint = codes_fingerprint(self.codes)
         elif (PREPACK_MIN_CODES and self.out_features * (self.in_features // self.in_group_size) * 8 >= PREPACK_MIN_CODES
                 and self.num_codebooks == 8 and self.nbits_per_codebook == 8 and self.in_group_size in (8, 16, 32) and self.out_group_size == 1
                 and self.codes.is_cuda and self.codebooks.dtype in (torch.float16, torch.bfloat16)):
             # 8 x 8-bit schemes: planar copy of the codes for the look-up-table matvec (same size as `codes`, lossless)
             if torch.cuda.is_current_stream_capturing():
-                self._prepack_deferred = True  # the codebook bound is a host read-back: first forward outside a capture
-                return
+                return  # the codebook bound is a host read-back: first forward outside a capture
             from .inference_kernels import hip_kernel
 
             self._packed_codes = hip_kernel.planar_8x8_pack(self.codes, self.in_group_size, codebooks=self.codebooks)
-            self._packed_fingerprint = self._codes_fingerprint()
-        self._build_fast_lane()
+            self._packed_fingerprint = codes_fingerprint(self.codes)
 
     def _build_fast_lane(self) -> None:
         """The compiled fast lane of decode calls (<= GEMV_MAX_ROWS rows, no grad): flatten / allocate / launch without the

@@ -37,6 +37,7 @@ import contextlib
 import torch
 import torch.nn as nn
 
+from .derived import tensor_version
 from .inference import GEMV_MAX_ROWS, QuantizedLinear, _get_autograd_matmul_op
 from .inference_kernels.kernel_selector import get_backward_pass_kernel, get_forward_pass_kernel
 
@@ -145,7 +146,7 @@ class QuantizedMixtralExperts(nn.Module):
         from .inference_kernels import hip_kernel
 
         layers13, layers2 = self._table_tensors(_SEGMENTS_13), self._table_tensors(("w2",))
-        key = (device, tuple((t.data_ptr(), hip_kernel._version(t)) for per in layers13 + layers2 for seg in per
+        key = (device, tuple((t.data_ptr(), tensor_version(t)) for per in layers13 + layers2 for seg in per
                              for t in seg if t is not None))
         if self._tables is None or self._tables[0] != key:
             if torch.cuda.is_current_stream_capturing():

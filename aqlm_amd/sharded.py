@@ -39,6 +39,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .derived import codes_fingerprint
 from .inference_kernels import get_forward_pass_kernel
 
 
@@ -91,8 +92,6 @@ class ShardedQuantizedLinear(nn.Module):
         assert collective in ("rccl", "xgmi")
         self.collective = collective
         self._bias_all = bias_all      # the full bias on every rank (the fused finalize writes the full y everywhere)
-        self._xgmi = None              # OneShotAllReduce, built collectively at first use
-        self._xgmi_ok = None
         assert mode in ("in", "out")
         self.mode = mode
         self.group = group
@@ -106,35 +105,29 @@ class ShardedQuantizedLinear(nn.Module):
         self.scales = nn.Parameter(scales, requires_grad=False)
         self.bias = nn.Parameter(bias, requires_grad=False) if bias is not None else None
         self._kernel = kernel
-        self._packed = None      # prepacked codes of this shard (derived; built at first use on the GPU)
-        self._packed_tried = False
-        self._packed_fingerprint = None  # identity / storage / version of `codes` at pack time (as QuantizedLinear does)
-        self._selector_kernel = None
         self._gather_sizes = None
-        self._cpu_codes_alt = None  # (fingerprint, codes permuted for the host LUT kernel); derived
+        self._reset_derived()
 
-    def _codes_fingerprint(self):
-        c = self.codes
-        try:
-            v = c._version
-        except RuntimeError:  # inference tensors carry no version counter
-            v = 0
-        return (id(c), c.data_ptr() if c.numel() else 0, tuple(c.shape), v)
+    def _reset_derived(self) -> None:
+        """Forget everything derived from the parameters; it is rebuilt at first use."""
+        self._packed = None               # prepacked codes of this shard (built at first use on the GPU)
+        self._packed_tried = False
+        self._packed_fingerprint = None   # codes_fingerprint(codes) at pack time (as QuantizedLinear does)
+        self._cpu_codes_alt = None        # (fingerprint, codes permuted for the host LUT kernel)
+        self._selector_kernel = None      # depends on the codebooks' device / dtype
+        self._xgmi = None                 # OneShotAllReduce, built collectively at first use
+        self._xgmi_ok = None              # the collective decision: it depends on every shard being packed
 
     def _drop_derived_if_stale(self) -> None:
         """The prepacked buffer (and the one-shot all-reduce state sized for it) is derived from ``codes``: after
         ``load_state_dict`` / an in-place write / a rebind it is rebuilt at this call instead of being multiplied with."""
-        if self._packed_tried and self._packed_fingerprint != self._codes_fingerprint():
-            self._packed, self._packed_tried, self._packed_fingerprint = None, False, None
-            self._xgmi_ok = None  # the collective decision depends on every shard being packed: agree again
+        if self._packed_tried and self._packed_fingerprint != codes_fingerprint(self.codes):
+            self._reset_derived()
 
     def _apply(self, fn, *args, **kwargs):
         """``.to()`` / ``.cuda()`` / ``.half()`` replace the parameters: everything derived from them goes."""
         out = super()._apply(fn, *args, **kwargs)
-        self._packed, self._packed_tried, self._packed_fingerprint = None, False, None
-        self._xgmi, self._xgmi_ok = None, None
-        self._selector_kernel = None
-        self._cpu_codes_alt = None
+        self._reset_derived()
         return out
 
     @classmethod
@@ -167,7 +160,7 @@ class ShardedQuantizedLinear(nn.Module):
     def _k(self):
         if self._kernel is not None:  # injected (tests): used as is
             return self._kernel
-        if self._selector_kernel is None:  # depends on the codebooks' device / dtype: dropped by _apply
+        if self._selector_kernel is None:
             self._selector_kernel = get_forward_pass_kernel(self.codebooks, False)
         return self._selector_kernel
 
@@ -185,7 +178,7 @@ class ShardedQuantizedLinear(nn.Module):
 
             self._packed_tried = True
             self._packed = hip_kernel.prepack_1x16(self.codes, 8, codebooks=self.codebooks)
-            self._packed_fingerprint = self._codes_fingerprint()
+            self._packed_fingerprint = codes_fingerprint(self.codes)
         if (self._packed is not None and x.dtype == self.codebooks.dtype
                 and x.numel() // x.shape[-1] <= inference.GEMV_MAX_ROWS):
             from .inference_kernels import hip_kernel
@@ -197,7 +190,7 @@ class ShardedQuantizedLinear(nn.Module):
             if cpu_kernel_takes_permuted_codes(self.codebooks):
                 # host shards with 8-bit codebooks: the native LUT kernel reads codes permuted to [in_groups, out, K]; a derived
                 # copy, as in QuantizedLinear.prepare_matmul_op (the reference permutes the parameter in place, inference.py:78-83)
-                fp = self._codes_fingerprint()
+                fp = codes_fingerprint(self.codes)
                 if self._cpu_codes_alt is None or self._cpu_codes_alt[0] != fp:
                     from .inference_kernels.cpu_kernel import permute_codes_for_lut
 
@@ -215,7 +208,7 @@ class ShardedQuantizedLinear(nn.Module):
         if self._xgmi_ok is None:  # first use: collective decision + state exchange
             if not self._packed_tried and self.codes.is_cuda and self.codes.shape[1] > 0:
                 self._packed_tried = True
-                self._packed_fingerprint = self._codes_fingerprint()
+                self._packed_fingerprint = codes_fingerprint(self.codes)
                 if (tuple(self.codebooks.shape[:3]) == (1, 65536, 1) and self.codebooks.shape[3] == 8
                         and self.codes.shape[0] * self.codes.shape[1] >= inference.PREPACK_MIN_CODES):
                     # (the publish form of the matvec exists for the 16 x 16 geometry only)
@@ -232,7 +225,7 @@ class ShardedQuantizedLinear(nn.Module):
         dt = hip_kernel._dtype_id(xs)
         y = torch.empty((rows, self.out_features), dtype=xs.dtype, device=xs.device)
         stream = hip_kernel._stream_ptr(xs.device)
-        hip_kernel._refresh_range(self._packed, self.codebooks)
+        hip_kernel.refresh_range(self._packed, self.codebooks)
         if XGMI_FUSED_PUBLISH and hip_kernel.FUSED_FINALIZE and self._packed.desc.codebook_absmax > 0.0:
             # two launches: the matvec publishes the shard's totals itself (last-arrival branch of its finalize), then the
             # reduce.  Falls back to partials + publish + reduce when the rows do not fit one launch.

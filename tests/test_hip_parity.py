@@ -2439,6 +2439,63 @@ def test_derived_state_notices_writes_behind_the_version_counter(hk, monkeypatch
     hk.clear_raw_op_prepack_cache()
 
 
+def test_prepack_model_default_keeps_the_fast_lane(hk, monkeypatch):
+    """`prepack_model()` drops the canonical 1x16 codes by default.  The periodic check must then compare what exists: it once kept
+    the checksum of the dropped codes, invalidated the layer within one period and left it off the compiled fast lane for good
+    (the interpreter's ~17-19 us per eager call instead of ~5).  After an explicit invalidation the next forward has a lane again."""
+    import aqlm_amd.inference as inf
+    from aqlm.checkpoint import prepack_model
+    from aqlm_amd import _front
+
+    if not _front.available():
+        pytest.skip("compiled front end not built (aqlm_amd/_aqlm_front.so)")
+    monkeypatch.setattr(inf, "DERIVED_CHECK_EVERY", 8)
+    invalidations = []
+    invalidate = inf.QuantizedLinear.invalidate_derived_state
+    monkeypatch.setattr(inf.QuantizedLinear, "invalidate_derived_state", lambda self: (invalidations.append(self), invalidate(self))[1])
+    fin, fout = 2048, 1536
+    m, T = _module_from(orc.make_layer(43, fin, fout, 1, 16, 8, batch=1, bias=True), 1, 16, 8, fin, fout, torch.float16)
+    with torch.no_grad():
+        prepack_model(torch.nn.ModuleDict({"l": m}), min_codes=100_000)
+        assert m._codes_dropped
+        ys = [m(T["x"]) for _ in range(24)]
+        assert m._fast is not None and not invalidations
+        assert all(torch.equal(y, ys[0]) for y in ys)
+        m.invalidate_derived_state()
+        m(T["x"])
+        assert m._fast is not None
+
+
+@pytest.mark.raw_prepack
+def test_raw_op_checks_each_cached_layer_on_its_own_hits(hk, monkeypatch):
+    """The raw op's cache re-checks a layer's codes once per RAW_OP_CHECK_EVERY hits of THAT layer, served by Python or by the
+    compiled op.  It once counted the compiled op's hits of every layer, so a layer whose calls the compiled op hands back
+    (grad mode) paid a checksum + host sync on nearly every call in a model of many layers."""
+    from aqlm_amd import _front
+
+    if not (_front.available() and hk._RAW_FAST is not None):
+        pytest.skip("compiled raw ops not installed (aqlm_amd/_aqlm_front.so not built)")
+    monkeypatch.setattr(hk, "RAW_OP_PREPACK_MIN_CODES", 100_000)
+    monkeypatch.setattr(hk, "RAW_OP_CHECK_EVERY", 8)
+    hk.clear_raw_op_prepack_cache()
+    op = torch.ops.aqlm.code1x16_matmat
+    TA, TB = (to_dev(orc.make_layer(seed, 2048, 640, 1, 16, 8, batch=1, bias=False), torch.float16) for seed in (7201, 7202))
+    for T in (TA, TB):
+        op(T["x"], T["codes"], T["codebooks"], T["scales"], None)     # Python packs and registers the layer
+    assert id(TA["codes"]) in hk._RAW_FAST_KEYS and id(TB["codes"]) in hk._RAW_FAST_KEYS
+    checked = []
+    checksum = hk.tensor_checksum
+    monkeypatch.setattr(hk, "tensor_checksum", lambda t: (checked.append(t.data_ptr()), checksum(t))[1])
+    xa = TA["x"].clone().requires_grad_(True)
+    with torch.enable_grad():
+        for _ in range(4):
+            for _ in range(25):
+                op(TB["x"], TB["codes"], TB["codebooks"], TB["scales"], None)
+            op(xa, TA["codes"], TA["codebooks"], TA["scales"], None)  # handed back to Python by the compiled op
+    assert TA["codes"].data_ptr() not in checked
+    assert TB["codes"].data_ptr() in checked  # B's periods came round: the compiled op's hand-back ends in a verification
+
+
 # ------------------------------------------------------------------ fused finalize + one-shot all-reduce (xGMI path)
 @pytest.mark.parametrize("fused_publish", [True, False])
 def test_xgmi_fused_finalize_world1(hk, fused_publish):

@@ -268,6 +268,11 @@ def test_module_copies_and_pickles_after_a_forward_cpu(K, nbits, g):
     buf.seek(0)
     assert torch.equal(torch.load(buf, weights_only=False)(x), y)
     assert m.gemv_op is not None  # the original keeps its derived state
+    if nbits == 8:  # permuted codes of the LUT kernel: checks recorded; a conversion forgets them with the rest
+        assert m._derived_checks is not None
+        m.cpu()
+        assert m._derived_checks is None and m._calls_since_check == 0
+        assert torch.equal(m(x), y) and m._derived_checks is not None
 
 
 def test_fused_8x8_switch_rows_follow_the_measured_cost_model():
