@@ -98,6 +98,31 @@ class Xgmi(ctypes.Structure):
 
 _xgp = ctypes.POINTER(Xgmi)
 
+
+class RoutedPackedEntry(ctypes.Structure):
+    """aqlm_hip_routed_packed_entry (include/aqlm_hip.h): one prepacked (expert, projection) of the routed packed launch; filled by
+    aqlm_hip_routed_packed_entry_fill, copied to the device as part of the launch's table."""
+
+    _fields_ = [("entries", _vp), ("wave_info", _vp), ("row_starts", _vp), ("codebook", _vp), ("scales", _vp), ("bias", _vp),
+                ("out_features", ctypes.c_int32), ("rows_per_group", ctypes.c_int32), ("waves", ctypes.c_int32),
+                ("steps", ctypes.c_int32), ("x_copies", ctypes.c_int32), ("entry_stream_bytes", ctypes.c_uint32),
+                ("codebook_absmax", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+ROUTED_PACKED_ENTRY_WORDS = ctypes.sizeof(RoutedPackedEntry) // 8   # 64-bit words of a table entry
+
+
+class RoutedPackedGeometry(ctypes.Structure):
+    """aqlm_hip_routed_packed_geometry: the launch-wide values of one table (aqlm_hip_gemv_1x16_routed_packed_geometry)."""
+
+    _fields_ = [("out_features", ctypes.c_int32), ("in_features", ctypes.c_int32), ("in_group_size", ctypes.c_int32),
+                ("rows_per_group", ctypes.c_int32), ("max_waves", ctypes.c_int32), ("slice_first", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+_rpep = ctypes.POINTER(RoutedPackedEntry)
+_rpgp = ctypes.POINTER(RoutedPackedGeometry)
+
 # name -> (restype, argtypes); mirrors include/aqlm_hip.h one to one
 SIGNATURES = {
     "aqlm_hip_abi_version": (_ci, []),
@@ -111,6 +136,11 @@ SIGNATURES = {
     "aqlm_hip_gemm_1x16_grouped": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _ci, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi_cells": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_gemv_1x16_routed_packed_lds_bytes": (_sz, [_ci, _ci, _ci]),
+    "aqlm_hip_routed_packed_entry_fill": (_ci, [_descp, _vp, _vp, _vp, _vp, _rpep]),
+    "aqlm_hip_gemv_1x16_routed_packed_geometry": (_ci, [_descpp, _ci, _rpgp]),
+    "aqlm_hip_gemv_1x16_routed_packed_supported": (_ci, [_descpp, _ci]),
+    "aqlm_hip_gemv_1x16_routed_packed": (_ci, [_vp, _rpgp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

@@ -129,7 +129,7 @@ _DEFAULT = object()
 
 
 def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_canonical=_DEFAULT, compact: bool = False,
-                  thorough: bool = False) -> Dict[str, float]:
+                  thorough: bool = False, experts: bool = False) -> Dict[str, float]:
     """Resolve the kernels and run the load-time repack of every eligible QuantizedLinear now (GPU-resident modules
     only) instead of at its first forward; ``min_codes`` overrides ``inference.PREPACK_MIN_CODES`` for this call.
     ``drop_canonical``: free the checkpoint-layout ``codes`` of repacked layers -- the packed buffer is lossless; ``state_dict()``,
@@ -147,6 +147,9 @@ def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_
     ``compact=True`` packs 1x16 g8 layers with 24-bit entries (3.5 instead of 4.5 bytes per code: a 70B model holds 30 GB of
     packed codes instead of 39; measured 1-5 % slower matvecs).  ``thorough=True`` runs the local search of the entry order on
     every layer, not only on those of <= 8 Mi codes (1-3 % faster matvecs on the big layers for ~5x their prepack time).
+    ``experts=True`` also prepacks the experts of every ``QuantizedMixtralExperts`` (``aqlm_amd.moe.prepack_experts`` with the same
+    ``min_codes`` and ``thorough``; their canonical codes stay, whatever ``drop_canonical`` says: 4.8 more resident bits per expert
+    weight); its report is returned under ``"experts"``.  By default experts are left alone.
     Returns ``memory_report(model)`` plus ``prepack_seconds``."""
     import time
 
@@ -186,8 +189,15 @@ def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_
         _native.set_tuning("packed_arrange", old_arr)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
+    expert_report = None
+    if experts:
+        from .moe import prepack_experts
+
+        expert_report = prepack_experts(model, min_codes=min_codes, thorough=thorough)
     rep = memory_report(model)
     rep["prepack_seconds"] = time.perf_counter() - t0
+    if expert_report is not None:
+        rep["experts"] = expert_report
     return rep
 
 

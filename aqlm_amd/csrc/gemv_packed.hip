@@ -82,6 +82,11 @@
 #define aqlm_hip_gemv_1x16_packed_publish aqlm_hip_g16_gemv_1x16_packed_publish
 #define aqlm_hip_gemv_1x16_packed_multi aqlm_hip_g16_gemv_1x16_packed_multi
 #define aqlm_hip_gemv_1x16_packed_multi_cells aqlm_hip_g16_gemv_1x16_packed_multi_cells
+#define aqlm_hip_gemv_1x16_routed_packed_lds_bytes aqlm_hip_g16_gemv_1x16_routed_packed_lds_bytes
+#define aqlm_hip_routed_packed_entry_fill aqlm_hip_g16_routed_packed_entry_fill
+#define aqlm_hip_gemv_1x16_routed_packed_geometry aqlm_hip_g16_gemv_1x16_routed_packed_geometry
+#define aqlm_hip_gemv_1x16_routed_packed_supported aqlm_hip_g16_gemv_1x16_routed_packed_supported
+#define aqlm_hip_gemv_1x16_routed_packed aqlm_hip_g16_gemv_1x16_routed_packed
 #define PK_API __attribute__((visibility("hidden")))  // internal to libaqlm_hip.so: reached through the public entries only
 #else
 #define PK_NS pk_g8
@@ -1030,7 +1035,9 @@ struct PackedVgArgs {
   uint32_t ns[4];
 };
 
-template <class T_, int B, int PD, uint32_t XWIN, int EB, bool PUB = false, bool VG = false>
+// NOPF: the launch has no prefetch waves (p.NPW == 0 by construction: the expert-routed launch) -- their branches go away at
+// compile time.  (A run-time p.NPW == 0 leaves them in, and with them a path on which hipcc sees the LDS-DMA still in flight.)
+template <class T_, int B, int PD, uint32_t XWIN, int EB, bool PUB = false, bool VG = false, bool NOPF = false>
 __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p, const int block, const int NWB,
                                                       const PackedVgArgs& vg = PackedVgArgs{}) {
   using LDS = PackedLds<B, XWIN>;
@@ -1102,7 +1109,7 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   // layer's bytes (LDS-DMA into a 1 KiB dump zone each: no registers, nothing to wait for before the fill barrier) and
   // meet the others at the barriers.
   const int NWD = NWB - p.NPW;  // waves that fill and compute
-  const bool pfw = wave >= NWD;
+  const bool pfw = !NOPF && wave >= NWD;
   if (pfw) {
     const int pw = wave - NWD;
     const uint32_t dump = LDS::dump(p.in_groups, p.RG) + (uint32_t)pw * 1024u;
@@ -2348,6 +2355,12 @@ int aqlm_hip_g16_gemv_1x16_packed_multi(const aqlm_hip_segment*, const aqlm_hip_
                                         size_t, void*);
 int aqlm_hip_g16_gemv_1x16_packed_multi_cells(const aqlm_hip_segment*, const aqlm_hip_packed_desc* const*, int, const void*, int, int, long, int,
                                               void*, size_t, void*);
+size_t aqlm_hip_g16_gemv_1x16_routed_packed_lds_bytes(int, int, int);
+int aqlm_hip_g16_routed_packed_entry_fill(const aqlm_hip_packed_desc*, const void*, const void*, const void*, const void*,
+                                          aqlm_hip_routed_packed_entry*);
+int aqlm_hip_g16_gemv_1x16_routed_packed_geometry(const aqlm_hip_packed_desc* const*, int, aqlm_hip_routed_packed_geometry*);
+int aqlm_hip_g16_gemv_1x16_routed_packed(const aqlm_hip_routed_packed_entry*, const aqlm_hip_routed_packed_geometry*, int, int, const void*,
+                                         int, int, int, const void*, long, int, void*, int, void*, size_t, void*);
 }
 #pragma GCC visibility pop
 // a descriptor of the twin's format (32 slices)
@@ -3313,3 +3326,6 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
     hipLaunchKernelGGL(gemv_1x16_packed_finalize_multi<BF16>, dim3(fblocks), dim3(256), 0, stream, fm);
   return check_hip(hipGetLastError(), "gemv_1x16_packed_finalize_multi launch");
 }
+
+// ---------------------------------------------------------------------------------------------- expert-routed launch (MoE decode)
+#include "gemv_packed_routed.h"

@@ -587,6 +587,141 @@ def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
 
 
 # ------------------------------------------------------------------------------------------------------
+# expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
+# ------------------------------------------------------------------------------------------------------
+ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
+
+
+def _desc_array(packed_list):
+    return (_native._descp * len(packed_list))(*[ctypes.pointer(p.desc) for p in packed_list])
+
+
+def routed_packed_supported(packed_list) -> bool:
+    """Will aqlm_hip_gemv_1x16_routed_packed serve a table of these ``PackedCodes`` (one shape; 4-byte entries, uniform geometry, a
+    codebook range each)?  A host query on the descriptors."""
+    if not packed_list or any(p is None or not isinstance(p, PackedCodes) for p in packed_list):
+        return False
+    return bool(_lib.aqlm_hip_gemv_1x16_routed_packed_supported(_desc_array(packed_list), len(packed_list)))
+
+
+def routed_packed_table(layers, device):
+    """The device-resident table of aqlm_hip_gemv_1x16_routed_packed and its launch geometry: ``layers[e][s] = (packed,
+    codebooks, scales, bias or None)`` with ``packed`` the layer's ``PackedCodes`` -> (int64 table on ``device``, entry [e * S + s]
+    as filled by aqlm_hip_routed_packed_entry_fill; geometry tail for ``code1x16_moe_matmat_packed``).  Every expert's codebook
+    range -- and the codebook image of a relabelled buffer -- is brought up to date first (``refresh_range``): the table bakes in
+    the bound and the image's address.  The table holds raw addresses: the caller keeps the tensors alive and rebuilds it when one
+    of them moves or is rewritten.  A host-to-device copy (and, for a stale range, a read-back): never while a hipGraph is being
+    captured.  NotImplementedError when the launch declines the table (the caller keeps the routed launch on the canonical
+    codes)."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("routed_packed_table: the table is built by a host-to-device copy; build it before capturing")
+    entries, packs = [], []
+    for per_expert in layers:
+        for packed, codebooks, scales, bias in per_expert:
+            for t in (codebooks, scales):
+                if not t.is_contiguous() or t.data_ptr() % 16:
+                    raise ValueError("routed packed table: codebooks / scales must be contiguous and 16-byte aligned")
+            if bias is not None and not bias.is_contiguous():
+                raise ValueError("routed packed table: bias must be contiguous")
+            refresh_range(packed, codebooks)
+            ent = _native.RoutedPackedEntry()
+            rc = _lib.aqlm_hip_routed_packed_entry_fill(ctypes.byref(packed.desc), packed.data_ptr(), codebooks.data_ptr(),
+                                                        scales.data_ptr(), _ptr(bias), ctypes.byref(ent))
+            if rc:
+                _native.check(rc, "aqlm routed_packed_entry_fill")
+            entries.append(ent)
+            packs.append(packed)
+    geom = _native.RoutedPackedGeometry()
+    rc = _lib.aqlm_hip_gemv_1x16_routed_packed_geometry(_desc_array(packs), len(packs), ctypes.byref(geom))
+    if rc:
+        _native.check(rc, "aqlm routed_packed_geometry")
+    raw = b"".join(bytes(e) for e in entries)
+    table = torch.frombuffer(bytearray(raw), dtype=torch.int64).clone().to(device)
+    tail = [int(geom.rows_per_group), int(geom.max_waves), int(geom.slice_first), int(geom.lds_bytes), int(table.numel())]
+    return table, tail
+
+
+# Accumulator cells of the routed packed launch: [pairs][segments][out_features] u64, zero at rest.  One zero-filled buffer per
+# table (= per block and projection launch) and size class, allocated at the first eager call and reused by every later call,
+# captured ones included -- a capture runs on a stream of its own, so a per-stream registry would find nothing there, and
+# nothing can be allocated for good inside a capture.  The kernel leaves every cell it touched at zero.  Like the cells inside a
+# packed buffer, a set serves one stream at a time: one block must not run on two streams at once.  A hipGraph may have captured
+# an address, so a buffer is never resized or freed behind its back: sizes are rounded up to a power of two and each size class
+# is allocated once (release_routed_packed_cells frees them when the caller knows no such graph is alive).
+_ROUTED_PACKED_CELLS = {}
+
+
+def routed_packed_cells(device: torch.device, owner: int, nbytes: int):
+    size = 1 << max(16, (int(nbytes) - 1).bit_length())
+    key = (device.index, owner, size)
+    cells = _ROUTED_PACKED_CELLS.get(key)
+    if cells is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("code1x16_moe_matmat_packed: the accumulator cells are allocated at the first eager call; run one "
+                               "eager forward of this size before capturing")
+        with torch.cuda.device(device):
+            cells = torch.zeros((size // 8,), dtype=torch.int64, device=device)
+        _ROUTED_PACKED_CELLS[key] = cells
+    return cells
+
+
+def release_routed_packed_cells() -> int:
+    """Free every cell buffer of the routed packed launch (the caller knows that no hipGraph that captured one is alive)."""
+    n = len(_ROUTED_PACKED_CELLS)
+    _ROUTED_PACKED_CELLS.clear()
+    return n
+
+
+def code1x16_moe_matmat_packed(input, expert_ids, table, geometry, x_per_pair):
+    """``code1x16_moe_matmat`` on prepacked experts: every (token, expert) pair of one or two 1x16 projections of a
+    mixture-of-experts block in one launch per 64 pairs, each pair a batch-1 pass of the packed matvec on its expert's buffer.
+    geometry = [num_experts, num_segments, out_features, in_features, in_group_size, top_k] + the tail ``routed_packed_table``
+    returned with ``table``.  ``expert_ids`` [T, top_k] int64 / int32 on the device (read there only; ids outside
+    [0, num_experts) give zero rows); ``input`` [T, in] (token rows) or [T * top_k, in] (``x_per_pair``).
+    -> [T * top_k, num_segments, out_features]; row (t * top_k + j, s) is bit-identical to ``code1x16_matmat_packed`` of expert
+    expert_ids[t, j], projection s, on that row alone."""
+    if len(geometry) != ROUTED_PACKED_GEOMETRY_INTS:
+        raise ValueError(f"geometry must hold {ROUTED_PACKED_GEOMETRY_INTS} ints (shape + the tail of routed_packed_table)")
+    E, S, out_features, in_features, g, top_k, rpg, max_waves, slice_first, lds_bytes, words = (int(v) for v in geometry)
+    dt = _dtype_id(input)
+    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
+    T = expert_ids.shape[0]
+    rows = T * top_k if x_per_pair else T
+    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
+        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
+    if (table.dtype != torch.int64 or table.numel() != words or words != E * S * _native.ROUTED_PACKED_ENTRY_WORDS
+            or table.device != input.device):
+        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_PACKED_ENTRY_WORDS}] on {input.device}")
+    if expert_ids.device != input.device:
+        raise ValueError("expert_ids must be on the input's device")
+    x = _flat_rows(input)
+    if x.data_ptr() % 16 or (x.stride(0) * 2) % 16:
+        x = x.clone(memory_format=torch.contiguous_format)
+    ids = _c(expert_ids)
+    y = torch.empty((T * top_k, S, out_features), dtype=input.dtype, device=input.device)
+    if T == 0:
+        return y
+    geom = _native.RoutedPackedGeometry(out_features, in_features, g, rpg, max_waves, slice_first, lds_bytes, 0)
+    stream = _stream_ptr(input.device)
+    esz = ids.element_size()
+    chunks = routed_chunks(T, top_k)
+    max_pairs = max(t1 - t0 for t0, t1 in chunks) * top_k
+    cells = routed_packed_cells(input.device, table.data_ptr(), max_pairs * S * out_features * 8)
+    with _device_guard(input.device):
+        for t0, t1 in chunks:
+            p0, npairs = t0 * top_k, (t1 - t0) * top_k
+            xp = x.data_ptr() + (p0 if x_per_pair else t0) * x.stride(0) * 2
+            rc = _lib.aqlm_hip_gemv_1x16_routed_packed(table.data_ptr(), ctypes.byref(geom), E, S, ids.data_ptr() + p0 * esz,
+                                                       int(esz == 8), npairs, top_k, xp, x.stride(0), int(bool(x_per_pair)),
+                                                       y.data_ptr() + p0 * S * out_features * 2, dt, cells.data_ptr(),
+                                                       cells.numel() * 8, stream)
+            if rc:
+                _native.check(rc, "aqlm routed packed gemv")
+    return y
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-grouped 1x16 GEMM (mixture-of-experts prefill / training; aqlm_hip_moe_bucket + aqlm_hip_gemm_1x16_grouped)
 # ------------------------------------------------------------------------------------------------------
 def grouped_tile_pairs(num_pairs: int, num_experts: int) -> int:
@@ -1590,6 +1725,11 @@ def _fake_moe(input, expert_ids, table, geometry, x_per_pair):
 _LIB.define("code1x16_moe_matmat(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
 _LIB.impl("code1x16_moe_matmat", code1x16_moe_matmat, "CUDA")
 torch.library.register_fake("aqlm::code1x16_moe_matmat")(_fake_moe)
+
+
+_LIB.define("code1x16_moe_matmat_packed(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
+_LIB.impl("code1x16_moe_matmat_packed", code1x16_moe_matmat_packed, "CUDA")
+torch.library.register_fake("aqlm::code1x16_moe_matmat_packed")(_fake_moe)
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

@@ -12,6 +12,9 @@ Forward, same signature and semantics as ``MixtralExperts.forward``:
   * MI355X, 1x16 g8 / g16, T * top_k <= 64 (decode): two launches of the expert-routed matvec (``aqlm::code1x16_moe_matmat``:
     w1 and w3 together, then w2 on the pair rows), the activation in between and an fp32 weighted sum on the device.  The expert
     ids never reach the host: no synchronisation, and the step can be captured in a hipGraph;
+  * the same on PREPACKED experts (``prepack_experts``, opt-in: 4.8 more resident bits per expert weight), for up to
+    ``ROUTED_PACKED_MAX_PAIRS`` pairs: the two launches run the packed matvec (``aqlm::code1x16_moe_matmat_packed``, codebook slices
+    in LDS) instead of the direct one; same glue, no synchronisation, capturable;
   * MI355X, 1x16 g8 / g16, more pairs (prefill, batched decode) or a gradient needed (any T): the expert-grouped GEMM
     (``aqlm::moe_bucket`` groups the pairs by expert on the device, then ``aqlm::code1x16_moe_matmat_grouped`` runs the w1|w3 and the
     w2 launch on grids fixed by the shapes).  No synchronisation either: prefill steps can be captured in a hipGraph too.  Under
@@ -37,7 +40,7 @@ import contextlib
 import torch
 import torch.nn as nn
 
-from .derived import tensor_version
+from .derived import codes_fingerprint, tensor_version
 from .inference import GEMV_MAX_ROWS, QuantizedLinear, _get_autograd_matmul_op
 from .inference_kernels.kernel_selector import get_backward_pass_kernel, get_forward_pass_kernel
 
@@ -50,6 +53,13 @@ MAX_GROUPED_PAIRS = 1 << 18
 # grouped launches took 1.14x the loop's time, at 512 pairs 1.04x (profiles/moe_grouped.json).  Captures (the loop syncs with the
 # host) and calls that need a gradient take the grouped launches at any size.
 GROUPED_EAGER_MAX_PAIRS = 768
+# (token, expert) pairs up to which a prepacked block (``prepack_experts``) takes the routed PACKED launches; beyond it the routes above
+# apply unchanged.  A measured constant: the largest pair count, among T in {1, 2, 4, 8, 16, 32} at top_k 2, up to which the captured
+# prepacked block replayed faster than both the captured direct-routed block and the eager per-expert loop in the same call of
+# tools/moe_benchmark.py on the Mixtral-8x7B block shape (table, spread and command: profiles/moe_block_packed.json).
+# Measured: the prepacked block won at every T (85.8 against 223.5 us captured at T = 1, 1328 against 1942 us at T = 32), so the
+# constant is the launch's own limit of 64 pairs.
+ROUTED_PACKED_MAX_PAIRS = 64
 
 
 class _Expert(nn.Module):
@@ -85,6 +95,9 @@ class QuantizedMixtralExperts(nn.Module):
             self.add_module(str(e), _Expert(self.hidden_dim, self.intermediate_dim, scheme, device=device, dtype=dtype))
         self._tables = None  # (key, table w1|w3, table w2): device pointer tables of the routed launches (derived, never saved)
         self._grouped_shapes = None  # whether the grouped kernel takes both projections' shapes (a host query, asked once)
+        self._prepack = None  # options of prepack_experts() once it ran on this block (None: the experts are not prepacked)
+        self._packed_tables = None  # (key, (table, geometry tail) w1|w3, the same for w2) or (key, None): the launch declined
+        self._packed_calls = 0  # eager routed-packed forwards, for the periodic checksum of the parameters behind the packed copies
 
     def expert(self, e: int) -> _Expert:
         return self._modules[str(e)]
@@ -97,10 +110,15 @@ class QuantizedMixtralExperts(nn.Module):
     def __getstate__(self):
         state = dict(self.__dict__)
         state["_tables"] = None
+        state["_packed_tables"] = None
         return state
 
     # ------------------------------------------------------------------------------------------------------------------
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+        if self._prepack is not None and self.takes_routed_path(hidden_states, top_k_index):
+            tables = self._routed_packed_tables_for(hidden_states, top_k_index)
+            if tables is not None:
+                return self._forward_routed_packed(hidden_states, top_k_index, top_k_weights, tables)
         if self.takes_routed_path(hidden_states, top_k_index):
             return self._forward_routed(hidden_states, top_k_index, top_k_weights)
         if self.takes_grouped_path(hidden_states, top_k_index):
@@ -155,6 +173,102 @@ class QuantizedMixtralExperts(nn.Module):
             self._tables = (key, hip_kernel.routed_table(layers13, device), hip_kernel.routed_table(layers2, device))
         return self._tables[1], self._tables[2]
 
+    # -------------------------------------------------------------------------------------------- prepacked experts
+    def _expert_layers(self):
+        return [getattr(self.expert(e), name) for e in range(self.num_experts) for name in _SEGMENTS_13 + ("w2",)]
+
+    def _packed_layers(self, segments):
+        return [[(getattr(self.expert(e), s)._packed_codes, getattr(self.expert(e), s).codebooks, getattr(self.expert(e), s).scales,
+                  getattr(self.expert(e), s).bias) for s in segments] for e in range(self.num_experts)]
+
+    def _repack_stale_experts(self) -> None:
+        """Bring the packed copy of every expert layer in step with its ``codes`` (written in place, rebound, or forgotten by
+        ``invalidate_derived_state()``).  Repacks synchronise: never while a hipGraph is being captured."""
+        for lin in self._expert_layers():
+            if lin._packed_codes is None or codes_fingerprint(lin.codes) != lin._packed_fingerprint:
+                _prepack_layer(lin, **self._prepack)
+
+    def _packed_key(self, device):
+        return (device, tuple((codes_fingerprint(lin.codes), id(lin._packed_codes), lin._packed_fingerprint,
+                               lin.codebooks.data_ptr(), tensor_version(lin.codebooks), lin.scales.data_ptr(), tensor_version(lin.scales),
+                               0 if lin.bias is None else lin.bias.data_ptr(), 0 if lin.bias is None else tensor_version(lin.bias))
+                              for lin in self._expert_layers()))
+
+    def routed_packed_tables(self, device: torch.device):
+        """The device tables (+ launch geometry) of the two routed packed launches, or None when this call keeps today's route.
+        The packed buffers are derived from ``codes``, the tables bake in every buffer's address, the codebook range and -- for a
+        relabelled buffer -- its codebook image, so they are keyed on identity and version of codes, codebooks, scales and biases
+        and on the packed buffers themselves.  Anything out of step is rebuilt (repack, range, image, table) on an eager call;
+        inside a hipGraph capture nothing can be rebuilt, and the call takes the routed launch on the canonical codes."""
+        from .inference_kernels import hip_kernel
+
+        cached = self._packed_tables
+        if cached is not None and cached[0] == self._packed_key(device):
+            if cached[1] is None or all(lin._packed_codes.range_is_current(lin.codebooks) for lin in self._expert_layers()):
+                return cached[1]
+        if torch.cuda.is_current_stream_capturing():
+            return None  # stale and not rebuildable here: today's route reads the live tensors
+        self._repack_stale_experts()
+        if any(lin._packed_codes is None for lin in self._expert_layers()):
+            tables = None  # a layer below min_codes, or one the packed format does not take
+        else:
+            try:
+                tables = (hip_kernel.routed_packed_table(self._packed_layers(_SEGMENTS_13), device),
+                          hip_kernel.routed_packed_table(self._packed_layers(("w2",)), device))
+            except NotImplementedError:
+                tables = None  # the launch declines the block (compact entries, no codebook range, a shape it refuses)
+        for lin in self._expert_layers():  # the checksums the periodic check compares belong to the state that now exists
+            if lin._packed_codes is not None:
+                lin._record_derived_checks()
+        self._packed_tables = (self._packed_key(device), tables)
+        return tables
+
+    def served_by_routed_packed(self) -> bool:
+        """Whether the routed packed launch takes this block as it is now (prepacked, every layer packed, launch not declined)."""
+        if self._prepack is None or not self.expert(0).w1.codebooks.is_cuda:
+            return False
+        return self.routed_packed_tables(self.expert(0).w1.codebooks.device) is not None
+
+    def _routed_packed_tables_for(self, hidden_states, top_k_index):
+        """The tables when this call takes the routed packed launches (``takes_routed_packed_route``), else None."""
+        if top_k_index.numel() > ROUTED_PACKED_MAX_PAIRS:
+            return None
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self._verify_some_expert()
+        tables = self.routed_packed_tables(hidden_states.device)
+        if not takes_routed_packed_route(True, _needs_grad(hidden_states), top_k_index.numel(), tables is not None):
+            return None
+        return tables
+
+    def _verify_some_expert(self) -> None:
+        """Writes through ``.data`` change neither identity nor version: like every owner of derived state, the block re-takes the
+        checksums of its layers now and then (inference.DERIVED_CHECK_EVERY eager forwards for a full round, one layer at a time so
+        that no step pays for all of them).  Synchronises; never during capture."""
+        from . import inference
+
+        every = inference.DERIVED_CHECK_EVERY
+        if not every:
+            return
+        self._packed_calls += 1
+        layers = self._expert_layers()
+        step = max(1, every // len(layers))
+        if self._packed_calls % step == 0:
+            layers[(self._packed_calls // step) % len(layers)].verify_derived_state()
+
+    def _forward_routed_packed(self, hidden_states, top_k_index, top_k_weights, tables):
+        T, H = hidden_states.shape
+        k = top_k_index.shape[1]
+        w = self.expert(0).w1
+        (tab13, tail13), (tab2, tail2) = tables
+        ops = torch.ops.aqlm
+        gu = ops.code1x16_moe_matmat_packed(hidden_states, top_k_index, tab13,
+                                            [self.num_experts, 2, self.intermediate_dim, H, w.in_group_size, k] + tail13, False)
+        h = self.act_fn(gu[:, 0]) * gu[:, 1]  # [T * k, I]
+        y = ops.code1x16_moe_matmat_packed(h, top_k_index, tab2,
+                                           [self.num_experts, 1, H, self.intermediate_dim, w.in_group_size, k] + tail2, True)
+        return (y.view(T, k, H).float() * top_k_weights.float().unsqueeze(-1)).sum(dim=1).to(hidden_states.dtype)
+
     def _forward_routed(self, hidden_states, top_k_index, top_k_weights):
         T, H = hidden_states.shape
         k = top_k_index.shape[1]
@@ -199,6 +313,13 @@ class QuantizedMixtralExperts(nn.Module):
             y = _apply(ex.w2, h)
             out.index_add_(0, tok, y.float() * top_k_weights[tok, pos, None].float())
         return out.to(hidden_states.dtype)
+
+
+def takes_routed_packed_route(prepacked: bool, grad_needed: bool, pairs: int, supported: bool) -> bool:
+    """The route predicate of the routed packed launches, a pure function: the block is prepacked, no gradient is needed, there
+    are 1..ROUTED_PACKED_MAX_PAIRS (token, expert) pairs, and the launch takes the block's packed buffers.  (Device, scheme and
+    dtype are the routed path's own conditions, ``takes_routed_path``.)"""
+    return bool(prepacked and not grad_needed and 0 < pairs <= min(ROUTED_PACKED_MAX_PAIRS, MAX_ROUTED_PAIRS) and supported)
 
 
 def _needs_grad(x: torch.Tensor) -> bool:
@@ -267,6 +388,82 @@ def _apply(lin: QuantizedLinear, x: torch.Tensor) -> torch.Tensor:
     if fn is None:
         fn = _AUTOGRAD_OPS[key] = _get_autograd_matmul_op(op, get_backward_pass_kernel(cb, training))
     return fn.apply(x, lin.codes, cb, lin.scales, lin.bias)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# prepacked experts
+# ----------------------------------------------------------------------------------------------------------------------
+def _prepack_layer(lin: QuantizedLinear, min_codes: int, relabel: bool) -> bool:
+    """The packed copy of one expert layer, next to its canonical codes (the grouped GEMM and backward read those).  Uniform
+    geometry always: the routed packed launch does not instantiate the variable-geometry kernel."""
+    from .inference_kernels import hip_kernel
+
+    lin._packed_codes = None
+    lin._fast = None
+    codes = lin.out_features * (lin.in_features // lin.in_group_size)
+    if (min_codes and codes >= min_codes and (lin.num_codebooks, lin.nbits_per_codebook, lin.out_group_size) == (1, 16, 1)
+            and lin.in_group_size in (8, 16) and lin.codes.is_cuda and lin.codebooks.dtype in (torch.float16, torch.bfloat16)):
+        lin._packed_codes = hip_kernel.prepack_1x16(lin.codes, lin.in_group_size, codebooks=lin.codebooks, relabel=relabel,
+                                                    uniform_only=True)
+        lin._packed_fingerprint = codes_fingerprint(lin.codes)
+    if lin._packed_codes is not None:
+        lin._derived_checks = None
+        lin._record_derived_checks()
+    return lin._packed_codes is not None
+
+
+def prepack_experts(model_or_block: nn.Module, min_codes=None, thorough: bool = False, relabel: bool = False) -> dict:
+    """Prepack w1, w3 and w2 of every ``QuantizedMixtralExperts`` under ``model_or_block`` (GPU-resident, 1x16 g8 / g16 layers of at
+    least ``min_codes`` codes; default ``inference.PREPACK_MIN_CODES``) so that decode steps of up to ``ROUTED_PACKED_MAX_PAIRS``
+    pairs run the routed PACKED launches.  Strictly opt-in: ``checkpoint.prepack_model`` keeps leaving experts alone.
+
+    The canonical codes are KEPT (the expert-grouped GEMM of prefill and the backward read them), so the price is the packed
+    copy on top: 4.8 resident bits per expert weight in addition to the 2.0 of the codes.  Mixtral-8x7B has
+    32 x 8 x 3 x 14336 x 4096 = 45.1 G expert weights: about 27 GB more.
+
+    ``thorough`` as in ``prepack_model`` (local search of the entry order on every layer).  ``relabel=False`` (default) keeps the
+    checkpoint's codebook labels, so the kernels read the live codebook tensor and a codebook rewritten through ``.data`` is picked
+    up by the very next forward; ``relabel=True`` deals the codebook entries to the slices by use (faster on checkpoints whose
+    label use is skewed) at the price of a derived codebook image, which follows a ``.data`` write only at the next periodic
+    checksum or after ``invalidate_derived_state()``.  Variable-geometry buffers are never built here (the routed packed launch
+    declines them).
+
+    Returns ``{"blocks", "layers_packed", "layers_skipped", "packed_bytes", "blocks_served", "blocks_fallback",
+    "prepack_seconds"}``: ``blocks_fallback`` blocks keep today's routes (a layer below ``min_codes`` or refused by the packed
+    format, or a table the launch declines)."""
+    import time
+
+    from . import _native, inference
+
+    blocks = [m for m in model_or_block.modules() if isinstance(m, QuantizedMixtralExperts)]
+    min_codes = inference.PREPACK_MIN_CODES if min_codes is None else int(min_codes)
+    old_arr = _native.get_tuning("packed_arrange")
+    if thorough:
+        _native.set_tuning("packed_arrange", 3)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rep = {"blocks": len(blocks), "layers_packed": 0, "layers_skipped": 0, "packed_bytes": 0, "blocks_served": 0, "blocks_fallback": 0}
+    try:
+        for block in blocks:
+            if not block.expert(0).w1.codes.is_cuda:
+                raise NotImplementedError("prepack_experts needs the experts on an MI355X (`model.to('cuda')` first)")
+            block._prepack = {"min_codes": min_codes, "relabel": bool(relabel)}
+            block._packed_tables = None
+            for lin in block._expert_layers():
+                if _prepack_layer(lin, **block._prepack):
+                    rep["layers_packed"] += 1
+                    rep["packed_bytes"] += lin._packed_codes.numel()
+                else:
+                    rep["layers_skipped"] += 1
+            served = block.served_by_routed_packed()
+            rep["blocks_served" if served else "blocks_fallback"] += 1
+    finally:
+        _native.set_tuning("packed_arrange", old_arr)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    rep["prepack_seconds"] = time.perf_counter() - t0
+    return rep
 
 
 # ----------------------------------------------------------------------------------------------------------------------

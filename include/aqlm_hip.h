@@ -405,6 +405,64 @@ int aqlm_hip_gemv_1x16_packed_multi_cells(const aqlm_hip_segment* segments, cons
                                           int dtype, void* cells, size_t cells_bytes, void* stream);
 
 /*
+ * aqlm_hip_gemv_1x16_routed on PREPACKED experts (Mixtral decode on the packed matvec): every (token, expert) pair of one or two
+ * projections in one launch of 256 x num_segments x num_experts workgroups, each pair as its own batch-1 pass of
+ * aqlm_hip_gemv_1x16_packed on its expert's packed buffer.  `table` is a DEVICE array of num_experts * num_segments
+ * aqlm_hip_routed_packed_entry, entry [e * num_segments + s]; an entry is filled ON THE HOST by
+ * aqlm_hip_routed_packed_entry_fill from the layer's descriptor, packed buffer (device address), codebook, scales and bias, so
+ * that callers never derive offsets inside a packed buffer (a relabelled buffer's entry points at the codebook image inside the
+ * buffer: aqlm_hip_packed_set_codebook first, and fill again whenever the codebook or its range changes -- the entry bakes
+ * codebook_absmax in).  aqlm_hip_gemv_1x16_routed_packed_geometry checks the descriptors of one table (all of one shape, g8 or
+ * g16) and returns the launch-wide values -- the largest wave count, the LDS image -- as a HOST struct the launch takes;
+ * ..._supported is the same check as a yes / no.  AQLM_HIP_E_UNSUPPORTED (the caller keeps aqlm_hip_gemv_1x16_routed for the whole
+ * block) for 3-byte entries, variable-geometry buffers (AQLM_HIP_PACKED_VARGEOM), descriptors without a codebook range, and
+ * shapes the packed format refuses.
+ *
+ * expert_ids, x, x_row_stride, x_per_pair, top_k and y as for aqlm_hip_gemv_1x16_routed:
+ *     y[(p * num_segments + s) * out_features + o] = (W[e_p, s] x_row(p))[o] * scales[o] + bias[o]
+ * bit-identical to aqlm_hip_gemv_1x16_packed (batch 1) of that expert on that row, whatever the other pairs are and however
+ * many there are.  Ids are only ever compared for equality with an expert index: a pair whose id lies outside
+ * [0, num_experts) gets a zero row; duplicates, one expert for every pair and garbage are safe.  The grid depends on the shapes
+ * only: a captured launch stays valid when the routing changes; a workgroup whose expert has no pair exits at once, an expert
+ * with several pairs takes them one after the other.  `cells`: caller-owned accumulator cells [num_pairs][num_segments]
+ * [out_features] u64, 8-byte aligned, ZERO at rest and zero again after the launch whatever the routing was (one set per stream).
+ * x rows 16-byte aligned (x_row_stride % 8 == 0).  num_pairs <= AQLM_HIP_MAX_ROUTED_PAIRS.  Stream-ordered, no allocation, no
+ * synchronisation.  aqlm_hip_gemv_1x16_routed_packed_lds_bytes: the dynamic LDS of a launch on that shape (0: shape refused).
+ */
+typedef struct aqlm_hip_routed_packed_entry {
+  const void* entries;    /* entry stream of the packed buffer */
+  const void* wave_info;
+  const void* row_starts;
+  const void* codebook;   /* [65536][in_group_size], or the permuted image inside a relabelled buffer */
+  const void* scales;     /* [out_features] */
+  const void* bias;       /* [out_features] or NULL */
+  int32_t out_features, rows_per_group, waves, steps, x_copies;
+  uint32_t entry_stream_bytes;
+  float codebook_absmax;
+  int32_t reserved;
+} aqlm_hip_routed_packed_entry;
+
+typedef struct aqlm_hip_routed_packed_geometry {
+  int32_t out_features, in_features, in_group_size;
+  int32_t rows_per_group; /* of every entry (uniform geometry) */
+  int32_t max_waves;      /* workgroup size of the launch / 64 */
+  int32_t slice_first;    /* LDS map of the launch: 1 = slice in front (row tables that do not fit behind the x window) */
+  uint32_t lds_bytes;
+  int32_t reserved;
+} aqlm_hip_routed_packed_geometry;
+
+size_t aqlm_hip_gemv_1x16_routed_packed_lds_bytes(int out_features, int in_features, int in_group_size);
+int aqlm_hip_routed_packed_entry_fill(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                      const void* scales, const void* bias, aqlm_hip_routed_packed_entry* entry);
+int aqlm_hip_gemv_1x16_routed_packed_geometry(const aqlm_hip_packed_desc* const* descs, int n,
+                                              aqlm_hip_routed_packed_geometry* geom);
+int aqlm_hip_gemv_1x16_routed_packed_supported(const aqlm_hip_packed_desc* const* descs, int n);
+int aqlm_hip_gemv_1x16_routed_packed(const aqlm_hip_routed_packed_entry* table, const aqlm_hip_routed_packed_geometry* geom,
+                                     int num_experts, int num_segments, const void* expert_ids, int ids_int64, int num_pairs,
+                                     int top_k, const void* x, long x_row_stride, int x_per_pair, void* y, int dtype,
+                                     void* cells, size_t cells_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the

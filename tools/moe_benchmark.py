@@ -14,7 +14,15 @@ T up to 512; eager calls of the old and the new route alternate within one proce
 grouped_graph_us (captured and replayed) and one forward + backward row at the largest T for the grouped path and the
 differentiable loop.  Writes --out (default profiles/moe_grouped.json).
 
+--only packed: the routed PACKED launches on a block prepacked with aqlm_amd.moe.prepack_experts (routed_packed_eager_us,
+routed_packed_graph_us) next to today's routes measured in the same call -- the captured direct-routed block (routed_graph_us, on a
+second, not prepacked block of the same weights) and the eager per-expert loop (loop_eager_us) -- their calls alternating, --repeats
+times over.  The route is forced for every T (ROUTED_PACKED_MAX_PAIRS is what this run measures): the largest pair count up to which
+the captured prepacked block beat both other routes by more than the spread of the direct-routed figure goes into the output as
+"routed_packed_max_pairs", beside ESTIMATE["packed_t1_us"].  Writes --out (default profiles/moe_block_packed.json).
+
     python tools/moe_benchmark.py [--only graph] [--tokens 1,2,4,8,16]
+    python tools/moe_benchmark.py --only packed [--tokens 1,2,4,8,16,32] [--repeats 3]
     python tools/moe_benchmark.py --grouped [--tokens 1,2,4,8,16,32,40,64,128,256,512]
 """
 import argparse
@@ -166,11 +174,62 @@ def grouped_main(args):
     print(json.dumps(result))
 
 
+def packed_main(args):
+    import aqlm_amd.moe as moe
+
+    dev = torch.device("cuda:0")
+    q, _ = build(dev, False)
+    qp, _ = build(dev, False)  # same seed: the same weights, prepacked
+    report = moe.prepack_experts(qp)
+    moe.ROUTED_PACKED_MAX_PAIRS = moe.MAX_ROUTED_PAIRS  # measure the route at every T; the constant is this run's result
+    gen = torch.Generator(device=dev).manual_seed(1)
+    names = ["routed_graph_us", "routed_packed_graph_us", "loop_eager_us", "routed_packed_eager_us"]
+    rows = []
+    with torch.no_grad():
+        for T in [int(t) for t in args.tokens.split(",")]:
+            x = torch.randn((T, H), generator=gen, device=dev).half()
+            logits = torch.randn((T, E), generator=gen, device=dev)
+            w, ids = torch.topk(torch.softmax(logits, -1), K, dim=-1)
+            w = w / w.sum(-1, keepdim=True)
+            assert qp._routed_packed_tables_for(x, ids) is not None, "the prepacked block does not take the routed packed launches"
+            g_direct, g_packed = captured(lambda: q(x, ids, w)), captured(lambda: qp(x, ids, w))
+            fns = [g_direct.replay, g_packed.replay, lambda: loop_forward(q, x, ids, w), lambda: qp(x, ids, w)]
+            runs = [timed_alternating(fns, args.iters, args.warmup) for _ in range(args.repeats)]
+            row = {"tokens": T, "pairs": T * K, "experts_hit": len(set(ids.view(-1).tolist()))}
+            for i, name in enumerate(names):
+                vals = sorted(r[i] for r in runs)
+                row[name] = vals[len(vals) // 2]
+                row[name.replace("_us", "_runs_us")] = [r[i] for r in runs]
+            row["routed_graph_spread_us"] = round(max(r[0] for r in runs) - min(r[0] for r in runs), 2)
+            row["packed_wins"] = bool(max(r[1] for r in runs) < min(r[0] for r in runs) - row["routed_graph_spread_us"]
+                                      and max(r[1] for r in runs) < min(r[2] for r in runs))
+            del g_direct, g_packed
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    best = 0
+    for row in rows:  # the largest pair count UP TO which the prepacked block wins
+        if not row["packed_wins"]:
+            break
+        best = row["pairs"]
+    result = {"block": {"hidden": H, "intermediate": I, "experts": E, "top_k": K, "scheme": "1x16g8", "dtype": "float16"},
+              "device": torch.cuda.get_device_name(dev), "iters": args.iters, "repeats": args.repeats, "estimate": ESTIMATE,
+              "prepack_experts": report, "rows": rows, "routed_packed_max_pairs": best,
+              "rule": "packed_wins: every repeat of routed_packed_graph_us below the smallest routed_graph_us minus its spread over "
+                      "the repeats, and below every loop_eager_us; routed_packed_max_pairs: the largest pairs up to which all rows win",
+              "command": f"python tools/moe_benchmark.py --only packed --tokens {args.tokens} --iters {args.iters} --repeats {args.repeats}"}
+    out = args.out or os.path.join("profiles", "moe_block_packed.json")
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default=None)
     ap.add_argument("--grouped", action="store_true")
-    ap.add_argument("--only", choices=["routed", "graph", "loop", "dense"], default=None)
+    ap.add_argument("--only", choices=["routed", "graph", "loop", "dense", "packed"], default=None)
+    ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -178,6 +237,9 @@ def main():
     if args.grouped:
         args.tokens = args.tokens or "1,2,4,8,16,32,40,64,128,256,512"
         return grouped_main(args)
+    if args.only == "packed":
+        args.tokens = args.tokens or "1,2,4,8,16,32"
+        return packed_main(args)
     args.tokens = args.tokens or "1,2,4,8,16"
     args.out = args.out or os.path.join("profiles", "moe_block.json")
     dev = torch.device("cuda:0")
