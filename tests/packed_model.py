@@ -117,6 +117,16 @@ def rowblock_codes(M, in_groups, p, seed):
     return np.where(rng.random((M, in_groups)) < p, own, uni).astype(np.int64)
 
 
+def zipf_codes(fout, in_groups, alpha, sorted_labels, seed):
+    """Codes as k-means + beam search leave them (src/aq.py:286-356 of the reference: not uniform): entry of rank r is used
+    with probability ~ (r + 1)^-alpha; labels sorted by frequency, or shuffled."""
+    rng = np.random.default_rng(seed)
+    p = np.arange(1, 65537, dtype=np.float64) ** (-alpha)
+    p /= p.sum()
+    labels = np.arange(65536) if sorted_labels else rng.permutation(65536)
+    return labels[rng.choice(65536, size=(fout, in_groups), p=p)].astype(np.int64)
+
+
 def plan_labels(codes_unsigned):
     """The repack's decision about the labels, as aqlm_hip_prepack_1x16 takes it: balanced layout -> the checkpoint's labels (None);
     else the forced deal, kept only if the longest stream then runs fewer wave-steps."""

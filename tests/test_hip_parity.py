@@ -14,6 +14,7 @@ import pytest
 
 from oracle import aqlm_oracle as orc
 from oracle import c_oracle
+from tests.packed_model import zipf_codes  # skewed codes: one source for this suite and the MoE suites
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -808,16 +809,6 @@ def test_prepack_local_search_lowers_bank_conflicts(hk):
     print(f"LDS cycles per service group and read: greedy {cycles[2]:.3f}, greedy + local search {cycles[1]:.3f}")
     assert cycles[2] < 2.1 and cycles[1] < 0.86 * cycles[2], cycles
 
-
-
-def zipf_codes(fout, in_groups, alpha, sorted_labels, seed):
-    """Codes as k-means + beam search leave them (src/aq.py:286-356 of the reference: not uniform): entry of rank r is used
-    with probability ~ (r + 1)^-alpha; labels sorted by frequency, or shuffled."""
-    rng = np.random.default_rng(seed)
-    p = np.arange(1, 65537, dtype=np.float64) ** (-alpha)
-    p /= p.sum()
-    labels = np.arange(65536) if sorted_labels else rng.permutation(65536)
-    return labels[rng.choice(65536, size=(fout, in_groups), p=p)].astype(np.int64)
 
 
 @pytest.mark.parametrize("alpha,sorted_labels", [(0.8, False), (0.8, True), (1.2, False), (1.2, True)])

@@ -103,6 +103,52 @@ def test_routed_op_matches_oracle_and_direct_kernel(g, dtype, shape):
     torch.cuda.synchronize()
 
 
+OFF_TRACK_SHAPES = [("w13", 2, 1024, 808, False), ("w2", 1, 2048, 512, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("top_k", [1, 4, 8])
+@pytest.mark.parametrize("num_experts", [1, 3, 60])
+def test_routed_op_with_other_expert_counts_top_k_bias_and_strided_x(num_experts, top_k, dtype):
+    """Off the 8 experts / top-2 / no bias track of the test above: 1, 3 and 60 experts (ids E - 1, E and -1 present), top_k
+    1 / 4 / 8 up to exactly 64 pairs, a bias per expert and projection, x rows taken from a wider tensor.  Same bounds, same
+    bit-identity partner (aqlm_hip_gemv_1x16 of that expert on that row)."""
+    from aqlm_amd.inference_kernels import hip_kernel as hk
+    from tests import moe_experts as mx
+
+    dev, g, n = torch.device("cuda:0"), 8, num_experts
+    gen = torch.Generator(device=dev).manual_seed(9)
+    for name, S, fin, fout, per_pair in OFF_TRACK_SHAPES:
+        layers = mx.plain_experts(n, 400 + n, S, fin, fout, g, dtype, dev, bias=True)
+        table = hk.routed_table(layers, dev)
+        w64 = {}
+        for T in (64 // top_k, 3):
+            for ids_dtype in (torch.int64, torch.int32):
+                ids = mx.router_ids(T, top_k, n, gen, dev, ids_dtype)
+                flat = ids.view(-1)
+                flat[0] = n - 1
+                if flat.numel() > 2:
+                    flat[1], flat[2] = n, -1
+                x = mx.strided_rows(T * top_k if per_pair else T, fin, gen, dev, dtype)
+                y = torch.ops.aqlm.code1x16_moe_matmat(x, ids, table, [n, S, fout, fin, g, top_k], per_pair)
+                assert tuple(y.shape) == (T * top_k, S, fout)
+                for p, e in enumerate(flat.cpu().tolist()):
+                    xr = x[p if per_pair else p // top_k]
+                    what = f"{name} E{n} k{top_k} {dtype} T{T} {ids_dtype} pair {p} expert {e}"
+                    if not 0 <= e < n:
+                        assert torch.count_nonzero(y[p]) == 0, what
+                        continue
+                    for s in range(S):
+                        codes, cb, sc, bias = layers[e][s]
+                        if (e, s) not in w64:
+                            w64[(e, s)] = _w64(layers[e][s])
+                        _check(y[p, s], w64[(e, s)] @ xr.double() + bias.double(), dtype, f"{what} seg {s}")
+                        ref = hk._gemv(xr.view(1, -1), codes, cb, sc, bias, "1x16")
+                        assert torch.equal(y[p, s].view(1, -1), ref), f"{what} seg {s}: not bit-identical to aqlm_hip_gemv_1x16"
+    torch.cuda.synchronize()
+
+
 def _module(H, I, dtype, dev, seed=0):
     from transformers import MixtralConfig
     from transformers.models.mixtral.modeling_mixtral import MixtralExperts

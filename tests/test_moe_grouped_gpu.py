@@ -137,10 +137,122 @@ def test_out_of_range_ids_give_zero_rows(ids_dtype):
     torch.cuda.synchronize()
 
 
-def _bucket_model(ids, tp):
+# ---------------------------------------------------------------------------------------------------------------------------
+# off the 8 experts / top-2 / no bias track, and the tile edges
+# ---------------------------------------------------------------------------------------------------------------------------
+def _grouped_n(x, ids, table, n, S, fin, fout, g, per_pair):
+    """``_grouped`` for ``n`` experts and the ids' own top_k -> (y, tile_pairs, bucket)"""
+    from aqlm_amd.inference_kernels import hip_kernel as hk
+
+    P, k = ids.numel(), ids.shape[1]
+    tp = hk.grouped_tile_pairs(P, n)
+    bucket = torch.ops.aqlm.moe_bucket(ids, n, tp)
+    return torch.ops.aqlm.code1x16_moe_matmat_grouped(x, bucket, table, [n, S, fout, fin, g, k, tp, P], per_pair), tp, bucket
+
+
+def _check_grouped_n(y, x, ids, layers, per_pair, dtype, what):
+    """Every pair: the fp64 oracle within ``_check``; bit for bit code1x16_matmat_dequant (+ bias) of its expert under
+    gemm_variant = 2, in slabs of at most FUSED_MFMA_MAX_ROWS rows (beyond, that op dequantises and calls the library GEMM); pairs
+    without an expert: zero rows."""
+    from aqlm_amd.inference_kernels import hip_kernel as hk
+
+    n, k = len(layers), ids.shape[1]
+    flat = ids.reshape(-1).long()
+    orphans = (flat < 0) | (flat >= n)
+    assert torch.count_nonzero(y[orphans]) == 0, f"{what}: rows of pairs without an expert must be zero"
+    seen = int(orphans.sum())
+    for e in range(n):
+        pairs = torch.nonzero(flat == e).squeeze(1)
+        if pairs.numel() == 0:
+            continue
+        seen += pairs.numel()
+        xe = x[pairs if per_pair else pairs // k]
+        for s, (codes, cb, sc, bias) in enumerate(layers[e]):
+            y64 = xe.double() @ _w64(layers[e][s]).T
+            if bias is not None:
+                y64 = y64 + bias.double()
+            _check(y[pairs, s], y64, dtype, f"{what} expert {e} seg {s}")
+            with _Variant():
+                for r0 in range(0, pairs.numel(), hk.FUSED_MFMA_MAX_ROWS):
+                    sl = slice(r0, r0 + hk.FUSED_MFMA_MAX_ROWS)
+                    ref = torch.ops.aqlm.code1x16_matmat_dequant(xe[sl].contiguous(), codes, cb, sc, bias)
+                    assert torch.equal(y[pairs[sl], s], ref), f"{what} expert {e} seg {s}: not bit-identical to code1x16_matmat_dequant"
+    assert seen == flat.numel()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("top_k", [1, 4, 8])
+@pytest.mark.parametrize("num_experts", [1, 3, 60])
+def test_grouped_op_with_other_expert_counts_top_k_bias_and_strided_x(num_experts, top_k, dtype):
+    """1, 3 and 60 experts (ids E - 1, E and -1 present), top_k 1 / 4 / 8, a bias per expert and projection, x rows taken from a
+    wider tensor; 99 / 100 / 104 pairs: more than the routed launch takes, none a multiple of 16."""
+    from aqlm_amd.inference_kernels import hip_kernel as hk
+    from tests import moe_experts as mx
+
+    dev, g, n = torch.device("cuda:0"), 8, num_experts
+    gen = torch.Generator(device=dev).manual_seed(23)
+    T = {1: 99, 4: 25, 8: 13}[top_k]
+    assert (T * top_k) % 16 != 0 and T * top_k > 64
+    for name, S, fin, fout, per_pair in OP_SHAPES:
+        layers = mx.plain_experts(n, 500 + n, S, fin, fout, g, dtype, dev, bias=True)
+        table = hk.routed_table(layers, dev)
+        for ids_dtype in (torch.int64, torch.int32):
+            ids = mx.router_ids(T, top_k, n, gen, dev, ids_dtype)
+            ids.view(-1)[:3] = torch.tensor([n - 1, n, -1], dtype=ids_dtype, device=dev)
+            x = mx.strided_rows(T * top_k if per_pair else T, fin, gen, dev, dtype)
+            y, _, _ = _grouped_n(x, ids, table, n, S, fin, fout, g, per_pair)
+            assert tuple(y.shape) == (T * top_k, S, fout)
+            _check_grouped_n(y, x, ids, layers, per_pair, dtype, f"{name} E{n} k{top_k} {dtype} {ids_dtype}")
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("tile_pairs", [16, 32, 64, 128])
+def test_grouped_op_at_the_tile_edges(tile_pairs, dtype):
+    """For every tile size ``grouped_tile_pairs`` returns: an expert that holds exactly one tile of pairs next to one that holds
+    one pair more; every one of 300 pairs on ONE expert (the most tiles an expert can have, within the tile-slot bound
+    ceil(P / tp) + min(E, P)); 65 pairs, the first count the module hands to this kernel.  No count is a multiple of 16."""
+    from aqlm_amd.inference_kernels import hip_kernel as hk
+    from tests import moe_experts as mx
+
+    dev, g, tp = torch.device("cuda:0"), 8, tile_pairs
+    name, S, fin, fout, per_pair = OP_SHAPES[0]
+    all_layers = mx.plain_experts(60, 600, S, fin, fout, g, dtype, dev, bias=True)
+    gen = torch.Generator(device=dev).manual_seed(24)
+
+    def run(n, ids, what):
+        layers = all_layers[:n]
+        P = ids.numel()
+        assert P % 16 != 0 and hk.grouped_tile_pairs(P, n) == tp, (what, P, n, hk.grouped_tile_pairs(P, n))
+        x = torch.randn((P, fin), generator=gen, device=dev).to(dtype)  # top_k = 1: token rows are pair rows
+        y, got_tp, bucket = _grouped_n(x, ids, hk.routed_table(layers, dev), n, S, fin, fout, g, per_pair)
+        counts = torch.bincount(ids.view(-1), minlength=n).tolist()
+        tiles = sum(-(-c // tp) for c in counts)
+        assert got_tp == tp and bucket[:4].tolist() == [tiles, 0, P, 0], (what, bucket[:4].tolist(), tiles)
+        assert tiles <= -(-P // tp) + min(n, P)
+        _check_grouped_n(y, x, ids, layers, per_pair, dtype, f"{what} tp{tp} {dtype}")
+        return tiles
+
+    # exactly one tile on expert 0, one pair more on expert 1, the rest on expert 2
+    P = 3 * tp - 5
+    ids = torch.cat([torch.full((tp,), 0), torch.full((tp + 1,), 1), torch.full((P - 2 * tp - 1,), 2)])
+    ids = ids[torch.randperm(P)].view(P, 1).to(dev)
+    assert run(3, ids, "full tile and full tile + 1") == 4
+    # 300 pairs on the last expert
+    n = {16: 60, 32: 16, 64: 8, 128: 3}[tp]
+    assert run(n, torch.full((300, 1), n - 1, dtype=torch.int64, device=dev), "300 pairs on one expert") == -(-300 // tp)
+    # 65 pairs as routed
+    n = {16: 60, 32: 3, 64: 2, 128: 1}[tp]
+    run(n, mx.router_ids(65, 1, n, gen, dev), "65 pairs")
+    torch.cuda.synchronize()
+
+
+def _bucket_model(ids, tp, num_experts):
     flat = ids.reshape(-1)
-    valid = (flat >= 0) & (flat < E)
-    lists = [np.nonzero(flat == e)[0] for e in range(E)]
+    valid = (flat >= 0) & (flat < num_experts)
+    lists = [np.nonzero(flat == e)[0] for e in range(num_experts)]
     tiles = []
     first = 0
     for e, lst in enumerate(lists):
@@ -157,23 +269,27 @@ def test_bucket_matches_a_numpy_model():
 
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(5)
-    cases = [rng.integers(0, E, size=(T, K)) for T in (33, 40, 100, 300, 700)]
-    cases.append(np.full((50, K), 3))                           # one expert
-    cases.append(rng.integers(-3, E + 3, size=(257, K)))        # out-of-range ids mixed in
-    cases.append(rng.integers(0, E, size=(4096, 4)))            # several scatter rounds
-    for ids in cases:
+    cases = [(E, rng.integers(0, E, size=(T, K))) for T in (33, 40, 100, 300, 700)]
+    cases.append((E, np.full((50, K), 3)))                           # one expert
+    cases.append((E, rng.integers(-3, E + 3, size=(257, K))))        # out-of-range ids mixed in
+    cases.append((E, rng.integers(0, E, size=(4096, 4))))            # several scatter rounds
+    for n in (1, 3, 60, 256):                                        # other expert counts, up to the entry's limit
+        cases += [(n, rng.integers(0, n, size=(T, k))) for T, k in ((33, 2), (300, 1), (130, 8))]
+        cases.append((n, np.full((75, 4), n - 1)))                   # every pair on the last expert
+        cases.append((n, rng.integers(-3, n + 3, size=(257, 2))))    # n and n - 1 both present, negative ids
+    for n, ids in cases:
         P = ids.size
         for tp in (16, 32, 64, 128):
             for dt in (torch.int64, torch.int32):
-                got = torch.ops.aqlm.moe_bucket(torch.from_numpy(ids).to(dev, dt), E, tp).cpu().numpy()
-                tiles, nbad, order = _bucket_model(ids, tp)
-                max_tiles = -(-P // tp) + min(E, P)
-                assert got.size * 4 == hk._lib.aqlm_hip_moe_bucket_bytes(P, E, tp)
-                assert list(got[:4]) == [len(tiles), nbad, P - nbad, 0], (ids.shape, tp)
+                got = torch.ops.aqlm.moe_bucket(torch.from_numpy(ids).to(dev, dt), n, tp).cpu().numpy()
+                tiles, nbad, order = _bucket_model(ids, tp, n)
+                max_tiles = -(-P // tp) + min(n, P)
+                assert got.size * 4 == hk._lib.aqlm_hip_moe_bucket_bytes(P, n, tp)
+                assert list(got[:4]) == [len(tiles), nbad, P - nbad, 0], (n, ids.shape, tp)
                 assert len(tiles) <= max_tiles
                 table = got[4:4 + 4 * max_tiles].reshape(max_tiles, 4)[:len(tiles)]
-                assert [tuple(t[:3]) for t in table] == tiles, (ids.shape, tp)
-                assert np.array_equal(got[4 + 4 * max_tiles:4 + 4 * max_tiles + P], order), (ids.shape, tp)
+                assert [tuple(t[:3]) for t in table] == tiles, (n, ids.shape, tp)
+                assert np.array_equal(got[4 + 4 * max_tiles:4 + 4 * max_tiles + P], order), (n, ids.shape, tp)
 
 
 @pytest.mark.gpu
