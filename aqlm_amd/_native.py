@@ -134,6 +134,8 @@ SIGNATURES = {
     "aqlm_hip_moe_bucket": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
     "aqlm_hip_gemm_1x16_grouped_supported": (_ci, [_ci, _ci, _ci]),
     "aqlm_hip_gemm_1x16_grouped": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "aqlm_hip_gemm_1x16_grouped_transposed_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_gemm_1x16_grouped_transposed": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _vp, _cl, _vp, _ci, _ci, _ci, _ci, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_multi_cells": (_ci, [_segp, _descpp, _ci, _vp, _ci, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_routed_packed_lds_bytes": (_sz, [_ci, _ci, _ci]),

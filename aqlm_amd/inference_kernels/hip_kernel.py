@@ -793,6 +793,39 @@ def code1x16_moe_matmat_grouped(input, bucket, table, geometry, x_per_pair):
     return y
 
 
+def grouped_transposed_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
+    """Whether aqlm_hip_gemm_1x16_grouped_transposed takes a layer of this shape (a host query: decide before a capture)."""
+    return bool(_lib.aqlm_hip_gemm_1x16_grouped_transposed_supported(int(out_features), int(in_features), int(in_group_size)))
+
+
+def code1x16_moe_matmat_grouped_transposed(grad_output, bucket, table, geometry):
+    """The input gradient of ``code1x16_moe_matmat_grouped``: ``grad_output`` [num_pairs, num_segments, out_features] (fp16 / bf16),
+    ``bucket``, ``table`` and ``geometry`` those of the forward call -> fp32 [num_pairs, in_features],
+    gx[p] = sum_s (grad_output[p, s] * scales[e_p, s]) @ Wq[e_p, s]; pairs whose id lies outside [0, num_experts) get zero rows.
+    One launch, W never leaves the chip, no host synchronisation."""
+    E, S, out_features, in_features, g, top_k, tile_pairs, P = (int(v) for v in geometry)
+    dt = _dtype_id(grad_output)
+    if grad_output.dim() != 3 or tuple(grad_output.shape) != (P, S, out_features):
+        raise ValueError(f"grad_output must be [{P}, {S}, {out_features}], got {tuple(grad_output.shape)}")
+    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != grad_output.device:
+        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {grad_output.device}")
+    if bucket.dtype != torch.int32 or bucket.numel() != _bucket_words(P, E, tile_pairs) or bucket.device != grad_output.device:
+        raise ValueError("bucket must come from moe_bucket with the same pairs, experts and tile size")
+    gx = torch.empty((P, in_features), dtype=torch.float32, device=grad_output.device)
+    if P == 0:
+        return gx
+    gy = _c(grad_output)
+    if gy.data_ptr() % 16 != 0:
+        gy = gy.clone()
+    with _device_guard(gy.device):
+        rc = _lib.aqlm_hip_gemm_1x16_grouped_transposed(table.data_ptr(), E, S, bucket.data_ptr(), tile_pairs, P, gy.data_ptr(),
+                                                        gy.stride(0), gx.data_ptr(), out_features, in_features, g, dt,
+                                                        _stream_ptr(gy.device))
+    if rc:
+        _native.check(rc, "aqlm grouped transposed gemm")
+    return gx
+
+
 # Zero-at-rest accumulator cells of the single-kernel look-up-table matvec (aqlm_hip_gemv_8x8_lut_fused): one persistent
 # int64 buffer per (device, stream) -- launches on one stream are ordered, so consecutive layers can share it; every launch
 # leaves it zero.  Never allocated while a hipGraph is being captured (a captured torch.zeros would replay a memset per
@@ -1748,6 +1781,16 @@ torch.library.register_fake("aqlm::moe_bucket")(_fake_bucket)
 _LIB.define("code1x16_moe_matmat_grouped(Tensor input, Tensor bucket, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
 _LIB.impl("code1x16_moe_matmat_grouped", code1x16_moe_matmat_grouped, "CUDA")
 torch.library.register_fake("aqlm::code1x16_moe_matmat_grouped")(_fake_grouped)
+
+
+
+def _fake_grouped_transposed(grad_output, bucket, table, geometry):
+    return grad_output.new_empty((int(geometry[7]), int(geometry[3])), dtype=torch.float32)
+
+
+_LIB.define("code1x16_moe_matmat_grouped_transposed(Tensor grad_output, Tensor bucket, Tensor table, int[] geometry) -> Tensor")
+_LIB.impl("code1x16_moe_matmat_grouped_transposed", code1x16_moe_matmat_grouped_transposed, "CUDA")
+torch.library.register_fake("aqlm::code1x16_moe_matmat_grouped_transposed")(_fake_grouped_transposed)
 
 
 # the prepacked op as a dispatcher op, so that a QuantizedLinear on the packed path traces under torch.compile

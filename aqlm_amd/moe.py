@@ -18,7 +18,9 @@ Forward, same signature and semantics as ``MixtralExperts.forward``:
   * MI355X, 1x16 g8 / g16, more pairs (prefill, batched decode) or a gradient needed (any T): the expert-grouped GEMM
     (``aqlm::moe_bucket`` groups the pairs by expert on the device, then ``aqlm::code1x16_moe_matmat_grouped`` runs the w1|w3 and the
     w2 launch on grids fixed by the shapes).  No synchronisation either: prefill steps can be captured in a hipGraph too.  Under
-    autograd each launch is a ``torch.autograd.Function`` whose backward runs per expert on ``code1x16_matmat_dequant_transposed``;
+    autograd each launch is a ``torch.autograd.Function`` whose backward is ONE launch of the transposed grouped GEMM
+    (``aqlm::code1x16_moe_matmat_grouped_transposed``) on the same bucket: no synchronisation, so a whole training step can be captured
+    (``GROUPED_BACKWARD = False`` or a shape that launch declines: per expert on ``code1x16_matmat_dequant_transposed``, with host syncs);
   * anything else (other schemes, host tensors, shapes the grouped kernel declines): a per-expert loop on the existing ops (host
     syncs allowed), differentiable through the layers' autograd op when a gradient is needed.
 Either way each expert's output is multiplied by its fp32 router weight and the sum over top_k is rounded once to the activation
@@ -60,6 +62,10 @@ GROUPED_EAGER_MAX_PAIRS = 768
 # Measured: the prepacked block won at every T (85.8 against 223.5 us captured at T = 1, 1328 against 1942 us at T = 32), so the
 # constant is the launch's own limit of 64 pairs.
 ROUTED_PACKED_MAX_PAIRS = 64
+# The backward of the grouped launches runs on the device (one transposed grouped launch per projection group, no host
+# synchronisation); False: the per-expert loop on code1x16_matmat_dequant_transposed, as before that launch existed (A/B runs;
+# also the fallback for shapes the launch declines).
+GROUPED_BACKWARD = True
 
 
 class _Expert(nn.Module):
@@ -95,6 +101,7 @@ class QuantizedMixtralExperts(nn.Module):
             self.add_module(str(e), _Expert(self.hidden_dim, self.intermediate_dim, scheme, device=device, dtype=dtype))
         self._tables = None  # (key, table w1|w3, table w2): device pointer tables of the routed launches (derived, never saved)
         self._grouped_shapes = None  # whether the grouped kernel takes both projections' shapes (a host query, asked once)
+        self._grouped_bwd_shapes = {}  # (out, in, g) -> whether the transposed grouped launch (the backward) takes the shape
         self._prepack = None  # options of prepack_experts() once it ran on this block (None: the experts are not prepacked)
         self._packed_tables = None  # (key, (table, geometry tail) w1|w3, the same for w2) or (key, None): the launch declined
         self._packed_calls = 0  # eager routed-packed forwards, for the periodic checksum of the parameters behind the packed copies
@@ -154,6 +161,15 @@ class QuantizedMixtralExperts(nn.Module):
             self._grouped_shapes = (self.num_experts <= hip_kernel._native.MAX_ROUTED_EXPERTS
                                     and hip_kernel.grouped_supported(I, H, g) and hip_kernel.grouped_supported(H, I, g))
         return self._grouped_shapes
+
+    def _grouped_backward_shapes(self, out_features: int, in_features: int, in_group_size: int) -> bool:
+        """Whether the transposed grouped launch takes a projection of this shape (a host query, asked once per shape)."""
+        key = (out_features, in_features, in_group_size)
+        if key not in self._grouped_bwd_shapes:
+            from .inference_kernels import hip_kernel
+
+            self._grouped_bwd_shapes[key] = hip_kernel.grouped_transposed_supported(*key)
+        return self._grouped_bwd_shapes[key]
 
     def _table_tensors(self, segments):
         return [[(getattr(self.expert(e), s).codes, getattr(self.expert(e), s).codebooks, getattr(self.expert(e), s).scales,
@@ -322,28 +338,44 @@ def takes_routed_packed_route(prepacked: bool, grad_needed: bool, pairs: int, su
     return bool(prepacked and not grad_needed and 0 < pairs <= min(ROUTED_PACKED_MAX_PAIRS, MAX_ROUTED_PAIRS) and supported)
 
 
+def takes_grouped_backward(enabled: bool, supported: bool) -> bool:
+    """The route predicate of the device-side grouped backward (``aqlm::code1x16_moe_matmat_grouped_transposed``), a pure function:
+    the route is switched on (``GROUPED_BACKWARD``) and the launch takes the projection's shape.  Pair count and capture state do
+    not enter: the device route serves every size (the per-expert loop cannot be captured at all).  (Device, scheme and dtype are
+    the grouped forward's own conditions, ``takes_grouped_path``: only its calls reach a backward.)"""
+    return bool(enabled and supported)
+
+
 def _needs_grad(x: torch.Tensor) -> bool:
     return torch.is_grad_enabled() and x.requires_grad
 
 
 class _GroupedProjection(torch.autograd.Function):
     """One grouped launch (one or two projections of every pair) with a gradient for its input rows:
-    grad_x[row(p)] += sum_s (grad_y[p, s] * scales_{e_p, s}) @ W_{e_p, s}, per expert on ``code1x16_matmat_dequant_transposed``, summed
-    over pairs and segments in fp32 and rounded once.  Codes, codebooks and scales get none (as in ``QuantizedLinear``)."""
+    grad_x[row(p)] += sum_s (grad_y[p, s] * scales_{e_p, s}) @ W_{e_p, s}, summed over pairs and segments in fp32 and rounded once.
+    ONE launch of ``aqlm::code1x16_moe_matmat_grouped_transposed`` on the forward's bucket (no host synchronisation, capturable; it
+    rounds grad_y * scales once to the storage type, W stays exact), or -- for shapes that launch declines, or with
+    ``GROUPED_BACKWARD`` off -- per expert on ``code1x16_matmat_dequant_transposed`` (host syncs, W * scales rounded instead).
+    Codes, codebooks and scales get none (as in ``QuantizedLinear``)."""
 
     @staticmethod
     def forward(ctx, x, bucket, table, geometry, x_per_pair, experts, segments, top_k_index):
         ctx.experts, ctx.segments, ctx.geometry, ctx.x_per_pair, ctx.rows = experts, segments, geometry, x_per_pair, x.shape[0]
-        ctx.save_for_backward(top_k_index)
+        ctx.save_for_backward(top_k_index, bucket, table)
         return torch.ops.aqlm.code1x16_moe_matmat_grouped(x, bucket, table, geometry, x_per_pair)
 
     @staticmethod
     def backward(ctx, grad_y):
-        (top_k_index,) = ctx.saved_tensors
-        E, S, _, K, _, k = (int(v) for v in ctx.geometry[:6])
+        top_k_index, bucket, table = ctx.saved_tensors
+        E, S, M, K, g, k = (int(v) for v in ctx.geometry[:6])
+        if takes_grouped_backward(GROUPED_BACKWARD, ctx.experts._grouped_backward_shapes(M, K, g)):
+            gx = torch.ops.aqlm.code1x16_moe_matmat_grouped_transposed(grad_y, bucket, table, ctx.geometry)
+            if not ctx.x_per_pair:
+                gx = gx.view(ctx.rows, k, K).sum(dim=1)  # fp32, the token's pairs in ascending order
+            return gx.to(grad_y.dtype), None, None, None, None, None, None, None
         flat = top_k_index.reshape(-1)
         grad_x = torch.zeros((ctx.rows, K), dtype=torch.float32, device=grad_y.device)
-        for e in torch.unique(flat).tolist():  # host syncs are fine in backward
+        for e in torch.unique(flat).tolist():  # host syncs: the fallback only
             if not 0 <= e < E:
                 continue  # zero rows in the forward: no gradient
             pairs = torch.nonzero(flat == e).squeeze(1)

@@ -157,6 +157,32 @@ int aqlm_hip_gemm_1x16_grouped(const aqlm_hip_routed_entry* table, int num_exper
                                void* y, int out_features, int in_features, int in_group_size, int dtype, void* stream);
 
 /*
+ * Input gradient of aqlm_hip_gemm_1x16_grouped: the transposed product, on the bucket and the table of the forward launch.
+ * For every pair p < num_pairs, in fp32:
+ *     gx[p * in_features + i] = sum_s sum_o (gy[p * gy_pair_stride + s * out_features + o] * scales[e_p, s][o]) * Wq[e_p, s][o][i]
+ * Wq is the unscaled dequantised matrix of expert e_p (the expert the bucket lists pair p under), segment s; the bias does
+ * not enter.  Pairs with an id outside [0, num_experts) get zero rows.  gy * scales is formed in fp32 and rounded once to
+ * the storage type (the one rounding this route adds); the products are exact, the sums fp32 in a fixed order (segment, then
+ * output row ascending), so a pair's bits depend on its own gy row and its expert only -- not on the other pairs, the
+ * tile size or the slot.  W is never written to memory: a block owns one tile's pairs x 128 columns over all output rows
+ * and segments, gathers the codebook vectors of 32 rows at a time into LDS and reads them column-major
+ * (ds_read_b64_tr_b16) as an operand of v_mfma_f32_16x16x32.  Grid: ceil(in_features / 128) x the forward's tile slots; no
+ * allocation, no synchronisation, no workspace: a captured launch stays valid when the routing changes.  gy and gx 16-byte
+ * aligned, gy_pair_stride (in elements) a multiple of 8 and >= num_segments * out_features.  AQLM_HIP_E_UNSUPPORTED outside
+ * aqlm_hip_gemm_1x16_grouped_transposed_supported (out_features % 16 == 0, in_features % 16 == 0, in_group_size 8 / 16): the
+ * caller runs those per expert on the dequantise + matmul ops.
+ *
+ * Replaces: the dequantise + matmul of cuda_kernel.cpp's *_transposed functions (code1x16_matmat_dequant_transposed,
+ *           cuda_kernel.cpp:303 ff.: input * scales rounded to the storage type, Code1x16Dequant into a whole weight matrix
+ *           in memory, then a library matmul), which a mixture-of-experts backward would run once per expert and projection.
+ */
+int aqlm_hip_gemm_1x16_grouped_transposed_supported(int out_features, int in_features, int in_group_size);
+int aqlm_hip_gemm_1x16_grouped_transposed(const aqlm_hip_routed_entry* table, int num_experts, int num_segments,
+                                          const void* bucket, int tile_pairs, int num_pairs, const void* gy, long gy_pair_stride,
+                                          void* gx, int out_features, int in_features, int in_group_size, int dtype,
+                                          void* stream);
+
+/*
  * Same contract for K x 8-bit schemes (256-entry codebooks held in LDS): num_codebooks in 1..16, any
  * in_group_size that is a multiple of 8 (tuned instances: 1x8 g8, 2x8 g8, 8x8 g32; other shapes run a generic kernel).
  *

@@ -21,9 +21,18 @@ times over.  The route is forced for every T (ROUTED_PACKED_MAX_PAIRS is what th
 the captured prepacked block beat both other routes by more than the spread of the direct-routed figure goes into the output as
 "routed_packed_max_pairs", beside ESTIMATE["packed_t1_us"].  Writes --out (default profiles/moe_block_packed.json).
 
+--backward: forward + backward of the block (x and top_k_weights requiring grad, a random grad-output) at T in {8, 32, 128, 512}:
+the device backward (one transposed grouped launch per projection group, aqlm_hip_gemm_1x16_grouped_transposed) eager and captured
+with the forward in one hipGraph, against the per-expert loop backward (aqlm_amd.moe.GROUPED_BACKWARD = False, eager: the behaviour
+before that launch existed).  The three alternate within one process over --repeats rounds of --iters steps, each step on the next
+of three input sets that route differently; median of the rounds' medians and the spread (max - min) over the rounds.  Also the
+peak-memory delta of one step (torch.cuda.max_memory_allocated over the memory allocated before it).  Writes --out (default
+profiles/moe_grouped_backward.json).
+
     python tools/moe_benchmark.py [--only graph] [--tokens 1,2,4,8,16]
     python tools/moe_benchmark.py --only packed [--tokens 1,2,4,8,16,32] [--repeats 3]
     python tools/moe_benchmark.py --grouped [--tokens 1,2,4,8,16,32,40,64,128,256,512]
+    python tools/moe_benchmark.py --backward [--tokens 8,32,128,512] [--iters 30] [--repeats 3]
 """
 import argparse
 import json
@@ -174,6 +183,95 @@ def grouped_main(args):
     print(json.dumps(result))
 
 
+def backward_main(args):
+    import aqlm_amd.moe as moe
+
+    dev = torch.device("cuda:0")
+    q, _ = build(dev, False)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    SETS = 3
+    rows = []
+    for T in [int(t) for t in args.tokens.split(",")]:
+        sets = []
+        for _ in range(SETS):
+            x = torch.randn((T, H), generator=gen, device=dev).half().requires_grad_()
+            w, ids = torch.topk(torch.softmax(torch.randn((T, E), generator=gen, device=dev), -1), K, dim=-1)
+            w = (w / w.sum(-1, keepdim=True)).requires_grad_()
+            sets.append((x, ids, w, torch.randn((T, H), generator=gen, device=dev).half()))
+        turn = [0, 0]
+
+        def eager(route, slot):
+            x, ids, w, gy = sets[turn[slot] % SETS]
+            turn[slot] += 1
+            moe.GROUPED_BACKWARD = route
+            try:
+                x.grad = w.grad = None
+                q(x, ids, w).backward(gy)
+            finally:
+                moe.GROUPED_BACKWARD = True
+
+        # the captured step: static inputs, refreshed from the next set before every replay (the copies are inside the timed window:
+        # four small device copies, which a training loop pays as well)
+        sx, sids, sw, sgy = (t.detach().clone() for t in sets[0])
+        sx.requires_grad_()
+        sw.requires_grad_()
+
+        def static_step():
+            sx.grad = sw.grad = None
+            q(sx, sids, sw).backward(sgy)
+
+        graph = captured(static_step)
+        gturn = [0]
+
+        def replay():
+            x, ids, w, gy = sets[gturn[0] % SETS]
+            gturn[0] += 1
+            with torch.no_grad():
+                sx.copy_(x)
+                sids.copy_(ids)
+                sw.copy_(w)
+                sgy.copy_(gy)
+            graph.replay()
+
+        fns = [lambda: eager(True, 0), replay, lambda: eager(False, 1)]
+        names = ["device_eager_us", "device_graph_us", "loop_eager_us"]
+        runs = [timed_alternating(fns, args.iters, args.warmup) for _ in range(args.repeats)]
+        row = {"tokens": T, "pairs": T * K, "experts_hit": [len(set(s[1].view(-1).tolist())) for s in sets]}
+        for i, name in enumerate(names):
+            vals = sorted(r[i] for r in runs)
+            row[name] = vals[len(vals) // 2]
+            row[name.replace("_us", "_spread_us")] = round(vals[-1] - vals[0], 2)
+        for name, route in (("device_peak_delta_mb", True), ("loop_peak_delta_mb", False)):
+            torch.cuda.synchronize()
+            for s in sets:
+                s[0].grad = s[2].grad = None
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            eager(route, 0)
+            torch.cuda.synchronize()
+            row[name] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+        x = sets[0][0]  # the two routes on the same step: the gradients differ in their last bits only
+        turn[0] = turn[1] = 0
+        eager(True, 0)
+        a = x.grad.float().clone()
+        eager(False, 1)
+        row["x_grad_rel_diff_device_vs_loop"] = float(((a - x.grad.float()).abs().mean() / x.grad.float().abs().mean()).item())
+        del graph
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    result = {"block": {"hidden": H, "intermediate": I, "experts": E, "top_k": K, "scheme": "1x16g8", "dtype": "float16"},
+              "device": torch.cuda.get_device_name(dev), "iters": args.iters, "repeats": args.repeats, "warmup": args.warmup,
+              "what": "forward + backward of one experts block, x and top_k_weights requiring grad; median over the repeats of the "
+                      "median step time (device events), spread = max - min over the repeats; three input sets in rotation",
+              "rows": rows,
+              "command": f"python tools/moe_benchmark.py --backward --tokens {args.tokens} --iters {args.iters} --repeats {args.repeats}"}
+    out = args.out or os.path.join("profiles", "moe_grouped_backward.json")
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps(result))
+
+
 def packed_main(args):
     import aqlm_amd.moe as moe
 
@@ -228,12 +326,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default=None)
     ap.add_argument("--grouped", action="store_true")
+    ap.add_argument("--backward", action="store_true")
     ap.add_argument("--only", choices=["routed", "graph", "loop", "dense", "packed"], default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.backward:
+        args.tokens = args.tokens or "8,32,128,512"
+        return backward_main(args)
     if args.grouped:
         args.tokens = args.tokens or "1,2,4,8,16,32,40,64,128,256,512"
         return grouped_main(args)
