@@ -129,7 +129,7 @@ _DEFAULT = object()
 
 
 def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_canonical=_DEFAULT, compact: bool = False,
-                  thorough: bool = False, experts: bool = False) -> Dict[str, float]:
+                  thorough: bool = False, experts: bool = False, single_copy: bool = False) -> Dict[str, float]:
     """Resolve the kernels and run the load-time repack of every eligible QuantizedLinear now (GPU-resident modules
     only) instead of at its first forward; ``min_codes`` overrides ``inference.PREPACK_MIN_CODES`` for this call.
     ``drop_canonical``: free the checkpoint-layout ``codes`` of repacked layers -- the packed buffer is lossless; ``state_dict()``,
@@ -144,6 +144,14 @@ def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_
         the smallest footprint, 2.0 / 4.8 bits per weight;
       * ``False``: keep everything (training, speculative verification at 7+ rows on every step).
     A module that was only packed lazily at its first forward keeps both copies.
+    What a dropped 1x16 layer does NOT need its codes for: a forward of more than 256 rows (or of 7+ rows when ``in_features % 64 !=
+    0``) and every backward dequantise W straight from the packed buffer (``aqlm_hip_dequant_1x16_packed``: the same bits as
+    unpack + dequant) -- such calls neither restore nor unpack, so the default keeps one copy through long
+    prompts and training steps; only a 7 .. 256-row forward (the fused MFMA op reads the canonical layout) takes the codes back.
+    ``single_copy=True``: one copy at EVERY row count -- drops like ``drop_canonical=True`` (never restores) and sets
+    ``rows_from_packed = 7`` on every packed 1x16 layer, whose no-grad forwards of 7+ rows then all run as packed dequant +
+    library GEMM + fp32 scale / bias (the large-batch op's > 256-row arithmetic): nothing unpacks, and 7 .. 256-row results differ
+    from the fused MFMA op's in the last bits (another accumulation order, same tolerance against the fp64 oracle).
     ``compact=True`` packs 1x16 g8 layers with 24-bit entries (3.5 instead of 4.5 bytes per code: a 70B model holds 30 GB of
     packed codes instead of 39; measured 1-5 % slower matvecs).  ``thorough=True`` runs the local search of the entry order on
     every layer, not only on those of <= 8 Mi codes (1-3 % faster matvecs on the big layers for ~5x their prepack time).
@@ -156,6 +164,10 @@ def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_
     from . import _native, inference
     from .inference import QuantizedLinear
 
+    if single_copy:
+        if drop_canonical is False:
+            raise ValueError("single_copy=True drops the canonical codes: it cannot be combined with drop_canonical=False")
+        drop_canonical = True
     explicit_drop = drop_canonical is not _DEFAULT
     if not explicit_drop:
         drop_canonical = True
@@ -183,6 +195,9 @@ def prepack_model(model: torch.nn.Module, min_codes: Optional[int] = None, drop_
                 # unless asked for.
                 if drop_canonical is True and (explicit_drop or m.nbits_per_codebook == 16):
                     m.drop_canonical_codes(strict=explicit_drop)
+                if single_copy and m._codes_dropped and m.nbits_per_codebook == 16:
+                    m._codes_drop_strict = True  # (also a layer an earlier default call had dropped)
+                    m.rows_from_packed = inference.GEMV_MAX_ROWS + 1
     finally:
         inference.PREPACK_MIN_CODES = old
         _native.set_tuning("packed_entry_bytes", old_eb)

@@ -175,6 +175,7 @@ struct Tuning {
   int packed_fill_rotate = 1;    // packed 1x16 kernel: 1 = the workgroups that share a codebook slice start their LDS fill at different pieces
   int lut_waves = 0;             // 8 x 8 look-up-table matvec: waves per workgroup (8 / 16); 0 = default
   int packed_prefetch_waves = 0; // chain prefetch: extra waves per workgroup that pull the next layer towards L2 (0 = 2, -1 = off)
+  int packed_dequant_by_xcd = 1; // aqlm_hip_dequant_1x16_packed, grid order: 1 = by the measured rule (16-B vectors: the streams that run together on an XCD are the slices of one row group, so their partial-line stores meet in one L2; 32-B vectors: stream-major like the unpack kernel), 0 = always stream-major, 2 = always by XCD (A/B runs)
 };
 Tuning& tuning();
 

@@ -75,6 +75,7 @@
 #define aqlm_hip_packed_plan_geometry aqlm_hip_g16_packed_plan_geometry
 #define aqlm_hip_packed_desc_read aqlm_hip_g16_packed_desc_read
 #define aqlm_hip_unpack_1x16 aqlm_hip_g16_unpack_1x16
+#define aqlm_hip_dequant_1x16_packed aqlm_hip_g16_dequant_1x16_packed
 #define aqlm_hip_gemv_1x16_packed_cells aqlm_hip_g16_gemv_1x16_packed_cells
 #define aqlm_hip_gemv_1x16_packed aqlm_hip_g16_gemv_1x16_packed
 #define aqlm_hip_gemv_1x16_packed_chain aqlm_hip_g16_gemv_1x16_packed_chain
@@ -911,6 +912,139 @@ __global__ __launch_bounds__(64) void pk_unpack_kernel(const uint32_t* __restric
         }
       }
       local += (int)(e[0] & 1u);
+    }
+  }
+}
+
+// W[M][in_features] straight from a packed buffer: the unpack kernels' walk, writing codebook vectors instead of labels (no int16
+// codes in between).  One wave per (stream, wave range); per round UB lane-steps of entries are requested before the first is
+// decoded, then all their permutation look-ups (relabelled buffers) and row scales, then the codebook vectors DB lane-steps at a
+// time -- every dependent level is one batch of independent loads, never a chain per entry.  Only the STORE is predicated (null /
+// padding entries: j >= in_groups or a row past the stream's last), so the loads stay unconditional and in flight together; the
+// indices they use are in range whatever the entry holds (labels < 65536, the scale of an invalid row is read from row 0).
+// The arithmetic is dequant.hip's, operation for operation (0 + entry, times the scale or 1, one rounding): same bits.
+// `by_xcd`: the 32 streams of consecutive blocks b, b + 8, ... (one XCD under the round-robin placement) are all slices of ONE
+// row group, so the 16-/32-B pieces of a row's lines meet in one L2 (uniform geometry; any bijection is correct).
+template <class T_, int EB, bool PERM>
+__global__ __launch_bounds__(64) void pk_dequant_kernel(const uint8_t* __restrict__ ent, const uint32_t* __restrict__ winfo,
+                                                        const uint16_t* __restrict__ old_of_new, const u32x4* __restrict__ codebook,
+                                                        const uint16_t* __restrict__ scales, uint16_t* __restrict__ W, const PkGeom G,
+                                                        int in_groups, int NW, int T, int by_xcd) {
+  constexpr int P = PK_G / 8;   // 16-B pieces of a codebook vector
+  constexpr int UB = 8;         // lane-steps per round
+  constexpr int DB = 4 / P;     // lane-steps whose vectors are gathered together: 16 x 16 B or 8 x 32 B per lane
+  static_assert(EB == 4 || (EB == 3 && PK_G == 8), "3-byte entries: 16-B vectors only");
+  const int xstride = pk_x_stride(in_groups);
+  const int l = threadIdx.x;
+  const uint32_t b = blockIdx.x;
+  int st, w;
+  if (by_xcd) {
+    const uint32_t x = b & 7u, q = b >> 3, i = q & (uint32_t)(PK_NST / 8 - 1);
+    w = (int)(q / (uint32_t)(PK_NST / 8));
+    st = (int)(((((i >> PK_S_LOG) * 8u) + x) << PK_S_LOG) | (i & (uint32_t)(PK_S - 1)));
+  } else {
+    st = (int)(b % (uint32_t)PK_NST);
+    w = (int)(b / (uint32_t)PK_NST);
+  }
+  int s, row0, nrows;
+  pk_stream_rows(G, st, s, row0, nrows);
+  const uint32_t* wi = winfo + ((size_t)st * NW + w) * 4;
+  const int steps = (int)wi[2];
+  const uint8_t* base = ent + ((size_t)st * NW + w) * T * (EB == 3 ? (size_t)PK_WREG3 : (size_t)1024);
+  int local = 0;
+  if constexpr (EB == 3) {  // start row of this column: the wave range's start row + the row ends in the columns before it
+    local = (int)wi[3];
+    for (int t = 0; t < steps; ++t) {
+      const unsigned long long fl = *reinterpret_cast<const unsigned long long*>(base + (size_t)t * 8);
+      local += __popcll(fl & ((1ull << l) - 1ull));
+    }
+  }
+  for (int t0 = 0; t0 < steps; t0 += UB) {
+    uint32_t e[UB][4], rowend[UB];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      const int t = t0 + u < steps ? t0 + u : steps - 1;
+      if constexpr (EB == 4) {
+        const u32x4 v = *reinterpret_cast<const u32x4*>(base + ((size_t)t * 64 + l) * 16);
+        e[u][0] = v.x; e[u][1] = v.y; e[u][2] = v.z; e[u][3] = v.w;
+        rowend[u] = 0;
+      } else {
+        const uint32_t* p3 = reinterpret_cast<const uint32_t*>(base + (size_t)T * 8 + (size_t)t * PK_STEP3 + (size_t)l * 12);
+        pk_unpack3(p3[0], p3[1], p3[2], e[u]);
+        const unsigned long long fl = *reinterpret_cast<const unsigned long long*>(base + (size_t)t * 8);
+        rowend[u] = (uint32_t)((fl >> l) & 1ull);
+      }
+    }
+    // decode: input group and label of every entry, row of every lane-step (the only sequential part)
+    int jj[UB][4], rowl[UB];
+    uint32_t lab[UB][4];
+    bool live[UB];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      if constexpr (EB == 4) {
+        if (t0 + u == 0) local = (int)pk_get_start_row(e[u][0], e[u][1], e[u][2], e[u][3]);
+        rowend[u] = e[u][0] & 1u;
+      }
+      live[u] = t0 + u < steps && local < nrows;
+      rowl[u] = live[u] ? row0 + local : 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t v = e[u][k];
+        if constexpr (EB == 4) {
+          jj[u][k] = (int)(v >> (16 + PK_VSH)) - (int)((v >> 16) & 3u) * xstride;
+          lab[u][k] = ((uint32_t)s << PK_CODE_BITS) | ((v >> PK_VSH) & (uint32_t)(PK_SLICE_ENTRIES - 1));
+        } else {
+          jj[u][k] = (int)(v >> 12) % xstride;
+          lab[u][k] = ((uint32_t)s << PK_CODE_BITS) | (v & 0xfffu);
+        }
+      }
+      if (t0 + u < steps) local += (int)rowend[u];
+    }
+    if constexpr (PERM) {  // back to the checkpoint's labels: the caller's codebook is indexed by them
+#pragma unroll
+      for (int u = 0; u < UB; ++u)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lab[u][k] = old_of_new[lab[u][k]];
+    }
+    float sc[UB];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) sc[u] = scales ? T_::to_float(scales[rowl[u]]) : 1.f;
+#pragma unroll
+    for (int d0 = 0; d0 < UB; d0 += DB) {
+      u32x4 vec[DB][4][P];
+#pragma unroll
+      for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int pp = 0; pp < P; ++pp) vec[d][k][pp] = codebook[(size_t)lab[d0 + d][k] * P + pp];
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+        const int u = d0 + d;
+        const float scale = sc[u];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!live[u] || jj[u][k] < 0 || jj[u][k] >= in_groups) continue;
+          uint16_t* out = W + ((size_t)rowl[u] * in_groups + jj[u][k]) * PK_G;
+#pragma unroll
+          for (int pp = 0; pp < P; ++pp) {
+            const u32x4 c = vec[d][k][pp];
+            float f[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) f[q] = 0.f;
+            f[0] += T_::lo(c.x); f[1] += T_::hi(c.x);
+            f[2] += T_::lo(c.y); f[3] += T_::hi(c.y);
+            f[4] += T_::lo(c.z); f[5] += T_::hi(c.z);
+            f[6] += T_::lo(c.w); f[7] += T_::hi(c.w);
+            u32x4 o;
+            o.x = (uint32_t)T_::from_float(f[0] * scale) | ((uint32_t)T_::from_float(f[1] * scale) << 16);
+            o.y = (uint32_t)T_::from_float(f[2] * scale) | ((uint32_t)T_::from_float(f[3] * scale) << 16);
+            o.z = (uint32_t)T_::from_float(f[4] * scale) | ((uint32_t)T_::from_float(f[5] * scale) << 16);
+            o.w = (uint32_t)T_::from_float(f[6] * scale) | ((uint32_t)T_::from_float(f[7] * scale) << 16);
+            *reinterpret_cast<u32x4*>(out + pp * 8) = o;
+          }
+        }
+      }
     }
   }
 }
@@ -2342,6 +2476,7 @@ int aqlm_hip_g16_packed_plan_relabel_ex(const uint32_t*, int, int, uint16_t*);
 int aqlm_hip_g16_packed_plan_geometry(const uint64_t*, int, int, int, uint8_t*);
 int aqlm_hip_g16_packed_desc_read(const void*, size_t, aqlm_hip_packed_desc*);
 int aqlm_hip_g16_unpack_1x16(const aqlm_hip_packed_desc*, const void*, void*, void*);
+int aqlm_hip_g16_dequant_1x16_packed(const aqlm_hip_packed_desc*, const void*, const void*, const void*, void*, int, void*);
 int aqlm_hip_g16_gemv_1x16_packed_cells(const aqlm_hip_packed_desc*, const void*, const void*, const void*, const void*, const void*, void*, int,
                                         long, long, int, void*, size_t, void*);
 int aqlm_hip_g16_gemv_1x16_packed(const aqlm_hip_packed_desc*, void*, const void*, const void*, const void*, const void*, void*, int, long, long,
@@ -2764,6 +2899,44 @@ extern "C" PK_API int aqlm_hip_unpack_1x16(const aqlm_hip_packed_desc* desc, con
     hipLaunchKernelGGL(pk_unpack_kernel, dim3((unsigned)L.nst, L.NW), dim3(64), 0, stream, (const uint32_t*)(base + L.off_ent),
                        (const uint32_t*)(base + L.off_winfo), perm, (uint16_t*)codes, L.G, L.in_groups, L.NW, L.T);
   return check_hip(hipGetLastError(), "unpack launch");
+}
+
+// W from the packed buffer (pk_dequant_kernel).  Reads the entries, the permutation stored behind them and the CALLER's codebook:
+// never the permuted codebook image, whose flag and the descriptor's codebook range are not looked at.
+extern "C" PK_API int aqlm_hip_dequant_1x16_packed(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                                   const void* scales, void* W, int dtype, void* stream_) {
+  PK_G16_FORWARD(desc, aqlm_hip_g16_dequant_1x16_packed(desc, packed, codebook, scales, W, dtype, stream_));
+  hipStream_t stream = (hipStream_t)stream_;
+  PackedLayout L;
+  if (!packed || !codebook || !W || !desc_layout(desc, L)) {
+    set_last_error("aqlm_hip_dequant_1x16_packed: null pointer or invalid descriptor");
+    return AQLM_HIP_E_INVALID;
+  }
+  if (!aligned16(packed) || !aligned16(codebook) || !aligned16(W)) {
+    set_last_error("aqlm_hip_dequant_1x16_packed: packed, codebook and W must be 16-byte aligned");
+    return AQLM_HIP_E_INVALID;
+  }
+  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
+    set_last_error("aqlm_hip_dequant_1x16_packed: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
+    return AQLM_HIP_E_UNSUPPORTED;
+  }
+  const uint8_t* base = (const uint8_t*)packed;
+  const uint16_t* perm = L.relabel ? (const uint16_t*)(base + L.off_perm) : nullptr;
+  // grid order (measured, profiles/packed_dequant.json): one row group per XCD is 7 % / 4 % faster at 4096 x 4096 / 8192 -> 28672 and 2 %
+  // slower at 4096 <-> 14336 for 16-B vectors; with 32-B vectors (a quarter of a line per store) the stream-major grid is 6 % faster
+  const int knob = tuning().packed_dequant_by_xcd;
+  const int by_xcd = !L.G.vg && (knob == 2 || (knob == 1 && PK_G == 8)) ? 1 : 0;
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)(L.nst * L.NW)), dim3(64), 0, stream, base + L.off_ent, (const uint32_t*)(base + L.off_winfo), perm,
+                       (const u32x4*)codebook, (const uint16_t*)scales, (uint16_t*)W, L.G, L.in_groups, L.NW, L.T, by_xcd);
+    return check_hip(hipGetLastError(), "packed dequant launch");
+  };
+#define AQLM_PK_DQ(TT, EE) (perm ? go(pk_dequant_kernel<TT, EE, true>) : go(pk_dequant_kernel<TT, EE, false>))
+#if AQLM_PK_G == 8
+  if (L.EB == 3) return dtype == AQLM_HIP_F16 ? AQLM_PK_DQ(F16, 3) : AQLM_PK_DQ(BF16, 3);
+#endif
+  return dtype == AQLM_HIP_F16 ? AQLM_PK_DQ(F16, 4) : AQLM_PK_DQ(BF16, 4);
+#undef AQLM_PK_DQ
 }
 
 // The fused finalize needs the layer's codebook range (descriptor field) and can be switched off for A/B runs.

@@ -38,6 +38,43 @@ PREPACK_MIN_CODES = 500_000
 # re-capture.  The modules of a model start their counters at different offsets, so the checks do not land on the same step.
 DERIVED_CHECK_EVERY = 256
 
+# Rows above which the large-batch 1x16 op dequantises W and calls the library GEMM (hip_kernel.FUSED_MFMA_MAX_ROWS; restated here so
+# that the route predicate below needs no GPU library -- tests hold the two together).
+PACKED_DEQUANT_ABOVE_ROWS = 256
+
+ROUTE_CANONICAL = "canonical"                # the layer has its codes: nothing below applies
+ROUTE_PACKED_MATVEC = "packed_matvec"        # <= GEMV_MAX_ROWS rows, no gradient: the packed matvec
+ROUTE_PACKED_DEQUANT = "packed_dequant"      # W straight from the packed buffer (aqlm_hip_dequant_1x16_packed) + library GEMM
+ROUTE_RESTORE = "restore"                    # the canonical codes come back for good (one unpack), then the ordinary op
+ROUTE_TRANSIENT_UNPACK = "transient_unpack"  # one unpack for this call, then the ordinary op
+
+
+def dropped_layer_route(dropped: bool, strict: bool, rows_from_packed: int, rows: int, in_features_mod_64: int,
+                        grad_needed: bool) -> str:
+    """How a 1x16 layer whose canonical codes were dropped (its ``_packed_codes`` is a ``PackedCodes``) serves a forward of
+    ``rows`` input rows -- a pure function, so the table can be tested without a GPU:
+      * <= GEMV_MAX_ROWS rows without a gradient: the packed matvec;
+      * more than PACKED_DEQUANT_ABOVE_ROWS rows, or ``in_features % 64 != 0`` at 7+ rows -- where the large-batch op is dequant +
+        library GEMM + fp32 scale / bias anyway: W comes straight from the packed buffer, same arithmetic, same bits, and the
+        layer stays dropped (with or without a gradient);
+      * ``rows_from_packed`` > 0 (the opt-in, ``prepack_model(single_copy=True)``): every no-grad forward of at least that many
+        rows (never fewer than 7) takes that route as well -- 7 .. 256-row results then differ from the fused MFMA op's in the
+        last bits (another accumulation order);
+      * anything else needs the canonical codes (the fused MFMA op of 7 .. 256 rows, a forward of <= 6 rows with a gradient): a
+        strict drop unpacks for the call, a non-strict one restores the codes for good.
+    The BACKWARD of a layer that is still dropped when it runs always dequantises from the packed buffer, whatever the forward
+    took."""
+    if not dropped:
+        return ROUTE_CANONICAL
+    if rows <= GEMV_MAX_ROWS and not grad_needed:
+        return ROUTE_PACKED_MATVEC
+    if rows > GEMV_MAX_ROWS:
+        if rows > PACKED_DEQUANT_ABOVE_ROWS or in_features_mod_64 != 0:
+            return ROUTE_PACKED_DEQUANT
+        if rows_from_packed > 0 and rows >= rows_from_packed and not grad_needed:
+            return ROUTE_PACKED_DEQUANT
+    return ROUTE_TRANSIENT_UNPACK if strict else ROUTE_RESTORE
+
 
 class QuantizedLinear(nn.Module):
     def __init__(
@@ -86,6 +123,10 @@ class QuantizedLinear(nn.Module):
         # format exists to save (2 bytes per weight for every layer that uses it), so it is off (0) unless asked for:
         # `module.prefer_dense_below_rows = 129`, or `aqlm.checkpoint.enable_dense_below_rows(model, 129)`.
         self.prefer_dense_below_rows = 0
+        # Opt-in (`prepack_model(single_copy=True)` sets 7): a layer whose canonical codes were dropped serves every no-grad forward
+        # of at least this many rows as W-from-the-packed-buffer + library GEMM + fp32 scale / bias -- the large-batch op's > 256-row
+        # arithmetic at any row count -- so that no call of an inference deployment ever unpacks.  0 = off (`dropped_layer_route`).
+        self.rows_from_packed = 0
         self._reset_derived()
 
     # Everything the module derives from its parameters, in the state "not built yet": the kernel choice and autograd ops, the
@@ -240,7 +281,47 @@ class QuantizedLinear(nn.Module):
                 and not torch.compiler.is_compiling()):
             return torch.nn.functional.linear(input, self._dense_weight(), self.bias)
         op = self.gemv_op if self.use_gemv_rule(input) else self.gemm_op
+        if self._codes_dropped and self._serves_from_packed(input):
+            grad_needed = torch.is_grad_enabled() and input.requires_grad
+            route = dropped_layer_route(True, self._codes_drop_strict, self.rows_from_packed, math.prod(input.shape[:-1]),
+                                        self.in_features % 64, grad_needed)
+            if route == ROUTE_PACKED_DEQUANT:
+                if not grad_needed:
+                    return self._forward_from_packed(input)
+                return _MatmulFromPacked.apply(input, self, self._forward_from_packed)
+            if route == ROUTE_TRANSIENT_UNPACK and grad_needed:
+                # the ordinary forward on codes unpacked for this call; nothing unpacked is kept for the backward
+                kernel = op.forward_pass_kernel
+                return _MatmulFromPacked.apply(input, self, lambda x: kernel(x, self._canonical_codes(), self.codebooks, self.scales, self.bias))
         return op.apply(input, self._codes_for_ops(), self.codebooks, self.scales, self.bias)
+
+    def _serves_from_packed(self, input: torch.Tensor) -> bool:
+        """A call the packed-dequant routes can take: a 1x16 layer on slice-bucketed codes, input on the GPU in the codebook dtype."""
+        from .inference_kernels import hip_kernel
+
+        return (isinstance(self._packed_codes, hip_kernel.PackedCodes) and input.is_cuda and input.dtype == self.codebooks.dtype
+                and self.scales.dtype == self.codebooks.dtype)
+
+    def _weight_from_packed(self, scaled: bool) -> torch.Tensor:
+        """W [out, in] straight from the packed buffer and the live codebook (aqlm_hip_dequant_1x16_packed): the bits of the dequant
+        kernel on the unpacked codes, without unpacking."""
+        from .inference_kernels import hip_kernel
+
+        packed, scales = self._packed_codes, (self.scales if scaled else None)
+        if torch.compiler.is_compiling():  # traced: the dispatcher op (it has a fake implementation)
+            return torch.ops.aqlm.code1x16_dequant_packed(packed.buf, self.codebooks, scales, packed.op_ints())
+        return hip_kernel.dequant_1x16_packed(packed, self.codebooks, scales)
+
+    def _forward_from_packed(self, input: torch.Tensor) -> torch.Tensor:
+        """The large-batch op's dequant route (hip_kernel.code1x16_matmat_dequant above FUSED_MFMA_MAX_ROWS) with W taken from the
+        packed buffer: unscaled W (exact in the storage dtype), one library GEMM, scale + bias in fp32 with one rounding."""
+        from .inference_kernels import hip_kernel
+
+        if input.shape[-1] != self.in_features:
+            raise ValueError(f"input has {input.shape[-1]} features, layer expects {self.in_features}")
+        x = hip_kernel._flat_rows(input)
+        y = torch.nn.functional.linear(x, self._weight_from_packed(scaled=False))
+        return hip_kernel._scale_bias_fp32(y, self.scales, self.bias).reshape(input.shape[:-1] + (self.out_features,))
 
     def _rows_take_the_fused_8x8_op(self, input: torch.Tensor) -> bool:
         from .inference_kernels import hip_kernel
@@ -263,7 +344,10 @@ class QuantizedLinear(nn.Module):
             from .utils import _dequantize_weight, unpack_int_data
 
             with torch.no_grad():
-                w = _dequantize_weight(unpack_int_data(self._canonical_codes(), self.nbits_per_codebook), self.codebooks, self.scales)
+                if self._codes_dropped and self._serves_from_packed(self.codebooks):
+                    w = self._weight_from_packed(scaled=True)  # the same bits (codebook entry x scale, one rounding) without an unpack
+                else:
+                    w = _dequantize_weight(unpack_int_data(self._canonical_codes(), self.nbits_per_codebook), self.codebooks, self.scales)
             self._dense = (fp, w.to(self.codebooks.dtype).contiguous())
             self._settle()
         return self._dense[1]
@@ -458,4 +542,26 @@ def _get_autograd_matmul_op(forward_pass_kernel, backward_pass_kernel):
             grad_input = backward_pass_kernel(grad_output.contiguous(), codes, codebooks, scales, None)
             return grad_input, None, None, None, None
 
+    _QuantizedMatmul.forward_pass_kernel = staticmethod(forward_pass_kernel)
     return _QuantizedMatmul
+
+
+class _MatmulFromPacked(torch.autograd.Function):
+    """A forward of a layer whose canonical codes were dropped, with a gradient for its input: ``forward_fn(input)`` is the
+    forward, and the backward is the ordinary one -- grad_input = grad_output @ W with the scales folded into W
+    (hip_kernel._matmat_dequant_transposed) -- on a W dequantised straight from the packed buffer.  Nothing unpacked lives between
+    the two; the packed buffer (which IS the weights) and the codebooks / scales the forward used are what the backward reads."""
+
+    @staticmethod
+    def forward(ctx, input, layer, forward_fn):
+        ctx.packed = layer._packed_codes
+        ctx.save_for_backward(layer.codebooks, layer.scales)
+        return forward_fn(input)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from .inference_kernels import hip_kernel
+
+        codebooks, scales = ctx.saved_tensors
+        W = hip_kernel.dequant_1x16_packed(ctx.packed, codebooks, scales)
+        return torch.matmul(grad_output.contiguous(), W), None, None

@@ -304,6 +304,30 @@ def unpack_1x16(packed: PackedCodes) -> torch.Tensor:
     return codes
 
 
+def dequant_1x16_packed(packed: PackedCodes, codebooks: torch.Tensor, scales: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W [out, in] in the codebook dtype straight from a prepacked buffer (aqlm_hip_dequant_1x16_packed): the bits of
+    ``code1x16_dequant(unpack_1x16(packed), codebooks, scales)`` without the int16 codes in between.  Reads the entries, the
+    permutation inside the buffer and ``codebooks`` as passed -- never the buffer's codebook image or range, so it needs no
+    ``refresh_range`` and is stream-ordered (no allocation beyond W, no synchronisation: it can be captured in a hipGraph)."""
+    dt = _dtype_id(codebooks)
+    if tuple(codebooks.shape) != (1, 65536, 1, packed.in_group_size):
+        raise NotImplementedError(f"dequant_1x16_packed needs codebooks [1, 65536, 1, {packed.in_group_size}], got {tuple(codebooks.shape)}")
+    if codebooks.device != packed.device:
+        raise ValueError(f"codebooks on {codebooks.device}, packed codes on {packed.device}")
+    if scales is not None:
+        if scales.dtype != codebooks.dtype or scales.numel() != packed.out_features:
+            raise ValueError(f"scales must hold {packed.out_features} values of {codebooks.dtype}")
+        scales = _c(scales)
+    codebooks = _c(codebooks)
+    W = torch.empty((packed.out_features, packed.in_features), dtype=codebooks.dtype, device=codebooks.device)
+    with _device_guard(codebooks.device):
+        rc = _lib.aqlm_hip_dequant_1x16_packed(ctypes.byref(packed.desc), packed.data_ptr(), codebooks.data_ptr(), _ptr(scales),
+                                               W.data_ptr(), dt, _stream_ptr(codebooks.device))
+    if rc:
+        _native.check(rc, "aqlm dequant_1x16_packed")
+    return W
+
+
 # fp32 partial workspaces, one per (device, stream): a decode loop calls the packed op hundreds of times per token and
 # the allocator round trip is a measurable part of an eager call.  Not used while a hipGraph is being captured (the
 # capture's private pool must own what the graph touches).
@@ -1819,6 +1843,20 @@ _LIB.define("code1x16_matmat_packed(Tensor input, Tensor packed, Tensor codebook
             "int[] desc) -> Tensor")
 _LIB.impl("code1x16_matmat_packed", _packed_op, "CUDA")
 torch.library.register_fake("aqlm::code1x16_matmat_packed")(_fake_packed)
+
+
+# W from a packed buffer as a dispatcher op (the packed-dequant routes of QuantizedLinear under torch.compile)
+def _packed_dequant_op(packed, codebooks, scales, desc):
+    return dequant_1x16_packed(PackedCodes(packed, _native.PackedDesc.from_ints(desc[:_N_DESC_INTS])), codebooks, scales)
+
+
+def _fake_packed_dequant(packed, codebooks, scales, desc):
+    return torch.empty((int(desc[2]), int(desc[3])), device=codebooks.device, dtype=codebooks.dtype)
+
+
+_LIB.define("code1x16_dequant_packed(Tensor packed, Tensor codebooks, Tensor? scales, int[] desc) -> Tensor")
+_LIB.impl("code1x16_dequant_packed", _packed_dequant_op, "CUDA")
+torch.library.register_fake("aqlm::code1x16_dequant_packed")(_fake_packed_dequant)
 
 
 # the planar 8x8 matvec as a dispatcher op (same reason; geometry = [out_features, in_features, in_group_size], the codebook bound

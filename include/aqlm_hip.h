@@ -317,6 +317,17 @@ int aqlm_hip_gemm_1x16_scan(const void* codes_i16, const void* codebook, const v
  *                                AQLM_HIP_PACKED_HAS_CODEBOOK in `*desc`; stream-ordered, no synchronisation.
  *   aqlm_hip_packed_desc_read    descriptor from the first sizeof(desc) bytes of a packed buffer copied to the host.
  *   aqlm_hip_unpack_1x16         the inverse: canonical int16 codes [out][in/8] from a packed buffer (lossless).
+ *   aqlm_hip_dequant_1x16_packed W[out_features][in_features] (row-major, fp16 / bf16: `dtype`) straight from a packed buffer, without
+ *                                the int16 codes in between: W[r, j*g:(j+1)*g] = codebook[label(r, j)], times scales[r] in fp32 with
+ *                                one rounding when `scales` is not NULL -- bit-identical to aqlm_hip_dequant_1x16 on the output of
+ *                                aqlm_hip_unpack_1x16.  Covers what the unpack entry covers (g 8 / 16, 4- and 3-byte entries, uniform
+ *                                and variable geometry, relabelled or not).  W depends on the entries, on the permutation stored in
+ *                                the buffer and on the `codebook` passed in (the checkpoint's labelling, [65536][g]) only: the
+ *                                permuted codebook image, AQLM_HIP_PACKED_HAS_CODEBOOK and desc->codebook_absmax are not looked at.
+ *                                Every element of W is written exactly once, nothing else is written.  `packed`, `codebook` and W
+ *                                must be 16-byte aligned.  Stream-ordered: no allocation, no synchronisation, no workspace
+ *                                (hipGraph-capturable).  AQLM_HIP_E_INVALID: null / misaligned pointer or a descriptor that does
+ *                                not describe a packed buffer; AQLM_HIP_E_UNSUPPORTED: dtype other than fp16 / bf16.
  *   aqlm_hip_packed_plan_*       the two host-side planning steps of the repack (pure functions, exposed for tests and tools).
  */
 #define AQLM_HIP_PACKED_RELABELLED 1u   /* codebook entries were dealt to the slices: permutation + codebook image inside the buffer */
@@ -358,6 +369,8 @@ int aqlm_hip_prepack_1x16_ex(const void* codes_i16, int out_features, int in_fea
 int aqlm_hip_packed_set_codebook(aqlm_hip_packed_desc* desc, void* packed, const void* codebook, void* stream);
 int aqlm_hip_packed_desc_read(const void* header_host, size_t header_bytes, aqlm_hip_packed_desc* desc);
 int aqlm_hip_unpack_1x16(const aqlm_hip_packed_desc* desc, const void* packed, void* codes_i16, void* stream);
+int aqlm_hip_dequant_1x16_packed(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                 const void* scales /* nullable */, void* W, int dtype, void* stream);
 /* Host-side planning steps (no GPU work).  relabel: usage counts of the 65536 entries -> new_of_old[65536] (returns 1 and
  * fills it when the entries should be re-dealt, 0 when the slices are already even within 2 %).  geometry: lane-steps
  * (units of 4 entries) of every slice -> slice_groups[1 << slices_log2] (returns 1 when the result is not uniform). */
