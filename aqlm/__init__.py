@@ -51,3 +51,4 @@ inference_kernels = importlib.import_module(__name__ + ".inference_kernels")
 checkpoint = importlib.import_module(__name__ + ".checkpoint")
 fusion = importlib.import_module(__name__ + ".fusion")
 moe = importlib.import_module(__name__ + ".moe")
+lora = importlib.import_module(__name__ + ".lora")

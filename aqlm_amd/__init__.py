@@ -8,6 +8,7 @@ from .fusion import SharedInputGroup, fuse_shared_input_linears, unfuse_shared_i
 from .inference import QuantizedLinear
 from .inference_kernels import get_backward_pass_kernel, get_forward_pass_kernel, optimize_for_training
 from .moe import QuantizedMixtralExperts, quantized_experts, replace_moe_experts
+from . import lora  # noqa: E402  (LoRA adapters on quantized layers: attach_adapters, AdapterBank)
 
 __version__ = "1.1.7"
 
@@ -24,4 +25,5 @@ __all__ = [
     "QuantizedMixtralExperts",
     "quantized_experts",
     "replace_moe_experts",
+    "lora",
 ]

@@ -120,6 +120,16 @@ class RoutedPackedGeometry(ctypes.Structure):
                 ("lds_bytes", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
 
 
+class LoraEntry(ctypes.Structure):
+    """aqlm_hip_lora_entry (include/aqlm_hip.h): one adapter of a layer's device table -- A [rank][in], B [out][rank], rank, scaling."""
+
+    _fields_ = [("a", _vp), ("b", _vp), ("rank", ctypes.c_int32), ("scaling", ctypes.c_float)]
+
+
+LORA_ENTRY_WORDS = ctypes.sizeof(LoraEntry) // 8   # 64-bit words of a table entry
+MAX_LORA_ROWS = 256      # aqlm_hip_lora_bgmv: rows per call
+MAX_LORA_RANK = 128
+
 _rpep = ctypes.POINTER(RoutedPackedEntry)
 _rpgp = ctypes.POINTER(RoutedPackedGeometry)
 
@@ -143,6 +153,9 @@ SIGNATURES = {
     "aqlm_hip_gemv_1x16_routed_packed_geometry": (_ci, [_descpp, _ci, _rpgp]),
     "aqlm_hip_gemv_1x16_routed_packed_supported": (_ci, [_descpp, _ci]),
     "aqlm_hip_gemv_1x16_routed_packed": (_ci, [_vp, _rpgp, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_lora_workspace_bytes": (_sz, [_ci, _ci]),
+    "aqlm_hip_lora_bgmv_supported": (_ci, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_bgmv": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _vp, _cl, _vp, _cl, _ci, _ci, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

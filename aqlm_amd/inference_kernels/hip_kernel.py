@@ -611,6 +611,66 @@ def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
 
 
 # ------------------------------------------------------------------------------------------------------
+# LoRA adapters per row of a decode batch (aqlm_hip_lora_bgmv; aqlm_amd/lora.py is the module-level interface)
+# ------------------------------------------------------------------------------------------------------
+def lora_table(adapters, device) -> torch.Tensor:
+    """The device-resident table of aqlm_hip_lora_bgmv: ``adapters[a] = (A [rank, in], B [out, rank], scaling)`` -> int64
+    [num_adapters * 3] holding the aqlm_hip_lora_entry structs, entry a = adapter id a.  Filled on the host and copied once, like
+    ``routed_table``: the table holds raw addresses, so the caller keeps the tensors alive and rebuilds it when one of them moves
+    or is written (``aqlm_amd.lora`` keys it on data_ptr + version).  Never while a hipGraph is being captured."""
+    entries = (_native.LoraEntry * len(adapters))()
+    for ent, (a, b, scaling) in zip(entries, adapters):
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.dtype != b.dtype:
+            raise ValueError(f"lora table: A must be [rank, in] and B [out, rank] of one dtype, got {tuple(a.shape)} / {tuple(b.shape)}")
+        for t in (a, b):
+            if not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError("lora table: A and B must be contiguous and 16-byte aligned")
+        ent.a, ent.b, ent.rank, ent.scaling = a.data_ptr(), b.data_ptr(), int(a.shape[0]), float(scaling)
+    words = torch.frombuffer(bytearray(bytes(entries)), dtype=torch.int64) if len(adapters) else torch.empty(0, dtype=torch.int64)
+    return words.to(device)
+
+
+def lora_bgmv_supported(out_features: int, in_features: int, max_rank: int, rows: int) -> bool:
+    return bool(_lib.aqlm_hip_lora_bgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
+
+
+def lora_bgmv_(y, x, ids, table, geometry) -> None:
+    """``y[b] += scaling_a * B_a (A_a x[b])`` with a = ids[b], in place, for every row of a decode batch in two launches
+    (include/aqlm_hip.h, aqlm_hip_lora_bgmv: fp32 sums, the rank-sized intermediate is never rounded, y is rounded once).
+    geometry = [num_adapters, max_rank, out_features, in_features]; ``y`` [rows, out] and ``x`` [rows, in] fp16 / bf16 with unit
+    inner strides; ``ids`` [rows] int64 / int32 on the device (read there only; a row whose id lies outside [0, num_adapters) is
+    left as it is) or None = adapter 0 for every row; ``table`` from ``lora_table``.  The fp32 workspace comes from the caching
+    allocator, so the call can be captured."""
+    n, max_rank, out_features, in_features = (int(v) for v in geometry)
+    dt = _dtype_id(y)
+    if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0] or y.shape[1] != out_features or x.shape[1] != in_features:
+        raise ValueError(f"y must be [rows, {out_features}] and x [rows, {in_features}], got {tuple(y.shape)} / {tuple(x.shape)}")
+    if x.dtype != y.dtype or x.device != y.device or table.device != y.device:
+        raise ValueError("x, y and the table must share dtype and device")
+    if y.stride(1) != 1:
+        raise ValueError("y must have a unit inner stride (it is written in place)")
+    if table.dtype != torch.int64 or table.numel() != n * _native.LORA_ENTRY_WORDS:
+        raise ValueError(f"table must be int64 [{n * _native.LORA_ENTRY_WORDS}]")
+    rows = y.shape[0]
+    if ids is not None:
+        if ids.dim() != 1 or ids.shape[0] != rows or ids.dtype not in (torch.int64, torch.int32) or ids.device != y.device:
+            raise ValueError(f"ids must be [{rows}] int64 / int32 on {y.device}, got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
+        ids = _c(ids)
+    if rows == 0:
+        return
+    x = _flat_rows(x)
+    nbytes = _lib.aqlm_hip_lora_workspace_bytes(rows, max_rank)
+    ws = _workspace(y.device, max(nbytes, 16))
+    with _device_guard(y.device):
+        rc = _lib.aqlm_hip_lora_bgmv(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8),
+                                     rows, x.data_ptr(), x.stride(0) if rows > 1 else in_features, y.data_ptr(),
+                                     y.stride(0) if rows > 1 else out_features, out_features, in_features, dt, ws.data_ptr(),
+                                     ws.numel() * 4, _stream_ptr(y.device))
+    if rc:
+        _native.check(rc, "aqlm lora bgmv")
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
@@ -1787,6 +1847,16 @@ torch.library.register_fake("aqlm::code1x16_moe_matmat")(_fake_moe)
 _LIB.define("code1x16_moe_matmat_packed(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
 _LIB.impl("code1x16_moe_matmat_packed", code1x16_moe_matmat_packed, "CUDA")
 torch.library.register_fake("aqlm::code1x16_moe_matmat_packed")(_fake_moe)
+
+
+# per-row LoRA adapters on top of a layer's output (no reference counterpart); mutates y, returns nothing
+def _fake_lora_bgmv(y, x, ids, table, geometry):
+    return None
+
+
+_LIB.define("lora_bgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
+_LIB.impl("lora_bgmv_", lora_bgmv_, "CUDA")
+torch.library.register_fake("aqlm::lora_bgmv_")(_fake_lora_bgmv)
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

@@ -502,6 +502,45 @@ int aqlm_hip_gemv_1x16_routed_packed(const aqlm_hip_routed_packed_entry* table, 
                                      void* cells, size_t cells_bytes, void* stream);
 
 /*
+ * LoRA adapters on top of a quantized layer, a different adapter for every row of a decode batch if need be (batched adapter
+ * matvec; no reference counterpart -- the reference leaves adapters to PEFT's x @ A^T @ B^T * scaling + add, four generic launches
+ * per layer).  An adapter cannot be merged into an AQLM base (the weights exist as codes + codebooks only), so it runs at every
+ * token.  `table` is a DEVICE array of num_adapters aqlm_hip_lora_entry (8-byte aligned): A_a [rank][in_features] and B_a
+ * [out_features][rank], row-major, 16-byte aligned, in the storage type of x and y; rank a multiple of 8 in 8..max_rank (an entry
+ * with any other rank counts as "no adapter"); max_rank a multiple of 8 in 8..128.  ids: DEVICE [rows] int64 (ids_int64 != 0) or
+ * int32, or NULL = adapter 0 for every row.  For every row b < rows with a = ids[b]:
+ *     t[b, r] = sum_k A_a[r, k] * x[b, k]                                      r < rank_a   (fp32)
+ *     y[b, i] = round(float(y[b, i]) + scaling_a * sum_r B_a[i, r] * t[b, r])
+ * Products of storage-type operands are exact, all sums are fp32 in a fixed order, t is NEVER rounded to the storage type (PEFT
+ * rounds it), y is rounded exactly once more.  An id is range-checked before it indexes the table: a row whose id lies outside
+ * [0, num_adapters) is left bit for bit as it was and nothing is loaded through its table slot.  Two launches -- shrink (t into
+ * `workspace`, fp32 [rows][max_rank]: aqlm_hip_lora_workspace_bytes, 16-byte aligned) and expand + add (read-modify-write of y) --
+ * whose grids depend on rows, max_rank and out_features only; adapters of different rank share them.  No atomics, no
+ * inter-workgroup communication: a row's bits depend on its own x row, its own y row and its adapter, never on the other rows,
+ * their number or their order.  Stream-ordered, no allocation, no synchronisation (hipGraph-capturable; ids may be rewritten in
+ * place between replays).  x / y row strides in elements; y 2-byte aligned with y_row_stride >= out_features (columns past
+ * out_features are not touched); y must not overlap x.
+ * AQLM_HIP_E_UNSUPPORTED (the caller runs the adapters as generic ops): max_rank not a multiple of 8 in 8..128, in_features % 8
+ * != 0, rows > AQLM_HIP_MAX_LORA_ROWS, x rows not 16-byte aligned, dtype other than fp16 / bf16; aqlm_hip_lora_bgmv_supported
+ * answers for the four sizes beforehand.  AQLM_HIP_E_INVALID: null / misaligned table, ids, y or workspace, non-positive sizes,
+ * strides shorter than the rows, y overlapping x, a workspace smaller than aqlm_hip_lora_workspace_bytes.
+ */
+typedef struct aqlm_hip_lora_entry {
+  const void* a;  /* [rank][in_features] */
+  const void* b;  /* [out_features][rank] */
+  int32_t rank;
+  float scaling;
+} aqlm_hip_lora_entry; /* 24 bytes */
+
+#define AQLM_HIP_MAX_LORA_ROWS 256
+
+size_t aqlm_hip_lora_workspace_bytes(int rows, int max_rank); /* rows * max_rank * 4; 0 when unsupported */
+int aqlm_hip_lora_bgmv_supported(int out_features, int in_features, int max_rank, int rows);
+int aqlm_hip_lora_bgmv(const aqlm_hip_lora_entry* table, int num_adapters, int max_rank, const void* ids, int ids_int64, int rows,
+                       const void* x, long x_row_stride, void* y, long y_row_stride, int out_features, int in_features, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the
