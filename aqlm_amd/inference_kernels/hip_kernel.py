@@ -670,6 +670,47 @@ def lora_bgmv_(y, x, ids, table, geometry) -> None:
         _native.check(rc, "aqlm lora bgmv")
 
 
+def lora_sgmv_supported(out_features: int, in_features: int, max_rank: int, rows: int) -> bool:
+    return bool(_lib.aqlm_hip_lora_sgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
+
+
+def lora_sgmv_(y, x, ids, table, geometry) -> None:
+    """``lora_bgmv_`` at any row count (prefill, large batches): the segmented adapter GEMM on the matrix unit
+    (include/aqlm_hip.h, aqlm_hip_lora_sgmv), two launches, one pass per distinct adapter of every 16-row tile.  Same arguments
+    as ``lora_bgmv_``; in addition ``y`` must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written
+    in groups of 4 outputs).  Not bit-equal to ``lora_bgmv_``: the sums run in another order, and the rank-sized intermediate
+    enters the second product as a pair of storage-type values."""
+    n, max_rank, out_features, in_features = (int(v) for v in geometry)
+    dt = _dtype_id(y)
+    if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0] or y.shape[1] != out_features or x.shape[1] != in_features:
+        raise ValueError(f"y must be [rows, {out_features}] and x [rows, {in_features}], got {tuple(y.shape)} / {tuple(x.shape)}")
+    if x.dtype != y.dtype or x.device != y.device or table.device != y.device:
+        raise ValueError("x, y and the table must share dtype and device")
+    if y.stride(1) != 1:
+        raise ValueError("y must have a unit inner stride (it is written in place)")
+    rows = y.shape[0]
+    if y.data_ptr() % 8 or (rows > 1 and y.stride(0) % 4):
+        raise ValueError("y must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written in groups of 4)")
+    if table.dtype != torch.int64 or table.numel() != n * _native.LORA_ENTRY_WORDS:
+        raise ValueError(f"table must be int64 [{n * _native.LORA_ENTRY_WORDS}]")
+    if ids is not None:
+        if ids.dim() != 1 or ids.shape[0] != rows or ids.dtype not in (torch.int64, torch.int32) or ids.device != y.device:
+            raise ValueError(f"ids must be [{rows}] int64 / int32 on {y.device}, got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
+        ids = _c(ids)
+    if rows == 0:
+        return
+    x = _flat_rows(x)
+    nbytes = _lib.aqlm_hip_lora_sgmv_workspace_bytes(rows, max_rank, in_features)
+    ws = _workspace(y.device, max(nbytes, 16))
+    with _device_guard(y.device):
+        rc = _lib.aqlm_hip_lora_sgmv(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8),
+                                     rows, x.data_ptr(), x.stride(0) if rows > 1 else in_features, y.data_ptr(),
+                                     y.stride(0) if rows > 1 else out_features, out_features, in_features, dt, ws.data_ptr(),
+                                     ws.numel() * 4, _stream_ptr(y.device))
+    if rc:
+        _native.check(rc, "aqlm lora sgmv")
+
+
 # ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
@@ -1857,6 +1898,10 @@ def _fake_lora_bgmv(y, x, ids, table, geometry):
 _LIB.define("lora_bgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
 _LIB.impl("lora_bgmv_", lora_bgmv_, "CUDA")
 torch.library.register_fake("aqlm::lora_bgmv_")(_fake_lora_bgmv)
+
+_LIB.define("lora_sgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
+_LIB.impl("lora_sgmv_", lora_sgmv_, "CUDA")
+torch.library.register_fake("aqlm::lora_sgmv_")(_fake_lora_bgmv)
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

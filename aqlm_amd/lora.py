@@ -11,8 +11,10 @@ its adapters at inference, at every token.  ``attach_adapters(model, {...})`` wr
     bank.select(None)              # base model only: no adapter launch at all
 
 Decode-sized calls run ``aqlm_hip_lora_bgmv`` (aqlm_amd/csrc/lora_bgmv.hip): two launches per layer whatever the mix of adapters,
-ids read on the device only, capturable.  Everything else -- prefill, training, host tensors, shapes the kernels decline -- runs
-the adapters as torch ops, differentiable in x, A and B, so the same module trains.
+ids read on the device only, capturable.  Larger calls -- prefill, big batches -- have ``aqlm_hip_lora_sgmv``
+(aqlm_amd/csrc/lora_sgmv.hip), the same two launches on the matrix unit, one pass per distinct adapter of every 16-row tile, for
+the row counts at which it was measured to win (``SGMV_MAX_ROWS``).  Everything else -- training, host tensors, shapes the kernels
+decline -- runs the adapters as torch ops, differentiable in x, A and B, so the same module trains.
 
 The directory format is PEFT's (``adapter_config.json`` + ``adapter_model.safetensors``) and the parameter names are PEFT's
 (``...q_proj.lora_A.<name>.weight``, ``...q_proj.base_layer.codes``); ``peft`` itself is not needed.
@@ -40,6 +42,16 @@ AQLM_HIP_MAX_LORA_ROWS = 256  # include/aqlm_hip.h: rows one aqlm_hip_lora_bgmv 
 # the route off.
 BGMV_MAX_ROWS = 64
 
+AQLM_HIP_MAX_LORA_SGMV_ROWS = 65536  # include/aqlm_hip.h: rows one aqlm_hip_lora_sgmv call takes
+
+# Calls of SGMV_MIN_ROWS .. SGMV_MAX_ROWS rows run the segmented adapter GEMM (aqlm_hip_lora_sgmv); below, the BGMV route keeps
+# every call it had.  SGMV_MAX_ROWS is the largest of the row counts 96 / 128 / 256 / 512 / 1024 / 2048 / 4096 up to which the
+# captured SGMV route beat the captured torch path on the same block in all three adapter mixes (one adapter, 4 contiguous
+# sequences, 4 adapters interleaved row by row): profiles/lora_sgmv.json, written by `python tools/lora_benchmark.py --prefill`;
+# AQLM_HIP_MAX_LORA_SGMV_ROWS when it won at every measured count, which it did.  0 switches the route off.
+SGMV_MIN_ROWS = 65
+SGMV_MAX_ROWS = AQLM_HIP_MAX_LORA_SGMV_ROWS
+
 _PREFIX = "base_model.model."
 _DTYPES_OK = (torch.float16, torch.bfloat16)
 
@@ -50,6 +62,13 @@ def takes_bgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling
     the entry accepts."""
     return bool(is_cuda and dtype_ok and not grad_needed and not compiling
                 and 1 <= rows <= min(BGMV_MAX_ROWS, AQLM_HIP_MAX_LORA_ROWS) and supported)
+
+
+def takes_sgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling: bool, rows: int, supported: bool) -> bool:
+    """Whether a call that did not take the BGMV route runs the two SGMV launches (else the torch path): the same conditions as
+    ``takes_bgmv_route`` with SGMV_MIN_ROWS..SGMV_MAX_ROWS rows (never more than one launch takes)."""
+    return bool(is_cuda and dtype_ok and not grad_needed and not compiling
+                and SGMV_MIN_ROWS <= rows <= min(SGMV_MAX_ROWS, AQLM_HIP_MAX_LORA_SGMV_ROWS) and supported)
 
 
 class AdapterBank:
@@ -204,21 +223,39 @@ class LoraQuantizedLinear(nn.Module):
             if y2 is not None:
                 self._bgmv(y2, x.reshape(-1, self.in_features), sel if isinstance(sel, str) else self._row_ids(sel, x))
                 return y
+        supported = False
+        if (x.is_cuda and dtype_ok and not grad_needed and not compiling
+                and SGMV_MIN_ROWS <= rows <= min(SGMV_MAX_ROWS, AQLM_HIP_MAX_LORA_SGMV_ROWS)):
+            from .inference_kernels import hip_kernel
+
+            ranks = [a.shape[0] for a, _, _ in weights]
+            supported = (all(r % 8 == 0 for r in ranks) and y.stride(-1) == 1 and y.data_ptr() % 8 == 0
+                         and hip_kernel.lora_sgmv_supported(self.out_features, self.in_features, max(ranks), rows))
+        if takes_sgmv_route(x.is_cuda, dtype_ok, grad_needed, compiling, rows, supported):
+            try:
+                y2 = y.view(-1, self.out_features)
+            except RuntimeError:
+                y2 = None
+            if y2 is not None and y2.stride(0) % 4 == 0:  # y is written in groups of 4 outputs
+                self._bgmv(y2, x.reshape(-1, self.in_features), sel if isinstance(sel, str) else self._row_ids(sel, x),
+                           hip_kernel.lora_sgmv_)
+                return y
         return self._torch_path(y, x, sel, names)
 
-    def _bgmv(self, y2: torch.Tensor, x2: torch.Tensor, sel) -> None:
-        """``sel``: an adapter name, or one bank id per row of ``x2``."""
+    def _bgmv(self, y2: torch.Tensor, x2: torch.Tensor, sel, launch=None) -> None:
+        """``sel``: an adapter name, or one bank id per row of ``x2``.  ``launch``: ``hip_kernel.lora_sgmv_`` for the SGMV route
+        (the same table, ids and geometry); default the BGMV launch."""
         from .inference_kernels import hip_kernel
 
+        launch = hip_kernel.lora_bgmv_ if launch is None else launch
         table, ranks = self._device_table(x2.device)
         if isinstance(sel, str):
             # one adapter for every row: its slot of the table alone, NULL ids, and a grid sized by its own rank
             slot = [n for _, n in self._present()].index(sel)
             words = table.shape[0] // len(ranks)
-            hip_kernel.lora_bgmv_(y2, x2, None, table[slot * words:(slot + 1) * words],
-                                  [1, ranks[slot], self.out_features, self.in_features])
+            launch(y2, x2, None, table[slot * words:(slot + 1) * words], [1, ranks[slot], self.out_features, self.in_features])
             return
-        hip_kernel.lora_bgmv_(y2, x2, self._local_ids(sel), table, [len(ranks), max(ranks), self.out_features, self.in_features])
+        launch(y2, x2, self._local_ids(sel), table, [len(ranks), max(ranks), self.out_features, self.in_features])
 
     def _torch_path(self, y: torch.Tensor, x: torch.Tensor, sel, names: List[str]) -> torch.Tensor:
         """PEFT's formula per adapter of the bank, masked by ``ids == a``: a loop over the bank, not over the ids, so it never

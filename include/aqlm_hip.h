@@ -541,6 +541,37 @@ int aqlm_hip_lora_bgmv(const aqlm_hip_lora_entry* table, int num_adapters, int m
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same adapters at any row count (prefill, large batches): the segmented counterpart of aqlm_hip_lora_bgmv on the matrix
+ * unit, same table, same ids, same two launches.  For every row b < rows with a = ids[b] (NULL: adapter 0), a in
+ * [0, num_adapters) and the entry's rank a multiple of 8 in 8..max_rank, with T the storage type of x and y:
+ *     t[b, r] = sum_k A_a[r, k] * x[b, k]                                      r < rank_a   (fp32)
+ *     hi = round_T(t),  lo = round_T(t - float(hi))
+ *     y[b, i] = round_T(float(y[b, i]) + scaling_a * sum_r B_a[i, r] * (hi[b, r] + lo[b, r]))
+ * t enters the second product as a PAIR of storage-type values (two matrix instructions per step of a sum that is only rank
+ * long), which keeps the adapter term at roughly fp32 accuracy; in fp16 a |t| above 65504 has no such pair and makes the row NaN.
+ * Every other row -- id out of range, or an entry whose rank is no multiple of 8 in 8..max_rank -- is left bit for bit as it was,
+ * and nothing is loaded through its table slot (the id is range-checked before it forms an address).  Rows are cut into tiles of
+ * 16; a tile is served in one pass per DISTINCT valid adapter among its 16 ids, and a row is written exactly once per launch:
+ * per-sequence ids at prefill cost one pass per tile and two at a seam, 16 different adapters in one tile cost 16.  Both grids
+ * depend on rows, max_rank, in_features and out_features only; the sum over in_features is cut by a function of in_features alone
+ * and added in a fixed order, so a row's bits depend on its own x row, its own y row and its adapter, never on the other rows,
+ * their number or their order.  No atomics, stream-ordered, no allocation, no synchronisation (hipGraph-capturable; ids may be
+ * rewritten in place between replays).  Results are NOT bit-equal to aqlm_hip_lora_bgmv -- the sums run in another order -- but
+ * both sit within the same bound of the fp64 value.  `workspace`: fp32, aqlm_hip_lora_sgmv_workspace_bytes(rows, max_rank,
+ * in_features) bytes (at least rows * max_rank * 4), 16-byte aligned.  Columns of y past out_features are not touched.
+ * Argument checks as aqlm_hip_lora_bgmv, in the same order, with rows up to AQLM_HIP_MAX_LORA_SGMV_ROWS; in addition
+ * AQLM_HIP_E_UNSUPPORTED when y is not 8-byte aligned or, at more than one row, y_row_stride % 4 != 0 (y is written in groups of
+ * 4 outputs).  aqlm_hip_lora_sgmv_supported answers for the four sizes beforehand.
+ */
+#define AQLM_HIP_MAX_LORA_SGMV_ROWS 65536
+
+size_t aqlm_hip_lora_sgmv_workspace_bytes(int rows, int max_rank, int in_features); /* 0 when unsupported */
+int aqlm_hip_lora_sgmv_supported(int out_features, int in_features, int max_rank, int rows);
+int aqlm_hip_lora_sgmv(const aqlm_hip_lora_entry* table, int num_adapters, int max_rank, const void* ids, int ids_int64, int rows,
+                       const void* x, long x_row_stride, void* y, long y_row_stride, int out_features, int in_features, int dtype,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the
