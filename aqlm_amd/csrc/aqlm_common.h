@@ -187,5 +187,61 @@ int run(const void* codes, const void* codebook, const void* scales, const void*
 }  // namespace scan
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+// an id array (int64 or int32) is aligned to its element
+inline bool ids_aligned(const void* ids, int ids_int64) { return (reinterpret_cast<uintptr_t>(ids) & (ids_int64 ? 7u : 3u)) == 0; }
+
+// ---------------------------------------------------------------------------------------------
+// Argument checks that the indexed entry points share (routed, routed packed, bucket, grouped, transposed, LoRA).  Each sets the
+// message and returns the code when its condition is violated, else 0; an entry point calls them in the order in which it
+// reports: `if (int e = check_...(who, ...)) return e;`
+// ---------------------------------------------------------------------------------------------
+inline int check_not_null(const char* who, bool all_set) {
+  if (all_set) return 0;
+  set_last_error("%s: null pointer argument", who);
+  return AQLM_HIP_E_INVALID;
+}
+// `what` names the arguments, e.g. "table / bucket"
+inline int check_aligned(const char* who, const char* what, bool ok) {
+  if (ok) return 0;
+  set_last_error("%s: %s misaligned", who, what);
+  return AQLM_HIP_E_INVALID;
+}
+inline int check_experts(const char* who, int num_experts, int num_segments) {
+  if (num_experts >= 1 && num_experts <= AQLM_HIP_MAX_ROUTED_EXPERTS && num_segments >= 1 && num_segments <= 2) return 0;
+  set_last_error("%s: %d experts x %d segments (1..%d x 1..2 supported)", who, num_experts, num_segments, AQLM_HIP_MAX_ROUTED_EXPERTS);
+  return AQLM_HIP_E_INVALID;
+}
+inline int check_pairs(const char* who, int num_pairs, int top_k, int max_pairs) {
+  if (num_pairs >= 1 && num_pairs <= max_pairs && top_k >= 1 && num_pairs % top_k == 0) return 0;
+  set_last_error("%s: %d pairs with top_k %d (1..%d pairs, a multiple of top_k)", who, num_pairs, top_k, max_pairs);
+  return AQLM_HIP_E_INVALID;
+}
+inline int check_sizes(const char* who, int out_features, int in_features, int in_group_size) {
+  if (out_features > 0 && in_features > 0 && in_group_size > 0 && in_features % in_group_size == 0) return 0;
+  set_last_error("%s: bad sizes (out=%d in=%d g=%d)", who, out_features, in_features, in_group_size);
+  return AQLM_HIP_E_INVALID;
+}
+inline int check_dtype(const char* who, int dtype) {
+  if (dtype == AQLM_HIP_F16 || dtype == AQLM_HIP_BF16) return 0;
+  set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
+  return AQLM_HIP_E_UNSUPPORTED;
+}
+inline int check_group_size(const char* who, int in_group_size) {
+  if (in_group_size == 8 || in_group_size == 16) return 0;
+  set_last_error("%s: only codebooks with 8 or 16 features are supported, got %d", who, in_group_size);
+  return AQLM_HIP_E_UNSUPPORTED;
+}
+
+template <int V>
+struct GroupSize {
+  static constexpr int value = V;
+};
+// the tail of an entry point with checked arguments: f(F16{} or BF16{}, GroupSize<8>{} or GroupSize<16>{})
+template <class F>
+inline int dispatch_dtype_group(int dtype, int in_group_size, F&& f) {
+  if (dtype == AQLM_HIP_F16) return in_group_size == 8 ? f(F16{}, GroupSize<8>{}) : f(F16{}, GroupSize<16>{});
+  return in_group_size == 8 ? f(BF16{}, GroupSize<8>{}) : f(BF16{}, GroupSize<16>{});
+}
 
 }  // namespace aqlm

@@ -224,28 +224,11 @@ extern "C" PK_API int aqlm_hip_gemv_1x16_routed_packed(const aqlm_hip_routed_pac
                     aqlm_hip_g16_gemv_1x16_routed_packed(table, geom, num_experts, num_segments, expert_ids, ids_int64, num_pairs, top_k, x,
                                                          x_row_stride, x_per_pair, y, dtype, cells, cells_bytes, stream_));
   static const char* who = "aqlm_hip_gemv_1x16_routed_packed";
-  if (!table || !geom || !expert_ids || !x || !y || !cells) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(table) & 7u) || (reinterpret_cast<uintptr_t>(expert_ids) & (ids_int64 ? 7u : 3u))) {
-    set_last_error("%s: table / expert_ids misaligned", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_experts < 1 || num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS || num_segments < 1 || num_segments > 2) {
-    set_last_error("%s: %d experts x %d segments (1..%d x 1..2 supported)", who, num_experts, num_segments,
-                   AQLM_HIP_MAX_ROUTED_EXPERTS);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_ROUTED_PAIRS || top_k < 1 || num_pairs % top_k != 0) {
-    set_last_error("%s: %d pairs with top_k %d (1..%d pairs, a multiple of top_k)", who, num_pairs, top_k,
-                   AQLM_HIP_MAX_ROUTED_PAIRS);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
+  if (int e = check_not_null(who, table && geom && expert_ids && x && y && cells)) return e;
+  if (int e = check_aligned(who, "table / expert_ids", aligned8(table) && ids_aligned(expert_ids, ids_int64))) return e;
+  if (int e = check_experts(who, num_experts, num_segments)) return e;
+  if (int e = check_pairs(who, num_pairs, top_k, AQLM_HIP_MAX_ROUTED_PAIRS)) return e;
+  if (int e = check_dtype(who, dtype)) return e;
   const int M = geom->out_features, RG = (M + PK_NG - 1) / PK_NG;
   if (geom->in_group_size != PK_G || !packed_shape_ok(M, geom->in_features, PK_G) || geom->rows_per_group != RG ||
       geom->max_waves < 1 || geom->max_waves > PK_MAX_NW) {

@@ -124,36 +124,13 @@ extern "C" int aqlm_hip_gemv_1x16_routed(const aqlm_hip_routed_entry* table, int
                                          long x_row_stride, int x_per_pair, void* y, int out_features, int in_features,
                                          int in_group_size, int dtype, void* stream_) {
   static const char* who = "aqlm_hip_gemv_1x16_routed";
-  if (!table || !expert_ids || !x || !y) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(table) & 7u) || (reinterpret_cast<uintptr_t>(expert_ids) & (ids_int64 ? 7u : 3u))) {
-    set_last_error("%s: table / expert_ids misaligned", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_experts < 1 || num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS || num_segments < 1 || num_segments > 2) {
-    set_last_error("%s: %d experts x %d segments (1..%d x 1..2 supported)", who, num_experts, num_segments,
-                   AQLM_HIP_MAX_ROUTED_EXPERTS);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_ROUTED_PAIRS || top_k < 1 || num_pairs % top_k != 0) {
-    set_last_error("%s: %d pairs with top_k %d (1..%d pairs, a multiple of top_k)", who, num_pairs, top_k,
-                   AQLM_HIP_MAX_ROUTED_PAIRS);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (out_features <= 0 || in_features <= 0 || in_group_size <= 0 || in_features % in_group_size != 0) {
-    set_last_error("%s: bad sizes (out=%d in=%d g=%d)", who, out_features, in_features, in_group_size);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (in_group_size != 8 && in_group_size != 16) {
-    set_last_error("%s: only codebooks with 8 or 16 features are supported, got %d", who, in_group_size);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
+  if (int e = check_not_null(who, table && expert_ids && x && y)) return e;
+  if (int e = check_aligned(who, "table / expert_ids", aligned8(table) && ids_aligned(expert_ids, ids_int64))) return e;
+  if (int e = check_experts(who, num_experts, num_segments)) return e;
+  if (int e = check_pairs(who, num_pairs, top_k, AQLM_HIP_MAX_ROUTED_PAIRS)) return e;
+  if (int e = check_sizes(who, out_features, in_features, in_group_size)) return e;
+  if (int e = check_dtype(who, dtype)) return e;
+  if (int e = check_group_size(who, in_group_size)) return e;
   const int in_groups = in_features / in_group_size;
   const size_t x_row_bytes = (size_t)in_features * 2;
   if (in_groups % 8 != 0 || !aligned16(x) || x_row_stride % 8 != 0 || x_row_bytes > kRoutedMaxXTileBytes ||
@@ -196,7 +173,7 @@ extern "C" int aqlm_hip_gemv_1x16_routed(const aqlm_hip_routed_entry* table, int
   const int rows_per_block = kRoutedWaves * a.rpw;
   const dim3 grid((out_features + rows_per_block - 1) / rows_per_block, num_segments, num_experts);
   hipStream_t stream = (hipStream_t)stream_;
-  if (dtype == AQLM_HIP_F16)
-    return in_group_size == 8 ? dispatch_routed<F16, 8>(nbmax, a, grid, stream) : dispatch_routed<F16, 16>(nbmax, a, grid, stream);
-  return in_group_size == 8 ? dispatch_routed<BF16, 8>(nbmax, a, grid, stream) : dispatch_routed<BF16, 16>(nbmax, a, grid, stream);
+  return dispatch_dtype_group(dtype, in_group_size, [&](auto t, auto g) {
+    return dispatch_routed<decltype(t), decltype(g)::value>(nbmax, a, grid, stream);
+  });
 }

@@ -5,8 +5,9 @@
 //     y[b, i] = round(float(y[b, i]) + scaling_a * sum_r B_a[i, r] * t[b, r])
 // in two launches whose grids depend on the shapes only, in the style of the routed launches (gemv_routed.hip): the ids stay on
 // the device, nothing is synchronised, a captured launch stays valid when the ids change.  Unlike there an id selects a table
-// entry, so it is range-checked BEFORE it forms an address: a row whose id lies outside [0, num_adapters) exits both kernels
-// before its table slot is touched, and its y row is never written.
+// entry: lora_common.h states the rules (range check before the address, ranks that count as "no adapter") and holds them for
+// this file and lora_sgmv.hip; a row without an adapter exits both kernels before its table slot is touched, and its y row is
+// never written.
 //   * shrink: one workgroup per (row, kShrinkRanks ranks); its waves own fixed contiguous shares of K (steps of 64 lanes x 16
 //     bytes), every lane keeps one x piece and kShrinkRanks A pieces in flight per step; the wave sums meet in LDS and are added
 //     in wave order.  A wave per rank would leave 16 waves streaming a whole row of 14336 elements each at rank 16 and one row.
@@ -16,7 +17,7 @@
 // depend on its own x row, its own y row and its adapter -- not on the other rows, their number or their order.
 #include <algorithm>
 
-#include "aqlm_common.h"
+#include "lora_common.h"
 
 namespace aqlm {
 
@@ -24,24 +25,6 @@ constexpr int kShrinkWaves = 8;
 constexpr int kShrinkRanks = 2;   // ranks per workgroup; divides every supported rank (multiples of 8)
 constexpr int kShrinkStep = 512;  // elements of K per wave step: 64 lanes x 16 bytes
 constexpr int kExpandThreads = 256;
-constexpr int kMaxRank = 128;
-
-// the table is read through the constant address space (a uniform address: the fields arrive by s_load), and the pointers it
-// holds are device-global: said through the address space, or every access through them is a FLAT one
-typedef const aqlm_hip_lora_entry __attribute__((address_space(4)))* lora_entry_ptr;
-typedef __attribute__((address_space(1))) const u32x4* lora_gbl_u32x4_ptr;
-
-// id of row b, or -1 when it names no adapter; ids == NULL: adapter 0 for every row
-__device__ __forceinline__ long lora_row_id(const void* ids, int ids_int64, int b, int nadapters) {
-  long id = 0;
-  if (ids) id = ids_int64 ? reinterpret_cast<const long*>(ids)[b] : (long)reinterpret_cast<const int*>(ids)[b];
-  return (id < 0 || id >= (long)nadapters) ? -1 : id;
-}
-
-// rank of an entry as the kernels use it: an entry whose rank is no multiple of 8 in 8..max_rank (a table that does not belong
-// to this launch) counts as rank 0 -- its rows are left alone, and nothing is indexed past the workspace row or with a row
-// length of B that is not whole 16-byte pieces
-__device__ __forceinline__ int lora_rank(int rank, int max_rank) { return (rank < 8 || rank > max_rank || (rank & 7)) ? 0 : rank; }
 
 template <class T>
 __global__ __launch_bounds__(kShrinkWaves * 64) void lora_shrink_kernel(const aqlm_hip_lora_entry* table, const void* ids,
@@ -102,7 +85,7 @@ __global__ __launch_bounds__(kExpandThreads) void lora_expand_kernel(const aqlm_
   if (rank == 0) return;
   const float scaling = ent->scaling;
 
-  __shared__ __attribute__((aligned(16))) float ts[kMaxRank];
+  __shared__ __attribute__((aligned(16))) float ts[kLoraMaxRank];
   if ((int)threadIdx.x < rank) ts[threadIdx.x] = t[(long)b * max_rank + threadIdx.x];
   __syncthreads();
 
@@ -129,11 +112,6 @@ __global__ __launch_bounds__(kExpandThreads) void lora_expand_kernel(const aqlm_
   *yp = T::from_float(fmaf(scaling, acc, T::to_float(y0)));
 }
 
-static bool lora_shape_ok(int out_features, int in_features, int max_rank, int rows) {
-  return out_features >= 1 && in_features >= 8 && in_features % 8 == 0 && max_rank >= 8 && max_rank <= kMaxRank &&
-         max_rank % 8 == 0 && rows >= 1 && rows <= AQLM_HIP_MAX_LORA_ROWS;
-}
-
 template <class T>
 static int launch_lora(const aqlm_hip_lora_entry* table, int nadapters, int max_rank, const void* ids, int ids_int64, int rows,
                        const uint16_t* x, long xs, uint16_t* y, long ys, int M, int K, float* t, hipStream_t stream) {
@@ -153,65 +131,25 @@ static int launch_lora(const aqlm_hip_lora_entry* table, int nadapters, int max_
 using namespace aqlm;
 
 extern "C" size_t aqlm_hip_lora_workspace_bytes(int rows, int max_rank) {
-  if (!lora_shape_ok(1, 8, max_rank, rows)) return 0;
+  if (!lora_shape_ok(1, 8, max_rank, rows, AQLM_HIP_MAX_LORA_ROWS)) return 0;
   return (size_t)rows * (size_t)max_rank * 4;
 }
 
 extern "C" int aqlm_hip_lora_bgmv_supported(int out_features, int in_features, int max_rank, int rows) {
-  return lora_shape_ok(out_features, in_features, max_rank, rows) ? 1 : 0;
+  return lora_shape_ok(out_features, in_features, max_rank, rows, AQLM_HIP_MAX_LORA_ROWS) ? 1 : 0;
 }
 
 extern "C" int aqlm_hip_lora_bgmv(const aqlm_hip_lora_entry* table, int num_adapters, int max_rank, const void* ids, int ids_int64,
                                   int rows, const void* x, long x_row_stride, void* y, long y_row_stride, int out_features,
                                   int in_features, int dtype, void* workspace, size_t workspace_bytes, void* stream_) {
   static const char* who = "aqlm_hip_lora_bgmv";
-  if (!table || !x || !y || !workspace) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(table) & 7u) || (ids && (reinterpret_cast<uintptr_t>(ids) & (ids_int64 ? 7u : 3u))) ||
-      (reinterpret_cast<uintptr_t>(y) & 1u) || !aligned16(workspace)) {
-    set_last_error("%s: table / ids / y / workspace misaligned (8 bytes / the id size / 2 bytes / 16 bytes)", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_adapters < 1 || rows < 1 || out_features < 1 || in_features < 1 || max_rank < 1) {
-    set_last_error("%s: bad sizes (adapters=%d rows=%d out=%d in=%d max_rank=%d)", who, num_adapters, rows, out_features,
-                   in_features, max_rank);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (y_row_stride < out_features || x_row_stride < in_features) {
-    set_last_error("%s: row strides (x %ld, y %ld) shorter than the rows (in=%d, out=%d)", who, x_row_stride, y_row_stride,
-                   in_features, out_features);
-    return AQLM_HIP_E_INVALID;
-  }
-  {
-    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
-    const uintptr_t x1 = x0 + ((uintptr_t)(rows - 1) * (uintptr_t)x_row_stride + (uintptr_t)in_features) * 2;
-    const uintptr_t y1 = y0 + ((uintptr_t)(rows - 1) * (uintptr_t)y_row_stride + (uintptr_t)out_features) * 2;
-    if (x0 < y1 && y0 < x1) {
-      set_last_error("%s: y aliases x (y is read and written in place while other workgroups still read x)", who);
-      return AQLM_HIP_E_INVALID;
-    }
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (!lora_shape_ok(out_features, in_features, max_rank, rows) || !aligned16(x) || (rows > 1 && x_row_stride % 8 != 0)) {
-    set_last_error("%s: shape outside the kernels (rank a multiple of 8 in 8..%d, in_features %% 8 == 0, 1..%d rows, x rows "
-                   "16-byte aligned; got max_rank=%d in=%d rows=%d x stride %ld)", who, kMaxRank, AQLM_HIP_MAX_LORA_ROWS, max_rank,
-                   in_features, rows, x_row_stride);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  const size_t need = aqlm_hip_lora_workspace_bytes(rows, max_rank);
-  if (workspace_bytes < need) {
-    set_last_error("%s: workspace of %zu bytes, %zu bytes needed", who, workspace_bytes, need);
-    return AQLM_HIP_E_INVALID;
-  }
-  hipStream_t stream = (hipStream_t)stream_;
-  if (dtype == AQLM_HIP_F16)
-    return launch_lora<F16>(table, num_adapters, max_rank, ids, ids_int64 ? 1 : 0, rows, (const uint16_t*)x, x_row_stride,
-                            (uint16_t*)y, y_row_stride, out_features, in_features, (float*)workspace, stream);
-  return launch_lora<BF16>(table, num_adapters, max_rank, ids, ids_int64 ? 1 : 0, rows, (const uint16_t*)x, x_row_stride,
-                           (uint16_t*)y, y_row_stride, out_features, in_features, (float*)workspace, stream);
+  if (int e = lora_check_args(who, table, num_adapters, max_rank, ids, ids_int64, rows, x, x_row_stride, y, y_row_stride, out_features,
+                              in_features, dtype, workspace, AQLM_HIP_MAX_LORA_ROWS))
+    return e;
+  if (int e = lora_check_workspace(who, workspace_bytes, aqlm_hip_lora_workspace_bytes(rows, max_rank))) return e;
+  auto go = [&](auto t) {
+    return launch_lora<decltype(t)>(table, num_adapters, max_rank, ids, ids_int64 ? 1 : 0, rows, (const uint16_t*)x, x_row_stride,
+                                    (uint16_t*)y, y_row_stride, out_features, in_features, (float*)workspace, (hipStream_t)stream_);
+  };
+  return dtype == AQLM_HIP_F16 ? go(F16{}) : go(BF16{});
 }

@@ -6,9 +6,9 @@
 //     hi = round_T(t), lo = round_T(t - float(hi))                           T = the storage type
 //     y[b, i] = round_T(float(y[b, i]) + scaling_a * sum_r B_a[i, r] * (hi[b, r] + lo[b, r]))
 // in two launches whose grids depend on rows, max_rank, in_features and out_features only: the ids stay on the device, nothing is
-// synchronised or allocated, a captured launch stays valid when the ids change.  As in lora_bgmv.hip an id is range-checked BEFORE
-// it forms an address, and an entry whose rank is no multiple of 8 in 8..max_rank counts as "no adapter": such rows are never
-// written and nothing is loaded through their table slot.
+// synchronised or allocated, a captured launch stays valid when the ids change.  Which rows have an adapter is decided by the
+// id and rank rules of lora_common.h, shared with lora_bgmv.hip: the others are never written and nothing is loaded through their
+// table slot.
 //
 // Rows are cut into tiles of 16.  A workgroup reads its tile's 16 ids and serves the distinct valid adapters among them one after
 // the other: the first unserved lane's id, the rows that share it by ballot, one pass, until no row is left.  In every pass ALL 16
@@ -30,11 +30,11 @@
 // a fixed order that depends on the shapes only, and the rows and columns of an MFMA do not mix: a row's bits depend on its own x
 // row, its own y row and its adapter.  fp16 only: |t| above 65504 has no hi / lo pair (hi is infinite) and turns the row into NaN.
 #include "gemm_rows16.h"
+#include "lora_common.h"
 
 namespace aqlm {
 
 constexpr int kSgmvWaves = 4;
-constexpr int kSgmvMaxRank = 128;
 constexpr int kSgmvTilesPerWave = 4;                      // neighbouring 16-output tiles of an expand wave: 128 bytes of a y row
 constexpr int kSgmvSpan = kSgmvWaves * kSgmvTilesPerWave;  // 16-output tiles per expand workgroup
 constexpr int kSgmvSliceK = 1024;   // elements of K a shrink workgroup aims at ...
@@ -42,24 +42,8 @@ constexpr int kSgmvMaxSplits = 8;   // ... with at most this many slices (the wo
 constexpr int kSgmvInFlight = 8;    // k-steps a shrink wave loads before it multiplies
 static_assert(kSgmvWaves == 4, "the shrink's LDS sum gives wave w the accumulator register w of every lane");
 
-// the table is read through the constant address space and its pointers are device-global (lora_bgmv.hip)
-typedef const aqlm_hip_lora_entry __attribute__((address_space(4)))* sgmv_entry_ptr;
-typedef __attribute__((address_space(1))) const u32x4* sgmv_gbl_u32x4_ptr;
-
 // slices of K over workgroups: a function of in_features alone
 static inline int sgmv_splits(int K) { return std::min(std::max((K + kSgmvSliceK - 1) / kSgmvSliceK, 1), kSgmvMaxSplits); }
-
-// lanes 0..15: the id of row b0 + lane, or -1 when the row does not exist or names no adapter; lanes 16..63: -1
-__device__ __forceinline__ int sgmv_tile_id(const void* ids, int ids_int64, int b0, int rows, int nadapters, int lane) {
-  const int b = b0 + lane;
-  if (lane >= 16 || b >= rows) return -1;
-  long id = 0;
-  if (ids) id = ids_int64 ? reinterpret_cast<const long*>(ids)[b] : (long)reinterpret_cast<const int*>(ids)[b];
-  return (id < 0 || id >= (long)nadapters) ? -1 : (int)id;
-}
-
-// an entry that does not belong to this launch counts as rank 0 (lora_rank of lora_bgmv.hip)
-__device__ __forceinline__ int sgmv_rank(int rank, int max_rank) { return (rank < 8 || rank > max_rank || (rank & 7)) ? 0 : rank; }
 
 template <class T>
 __device__ __forceinline__ uint32_t sgmv_hi2(float a, float b) {
@@ -78,7 +62,7 @@ __global__ __launch_bounds__(kSgmvWaves * 64) void lora_sgmv_shrink_kernel(const
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int split = blockIdx.x, r0 = blockIdx.y * 16, b0 = blockIdx.z * 16;
-  const int myid = sgmv_tile_id(ids, ids_int64, b0, rows, nadapters, lane);
+  const int myid = lora_tile_id(ids, ids_int64, b0, rows, nadapters, lane);
   uint64_t pending = __builtin_amdgcn_ballot_w64(myid >= 0);
   if (!pending) return;  // uniform over the workgroup: every wave reads the same 16 ids
 
@@ -91,10 +75,10 @@ __global__ __launch_bounds__(kSgmvWaves * 64) void lora_sgmv_shrink_kernel(const
     const int a = __builtin_amdgcn_readlane(myid, (int)__builtin_ctzll(pending));  // the first unserved row's adapter
     const uint64_t match = __builtin_amdgcn_ballot_w64(myid == a);
     pending &= ~match;
-    const sgmv_entry_ptr ent = (sgmv_entry_ptr)(uintptr_t)(table + a);
-    const int rank = sgmv_rank(ent->rank, max_rank);
+    const lora_entry_ptr ent = (lora_entry_ptr)(uintptr_t)(table + a);
+    const int rank = lora_rank(ent->rank, max_rank);
     if (r0 >= rank) continue;  // no adapter at all (rank 0), or a rank tile past this adapter's rank
-    const sgmv_gbl_u32x4_ptr A = (sgmv_gbl_u32x4_ptr)(uintptr_t)ent->a + (long)std::min(r0 + c, rank - 1) * K8;
+    const lora_gbl_u32x4_ptr A = (lora_gbl_u32x4_ptr)(uintptr_t)ent->a + (long)std::min(r0 + c, rank - 1) * K8;
 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < steps_per_wave; s += kSgmvInFlight) {  // kSgmvInFlight k-steps of both operands in flight
@@ -137,7 +121,7 @@ __global__ __launch_bounds__(kSgmvWaves * 64) void lora_sgmv_expand_kernel(const
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tile0 = blockIdx.x * kSgmvSpan, b0 = blockIdx.y * 16;
-  const int myid = sgmv_tile_id(ids, ids_int64, b0, rows, nadapters, lane);
+  const int myid = lora_tile_id(ids, ids_int64, b0, rows, nadapters, lane);
   uint64_t pending = __builtin_amdgcn_ballot_w64(myid >= 0);
   if (!pending) return;
 
@@ -149,16 +133,16 @@ __global__ __launch_bounds__(kSgmvWaves * 64) void lora_sgmv_expand_kernel(const
     const int a = __builtin_amdgcn_readlane(myid, (int)__builtin_ctzll(pending));
     const uint64_t match = __builtin_amdgcn_ballot_w64(myid == a);
     pending &= ~match;
-    const sgmv_entry_ptr ent = (sgmv_entry_ptr)(uintptr_t)(table + a);
-    const int rank = sgmv_rank(ent->rank, max_rank);
+    const lora_entry_ptr ent = (lora_entry_ptr)(uintptr_t)(table + a);
+    const int rank = lora_rank(ent->rank, max_rank);
     if (rank == 0) continue;
     const float scaling = ent->scaling;
     const int pieces = rank >> 3;
 
     // t[b = c][r = 32 ks + 8 q + j] of the tile, slices added in slice order, as the pair hi + lo of storage-type values
-    u32x4 hi[kSgmvMaxRank / 32], lo[kSgmvMaxRank / 32];
+    u32x4 hi[kLoraMaxRank / 32], lo[kLoraMaxRank / 32];
 #pragma unroll
-    for (int ks = 0; ks < kSgmvMaxRank / 32; ++ks) {
+    for (int ks = 0; ks < kLoraMaxRank / 32; ++ks) {
       hi[ks] = lo[ks] = zero;
       if (ks * 4 < pieces) {
         const int piece = ks * 4 + q;
@@ -188,10 +172,10 @@ __global__ __launch_bounds__(kSgmvWaves * 64) void lora_sgmv_expand_kernel(const
     f32x4 acc[kSgmvTilesPerWave];
 #pragma unroll
     for (int j = 0; j < kSgmvTilesPerWave; ++j) {
-      const sgmv_gbl_u32x4_ptr B = (sgmv_gbl_u32x4_ptr)(uintptr_t)ent->b + (long)std::min(i00 + j * 16 + c, M - 1) * pieces;
+      const lora_gbl_u32x4_ptr B = (lora_gbl_u32x4_ptr)(uintptr_t)ent->b + (long)std::min(i00 + j * 16 + c, M - 1) * pieces;
       acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < kSgmvMaxRank / 32; ++ks) {
+      for (int ks = 0; ks < kLoraMaxRank / 32; ++ks) {
         if (ks * 4 < pieces) {
           const int piece = ks * 4 + q;
           const bool live = piece < pieces;
@@ -229,11 +213,6 @@ __global__ __launch_bounds__(kSgmvWaves * 64) void lora_sgmv_expand_kernel(const
   }
 }
 
-static bool sgmv_shape_ok(int out_features, int in_features, int max_rank, int rows) {
-  return out_features >= 1 && in_features >= 8 && in_features % 8 == 0 && max_rank >= 8 && max_rank <= kSgmvMaxRank &&
-         max_rank % 8 == 0 && rows >= 1 && rows <= AQLM_HIP_MAX_LORA_SGMV_ROWS;
-}
-
 template <class T>
 static int launch_sgmv(const aqlm_hip_lora_entry* table, int nadapters, int max_rank, const void* ids, int ids_int64, int rows,
                        const uint16_t* x, long xs, uint16_t* y, long ys, int M, int K, float* t, hipStream_t stream) {
@@ -255,70 +234,30 @@ static int launch_sgmv(const aqlm_hip_lora_entry* table, int nadapters, int max_
 using namespace aqlm;
 
 extern "C" size_t aqlm_hip_lora_sgmv_workspace_bytes(int rows, int max_rank, int in_features) {
-  if (!sgmv_shape_ok(1, in_features, max_rank, rows)) return 0;
+  if (!lora_shape_ok(1, in_features, max_rank, rows, AQLM_HIP_MAX_LORA_SGMV_ROWS)) return 0;
   return (size_t)rows * (size_t)sgmv_splits(in_features) * (size_t)max_rank * 4;
 }
 
 extern "C" int aqlm_hip_lora_sgmv_supported(int out_features, int in_features, int max_rank, int rows) {
-  return sgmv_shape_ok(out_features, in_features, max_rank, rows) ? 1 : 0;
+  return lora_shape_ok(out_features, in_features, max_rank, rows, AQLM_HIP_MAX_LORA_SGMV_ROWS) ? 1 : 0;
 }
 
 extern "C" int aqlm_hip_lora_sgmv(const aqlm_hip_lora_entry* table, int num_adapters, int max_rank, const void* ids, int ids_int64,
                                   int rows, const void* x, long x_row_stride, void* y, long y_row_stride, int out_features,
                                   int in_features, int dtype, void* workspace, size_t workspace_bytes, void* stream_) {
   static const char* who = "aqlm_hip_lora_sgmv";
-  if (!table || !x || !y || !workspace) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(table) & 7u) || (ids && (reinterpret_cast<uintptr_t>(ids) & (ids_int64 ? 7u : 3u))) ||
-      (reinterpret_cast<uintptr_t>(y) & 1u) || !aligned16(workspace)) {
-    set_last_error("%s: table / ids / y / workspace misaligned (8 bytes / the id size / 2 bytes / 16 bytes)", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_adapters < 1 || rows < 1 || out_features < 1 || in_features < 1 || max_rank < 1) {
-    set_last_error("%s: bad sizes (adapters=%d rows=%d out=%d in=%d max_rank=%d)", who, num_adapters, rows, out_features,
-                   in_features, max_rank);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (y_row_stride < out_features || x_row_stride < in_features) {
-    set_last_error("%s: row strides (x %ld, y %ld) shorter than the rows (in=%d, out=%d)", who, x_row_stride, y_row_stride,
-                   in_features, out_features);
-    return AQLM_HIP_E_INVALID;
-  }
-  {
-    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
-    const uintptr_t x1 = x0 + ((uintptr_t)(rows - 1) * (uintptr_t)x_row_stride + (uintptr_t)in_features) * 2;
-    const uintptr_t y1 = y0 + ((uintptr_t)(rows - 1) * (uintptr_t)y_row_stride + (uintptr_t)out_features) * 2;
-    if (x0 < y1 && y0 < x1) {
-      set_last_error("%s: y aliases x (y is read and written in place while other workgroups still read x)", who);
-      return AQLM_HIP_E_INVALID;
-    }
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (!sgmv_shape_ok(out_features, in_features, max_rank, rows) || !aligned16(x) || (rows > 1 && x_row_stride % 8 != 0)) {
-    set_last_error("%s: shape outside the kernels (rank a multiple of 8 in 8..%d, in_features %% 8 == 0, 1..%d rows, x rows "
-                   "16-byte aligned; got max_rank=%d in=%d rows=%d x stride %ld)", who, kSgmvMaxRank, AQLM_HIP_MAX_LORA_SGMV_ROWS,
-                   max_rank, in_features, rows, x_row_stride);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
+  if (int e = lora_check_args(who, table, num_adapters, max_rank, ids, ids_int64, rows, x, x_row_stride, y, y_row_stride, out_features,
+                              in_features, dtype, workspace, AQLM_HIP_MAX_LORA_SGMV_ROWS))
+    return e;
   if ((reinterpret_cast<uintptr_t>(y) & 7u) || (rows > 1 && y_row_stride % 4 != 0)) {
     set_last_error("%s: y rows not 8-byte aligned (y %p, stride %ld elements): the expand writes groups of 4 outputs", who, y,
                    y_row_stride);
     return AQLM_HIP_E_UNSUPPORTED;
   }
-  const size_t need = aqlm_hip_lora_sgmv_workspace_bytes(rows, max_rank, in_features);
-  if (workspace_bytes < need) {
-    set_last_error("%s: workspace of %zu bytes, %zu bytes needed", who, workspace_bytes, need);
-    return AQLM_HIP_E_INVALID;
-  }
-  hipStream_t stream = (hipStream_t)stream_;
-  if (dtype == AQLM_HIP_F16)
-    return launch_sgmv<F16>(table, num_adapters, max_rank, ids, ids_int64 ? 1 : 0, rows, (const uint16_t*)x, x_row_stride,
-                            (uint16_t*)y, y_row_stride, out_features, in_features, (float*)workspace, stream);
-  return launch_sgmv<BF16>(table, num_adapters, max_rank, ids, ids_int64 ? 1 : 0, rows, (const uint16_t*)x, x_row_stride,
-                           (uint16_t*)y, y_row_stride, out_features, in_features, (float*)workspace, stream);
+  if (int e = lora_check_workspace(who, workspace_bytes, aqlm_hip_lora_sgmv_workspace_bytes(rows, max_rank, in_features))) return e;
+  auto go = [&](auto t) {
+    return launch_sgmv<decltype(t)>(table, num_adapters, max_rank, ids, ids_int64 ? 1 : 0, rows, (const uint16_t*)x, x_row_stride,
+                                    (uint16_t*)y, y_row_stride, out_features, in_features, (float*)workspace, (hipStream_t)stream_);
+  };
+  return dtype == AQLM_HIP_F16 ? go(F16{}) : go(BF16{});
 }

@@ -13,22 +13,13 @@
 // aqlm_hip_gemm_1x16_mfma on that expert's rows wherever that op runs the 16-row kernel, and no pair's bits depend on the
 // other pairs (an MFMA output column depends on its own B column only; the tile size changes the number of columns, never
 // their k order).
-#include <algorithm>
-
-#include "aqlm_common.h"
 #include "gemm_rows16.h"
+#include "moe_bucket.h"
 
 namespace aqlm {
 
-// bucket layout (int32): [0] tiles, [1] pairs with an id outside [0, E), [2] pairs with a valid id, [3] 0;
-// then max_tiles x {expert, first, count, 0}; then the pair list [num_pairs] (valid pairs by expert, then the others)
-constexpr int kBucketHeader = 4;
 constexpr int kBucketThreads = 1024;
 constexpr int kBucketWaves = kBucketThreads / 64;
-
-static inline int grouped_max_tiles(int num_pairs, int num_experts, int tile_pairs) {
-  return (num_pairs + tile_pairs - 1) / tile_pairs + std::min(num_experts, num_pairs);
-}
 
 __device__ __forceinline__ int bucket_of(const void* ids, int ids_int64, int p, int nexp) {
   const long id = ids_int64 ? reinterpret_cast<const long*>(ids)[p] : (long)reinterpret_cast<const int*>(ids)[p];
@@ -42,8 +33,8 @@ __global__ __launch_bounds__(kBucketThreads) void moe_bucket_kernel(const void* 
   __shared__ int wcnt[kBucketWaves][NB];  // pairs of bucket b in wave w's share of the current round
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nb = nexp + 1;
-  int4* tiles = reinterpret_cast<int4*>(bucket + kBucketHeader);
-  int* list = bucket + kBucketHeader + 4 * max_tiles;
+  int4* tiles = bucket_tiles(bucket);
+  int* list = bucket_list(bucket, max_tiles);
 
   for (int b = tid; b < nb; b += kBucketThreads) hist[b] = 0;
   __syncthreads();
@@ -139,17 +130,17 @@ template <class T, int G, int NBT, int CPB>
 __global__ __launch_bounds__((R16Lds<NBT, CPB>::WAVES * 64)) void gemm_1x16_grouped_kernel(const GroupedArgs a) {
   const int slot = blockIdx.y, s = blockIdx.z;
   const long ys = (long)a.nseg * a.M;  // pair stride of y
-  const int* list = a.bucket + kBucketHeader + 4 * a.max_tiles;
-  if (slot == 0) {  // the pairs of out-of-range ids get zero rows (from the blocks of slot 0, which every grid has)
-    const int nbad = std::min(a.bucket[1], a.npairs);
-    const int* bad = list + (a.npairs - nbad);
+  const int* list = bucket_list(a.bucket, a.max_tiles);
+  if (slot == 0) {  // the pairs of out-of-range ids get zero rows
+    int nbad;
+    const int* bad = bucket_bad_pairs(a.bucket, list, a.npairs, nbad);
     for (int i = threadIdx.x; i < nbad * 16; i += blockDim.x) {
       const int pr = bad[i >> 4];
       if ((unsigned)pr < (unsigned)a.npairs) a.y[(long)pr * ys + (long)s * a.M + blockIdx.x * 16 + (i & 15)] = 0;
     }
   }
   if (slot >= a.bucket[0]) return;
-  const int4 tile = reinterpret_cast<const int4*>(a.bucket + kBucketHeader)[slot];
+  const int4 tile = bucket_tile(a.bucket, slot);
   const int e = tile.x, first = tile.y, count = tile.z;
   if (e < 0 || e >= a.nexp || count < 1 || count > a.tile_pairs || first < 0 || first > a.npairs - count) return;  // (a foreign bucket)
   const aqlm_hip_routed_entry ent = a.table[e * a.nseg + s];
@@ -203,12 +194,10 @@ static int launch_grouped(const GroupedArgs& a, const R16Plan& r, dim3 grid, hip
 #undef AQLM_GR_CASE
 }
 
-static bool tile_pairs_ok(int t) { return t == 16 || t == 32 || t == 64 || t == 128; }
-
 static bool grouped_supported(int M, int K, int g) {
   if (M <= 0 || K <= 0 || M % 16 != 0 || (g != 8 && g != 16) || K % g != 0) return false;
   R16Plan r;
-  for (int t = 16; t <= 128; t *= 2)
+  for (int t = kTilePairsMin; t <= kTilePairsMax; t *= 2)
     if (!plan_rows16(t, K, g, r)) return false;
   return true;
 }
@@ -221,21 +210,14 @@ extern "C" size_t aqlm_hip_moe_bucket_bytes(int num_pairs, int num_experts, int 
   if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_GROUPED_PAIRS || num_experts < 1 || num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS ||
       !tile_pairs_ok(tile_pairs))
     return 0;
-  const size_t words = kBucketHeader + 4 * (size_t)grouped_max_tiles(num_pairs, num_experts, tile_pairs) + (size_t)num_pairs;
-  return (words * 4 + 15) / 16 * 16;
+  return (bucket_words(num_pairs, num_experts, tile_pairs) * 4 + 15) / 16 * 16;
 }
 
 extern "C" int aqlm_hip_moe_bucket(const void* expert_ids, int ids_int64, int num_pairs, int num_experts, int tile_pairs,
                                    void* bucket, void* stream) {
   static const char* who = "aqlm_hip_moe_bucket";
-  if (!expert_ids || !bucket) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(expert_ids) & (ids_int64 ? 7u : 3u)) || !aligned16(bucket)) {
-    set_last_error("%s: expert_ids / bucket misaligned", who);
-    return AQLM_HIP_E_INVALID;
-  }
+  if (int e = check_not_null(who, expert_ids && bucket)) return e;
+  if (int e = check_aligned(who, "expert_ids / bucket", ids_aligned(expert_ids, ids_int64) && aligned16(bucket))) return e;
   if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_GROUPED_PAIRS || num_experts < 1 || num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS ||
       !tile_pairs_ok(tile_pairs)) {
     set_last_error("%s: %d pairs, %d experts, tiles of %d (1..%d pairs, 1..%d experts, tiles of 16 / 32 / 64 / 128)", who, num_pairs,
@@ -243,7 +225,7 @@ extern "C" int aqlm_hip_moe_bucket(const void* expert_ids, int ids_int64, int nu
     return AQLM_HIP_E_INVALID;
   }
   hipLaunchKernelGGL(moe_bucket_kernel, dim3(1), dim3(kBucketThreads), 0, (hipStream_t)stream, expert_ids, ids_int64 ? 1 : 0,
-                     num_pairs, num_experts, tile_pairs, grouped_max_tiles(num_pairs, num_experts, tile_pairs), (int*)bucket);
+                     num_pairs, num_experts, tile_pairs, bucket_max_tiles(num_pairs, num_experts, tile_pairs), (int*)bucket);
   return check_hip(hipGetLastError(), "moe_bucket launch");
 }
 
@@ -255,36 +237,17 @@ extern "C" int aqlm_hip_gemm_1x16_grouped(const aqlm_hip_routed_entry* table, in
                                           int tile_pairs, int num_pairs, int top_k, const void* x, long x_row_stride, int x_per_pair,
                                           void* y, int out_features, int in_features, int in_group_size, int dtype, void* stream_) {
   static const char* who = "aqlm_hip_gemm_1x16_grouped";
-  if (!table || !bucket || !x || !y) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(table) & 7u) || !aligned16(bucket)) {
-    set_last_error("%s: table / bucket misaligned", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_experts < 1 || num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS || num_segments < 1 || num_segments > 2) {
-    set_last_error("%s: %d experts x %d segments (1..%d x 1..2 supported)", who, num_experts, num_segments,
-                   AQLM_HIP_MAX_ROUTED_EXPERTS);
-    return AQLM_HIP_E_INVALID;
-  }
+  if (int e = check_not_null(who, table && bucket && x && y)) return e;
+  if (int e = check_aligned(who, "table / bucket", aligned8(table) && aligned16(bucket))) return e;
+  if (int e = check_experts(who, num_experts, num_segments)) return e;
   if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_GROUPED_PAIRS || top_k < 1 || num_pairs % top_k != 0 || !tile_pairs_ok(tile_pairs)) {
     set_last_error("%s: %d pairs with top_k %d, tiles of %d (1..%d pairs, a multiple of top_k; tiles of 16 / 32 / 64 / 128)", who,
                    num_pairs, top_k, tile_pairs, AQLM_HIP_MAX_GROUPED_PAIRS);
     return AQLM_HIP_E_INVALID;
   }
-  if (out_features <= 0 || in_features <= 0 || in_group_size <= 0 || in_features % in_group_size != 0) {
-    set_last_error("%s: bad sizes (out=%d in=%d g=%d)", who, out_features, in_features, in_group_size);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (in_group_size != 8 && in_group_size != 16) {
-    set_last_error("%s: only codebooks with 8 or 16 features are supported, got %d", who, in_group_size);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
+  if (int e = check_sizes(who, out_features, in_features, in_group_size)) return e;
+  if (int e = check_dtype(who, dtype)) return e;
+  if (int e = check_group_size(who, in_group_size)) return e;
   R16Plan r;
   if (!grouped_supported(out_features, in_features, in_group_size) || !plan_rows16(tile_pairs, in_features, in_group_size, r) ||
       !aligned16(x) || x_row_stride % 8 != 0) {
@@ -304,13 +267,13 @@ extern "C" int aqlm_hip_gemm_1x16_grouped(const aqlm_hip_routed_entry* table, in
   a.top_k = top_k;
   a.x_per_pair = x_per_pair ? 1 : 0;
   a.tile_pairs = tile_pairs;
-  a.max_tiles = grouped_max_tiles(num_pairs, num_experts, tile_pairs);
+  a.max_tiles = bucket_max_tiles(num_pairs, num_experts, tile_pairs);
   a.M = out_features;
   a.in_groups = in_features / in_group_size;
   a.nsteps = r.nsteps;
   const dim3 grid((unsigned)(out_features / 16), (unsigned)a.max_tiles, (unsigned)num_segments);
   hipStream_t stream = (hipStream_t)stream_;
-  if (dtype == AQLM_HIP_F16)
-    return in_group_size == 8 ? launch_grouped<F16, 8>(a, r, grid, stream) : launch_grouped<F16, 16>(a, r, grid, stream);
-  return in_group_size == 8 ? launch_grouped<BF16, 8>(a, r, grid, stream) : launch_grouped<BF16, 16>(a, r, grid, stream);
+  return dispatch_dtype_group(dtype, in_group_size, [&](auto t, auto g) {
+    return launch_grouped<decltype(t), decltype(g)::value>(a, r, grid, stream);
+  });
 }

@@ -21,19 +21,11 @@
 // Numerics: exact products of storage-type operands, fp32 accumulation in a fixed order (segment, then output row ascending).
 // An MFMA output column depends on its own B column only, so a pair's bits depend on its gy row and its expert alone -- not on
 // the other pairs, the tile size or the slot.
-#include <algorithm>
-
-#include "aqlm_common.h"
 #include "gemm_rows16.h"
+#include "moe_bucket.h"
 
 namespace aqlm {
 namespace {
-
-// the bucket layout and the tile bound of moe_grouped.hip (aqlm_hip_moe_bucket writes it, this file only reads it)
-constexpr int kBwdBucketHeader = 4;
-inline int bwd_max_tiles(int num_pairs, int num_experts, int tile_pairs) {
-  return (num_pairs + tile_pairs - 1) / tile_pairs + std::min(num_experts, num_pairs);
-}
 
 constexpr int kBwdCols = 128;     // columns of gx per block
 constexpr int kBwdRows = 32;      // output rows of W per step (the k of one MFMA)
@@ -71,17 +63,17 @@ __global__ __launch_bounds__(kBwdThreads) void gemm_1x16_grouped_transposed_kern
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = blockIdx.y, col0 = blockIdx.x * kBwdCols;
-  const int* list = a.bucket + kBwdBucketHeader + 4 * a.max_tiles;
-  if (slot == 0) {  // the pairs of out-of-range ids get zero rows (from the blocks of slot 0, which every grid has)
-    const int nbad = std::min(a.bucket[1], a.npairs);
-    const int* bad = list + (a.npairs - nbad);
+  const int* list = bucket_list(a.bucket, a.max_tiles);
+  if (slot == 0) {  // the pairs of out-of-range ids get zero rows
+    int nbad;
+    const int* bad = bucket_bad_pairs(a.bucket, list, a.npairs, nbad);
     for (int i = tid; i < nbad * (kBwdCols / 4); i += kBwdThreads) {
       const int pr = bad[i / (kBwdCols / 4)], c = col0 + (i % (kBwdCols / 4)) * 4;
       if ((unsigned)pr < (unsigned)a.npairs && c < a.K) *reinterpret_cast<f32x4*>(a.gx + (size_t)pr * a.K + c) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
   if (slot >= a.bucket[0]) return;
-  const int4 tile = reinterpret_cast<const int4*>(a.bucket + kBwdBucketHeader)[slot];
+  const int4 tile = bucket_tile(a.bucket, slot);
   const int e = tile.x, first = tile.y, count = tile.z;
   if (e < 0 || e >= a.nexp || count < 1 || count > a.tile_pairs || count > TP || first < 0 || first > a.npairs - count) return;  // (a foreign bucket)
   // from here on every wave runs the same control flow with all lanes on: the transposed reads need EXEC all ones
@@ -266,8 +258,6 @@ int launch_bwd(const BwdArgs& a, dim3 grid, hipStream_t stream) {
   return check_hip(hipGetLastError(), "gemm_1x16_grouped_transposed launch");
 }
 
-bool bwd_tile_pairs_ok(int t) { return t == 16 || t == 32 || t == 64 || t == 128; }
-
 // (columns go in 16-byte pieces of 8 and stores in fours: any K of whole codebook vectors)
 bool bwd_supported(int M, int K, int g) { return M > 0 && K > 0 && M % 16 == 0 && K % 16 == 0 && (g == 8 || g == 16); }
 
@@ -285,36 +275,17 @@ extern "C" int aqlm_hip_gemm_1x16_grouped_transposed(const aqlm_hip_routed_entry
                                                      long gy_pair_stride, void* gx, int out_features, int in_features,
                                                      int in_group_size, int dtype, void* stream_) {
   static const char* who = "aqlm_hip_gemm_1x16_grouped_transposed";
-  if (!table || !bucket || !gy || !gx) {
-    set_last_error("%s: null pointer argument", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(table) & 7u) || !aligned16(bucket)) {
-    set_last_error("%s: table / bucket misaligned", who);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_experts < 1 || num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS || num_segments < 1 || num_segments > 2) {
-    set_last_error("%s: %d experts x %d segments (1..%d x 1..2 supported)", who, num_experts, num_segments,
-                   AQLM_HIP_MAX_ROUTED_EXPERTS);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_GROUPED_PAIRS || !bwd_tile_pairs_ok(tile_pairs)) {
+  if (int e = check_not_null(who, table && bucket && gy && gx)) return e;
+  if (int e = check_aligned(who, "table / bucket", aligned8(table) && aligned16(bucket))) return e;
+  if (int e = check_experts(who, num_experts, num_segments)) return e;
+  if (num_pairs < 1 || num_pairs > AQLM_HIP_MAX_GROUPED_PAIRS || !tile_pairs_ok(tile_pairs)) {
     set_last_error("%s: %d pairs, tiles of %d (1..%d pairs; tiles of 16 / 32 / 64 / 128)", who, num_pairs, tile_pairs,
                    AQLM_HIP_MAX_GROUPED_PAIRS);
     return AQLM_HIP_E_INVALID;
   }
-  if (out_features <= 0 || in_features <= 0 || in_group_size <= 0 || in_features % in_group_size != 0) {
-    set_last_error("%s: bad sizes (out=%d in=%d g=%d)", who, out_features, in_features, in_group_size);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", who, dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (in_group_size != 8 && in_group_size != 16) {
-    set_last_error("%s: only codebooks with 8 or 16 features are supported, got %d", who, in_group_size);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
+  if (int e = check_sizes(who, out_features, in_features, in_group_size)) return e;
+  if (int e = check_dtype(who, dtype)) return e;
+  if (int e = check_group_size(who, in_group_size)) return e;
   if (!bwd_supported(out_features, in_features, in_group_size) || !aligned16(gy) || !aligned16(gx) || gy_pair_stride % 8 != 0 ||
       gy_pair_stride < (long)num_segments * out_features) {
     set_last_error("%s: shape outside the transposed kernel (out=%d in=%d g=%d, gy stride %ld)", who, out_features, in_features,
@@ -331,13 +302,12 @@ extern "C" int aqlm_hip_gemm_1x16_grouped_transposed(const aqlm_hip_routed_entry
   a.nseg = num_segments;
   a.npairs = num_pairs;
   a.tile_pairs = tile_pairs;
-  a.max_tiles = bwd_max_tiles(num_pairs, num_experts, tile_pairs);
+  a.max_tiles = bucket_max_tiles(num_pairs, num_experts, tile_pairs);
   a.M = out_features;
   a.K = in_features;
   a.in_groups = in_features / in_group_size;
   a.msteps = (out_features + kBwdRows - 1) / kBwdRows;
   const dim3 grid((unsigned)((in_features + kBwdCols - 1) / kBwdCols), (unsigned)a.max_tiles, 1u);
   hipStream_t stream = (hipStream_t)stream_;
-  if (dtype == AQLM_HIP_F16) return in_group_size == 8 ? launch_bwd<F16, 8>(a, grid, stream) : launch_bwd<F16, 16>(a, grid, stream);
-  return in_group_size == 8 ? launch_bwd<BF16, 8>(a, grid, stream) : launch_bwd<BF16, 16>(a, grid, stream);
+  return dispatch_dtype_group(dtype, in_group_size, [&](auto t, auto g) { return launch_bwd<decltype(t), decltype(g)::value>(a, grid, stream); });
 }

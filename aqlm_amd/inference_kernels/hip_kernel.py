@@ -572,6 +572,33 @@ def routed_chunks(tokens: int, top_k: int):
     return [(t0, min(tokens, t0 + per)) for t0 in range(0, tokens, per)]
 
 
+def _check_routed_args(input, expert_ids, table, E, S, in_features, top_k, x_per_pair, entry_words, words) -> int:
+    """The id, input and table checks of the two routed ops (``words``: the table length the caller was told) -> tokens."""
+    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
+    T = expert_ids.shape[0]
+    rows = T * top_k if x_per_pair else T
+    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
+        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
+    if table.dtype != torch.int64 or table.numel() != words or words != E * S * entry_words or table.device != input.device:
+        raise ValueError(f"table must be int64 [{E * S * entry_words}] on {input.device}")
+    if expert_ids.device != input.device:
+        raise ValueError("expert_ids must be on the input's device")
+    return T
+
+
+def _routed_launches(x, ids, y, top_k, x_per_pair, what, launch) -> None:
+    """One ``launch(ids pointer, ids_int64, pairs, x pointer, y pointer) -> rc`` per chunk of ``routed_chunks``."""
+    esz = ids.element_size()
+    with _device_guard(x.device):
+        for t0, t1 in routed_chunks(ids.shape[0], top_k):
+            p0 = t0 * top_k
+            rc = launch(ids.data_ptr() + p0 * esz, int(esz == 8), (t1 - t0) * top_k,
+                        x.data_ptr() + (p0 if x_per_pair else t0) * x.stride(0) * 2, y.data_ptr() + p0 * y.stride(0) * 2)
+            if rc:
+                _native.check(rc, what)
+
+
 def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
     """Every (token, expert) pair of one or two 1x16 projections of a mixture-of-experts block in one launch per 64 pairs.
     geometry = [num_experts, num_segments, out_features, in_features, in_group_size, top_k]; ``expert_ids`` [T, top_k] int64 /
@@ -581,32 +608,17 @@ def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
     expert expert_ids[t, j] applied to its x row, bit-identical to code1x16_matmat of that expert on that row."""
     E, S, out_features, in_features, g, top_k = (int(v) for v in geometry)
     dt = _dtype_id(input)
-    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
-        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
-    T = expert_ids.shape[0]
-    rows = T * top_k if x_per_pair else T
-    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
-        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
-    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != input.device:
-        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {input.device}")
-    if expert_ids.device != input.device:
-        raise ValueError("expert_ids must be on the input's device")
+    T = _check_routed_args(input, expert_ids, table, E, S, in_features, top_k, x_per_pair, _native.ROUTED_ENTRY_WORDS,
+                           E * S * _native.ROUTED_ENTRY_WORDS)
     x = _flat_rows(input)
     ids = _c(expert_ids)
     y = torch.empty((T * top_k, S, out_features), dtype=input.dtype, device=input.device)
     if T == 0:
         return y
     stream = _stream_ptr(input.device)
-    esz = ids.element_size()
-    with _device_guard(input.device):
-        for t0, t1 in routed_chunks(T, top_k):
-            p0, npairs = t0 * top_k, (t1 - t0) * top_k
-            xp = x.data_ptr() + (p0 if x_per_pair else t0) * x.stride(0) * 2
-            rc = _lib.aqlm_hip_gemv_1x16_routed(table.data_ptr(), E, S, ids.data_ptr() + p0 * esz, int(esz == 8), npairs, top_k,
-                                                xp, x.stride(0), int(bool(x_per_pair)), y.data_ptr() + p0 * S * out_features * 2,
-                                                out_features, in_features, g, dt, stream)
-            if rc:
-                _native.check(rc, "aqlm routed gemv")
+    _routed_launches(x, ids, y, top_k, x_per_pair, "aqlm routed gemv", lambda idp, i64, npairs, xp, yp: _lib.aqlm_hip_gemv_1x16_routed(
+        table.data_ptr(), E, S, idp, i64, npairs, top_k, xp, x.stride(0), int(bool(x_per_pair)), yp, out_features, in_features, g, dt,
+        stream))
     return y
 
 
@@ -634,13 +646,9 @@ def lora_bgmv_supported(out_features: int, in_features: int, max_rank: int, rows
     return bool(_lib.aqlm_hip_lora_bgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
 
 
-def lora_bgmv_(y, x, ids, table, geometry) -> None:
-    """``y[b] += scaling_a * B_a (A_a x[b])`` with a = ids[b], in place, for every row of a decode batch in two launches
-    (include/aqlm_hip.h, aqlm_hip_lora_bgmv: fp32 sums, the rank-sized intermediate is never rounded, y is rounded once).
-    geometry = [num_adapters, max_rank, out_features, in_features]; ``y`` [rows, out] and ``x`` [rows, in] fp16 / bf16 with unit
-    inner strides; ``ids`` [rows] int64 / int32 on the device (read there only; a row whose id lies outside [0, num_adapters) is
-    left as it is) or None = adapter 0 for every row; ``table`` from ``lora_table``.  The fp32 workspace comes from the caching
-    allocator, so the call can be captured."""
+def _lora_gmv_(y, x, ids, table, geometry, entry, workspace_bytes, what, y_groups_of_4) -> None:
+    """The checks, the workspace and the call of ``lora_bgmv_`` / ``lora_sgmv_``: ``entry`` the native launch,
+    ``workspace_bytes(rows, max_rank, in_features)`` its workspace size."""
     n, max_rank, out_features, in_features = (int(v) for v in geometry)
     dt = _dtype_id(y)
     if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0] or y.shape[1] != out_features or x.shape[1] != in_features:
@@ -649,9 +657,11 @@ def lora_bgmv_(y, x, ids, table, geometry) -> None:
         raise ValueError("x, y and the table must share dtype and device")
     if y.stride(1) != 1:
         raise ValueError("y must have a unit inner stride (it is written in place)")
+    rows = y.shape[0]
+    if y_groups_of_4 and (y.data_ptr() % 8 or (rows > 1 and y.stride(0) % 4)):
+        raise ValueError("y must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written in groups of 4)")
     if table.dtype != torch.int64 or table.numel() != n * _native.LORA_ENTRY_WORDS:
         raise ValueError(f"table must be int64 [{n * _native.LORA_ENTRY_WORDS}]")
-    rows = y.shape[0]
     if ids is not None:
         if ids.dim() != 1 or ids.shape[0] != rows or ids.dtype not in (torch.int64, torch.int32) or ids.device != y.device:
             raise ValueError(f"ids must be [{rows}] int64 / int32 on {y.device}, got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
@@ -659,15 +669,25 @@ def lora_bgmv_(y, x, ids, table, geometry) -> None:
     if rows == 0:
         return
     x = _flat_rows(x)
-    nbytes = _lib.aqlm_hip_lora_workspace_bytes(rows, max_rank)
-    ws = _workspace(y.device, max(nbytes, 16))
+    ws = _workspace(y.device, max(workspace_bytes(rows, max_rank, in_features), 16))
     with _device_guard(y.device):
-        rc = _lib.aqlm_hip_lora_bgmv(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8),
-                                     rows, x.data_ptr(), x.stride(0) if rows > 1 else in_features, y.data_ptr(),
-                                     y.stride(0) if rows > 1 else out_features, out_features, in_features, dt, ws.data_ptr(),
-                                     ws.numel() * 4, _stream_ptr(y.device))
+        rc = entry(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8), rows, x.data_ptr(),
+                   x.stride(0) if rows > 1 else in_features, y.data_ptr(), y.stride(0) if rows > 1 else out_features, out_features,
+                   in_features, dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
     if rc:
-        _native.check(rc, "aqlm lora bgmv")
+        _native.check(rc, what)
+
+
+def lora_bgmv_(y, x, ids, table, geometry) -> None:
+    """``y[b] += scaling_a * B_a (A_a x[b])`` with a = ids[b], in place, for every row of a decode batch in two launches
+    (include/aqlm_hip.h, aqlm_hip_lora_bgmv: fp32 sums, the rank-sized intermediate is never rounded, y is rounded once).
+    geometry = [num_adapters, max_rank, out_features, in_features]; ``y`` [rows, out] and ``x`` [rows, in] fp16 / bf16 with unit
+    inner strides; ``ids`` [rows] int64 / int32 on the device (read there only; a row whose id lies outside [0, num_adapters) is
+    left as it is) or None = adapter 0 for every row; ``table`` from ``lora_table``.  The fp32 workspace comes from the caching
+    allocator, so the call can be captured."""
+    _lora_gmv_(y, x, ids, table, geometry, _lib.aqlm_hip_lora_bgmv,
+               lambda rows, max_rank, in_features: _lib.aqlm_hip_lora_workspace_bytes(rows, max_rank),
+               "aqlm lora bgmv", y_groups_of_4=False)
 
 
 def lora_sgmv_supported(out_features: int, in_features: int, max_rank: int, rows: int) -> bool:
@@ -680,35 +700,8 @@ def lora_sgmv_(y, x, ids, table, geometry) -> None:
     as ``lora_bgmv_``; in addition ``y`` must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written
     in groups of 4 outputs).  Not bit-equal to ``lora_bgmv_``: the sums run in another order, and the rank-sized intermediate
     enters the second product as a pair of storage-type values."""
-    n, max_rank, out_features, in_features = (int(v) for v in geometry)
-    dt = _dtype_id(y)
-    if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0] or y.shape[1] != out_features or x.shape[1] != in_features:
-        raise ValueError(f"y must be [rows, {out_features}] and x [rows, {in_features}], got {tuple(y.shape)} / {tuple(x.shape)}")
-    if x.dtype != y.dtype or x.device != y.device or table.device != y.device:
-        raise ValueError("x, y and the table must share dtype and device")
-    if y.stride(1) != 1:
-        raise ValueError("y must have a unit inner stride (it is written in place)")
-    rows = y.shape[0]
-    if y.data_ptr() % 8 or (rows > 1 and y.stride(0) % 4):
-        raise ValueError("y must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written in groups of 4)")
-    if table.dtype != torch.int64 or table.numel() != n * _native.LORA_ENTRY_WORDS:
-        raise ValueError(f"table must be int64 [{n * _native.LORA_ENTRY_WORDS}]")
-    if ids is not None:
-        if ids.dim() != 1 or ids.shape[0] != rows or ids.dtype not in (torch.int64, torch.int32) or ids.device != y.device:
-            raise ValueError(f"ids must be [{rows}] int64 / int32 on {y.device}, got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
-        ids = _c(ids)
-    if rows == 0:
-        return
-    x = _flat_rows(x)
-    nbytes = _lib.aqlm_hip_lora_sgmv_workspace_bytes(rows, max_rank, in_features)
-    ws = _workspace(y.device, max(nbytes, 16))
-    with _device_guard(y.device):
-        rc = _lib.aqlm_hip_lora_sgmv(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8),
-                                     rows, x.data_ptr(), x.stride(0) if rows > 1 else in_features, y.data_ptr(),
-                                     y.stride(0) if rows > 1 else out_features, out_features, in_features, dt, ws.data_ptr(),
-                                     ws.numel() * 4, _stream_ptr(y.device))
-    if rc:
-        _native.check(rc, "aqlm lora sgmv")
+    _lora_gmv_(y, x, ids, table, geometry, _lib.aqlm_hip_lora_sgmv, _lib.aqlm_hip_lora_sgmv_workspace_bytes, "aqlm lora sgmv",
+               y_groups_of_4=True)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -809,17 +802,7 @@ def code1x16_moe_matmat_packed(input, expert_ids, table, geometry, x_per_pair):
         raise ValueError(f"geometry must hold {ROUTED_PACKED_GEOMETRY_INTS} ints (shape + the tail of routed_packed_table)")
     E, S, out_features, in_features, g, top_k, rpg, max_waves, slice_first, lds_bytes, words = (int(v) for v in geometry)
     dt = _dtype_id(input)
-    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
-        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
-    T = expert_ids.shape[0]
-    rows = T * top_k if x_per_pair else T
-    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
-        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
-    if (table.dtype != torch.int64 or table.numel() != words or words != E * S * _native.ROUTED_PACKED_ENTRY_WORDS
-            or table.device != input.device):
-        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_PACKED_ENTRY_WORDS}] on {input.device}")
-    if expert_ids.device != input.device:
-        raise ValueError("expert_ids must be on the input's device")
+    T = _check_routed_args(input, expert_ids, table, E, S, in_features, top_k, x_per_pair, _native.ROUTED_PACKED_ENTRY_WORDS, words)
     x = _flat_rows(input)
     if x.data_ptr() % 16 or (x.stride(0) * 2) % 16:
         x = x.clone(memory_format=torch.contiguous_format)
@@ -829,20 +812,12 @@ def code1x16_moe_matmat_packed(input, expert_ids, table, geometry, x_per_pair):
         return y
     geom = _native.RoutedPackedGeometry(out_features, in_features, g, rpg, max_waves, slice_first, lds_bytes, 0)
     stream = _stream_ptr(input.device)
-    esz = ids.element_size()
-    chunks = routed_chunks(T, top_k)
-    max_pairs = max(t1 - t0 for t0, t1 in chunks) * top_k
+    max_pairs = max(t1 - t0 for t0, t1 in routed_chunks(T, top_k)) * top_k
     cells = routed_packed_cells(input.device, table.data_ptr(), max_pairs * S * out_features * 8)
-    with _device_guard(input.device):
-        for t0, t1 in chunks:
-            p0, npairs = t0 * top_k, (t1 - t0) * top_k
-            xp = x.data_ptr() + (p0 if x_per_pair else t0) * x.stride(0) * 2
-            rc = _lib.aqlm_hip_gemv_1x16_routed_packed(table.data_ptr(), ctypes.byref(geom), E, S, ids.data_ptr() + p0 * esz,
-                                                       int(esz == 8), npairs, top_k, xp, x.stride(0), int(bool(x_per_pair)),
-                                                       y.data_ptr() + p0 * S * out_features * 2, dt, cells.data_ptr(),
-                                                       cells.numel() * 8, stream)
-            if rc:
-                _native.check(rc, "aqlm routed packed gemv")
+    _routed_launches(x, ids, y, top_k, x_per_pair, "aqlm routed packed gemv",
+                     lambda idp, i64, npairs, xp, yp: _lib.aqlm_hip_gemv_1x16_routed_packed(
+                         table.data_ptr(), ctypes.byref(geom), E, S, idp, i64, npairs, top_k, xp, x.stride(0), int(bool(x_per_pair)),
+                         yp, dt, cells.data_ptr(), cells.numel() * 8, stream))
     return y
 
 
@@ -888,6 +863,14 @@ def moe_bucket(expert_ids, num_experts, tile_pairs):
     return bucket
 
 
+def _check_grouped_args(table, bucket, E, S, P, tile_pairs, device) -> None:
+    """The table and bucket checks of the grouped forward and its transposed op."""
+    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != device:
+        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {device}")
+    if bucket.dtype != torch.int32 or bucket.numel() != _bucket_words(P, E, tile_pairs) or bucket.device != device:
+        raise ValueError("bucket must come from moe_bucket with the same pairs, experts and tile size")
+
+
 def code1x16_moe_matmat_grouped(input, bucket, table, geometry, x_per_pair):
     """``code1x16_moe_matmat`` for any number of pairs, on the expert-grouped 16-row MFMA kernel.  geometry = [num_experts,
     num_segments, out_features, in_features, in_group_size, top_k, tile_pairs, num_pairs]; ``bucket`` from ``moe_bucket`` with
@@ -901,10 +884,7 @@ def code1x16_moe_matmat_grouped(input, bucket, table, geometry, x_per_pair):
     rows = P if x_per_pair else P // top_k
     if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
         raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
-    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != input.device:
-        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {input.device}")
-    if bucket.dtype != torch.int32 or bucket.numel() != _bucket_words(P, E, tile_pairs) or bucket.device != input.device:
-        raise ValueError("bucket must come from moe_bucket with the same pairs, experts and tile size")
+    _check_grouped_args(table, bucket, E, S, P, tile_pairs, input.device)
     y = torch.empty((P, S, out_features), dtype=input.dtype, device=input.device)
     if P == 0:
         return y
@@ -932,10 +912,7 @@ def code1x16_moe_matmat_grouped_transposed(grad_output, bucket, table, geometry)
     dt = _dtype_id(grad_output)
     if grad_output.dim() != 3 or tuple(grad_output.shape) != (P, S, out_features):
         raise ValueError(f"grad_output must be [{P}, {S}, {out_features}], got {tuple(grad_output.shape)}")
-    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != grad_output.device:
-        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {grad_output.device}")
-    if bucket.dtype != torch.int32 or bucket.numel() != _bucket_words(P, E, tile_pairs) or bucket.device != grad_output.device:
-        raise ValueError("bucket must come from moe_bucket with the same pairs, experts and tile size")
+    _check_grouped_args(table, bucket, E, S, P, tile_pairs, grad_output.device)
     gx = torch.empty((P, in_features), dtype=torch.float32, device=grad_output.device)
     if P == 0:
         return gx
