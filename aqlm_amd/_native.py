@@ -157,6 +157,10 @@ SIGNATURES = {
     "aqlm_hip_lora_workspace_bytes": (_sz, [_ci, _ci]),
     "aqlm_hip_lora_bgmv_supported": (_ci, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_lora_bgmv": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _vp, _cl, _vp, _cl, _ci, _ci, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_lora_bgmv_routed_workspace_bytes": (_sz, [_ci, _ci, _ci]),
+    "aqlm_hip_lora_bgmv_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_bgmv_routed": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _vp, _sz,
+                                  _vp]),
     "aqlm_hip_lora_sgmv_workspace_bytes": (_sz, [_ci, _ci, _ci]),
     "aqlm_hip_lora_sgmv_supported": (_ci, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_lora_sgmv": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _vp, _cl, _vp, _cl, _ci, _ci, _ci, _vp, _sz, _vp]),

@@ -1,4 +1,5 @@
-// What the two LoRA launches share (lora_bgmv.hip: per-row matvec; lora_sgmv.hip: segmented MFMA GEMM): the device contract of
+// What the LoRA launches share (lora_bgmv.hip: per-row matvec; lora_bgmv_routed.hip: the same per (token, expert) pair of a
+// mixture-of-experts block; lora_sgmv.hip: segmented MFMA GEMM): the device contract of
 // the adapter table and the ids, and the argument checks of the entry points.
 //
 // The contract: an id selects a table entry, so it is range-checked BEFORE it forms an address -- a row whose id lies outside
@@ -42,10 +43,14 @@ inline bool lora_shape_ok(int out_features, int in_features, int max_rank, int r
          max_rank % 8 == 0 && rows >= 1 && rows <= max_rows;
 }
 
-// the argument checks of both entry points up to the workspace size, in the order in which they report
+// the argument checks of the entry points up to the workspace size, in the order in which they report.  x_rows / y_rows: how many
+// rows x and y hold when that is not `rows` (the routed launch: token or pair rows of x, a y row per pair and projection)
 inline int lora_check_args(const char* who, const aqlm_hip_lora_entry* table, int num_adapters, int max_rank, const void* ids,
                            int ids_int64, int rows, const void* x, long x_row_stride, const void* y, long y_row_stride,
-                           int out_features, int in_features, int dtype, const void* workspace, int max_rows) {
+                           int out_features, int in_features, int dtype, const void* workspace, int max_rows, int x_rows = 0,
+                           int y_rows = 0) {
+  if (x_rows <= 0) x_rows = rows;
+  if (y_rows <= 0) y_rows = rows;
   if (int e = check_not_null(who, table && x && y && workspace)) return e;
   if (!aligned8(table) || (ids && !ids_aligned(ids, ids_int64)) || (reinterpret_cast<uintptr_t>(y) & 1u) || !aligned16(workspace)) {
     set_last_error("%s: table / ids / y / workspace misaligned (8 bytes / the id size / 2 bytes / 16 bytes)", who);
@@ -63,15 +68,15 @@ inline int lora_check_args(const char* who, const aqlm_hip_lora_entry* table, in
   }
   {
     const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
-    const uintptr_t x1 = x0 + ((uintptr_t)(rows - 1) * (uintptr_t)x_row_stride + (uintptr_t)in_features) * 2;
-    const uintptr_t y1 = y0 + ((uintptr_t)(rows - 1) * (uintptr_t)y_row_stride + (uintptr_t)out_features) * 2;
+    const uintptr_t x1 = x0 + ((uintptr_t)(x_rows - 1) * (uintptr_t)x_row_stride + (uintptr_t)in_features) * 2;
+    const uintptr_t y1 = y0 + ((uintptr_t)(y_rows - 1) * (uintptr_t)y_row_stride + (uintptr_t)out_features) * 2;
     if (x0 < y1 && y0 < x1) {
       set_last_error("%s: y aliases x (y is read and written in place while other workgroups still read x)", who);
       return AQLM_HIP_E_INVALID;
     }
   }
   if (int e = check_dtype(who, dtype)) return e;
-  if (!lora_shape_ok(out_features, in_features, max_rank, rows, max_rows) || !aligned16(x) || (rows > 1 && x_row_stride % 8 != 0)) {
+  if (!lora_shape_ok(out_features, in_features, max_rank, rows, max_rows) || !aligned16(x) || (x_rows > 1 && x_row_stride % 8 != 0)) {
     set_last_error("%s: shape outside the kernels (rank a multiple of 8 in 8..%d, in_features %% 8 == 0, 1..%d rows, x rows "
                    "16-byte aligned; got max_rank=%d in=%d rows=%d x stride %ld)", who, kLoraMaxRank, max_rows, max_rank,
                    in_features, rows, x_row_stride);

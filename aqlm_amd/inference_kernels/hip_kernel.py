@@ -705,6 +705,87 @@ def lora_sgmv_(y, x, ids, table, geometry) -> None:
 
 
 # ------------------------------------------------------------------------------------------------------
+# LoRA adapters on the routed experts of a mixture-of-experts block (aqlm_hip_lora_bgmv_routed; aqlm_amd/lora.py
+# LoraQuantizedMixtralExperts is the module-level interface)
+# ------------------------------------------------------------------------------------------------------
+def lora_routed_table(entries, device) -> torch.Tensor:
+    """The device-resident table of aqlm_hip_lora_bgmv_routed: ``entries[a][e][s]`` is ``(A [rank, in], B [out, rank], scaling)`` or
+    ``None`` (adapter a has no weights for projection s of expert e: a zero entry, "no adapter") -> int64 [A * E * S * 3] holding
+    the aqlm_hip_lora_entry structs, entry [(a * E + e) * S + s].  Same checks, same ownership rules as ``lora_table``: raw
+    addresses, the caller keeps the tensors alive and rebuilds the table when one moves or is written.  Never while a hipGraph
+    is being captured."""
+    flat = [ent for per_adapter in entries for per_expert in per_adapter for ent in per_expert]
+    E = len(entries[0]) if entries else 0
+    S = len(entries[0][0]) if E else 0
+    if any(len(pa) != E or any(len(pe) != S for pe in pa) for pa in entries):
+        raise ValueError("lora routed table: entries must be [adapters][experts][segments]")
+    structs = (_native.LoraEntry * len(flat))()
+    for ent, item in zip(structs, flat):
+        if item is None:
+            continue  # ctypes zero-fills: rank 0, null pointers
+        a, b, scaling = item
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.dtype != b.dtype:
+            raise ValueError(f"lora table: A must be [rank, in] and B [out, rank] of one dtype, got {tuple(a.shape)} / {tuple(b.shape)}")
+        for t in (a, b):
+            if not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError("lora table: A and B must be contiguous and 16-byte aligned")
+        ent.a, ent.b, ent.rank, ent.scaling = a.data_ptr(), b.data_ptr(), int(a.shape[0]), float(scaling)
+    words = torch.frombuffer(bytearray(bytes(structs)), dtype=torch.int64) if len(flat) else torch.empty(0, dtype=torch.int64)
+    return words.to(device)
+
+
+def lora_bgmv_routed_supported(out_features: int, in_features: int, max_rank: int, num_pairs: int, num_experts: int,
+                               num_segments: int) -> bool:
+    return bool(_lib.aqlm_hip_lora_bgmv_routed_supported(int(out_features), int(in_features), int(max_rank), int(num_pairs),
+                                                         int(num_experts), int(num_segments)))
+
+
+def lora_bgmv_routed_(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair) -> None:
+    """``y[p, s] += scaling * B (A x_row(p))`` with the adapter of ``table`` entry (adapter_ids[p // top_k], expert_ids[p], s), in
+    place, for every (token, expert) pair and projection of a mixture-of-experts launch in two launches (include/aqlm_hip.h,
+    aqlm_hip_lora_bgmv_routed; bit-identical per row to ``lora_bgmv_`` with that entry as a one-slot table).
+    geometry = [num_adapters, num_experts, num_segments, max_rank, out_features, in_features, top_k]; ``y`` contiguous
+    [T * top_k, num_segments, out] (or [T * top_k, out] with one segment), the output of the routed / grouped ops; ``x`` [T, in]
+    (token rows, ``x_per_pair`` False) or [T * top_k, in] (pair rows) with a unit inner stride; ``adapter_ids`` [T] int64 / int32 on
+    the device or None = adapter 0; ``expert_ids`` [T, top_k] int64 / int32 on the device; both are read on the device only, and a
+    pair with either id out of range is left as it is.  ``table`` from ``lora_routed_table``.  At most MAX_LORA_ROWS pairs per
+    call.  The fp32 workspace comes from the caching allocator, so the call can be captured."""
+    n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
+    dt = _dtype_id(y)
+    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
+    T = expert_ids.shape[0]
+    P = T * top_k
+    rows = P if x_per_pair else T
+    if tuple(y.shape) not in ((P, S, out_features),) + (((P, out_features),) if S == 1 else ()) or not y.is_contiguous():
+        raise ValueError(f"y must be contiguous [{P}, {S}, {out_features}], got {tuple(y.shape)} with strides {y.stride()}")
+    if x.dim() != 2 or tuple(x.shape) != (rows, in_features):
+        raise ValueError(f"x must be [{rows}, {in_features}], got {tuple(x.shape)}")
+    if x.dtype != y.dtype or x.device != y.device or table.device != y.device or expert_ids.device != y.device:
+        raise ValueError("x, y, expert_ids and the table must share a device, x and y a dtype")
+    if table.dtype != torch.int64 or table.numel() != n * E * S * _native.LORA_ENTRY_WORDS:
+        raise ValueError(f"table must be int64 [{n * E * S * _native.LORA_ENTRY_WORDS}]")
+    if adapter_ids is not None:
+        if (adapter_ids.dim() != 1 or adapter_ids.shape[0] != T or adapter_ids.dtype not in (torch.int64, torch.int32)
+                or adapter_ids.device != y.device):
+            raise ValueError(f"adapter_ids must be [{T}] int64 / int32 on {y.device}, got {tuple(adapter_ids.shape)} "
+                             f"{adapter_ids.dtype} on {adapter_ids.device}")
+        adapter_ids = _c(adapter_ids)
+    if P == 0:
+        return
+    x = _flat_rows(x)
+    eids = _c(expert_ids)
+    ws = _workspace(y.device, max(_lib.aqlm_hip_lora_bgmv_routed_workspace_bytes(P, S, max_rank), 16))
+    with _device_guard(y.device):
+        rc = _lib.aqlm_hip_lora_bgmv_routed(
+            table.data_ptr(), n, E, S, max_rank, _ptr(adapter_ids), int(adapter_ids is not None and adapter_ids.element_size() == 8),
+            eids.data_ptr(), int(eids.element_size() == 8), P, top_k, x.data_ptr(), x.stride(0) if rows > 1 else in_features,
+            int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
+    if rc:
+        _native.check(rc, "aqlm lora bgmv routed")
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
@@ -1875,6 +1956,11 @@ def _fake_lora_bgmv(y, x, ids, table, geometry):
 _LIB.define("lora_bgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
 _LIB.impl("lora_bgmv_", lora_bgmv_, "CUDA")
 torch.library.register_fake("aqlm::lora_bgmv_")(_fake_lora_bgmv)
+
+_LIB.define("lora_bgmv_routed_(Tensor(a!) y, Tensor x, Tensor? adapter_ids, Tensor expert_ids, Tensor table, int[] geometry, "
+            "bool x_per_pair) -> ()")
+_LIB.impl("lora_bgmv_routed_", lora_bgmv_routed_, "CUDA")
+torch.library.register_fake("aqlm::lora_bgmv_routed_")(lambda y, x, adapter_ids, expert_ids, table, geometry, x_per_pair: None)
 
 _LIB.define("lora_sgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
 _LIB.impl("lora_sgmv_", lora_sgmv_, "CUDA")

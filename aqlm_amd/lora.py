@@ -2,8 +2,9 @@
 
 An adapter cannot be merged into an AQLM base -- the weights exist as codes + codebooks only -- so a fine-tuned AQLM model keeps
 its adapters at inference, at every token.  ``attach_adapters(model, {...})`` wraps the targeted dense ``QuantizedLinear`` layers
-(attention and MLP projections, the attention projections of Mixtral included; adapters on the routed experts are not covered) in
-``LoraQuantizedLinear`` and returns the ``AdapterBank`` that says which adapter serves which row:
+(attention and MLP projections, the attention projections of Mixtral included) in ``LoraQuantizedLinear``, every
+``QuantizedMixtralExperts`` block whose experts an adapter targets (``...experts.<e>.w1`` / ``w2`` / ``w3``) in
+``LoraQuantizedMixtralExperts``, and returns the ``AdapterBank`` that says which adapter serves which row:
 
     bank = aqlm.lora.attach_adapters(model, {"math": "adapters/math", "code": "adapters/code"})
     bank.select("math")            # every row
@@ -15,6 +16,15 @@ ids read on the device only, capturable.  Larger calls -- prefill, big batches -
 (aqlm_amd/csrc/lora_sgmv.hip), the same two launches on the matrix unit, one pass per distinct adapter of every 16-row tile, for
 the row counts at which it was measured to win (``SGMV_MAX_ROWS``).  Everything else -- training, host tensors, shapes the kernels
 decline -- runs the adapters as torch ops, differentiable in x, A and B, so the same module trains.
+
+Adapters on the ROUTED EXPERTS of a Mixtral block ride on whichever launches the block takes: for up to
+``ROUTED_BGMV_MAX_PAIRS`` (token, expert) pairs ``aqlm_hip_lora_bgmv_routed`` (aqlm_amd/csrc/lora_bgmv_routed.hip) adds them in place to
+the output of the gate / up launch and of the down launch -- two launches each, adapter ids and expert ids read on the device only,
+capturable --; every other call (more pairs, a gradient needed, host tensors, ``torch.compile``) runs PEFT's formula per (adapter,
+expert) as masked torch ops in fp32 without a host sync, differentiable in x, A and B, so expert adapters serve prefill and train.  Their
+``state_dict()`` keys are ``<block>.base_layer.<e>.<w>.codes``, ``<block>.lora_A.<name>.<e>.<w>.weight`` and
+``<block>.lora_B.<name>.<e>.<w>.weight`` (PEFT has no per-expert module convention for fused experts to follow); adapter FILES name
+expert targets by the published layout, ``...block_sparse_moe.experts.<e>.w1.lora_A.weight``, or with ``.mlp.`` in its place.
 
 The directory format is PEFT's (``adapter_config.json`` + ``adapter_model.safetensors``) and the parameter names are PEFT's
 (``...q_proj.lora_A.<name>.weight``, ``...q_proj.base_layer.codes``); ``peft`` itself is not needed.
@@ -52,6 +62,15 @@ AQLM_HIP_MAX_LORA_SGMV_ROWS = 65536  # include/aqlm_hip.h: rows one aqlm_hip_lor
 SGMV_MIN_ROWS = 65
 SGMV_MAX_ROWS = AQLM_HIP_MAX_LORA_SGMV_ROWS
 
+# (token, expert) pairs up to which a call on the routed experts runs aqlm_hip_lora_bgmv_routed; beyond it, the torch path.  A
+# measured route constant (profiles/lora_moe.json, written by `python tools/lora_moe_benchmark.py`): the largest
+# of the pair counts 2 / 4 / 8 / 16 / 32 / 64 / 128 / 256 (T = 1 .. 128 at top_k 2) up to which the captured block with the HIP
+# route replayed faster than the captured block with the torch path at every smaller count too, in both adapter mixes (one
+# adapter; four adapters mixed per token), on a Mixtral-8x7B-shaped prepacked block with rank-16 adapters on w1 / w2 / w3 of all
+# experts.  Measured: it won at every count in both mixes (one token: 119.3 against 843 us captured, bare block 90.4; four adapters
+# over 128 tokens: 1707 against 6203 us), so the constant is the launch's own limit.  0 switches the route off.
+ROUTED_BGMV_MAX_PAIRS = 256
+
 _PREFIX = "base_model.model."
 _DTYPES_OK = (torch.float16, torch.bfloat16)
 
@@ -71,12 +90,19 @@ def takes_sgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling
                 and SGMV_MIN_ROWS <= rows <= min(SGMV_MAX_ROWS, AQLM_HIP_MAX_LORA_SGMV_ROWS) and supported)
 
 
+def takes_routed_bgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling: bool, pairs: int, supported: bool) -> bool:
+    """Whether a call on the routed experts runs the two launches of aqlm_hip_lora_bgmv_routed (else the torch path): the conditions
+    of ``takes_bgmv_route`` with 1..ROUTED_BGMV_MAX_PAIRS (token, expert) pairs (never more than one launch takes)."""
+    return bool(is_cuda and dtype_ok and not grad_needed and not compiling
+                and 1 <= pairs <= min(ROUTED_BGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_ROWS) and supported)
+
+
 class AdapterBank:
     """The adapters attached to one model and the current selection.  ``names[i]`` is the adapter that id ``i`` selects."""
 
     def __init__(self, names: List[str]):
         self.names: List[str] = list(names)
-        self.layers: List["LoraQuantizedLinear"] = []
+        self.layers: List[Union["LoraQuantizedLinear", "LoraQuantizedMixtralExperts"]] = []
         self.selection: Union[None, str, torch.Tensor] = None
         self._replaced: List[Tuple[nn.Module, str, nn.Module]] = []  # (parent, child name, the original module)
 
@@ -276,6 +302,229 @@ class LoraQuantizedLinear(nn.Module):
         return "adapters=" + ", ".join(f"{n} (r={self.lora_A[n].weight.shape[0]}, scaling={self.scaling[n]:g})" for n in self.lora_A)
 
 
+_EXPERT_SEGMENTS = (("w1", "w3"), ("w2",))  # the projections of the gate / up launch and of the down launch
+
+
+class LoraQuantizedMixtralExperts(nn.Module):
+    """An unchanged ``QuantizedMixtralExperts`` (``base_layer``, the very object) plus LoRA adapters on its experts' projections:
+    ``lora_A[name][e][w]`` / ``lora_B[name][e][w]`` (e = "0" .. "E-1", w = "w1" / "w2" / "w3") are bias-free ``nn.Linear`` and
+    ``scaling[name]`` the factor; an adapter may cover some experts and some projections only.  Same call signature as the block
+    it replaces.  Which adapter serves which TOKEN is the bank's selection: a name, or one id per row of the [T, H] input, or
+    one id per sequence (T a multiple of their number: broadcast over T / n consecutive rows on the device)."""
+
+    def __init__(self, base_layer, bank: Optional[AdapterBank] = None):
+        super().__init__()
+        from .moe import QuantizedMixtralExperts
+
+        if not isinstance(base_layer, QuantizedMixtralExperts):
+            raise TypeError(f"LoraQuantizedMixtralExperts wraps a QuantizedMixtralExperts, got {type(base_layer).__name__}")
+        self.base_layer = base_layer
+        self.lora_A = nn.ModuleDict()
+        self.lora_B = nn.ModuleDict()
+        self.scaling: Dict[str, float] = {}
+        self.bank = bank if bank is not None else AdapterBank([])
+        self.bank.layers.append(self)
+        self.num_experts = base_layer.num_experts
+        self._tables = None  # (key, {segments: (device table, max rank per bank adapter, every rank a multiple of 8)})
+
+    def _shape(self, w: str) -> Tuple[int, int]:
+        """(in_features, out_features) of projection ``w``."""
+        H, I = self.base_layer.hidden_dim, self.base_layer.intermediate_dim
+        return (I, H) if w == "w2" else (H, I)
+
+    def add_adapter(self, name: str, expert: int, w: str, a: torch.Tensor, b: torch.Tensor, scaling: float) -> None:
+        """Adapter ``name`` on projection ``w`` of expert ``expert``: ``a`` [rank, in], ``b`` [out, rank], copied into new bias-free
+        ``nn.Linear`` modules on the block's device (no gradients required: serving; ``requires_grad_(True)`` trains them)."""
+        if w not in ("w1", "w2", "w3") or not 0 <= int(expert) < self.num_experts:
+            raise ValueError(f"adapter {name!r}: no projection {w!r} of expert {expert} in a block of {self.num_experts} experts")
+        fin, fout = self._shape(w)
+        rank = a.shape[0]
+        if a.dim() != 2 or b.dim() != 2 or tuple(a.shape) != (rank, fin) or tuple(b.shape) != (fout, rank):
+            raise ValueError(f"adapter {name!r}: expert {expert} {w}: lora_A must be [r, {fin}] and lora_B [{fout}, r], got "
+                             f"{tuple(a.shape)} / {tuple(b.shape)}")
+        if name in self.scaling and self.scaling[name] != float(scaling):
+            raise ValueError(f"adapter {name!r}: one scaling per adapter and block ({self.scaling[name]} / {scaling})")
+        if name not in self.bank.names:
+            self.bank.names.append(name)
+        dev = self.base_layer.expert(0).w1.codebooks.device
+        la = nn.Linear(fin, rank, bias=False, device=dev, dtype=a.dtype)
+        lb = nn.Linear(rank, fout, bias=False, device=dev, dtype=b.dtype)
+        with torch.no_grad():
+            la.weight.copy_(a)
+            lb.weight.copy_(b)
+        la.weight.requires_grad_(False)
+        lb.weight.requires_grad_(False)
+        for store, lin in ((self.lora_A, la), (self.lora_B, lb)):
+            if name not in store:
+                store[name] = nn.ModuleDict()
+            if str(int(expert)) not in store[name]:
+                store[name][str(int(expert))] = nn.ModuleDict()
+            store[name][str(int(expert))][w] = lin
+        self.scaling[name] = float(scaling)
+        self._tables = None
+
+    def _weights(self, name: str, e: int, w: str):
+        """(A, B, scaling) of adapter ``name`` on projection ``w`` of expert ``e``, or None when it has none."""
+        per = self.lora_A[name] if name in self.lora_A else None
+        if per is None or str(e) not in per or w not in per[str(e)]:
+            return None
+        return per[str(e)][w].weight, self.lora_B[name][str(e)][w].weight, self.scaling[name]
+
+    def _all_weights(self, names):
+        return [wt for n in names for e in range(self.num_experts) for w in ("w1", "w3", "w2")
+                for wt in (self._weights(n, e, w),) if wt is not None]
+
+    def _device_tables(self, device: torch.device):
+        """The device tables of the two launches over ALL adapters of the bank ([bank][E][S]; what this block lacks is a zero
+        entry), keyed on data_ptr and version of every A and B and rebuilt on an eager call when one of them moved or was written."""
+        names = list(self.bank.names)
+        key = (device, tuple(names), tuple((a.data_ptr(), tensor_version(a), b.data_ptr(), tensor_version(b), s)
+                                           for a, b, s in self._all_weights(names)))
+        if self._tables is None or self._tables[0] != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LoraQuantizedMixtralExperts: the adapter table is built by a host-to-device copy; run one eager "
+                                   "forward before capturing (and again after moving or rewriting an adapter)")
+            from .inference_kernels import hip_kernel
+
+            tables = {}
+            for segments in _EXPERT_SEGMENTS:
+                entries = [[[self._weights(n, e, w) for w in segments] for e in range(self.num_experts)] for n in names]
+                ranks = [[wt[0].shape[0] for per in pa for wt in per if wt is not None] for pa in entries]
+                tables[segments] = (hip_kernel.lora_routed_table(entries, device), [max(r, default=0) for r in ranks],
+                                    all(v % 8 == 0 for r in ranks for v in r))
+            self._tables = (key, tables)
+        return self._tables[1]
+
+    def _token_ids(self, sel: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """The selection as one id per row of the [T, H] input; per-sequence ids are broadcast over T / n consecutive rows."""
+        T = x.shape[0]
+        if sel.device != x.device:
+            raise ValueError(f"adapter ids live on {sel.device}, the input on {x.device}")
+        n = sel.numel()
+        if n == T:
+            return sel
+        if n and T % n == 0:
+            return sel[:, None].expand(n, T // n).reshape(-1)
+        raise ValueError(f"{n} adapter ids for an input of shape {tuple(x.shape)}: one per row ({T}) or one per sequence (a divisor "
+                         f"of {T}) expected")
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+        sel = self.bank.selection
+        if sel is None or len(self.lora_A) == 0 or (isinstance(sel, str) and sel not in self.lora_A):
+            return self.base_layer(hidden_states, top_k_index, top_k_weights)  # bits and launches of the bare block
+        ids = None if isinstance(sel, str) else self._token_ids(sel, hidden_states)
+        return self.base_layer(hidden_states, top_k_index, top_k_weights, adapters=_ExpertAdapters(self, sel, ids))
+
+    def extra_repr(self) -> str:
+        return "adapters=" + ", ".join(f"{n} ({len(self._all_weights([n]))} projections, scaling={self.scaling[n]:g})" for n in self.lora_A)
+
+
+class _ExpertAdapters:
+    """The adapter provider of one ``LoraQuantizedMixtralExperts.forward`` (``QuantizedMixtralExperts.forward(adapters=...)``):
+    ``name`` selected for every token, or ``ids`` [T] bank ids per token."""
+
+    def __init__(self, layer: LoraQuantizedMixtralExperts, sel, ids: Optional[torch.Tensor]):
+        self.layer, self.ids = layer, ids
+        self._tables = None  # the layer's device tables, looked up (and their key compared) once per forward
+        self.names = [sel] if isinstance(sel, str) else [n for n in layer.bank.names if n in layer.lora_A]
+
+    def on_pairs(self, out: torch.Tensor, x: torch.Tensor, top_k_index: torch.Tensor, segments, x_per_pair: bool) -> torch.Tensor:
+        """``out`` [P, S, M], the output of a pair-batched launch on projections ``segments``; ``x`` [T, K] token rows or [P, K] pair
+        rows.  -> ``out`` with every pair's adapter term added: the very tensor (HIP route, in place) or a new one (torch path)."""
+        layer = self.layer
+        segments = tuple(segments)
+        P, S, M = out.shape
+        weights = [wt for n in self.names for e in range(layer.num_experts) for w in segments
+                   for wt in (layer._weights(n, e, w),) if wt is not None]
+        if not weights:
+            return out
+        compiling = torch.compiler.is_compiling()
+        dtype_ok = x.dtype in _DTYPES_OK and out.dtype == x.dtype and all(a.dtype == x.dtype and b.dtype == x.dtype for a, b, _ in weights)
+        grad_needed = torch.is_grad_enabled() and (x.requires_grad or out.requires_grad
+                                                   or any(a.requires_grad or b.requires_grad for a, b, _ in weights))
+        fast = (x.is_cuda and dtype_ok and not grad_needed and not compiling and top_k_index.dim() == 2 and out.is_contiguous()
+                and 1 <= P <= min(ROUTED_BGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_ROWS))
+        if fast:
+            from .inference_kernels import hip_kernel
+
+            if self._tables is None:
+                self._tables = layer._device_tables(x.device)
+            table, max_ranks, ranks_ok = self._tables[segments]
+            if self.ids is None:  # one adapter for every token: its [1][E][S] slice of the table, NULL ids, its own rank
+                a = layer.bank.index(self.names[0])
+                words = table.shape[0] // len(max_ranks)
+                table, n, max_rank = table[a * words:(a + 1) * words], 1, max_ranks[a]
+            else:
+                n, max_rank = len(max_ranks), max(max_ranks)
+            supported = ranks_ok and hip_kernel.lora_bgmv_routed_supported(M, x.shape[1], max_rank, P, layer.num_experts, S)
+            if takes_routed_bgmv_route(x.is_cuda, dtype_ok, grad_needed, compiling, P, supported):
+                hip_kernel.lora_bgmv_routed_(out, x, self.ids, top_k_index, table,
+                                             [n, layer.num_experts, S, max_rank, M, x.shape[1], top_k_index.shape[1]], x_per_pair)
+                return out
+        return self._torch_pairs(out, x, top_k_index, segments, x_per_pair)
+
+    def _torch_pairs(self, out, x, top_k_index, segments, x_per_pair):
+        """PEFT's formula per (adapter of the bank, expert, projection), masked by ``(adapter_id == a) & (expert_id == e)``: a loop
+        over bank x experts, never over the ids, so it never syncs; out of place; differentiable in x, A and B.  The rank-sized
+        intermediate is masked (a pair has at most one live term per projection), so the sum below adds zeros to it.  Evaluated
+        in fp32 and added to ``out`` with ONE rounding, as the HIP route does (PEFT rounds the intermediate and the term to the
+        storage type first): the term passes through the activation and the down projection, where two roundings more per
+        element of ``gu`` would show as a difference between the two routes of the size of the block's own rounding error."""
+        layer = self.layer
+        P, S, M = out.shape
+        eid = top_k_index.reshape(-1)
+        k = P // x.shape[0] if not x_per_pair else 1
+        aid = None
+        if self.ids is not None:
+            aid = self.ids if P == self.ids.numel() else self.ids[:, None].expand(self.ids.numel(), P // self.ids.numel()).reshape(-1)
+        deltas = [None] * S
+        xf = x.float()
+        for name in self.names:
+            amask = None if aid is None else aid == layer.bank.index(name)
+            for e in range(layer.num_experts):
+                mask = None
+                for s, w in enumerate(segments):
+                    wt = layer._weights(name, e, w)
+                    if wt is None:
+                        continue
+                    if mask is None:
+                        mask = (eid == e) if amask is None else (amask & (eid == e))
+                    a, b, scaling = wt
+                    t = F.linear(xf, a.float())  # [rows, r]
+                    if k > 1:
+                        t = t[:, None, :].expand(t.shape[0], k, t.shape[1]).reshape(P, t.shape[1])
+                    t = torch.where(mask[:, None], t, torch.zeros((), dtype=t.dtype, device=t.device))
+                    d = F.linear(t, b.float()) * scaling
+                    deltas[s] = d if deltas[s] is None else deltas[s] + d
+        if all(d is None for d in deltas):
+            return out
+        zero = None
+        cols = []
+        for d in deltas:
+            if d is None:
+                zero = torch.zeros((P, M), dtype=torch.float32, device=out.device) if zero is None else zero
+                d = zero
+            cols.append(d)
+        return (out.float() + torch.stack(cols, dim=1)).to(out.dtype)
+
+    def on_rows(self, out: torch.Tensor, x: torch.Tensor, e: int, w: str, tok: torch.Tensor) -> torch.Tensor:
+        """``out`` [n, M] = projection ``w`` of expert ``e`` on the rows ``x`` [n, K] of the tokens ``tok`` (the per-expert loop):
+        the torch path on those rows (fp32, one rounding, as ``_torch_pairs``), masked by the tokens' adapter ids."""
+        layer = self.layer
+        ids = None if self.ids is None else self.ids[tok]
+        total = None
+        for name in self.names:
+            wt = layer._weights(name, e, w)
+            if wt is None:
+                continue
+            a, b, scaling = wt
+            delta = F.linear(F.linear(x.float(), a.float()), b.float()) * scaling
+            if ids is not None:
+                delta = torch.where((ids == layer.bank.index(name))[:, None], delta, torch.zeros((), dtype=delta.dtype, device=delta.device))
+            total = delta if total is None else total + delta
+        return out if total is None else (out.float() + total).to(out.dtype)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # loading
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -333,8 +582,25 @@ def _adapter_modules(name: str, state: Dict[str, torch.Tensor]) -> Dict[str, Dic
     return modules
 
 
+def _expert_block(model: nn.Module, path: str):
+    """The ``QuantizedMixtralExperts`` two levels above the layer at ``path`` (``<block>.<e>.w{1,2,3}``), or None."""
+    from .moe import QuantizedMixtralExperts
+
+    parts = path.rsplit(".", 2)
+    if len(parts) != 3 or not parts[1].isdigit() or parts[2] not in ("w1", "w2", "w3"):
+        return None
+    try:
+        block = model.get_submodule(parts[0])
+    except AttributeError:
+        return None
+    return block if isinstance(block, QuantizedMixtralExperts) else None
+
+
 def attach_adapters(model: nn.Module, adapters: dict, target_modules=None) -> AdapterBank:
-    """Wrap every ``QuantizedLinear`` the adapters target in ``LoraQuantizedLinear`` and return the bank.  ``adapters`` maps a name
+    """Wrap every ``QuantizedLinear`` the adapters target in ``LoraQuantizedLinear`` -- and every ``QuantizedMixtralExperts`` block
+    with a targeted expert layer (``...experts.<e>.w1`` / ``w2`` / ``w3``; ``.block_sparse_moe.`` in a key is read as ``.mlp.`` when
+    only that exists) in ``LoraQuantizedMixtralExperts`` -- and return the bank.  An adapter may cover some experts and some
+    projections only, and mix expert targets with dense ones.  ``adapters`` maps a name
     to a PEFT adapter directory (``adapter_config.json`` + ``adapter_model.safetensors``) or to a ``(state_dict, config_dict)``
     pair with the same keys.  ``target_modules`` (names / path suffixes, or a regular expression) restricts the layers; default:
     every layer an adapter has weights for.  Apply ``fuse_shared_input_linears`` BEFORE attaching (it looks for
@@ -350,11 +616,30 @@ def attach_adapters(model: nn.Module, adapters: dict, target_modules=None) -> Ad
         modules = {p: ab for p, ab in _adapter_modules(name, state).items() if _is_target(p, target_modules)}
         if not modules:
             raise ValueError(f"adapter {name!r} has no weights for the targeted modules")
+        resolved = {}
         for path, ab in modules.items():
             try:
                 target = model.get_submodule(path)
             except AttributeError:
-                raise ValueError(f"adapter {name!r}: the model has no module {path!r}") from None
+                target = None
+                if ".block_sparse_moe.experts." in path:  # the published Mixtral layout; transformers names the block .mlp.
+                    renamed = path.replace(".block_sparse_moe.experts.", ".mlp.experts.")
+                    try:
+                        target, path = model.get_submodule(renamed), renamed
+                    except AttributeError:
+                        pass
+                if target is None:
+                    raise ValueError(f"adapter {name!r}: the model has no module {path!r}") from None
+            resolved[path] = ab
+            block = _expert_block(model, path) if getattr(target, "_moe_expert", False) else None
+            if block is not None:
+                fin, fout = target.in_features, target.out_features
+                if ab["A"].shape[0] != r or ab["B"].shape[1] != r:
+                    raise ValueError(f"adapter {name!r}: {path} has rank {ab['A'].shape[0]}, the config says r={r}")
+                if tuple(ab["A"].shape) != (r, fin) or tuple(ab["B"].shape) != (fout, r):
+                    raise ValueError(f"adapter {name!r}: {path}: lora_A must be [r, {fin}] and lora_B [{fout}, r], got "
+                                     f"{tuple(ab['A'].shape)} / {tuple(ab['B'].shape)}")
+                continue
             if getattr(target, "_moe_expert", False):
                 raise NotImplementedError(f"adapter {name!r}: {path} is a routed mixture-of-experts expert layer; adapters on the "
                                           "routed experts are not supported (only dense QuantizedLinear layers: attention and MLP "
@@ -363,12 +648,28 @@ def attach_adapters(model: nn.Module, adapters: dict, target_modules=None) -> Ad
                 raise TypeError(f"adapter {name!r}: target {path} is a {type(target).__name__}, not a QuantizedLinear")
             if ab["A"].shape[0] != r or ab["B"].shape[1] != r:
                 raise ValueError(f"adapter {name!r}: {path} has rank {ab['A'].shape[0]}, the config says r={r}")
-        loaded.append((name, scaling, modules))
+        loaded.append((name, scaling, resolved))
 
+    # expert targets "<block path>.<e>.<w>", found before any block is wrapped (a wrapped block moves its experts under base_layer)
+    expert_targets = {path: (path.rsplit(".", 2)[0], int(path.rsplit(".", 2)[1]), path.rsplit(".", 1)[1])
+                      for _, _, modules in loaded for path in modules if _expert_block(model, path) is not None}
     bank = AdapterBank([name for name, _, _ in loaded])
-    wrappers: Dict[str, LoraQuantizedLinear] = {}
+    wrappers: Dict[str, Union[LoraQuantizedLinear, LoraQuantizedMixtralExperts]] = {}
     for name, scaling, modules in loaded:
         for path, ab in modules.items():
+            if path in expert_targets:
+                block_path, e, w = expert_targets[path]
+                wrapper = wrappers.get(block_path)
+                if wrapper is None:
+                    base = model.get_submodule(block_path)
+                    parent_path, _, child = block_path.rpartition(".")
+                    parent = model.get_submodule(parent_path) if parent_path else model
+                    wrapper = wrappers[block_path] = LoraQuantizedMixtralExperts(base, bank)
+                    setattr(parent, child, wrapper)
+                    bank._replaced.append((parent, child, base))
+                dtype = wrapper.base_layer.expert(e).w1.codebooks.dtype
+                wrapper.add_adapter(name, e, w, ab["A"].to(dtype), ab["B"].to(dtype), scaling)
+                continue
             wrapper = wrappers.get(path)
             if wrapper is None:
                 base = model.get_submodule(path)
@@ -384,7 +685,7 @@ def attach_adapters(model: nn.Module, adapters: dict, target_modules=None) -> Ad
 
 
 def detach_adapters(model: nn.Module) -> None:
-    """Put the original ``QuantizedLinear`` modules back (the very objects ``attach_adapters`` found) and drop the bank."""
+    """Put the original ``QuantizedLinear`` modules and expert blocks back (the very objects ``attach_adapters`` found) and drop the bank."""
     bank = getattr(model, "_aqlm_adapter_bank", None)
     if bank is None:
         return

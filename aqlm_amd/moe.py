@@ -23,6 +23,11 @@ Forward, same signature and semantics as ``MixtralExperts.forward``:
     (``GROUPED_BACKWARD = False`` or a shape that launch declines: per expert on ``code1x16_matmat_dequant_transposed``, with host syncs);
   * anything else (other schemes, host tensors, shapes the grouped kernel declines): a per-expert loop on the existing ops (host
     syncs allowed), differentiable through the layers' autograd op when a gradient is needed.
+LoRA adapters on the experts (``lora.LoraQuantizedMixtralExperts``) enter through one seam: ``forward`` takes an optional adapter
+provider.  The three pair-batched routes call ``adapters.on_pairs`` twice -- on ``gu`` [P, 2, I] with the token rows, before the
+activation, and on ``y`` [P, 1, H] with the pair rows ``h``, before the weighted sum --, the per-expert loop calls
+``adapters.on_rows`` per expert and projection on that expert's rows; each returns the tensor to go on with (the same one, added to
+in place, or a new one).  Without a provider every route runs exactly the ops above in the same order.
 Either way each expert's output is multiplied by its fp32 router weight and the sum over top_k is rounded once to the activation
 dtype; activation, product and weighted sum are plain torch ops, so ``top_k_weights`` gets its gradient from autograd.  No gradient
 flows to codes, codebooks or scales (as in ``QuantizedLinear``).
@@ -121,16 +126,19 @@ class QuantizedMixtralExperts(nn.Module):
         return state
 
     # ------------------------------------------------------------------------------------------------------------------
-    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor,
+                adapters=None) -> torch.Tensor:
+        """``adapters``: the optional adapter provider of ``lora.LoraQuantizedMixtralExperts`` (module docstring); None runs
+        exactly the ops of the bare block."""
         if self._prepack is not None and self.takes_routed_path(hidden_states, top_k_index):
             tables = self._routed_packed_tables_for(hidden_states, top_k_index)
             if tables is not None:
-                return self._forward_routed_packed(hidden_states, top_k_index, top_k_weights, tables)
+                return self._forward_routed_packed(hidden_states, top_k_index, top_k_weights, tables, adapters)
         if self.takes_routed_path(hidden_states, top_k_index):
-            return self._forward_routed(hidden_states, top_k_index, top_k_weights)
+            return self._forward_routed(hidden_states, top_k_index, top_k_weights, adapters)
         if self.takes_grouped_path(hidden_states, top_k_index):
-            return self._forward_grouped(hidden_states, top_k_index, top_k_weights)
-        return self._forward_loop(hidden_states, top_k_index, top_k_weights)
+            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, adapters)
+        return self._forward_loop(hidden_states, top_k_index, top_k_weights, adapters)
 
     def takes_routed_path(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor) -> bool:
         w = self.expert(0).w1
@@ -272,7 +280,7 @@ class QuantizedMixtralExperts(nn.Module):
         if self._packed_calls % step == 0:
             layers[(self._packed_calls // step) % len(layers)].verify_derived_state()
 
-    def _forward_routed_packed(self, hidden_states, top_k_index, top_k_weights, tables):
+    def _forward_routed_packed(self, hidden_states, top_k_index, top_k_weights, tables, adapters=None):
         T, H = hidden_states.shape
         k = top_k_index.shape[1]
         w = self.expert(0).w1
@@ -280,12 +288,16 @@ class QuantizedMixtralExperts(nn.Module):
         ops = torch.ops.aqlm
         gu = ops.code1x16_moe_matmat_packed(hidden_states, top_k_index, tab13,
                                             [self.num_experts, 2, self.intermediate_dim, H, w.in_group_size, k] + tail13, False)
+        if adapters is not None:
+            gu = adapters.on_pairs(gu, hidden_states, top_k_index, _SEGMENTS_13, False)
         h = self.act_fn(gu[:, 0]) * gu[:, 1]  # [T * k, I]
         y = ops.code1x16_moe_matmat_packed(h, top_k_index, tab2,
                                            [self.num_experts, 1, H, self.intermediate_dim, w.in_group_size, k] + tail2, True)
+        if adapters is not None:
+            y = adapters.on_pairs(y, h, top_k_index, ("w2",), True)
         return (y.view(T, k, H).float() * top_k_weights.float().unsqueeze(-1)).sum(dim=1).to(hidden_states.dtype)
 
-    def _forward_routed(self, hidden_states, top_k_index, top_k_weights):
+    def _forward_routed(self, hidden_states, top_k_index, top_k_weights, adapters=None):
         T, H = hidden_states.shape
         k = top_k_index.shape[1]
         w = self.expert(0).w1
@@ -293,12 +305,16 @@ class QuantizedMixtralExperts(nn.Module):
         ops = torch.ops.aqlm
         gu = ops.code1x16_moe_matmat(hidden_states, top_k_index, tab13,
                                      [self.num_experts, 2, self.intermediate_dim, H, w.in_group_size, k], False)
+        if adapters is not None:
+            gu = adapters.on_pairs(gu, hidden_states, top_k_index, _SEGMENTS_13, False)
         h = self.act_fn(gu[:, 0]) * gu[:, 1]  # [T * k, I]
         y = ops.code1x16_moe_matmat(h, top_k_index, tab2,
                                     [self.num_experts, 1, H, self.intermediate_dim, w.in_group_size, k], True)
+        if adapters is not None:
+            y = adapters.on_pairs(y, h, top_k_index, ("w2",), True)
         return (y.view(T, k, H).float() * top_k_weights.float().unsqueeze(-1)).sum(dim=1).to(hidden_states.dtype)
 
-    def _forward_grouped(self, hidden_states, top_k_index, top_k_weights):
+    def _forward_grouped(self, hidden_states, top_k_index, top_k_weights, adapters=None):
         """Pairs bucketed by expert once on the device, then two grouped launches (w1|w3 on the token rows, w2 on the pair rows)."""
         from .inference_kernels import hip_kernel
 
@@ -311,11 +327,15 @@ class QuantizedMixtralExperts(nn.Module):
         bucket = torch.ops.aqlm.moe_bucket(top_k_index, E, tp)
         grad = _needs_grad(hidden_states)
         gu = _grouped(self, _SEGMENTS_13, hidden_states, bucket, tab13, [E, 2, I, H, g, k, tp, P], False, top_k_index, grad)
+        if adapters is not None:
+            gu = adapters.on_pairs(gu, hidden_states, top_k_index, _SEGMENTS_13, False)
         h = self.act_fn(gu[:, 0]) * gu[:, 1]  # [T * k, I]
         y = _grouped(self, ("w2",), h, bucket, tab2, [E, 1, H, I, g, k, tp, P], True, top_k_index, grad)
+        if adapters is not None:
+            y = adapters.on_pairs(y, h, top_k_index, ("w2",), True)
         return (y.view(T, k, H).float() * top_k_weights.float().unsqueeze(-1)).sum(dim=1).to(hidden_states.dtype)
 
-    def _forward_loop(self, hidden_states, top_k_index, top_k_weights):
+    def _forward_loop(self, hidden_states, top_k_index, top_k_weights, adapters=None):
         """Tokens grouped per expert, each group through the layer's ordinary ops (host syncs: the groups are sized on the host)."""
         out = torch.zeros(hidden_states.shape, dtype=torch.float32, device=hidden_states.device)
         hit = torch.unique(top_k_index).tolist()
@@ -325,8 +345,13 @@ class QuantizedMixtralExperts(nn.Module):
             tok, pos = torch.where(top_k_index == e)
             ex = self.expert(e)
             x = hidden_states[tok]
-            h = self.act_fn(_apply(ex.w1, x)) * _apply(ex.w3, x)
-            y = _apply(ex.w2, h)
+            if adapters is None:
+                h = self.act_fn(_apply(ex.w1, x)) * _apply(ex.w3, x)
+                y = _apply(ex.w2, h)
+            else:
+                h = (self.act_fn(adapters.on_rows(_apply(ex.w1, x), x, e, "w1", tok))
+                     * adapters.on_rows(_apply(ex.w3, x), x, e, "w3", tok))
+                y = adapters.on_rows(_apply(ex.w2, h), h, e, "w2", tok)
             out.index_add_(0, tok, y.float() * top_k_weights[tok, pos, None].float())
         return out.to(hidden_states.dtype)
 

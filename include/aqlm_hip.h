@@ -541,6 +541,40 @@ int aqlm_hip_lora_bgmv(const aqlm_hip_lora_entry* table, int num_adapters, int m
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same adapters on the ROUTED experts of a mixture-of-experts block: aqlm_hip_lora_bgmv with a row per (token, expert) pair
+ * and projection, on top of the output of aqlm_hip_gemv_1x16_routed / ..._routed_packed / aqlm_hip_gemm_1x16_grouped (no reference
+ * counterpart).  `table` is a DEVICE array of num_adapters x num_experts x num_segments aqlm_hip_lora_entry: entry
+ * [(a * num_experts + e) * num_segments + s] is adapter a on projection s of expert e (num_segments 2: w1, w3 of the gate / up
+ * launch; 1: w2).  A combination the adapter does not cover is an entry of rank 0 with null pointers: "no adapter", and nothing is
+ * loaded through it.  adapter_ids: DEVICE, one id per TOKEN (num_pairs / top_k of them), int64 or int32, or NULL = adapter 0.
+ * expert_ids: DEVICE [num_pairs] (= [tokens][top_k] row-major), int64 or int32, as for aqlm_hip_gemv_1x16_routed.  For every pair
+ * p with a = adapter_ids[p / top_k] and e = expert_ids[p] -- both range-checked BEFORE either forms an address -- and every
+ * segment s, with x_row(p) = x + (x_per_pair ? p : p / top_k) * x_row_stride and yrow = y + (p * num_segments + s) * out_features
+ * (y is contiguous, the routed entries' output layout):
+ *     t[r]    = sum_k A[r, k] * x_row(p)[k]                                    r < rank   (fp32, never rounded)
+ *     yrow[i] = round(float(yrow[i]) + scaling * sum_r B[i, r] * t[r])
+ * A pair whose adapter id or expert id is out of range keeps its y rows bit for bit, and so does a pair whose entry has a rank
+ * that is no multiple of 8 in 8..max_rank.  The arithmetic is aqlm_hip_lora_bgmv's, operation for operation and in the same
+ * order: a pair's y row is BIT-IDENTICAL to aqlm_hip_lora_bgmv called on that one row with that entry as a one-slot table, so it
+ * does not depend on the other pairs, their number or their order.  Two launches (shrink into `workspace`, fp32 [num_pairs]
+ * [num_segments][max_rank], 16-byte aligned; expand + add) on grids of max_rank / 2 x num_pairs x num_segments and
+ * ceil(out_features / 256) x num_pairs x num_segments workgroups: the shapes only.  No atomics, no inter-workgroup
+ * communication; stream-ordered, no allocation, no synchronisation (hipGraph-capturable; both id arrays may be rewritten in place
+ * between replays).
+ * Argument checks as aqlm_hip_lora_bgmv, in the same order (num_pairs in the place of rows), after: null expert_ids, misaligned
+ * expert_ids, and non-positive num_experts / num_segments / top_k / num_pairs or num_pairs % top_k != 0 (AQLM_HIP_E_INVALID).
+ * AQLM_HIP_E_UNSUPPORTED in addition for num_pairs > AQLM_HIP_MAX_LORA_ROWS, num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS and
+ * num_segments > 2; aqlm_hip_lora_bgmv_routed_supported answers for the six sizes beforehand.
+ */
+size_t aqlm_hip_lora_bgmv_routed_workspace_bytes(int num_pairs, int num_segments, int max_rank); /* 0 when unsupported */
+int aqlm_hip_lora_bgmv_routed_supported(int out_features, int in_features, int max_rank, int num_pairs, int num_experts,
+                                        int num_segments);
+int aqlm_hip_lora_bgmv_routed(const aqlm_hip_lora_entry* table, int num_adapters, int num_experts, int num_segments, int max_rank,
+                              const void* adapter_ids, int adapter_ids_int64, const void* expert_ids, int expert_ids_int64,
+                              int num_pairs, int top_k, const void* x, long x_row_stride, int x_per_pair, void* y,
+                              int out_features, int in_features, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same adapters at any row count (prefill, large batches): the segmented counterpart of aqlm_hip_lora_bgmv on the matrix
  * unit, same table, same ids, same two launches.  For every row b < rows with a = ids[b] (NULL: adapter 0), a in
  * [0, num_adapters) and the entry's rank a multiple of 8 in 8..max_rank, with T the storage type of x and y:
