@@ -64,254 +64,59 @@
 #ifndef AQLM_PK_G
 #define AQLM_PK_G 8
 #endif
-#if AQLM_PK_G == 16
-#define PK_NS pk_g16
-#define aqlm_hip_prepack_1x16_bytes aqlm_hip_g16_prepack_1x16_bytes
-#define aqlm_hip_prepack_1x16 aqlm_hip_g16_prepack_1x16
-#define aqlm_hip_prepack_1x16_ex aqlm_hip_g16_prepack_1x16_ex
-#define aqlm_hip_packed_set_codebook aqlm_hip_g16_packed_set_codebook
-#define aqlm_hip_packed_plan_relabel aqlm_hip_g16_packed_plan_relabel
-#define aqlm_hip_packed_plan_relabel_ex aqlm_hip_g16_packed_plan_relabel_ex
-#define aqlm_hip_packed_plan_geometry aqlm_hip_g16_packed_plan_geometry
-#define aqlm_hip_packed_desc_read aqlm_hip_g16_packed_desc_read
-#define aqlm_hip_unpack_1x16 aqlm_hip_g16_unpack_1x16
-#define aqlm_hip_dequant_1x16_packed aqlm_hip_g16_dequant_1x16_packed
-#define aqlm_hip_gemv_1x16_packed_cells aqlm_hip_g16_gemv_1x16_packed_cells
-#define aqlm_hip_gemv_1x16_packed aqlm_hip_g16_gemv_1x16_packed
-#define aqlm_hip_gemv_1x16_packed_chain aqlm_hip_g16_gemv_1x16_packed_chain
-#define aqlm_hip_gemv_1x16_packed_partials aqlm_hip_g16_gemv_1x16_packed_partials
-#define aqlm_hip_gemv_1x16_packed_publish aqlm_hip_g16_gemv_1x16_packed_publish
-#define aqlm_hip_gemv_1x16_packed_multi aqlm_hip_g16_gemv_1x16_packed_multi
-#define aqlm_hip_gemv_1x16_packed_multi_cells aqlm_hip_g16_gemv_1x16_packed_multi_cells
-#define aqlm_hip_gemv_1x16_routed_packed_lds_bytes aqlm_hip_g16_gemv_1x16_routed_packed_lds_bytes
-#define aqlm_hip_routed_packed_entry_fill aqlm_hip_g16_routed_packed_entry_fill
-#define aqlm_hip_gemv_1x16_routed_packed_geometry aqlm_hip_g16_gemv_1x16_routed_packed_geometry
-#define aqlm_hip_gemv_1x16_routed_packed_supported aqlm_hip_g16_gemv_1x16_routed_packed_supported
-#define aqlm_hip_gemv_1x16_routed_packed aqlm_hip_g16_gemv_1x16_routed_packed
-#define PK_API __attribute__((visibility("hidden")))  // internal to libaqlm_hip.so: reached through the public entries only
-#else
-#define PK_NS pk_g8
-#define PK_API
-#endif
-
-namespace aqlm {
-namespace PK_NS {
-
-constexpr int PK_G = AQLM_PK_G;                              // elements of a codebook vector
-constexpr int PK_VSH = PK_G == 8 ? 4 : 5;                    // log2(bytes of a vector)
-constexpr uint32_t PK_VB = 1u << PK_VSH;                     // bytes of a codebook vector == bytes of x per input group
-constexpr uint32_t PK_HMASK = 0xfff0u;                       // LDS byte offset inside a 16-bit half of an entry
-// 32-byte vectors are read as two 16-byte halves.  All vectors start at even 16-B slots, so a plain "first halves, then second
-// halves" would use only 8 of the 16 bank groups per read.  Odd lanes therefore read the halves in the opposite order: bit 4 of
-// BOTH halves of an entry (spare: the offsets are multiples of 32) is the parity of the lane the entry is stored for, the
-// first read uses the offsets as they are, the second flips bit 4.
-constexpr uint32_t PK_PARITY_BITS = PK_G == 16 ? 0x00100010u : 0u;
-static_assert(PK_G == 8 || PK_G == 16, "codebook vectors of 8 or 16 elements");
-
 #ifndef AQLM_PK_S_LOG
 #define AQLM_PK_S_LOG 4  // 16 slices of 64 KiB; 5 = 32 slices of 32 KiB (experiment builds: tools/microbench)
 #endif
-constexpr int PK_S_LOG = AQLM_PK_S_LOG;
-constexpr int PK_S = 1 << PK_S_LOG;          // slices
 #ifndef AQLM_PK_NG_LOG
 #define AQLM_PK_NG_LOG (8 - AQLM_PK_S_LOG)  // row groups: by default PK_S * PK_NG == 256 workgroups == CUs
 #endif
-constexpr int PK_NG = 1 << AQLM_PK_NG_LOG;   // row groups
-constexpr int PK_NST = PK_NG * PK_S;         // streams == workgroups of a layer
 #ifndef AQLM_PK_XFIRST
 #define AQLM_PK_XFIRST 1  // batch-1 LDS map: 1 = x first (a 64 KiB window, x copies possible), 0 = slice first (LDS = slice + x: several workgroups per CU)
 #endif
-constexpr int PK_CODE_BITS = 16 - PK_S_LOG;  // bits of a code inside its slice
-constexpr int PK_SLICE_ENTRIES = 1 << PK_CODE_BITS;
-constexpr uint32_t PK_SLICE_BYTES = PK_SLICE_ENTRIES * PK_VB;
-constexpr int PK_MAX_NW = 16;
-constexpr int PK_MAX_T = 1024;
-constexpr int PK_MAX_GROUPS = (int)(65536u / PK_VB) - 2;  // the x offset of a group is a 16-bit byte offset; in_groups itself is the null slot
-constexpr uint32_t PK_MAGIC = 0x37505141u;   // "AQP7"
-constexpr int PK_VERSION = 7;
-constexpr int PK_MIN_GROUPS = PK_NG / 2;     // variable geometry: workgroups of a slice (its rows per group stay <= 2 x the uniform count)
-constexpr int PK_VG_MIN_ROWS = 512;          // ... and only layers of at least this many rows (every group owns >= 1 row)
-constexpr uint32_t PK_XWIN_FULL = 65520;     // x window of the batch-1 kernel (x first, slice behind it)
-// accumulator cell of the fused finalize: [arrivals : CNT bits][non-finite contributions : CNT bits][fixed-point sum]
-constexpr int PK_CNT_BITS = PK_S_LOG + 1;                       // counts 0 .. PK_S
-constexpr unsigned long long PK_CNT_MASK = (1ull << PK_CNT_BITS) - 1ull;
-constexpr int PK_VAL_SHIFT = 2 * PK_CNT_BITS;                   // 10 for 16 slices
-// |slice sum| < 2^e is stored in units of 2^(e - PK_FIX_BITS).  The finite test lets an addend reach 2 x the bound (rounding slack, a
-// slightly stale codebook range), so PK_S addends stay below 2^(PK_FIX_BITS + 1 + PK_S_LOG), which must fit the signed sum field of
-// 64 - PK_VAL_SHIFT bits: PK_FIX_BITS <= 60 - 3 PK_S_LOG.  16 slices: 47 (the 51 - PK_S_LOG of rounds 2-3); 32 slices (g16): 45 -- with
-// 46 a stale range could wrap the sum instead of giving the NaN the header promises.
-constexpr int PK_FIX_BITS = (51 - PK_S_LOG) < (60 - 3 * PK_S_LOG) ? (51 - PK_S_LOG) : (60 - 3 * PK_S_LOG);
-static_assert(PK_FIX_BITS + 1 + PK_S_LOG <= 63 - 2 * (PK_S_LOG + 1), "PK_S addends of up to twice the bound must fit the sum field");
 
-// x copies (batch-1 kernel): copy c of x starts at 16-B slot c * stride with stride = 4 (mod 16), i.e. its bank-group
-// pattern is rotated by 4 c: an entry can read the copy whose bank group is still free in its service group.
-__host__ __device__ static inline int pk_x_stride(int in_groups) { return ((in_groups + 1 + 11) & ~15) + 4; }  // >= in_groups + 1
-static inline int pk_max_x_copies(int in_groups) { return std::max(1, std::min(4, 4095 / pk_x_stride(in_groups))); }
-// start row of a column: 15 bits over the low nibbles of its first lane-step (entry 0: bits 1-3, entries 1-3: bits 0-3)
-__host__ __device__ static inline uint32_t pk_get_start_row(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3) {
-  return ((e0 >> 1) & 7u) | ((e1 & 15u) << 3) | ((e2 & 15u) << 7) | ((e3 & 15u) << 11);
-}
+// The entry points that exist in both builds, without their aqlm_hip_ prefix.  Every one of them is declared in
+// include/aqlm_hip.h; its twin aqlm_hip_g16_<name> gets the SAME type from that declaration (hidden: reached through the public
+// entries only).  A definition names itself PK_ENTRY(<name>): the 8-element build defines the public symbol, the 16-element
+// build the twin, so each is compiled against a declaration taken from the header -- extern "C" does not overload, a parameter
+// that drifts is "conflicting types" in whichever build it happens.
+#define PK_TWIN_ENTRIES(X)                                                                                                     \
+  X(prepack_1x16_bytes) X(prepack_1x16) X(prepack_1x16_ex) X(packed_set_codebook) X(packed_plan_relabel)                       \
+  X(packed_plan_relabel_ex) X(packed_plan_geometry) X(packed_desc_read) X(unpack_1x16) X(dequant_1x16_packed)                  \
+  X(gemv_1x16_packed_cells) X(gemv_1x16_packed) X(gemv_1x16_packed_chain) X(gemv_1x16_packed_partials)                         \
+  X(gemv_1x16_packed_publish) X(gemv_1x16_packed_multi) X(gemv_1x16_packed_multi_cells) X(gemv_1x16_routed_packed_lds_bytes)   \
+  X(routed_packed_entry_fill) X(gemv_1x16_routed_packed_geometry) X(gemv_1x16_routed_packed_supported)                         \
+  X(gemv_1x16_routed_packed)
+#define PK_TWIN_DECLARE(name) extern "C" __attribute__((visibility("hidden"))) decltype(aqlm_hip_##name) aqlm_hip_g16_##name;
+PK_TWIN_ENTRIES(PK_TWIN_DECLARE)
+#undef PK_TWIN_DECLARE
 
-constexpr int PK_STEP3 = 768;   // bytes of one wave step of 3-byte entries (64 lanes x 12 B)
-constexpr int PK_WREG3 = 776;   // ... per step incl. its 8-B row-end flag word (flag words lead the wave range)
+// Per build: the namespace (PK_NS), the name a definition gives itself (PK_ENTRY) and its visibility (PK_API), and
+// PK_G16_FORWARD(descriptor, name, args...) / PK_G16_FORWARD_IF(condition, name, args...), the first statement of a public entry
+// of the 8-element build: hand the call to the twin when it is for the 32-slice format.  Nothing in the 16-element build.
+#if AQLM_PK_G == 16
+#define PK_NS pk_g16
+#define PK_ENTRY(name) aqlm_hip_g16_##name
+#define PK_API __attribute__((visibility("hidden")))  // internal to libaqlm_hip.so: reached through the public entries only
+#define PK_G16_FORWARD(desc_expr, name, ...)
+#define PK_G16_FORWARD_IF(cond, name, ...)
+#else
+#define PK_NS pk_g8
+#define PK_ENTRY(name) aqlm_hip_##name
+#define PK_API
+// a descriptor of the twin's format (32 slices)
+static inline bool pk_is_g16(const aqlm_hip_packed_desc* d) { return d && d->slices_log2 == 5; }
+#define PK_G16_FORWARD_IF(cond, name, ...) \
+  if (cond) return aqlm_hip_g16_##name(__VA_ARGS__)
+#define PK_G16_FORWARD(desc_expr, name, ...) PK_G16_FORWARD_IF(pk_is_g16(desc_expr), name, __VA_ARGS__)
+#endif
 
-// Stream geometry: which slice and which rows workgroup / stream `st` owns.
-//   uniform (vg == 0, formats <= v6): PK_NG row groups of RG rows for every slice, stream = group * PK_S + slice;
-//   variable (vg == 1): slice s has n[s] row groups, the rows are split evenly over them (the first M % n[s] groups hold one
-//   row more), streams are numbered slice by slice: stream = first[s] + group.
-struct PkGeom {
-  int M;
-  int vg;
-  int RG;                    // most rows of any stream: the row-start tables have RG + 1 entries per stream, the LDS row tables RG + 1
-  uint16_t first[PK_S + 1];  // first stream of slice s (vg)
-  uint8_t n[PK_S];           // row groups (= workgroups) of slice s
-};
+// packed_format.h, packed_gemv_kernels.h, packed_launch.h and gemv_packed_routed.h are sections of this file kept in files of
+// their own, not headers: no include guards (each is read once per build, i.e. twice per library), and the order of the kernels
+// here and in them is their order in the code object.
+namespace aqlm {
+namespace PK_NS {
 
-__host__ __device__ static inline void pk_group_rows(const PkGeom& G, int s, int k, int& row0, int& nrows) {
-  if (!G.vg) {
-    row0 = k * G.RG;
-    const int n = G.M - row0;
-    nrows = n < 0 ? 0 : (n < G.RG ? n : G.RG);
-    return;
-  }
-  const int n = G.n[s], base = G.M / n, extra = G.M - base * n;
-  row0 = k * base + (k < extra ? k : extra);
-  nrows = base + (k < extra ? 1 : 0);
-}
-__host__ __device__ static inline void pk_stream_slice(const PkGeom& G, int st, int& s, int& k) {
-  if (!G.vg) {
-    s = st & (PK_S - 1);
-    k = st >> PK_S_LOG;
-    return;
-  }
-  s = 0;
-  while (s + 1 < PK_S && (int)G.first[s + 1] <= st) ++s;
-  k = st - (int)G.first[s];
-}
-__host__ __device__ static inline void pk_stream_rows(const PkGeom& G, int st, int& s, int& row0, int& nrows) {
-  int k;
-  pk_stream_slice(G, st, s, k);
-  pk_group_rows(G, s, k, row0, nrows);
-}
-// stream and row-in-stream of (slice, row)
-__host__ __device__ static inline void pk_row_stream(const PkGeom& G, int s, int row, int& st, int& r) {
-  if (!G.vg) {
-    const int k = row / G.RG;
-    r = row - k * G.RG;
-    st = k * PK_S + s;
-    return;
-  }
-  const int n = G.n[s], base = G.M / n, extra = G.M - base * n, thr = extra * (base + 1);
-  int k;
-  if (row < thr) {
-    k = row / (base + 1);
-    r = row - k * (base + 1);
-  } else {
-    k = extra + (row - thr) / base;
-    r = row - thr - (k - extra) * base;
-  }
-  st = (int)G.first[s] + k;
-}
-
-// geometry from the row groups per slice (nullptr: uniform); false if they do not describe PK_NST workgroups
-static bool pk_make_geom(int M, const uint8_t* groups, PkGeom& G) {
-  G.M = M;
-  G.vg = 0;
-  int sum = 0, mn = PK_NG;
-  for (int s = 0; s < PK_S; ++s) {
-    const int n = groups ? (int)groups[s] : PK_NG;
-    if (n < 1) return false;
-    G.n[s] = (uint8_t)n;
-    G.first[s] = (uint16_t)sum;
-    sum += n;
-    mn = n < mn ? n : mn;
-    if (n != PK_NG) G.vg = 1;
-  }
-  G.first[PK_S] = (uint16_t)sum;
-  if (sum != PK_NST) return false;
-  if (G.vg && (PK_G != 8 || M < PK_VG_MIN_ROWS)) return false;
-  G.RG = G.vg ? (M + mn - 1) / mn : (M + PK_NG - 1) / PK_NG;
-  return true;
-}
-
-struct PackedLayout {
-  int M, in_groups, RG, NW, T, XC, EB;
-  size_t nst, off_winfo, off_rowstart, off_acc, off_ent, ent_bytes, used;
-  PkGeom G;
-  bool relabel;            // permutation (u16 old_of_new[65536]) at off_perm, codebook image at off_cb
-  size_t off_perm, off_cb;
-};
-
-__host__ __device__ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static int packed_max_batch(int in_groups, int RG);  // rows of x whose LDS image fits a CU (0: not even one)
-
-static bool packed_shape_ok(int out_features, int in_features, int g) {
-  return g == PK_G && out_features > 0 && in_features > 0 && in_features % PK_G == 0 && in_features / PK_G <= PK_MAX_GROUPS &&
-         (out_features + PK_NG - 1) / PK_NG <= 32767 - PK_MAX_NW &&
-         packed_max_batch(in_features / PK_G, (out_features + PK_NG - 1) / PK_NG) >= 1;  // slice + x + the row tables of a row group in 160 KiB
-}
-
-static bool packed_layout(int out_features, int in_features, int NW, int T, PackedLayout& L, int XC = 1, int EB = 4,
-                          const uint8_t* groups = nullptr, bool relabel = false) {
-  if (!packed_shape_ok(out_features, in_features, PK_G) || NW < 1 || NW > PK_MAX_NW || T < 1 || T > PK_MAX_T) return false;
-  if (XC < 1 || XC > pk_max_x_copies(in_features / PK_G) || (PK_G != 8 && XC != 1)) return false;
-  if (EB != 4 && !(EB == 3 && T <= 32 && PK_G == 8)) return false;  // 3-byte entries: the row-end flags of a column are one 32-bit mask
-  if (!pk_make_geom(out_features, groups, L.G)) return false;
-  if (L.G.vg && (EB != 4 || L.G.RG > 32767 - PK_MAX_NW || packed_max_batch(in_features / PK_G, L.G.RG) < 1)) return false;
-  L.XC = XC;
-  L.EB = EB;
-  L.M = out_features;
-  L.in_groups = in_features / PK_G;
-  L.RG = L.G.RG;
-  L.NW = NW;
-  L.T = T;
-  L.nst = (size_t)PK_NST;
-  L.off_winfo = 256;
-  L.off_rowstart = align_up(L.off_winfo + L.nst * PK_MAX_NW * 16, 256);         // [nst][RG + 1] u32 (offset independent of NW)
-  // accumulator cells of the fused finalize: [AQLM_HIP_MAX_GEMV_BATCH][M] u64, zero at rest (offset independent of NW, T)
-  L.off_acc = align_up(L.off_rowstart + L.nst * (size_t)(L.RG + 1) * 4, 256);
-  L.off_ent = align_up(L.off_acc + (size_t)AQLM_HIP_MAX_GEMV_BATCH * out_features * 8, 1024);
-  L.ent_bytes = L.nst * NW * T * (EB == 3 ? (size_t)PK_WREG3 : (size_t)1024);
-  L.relabel = relabel;
-  L.off_perm = align_up(L.off_ent + L.ent_bytes, 1024);
-  L.off_cb = L.off_perm + (size_t)65536 * 2;
-  L.used = relabel ? L.off_cb + (size_t)65536 * PK_VB : L.off_ent + L.ent_bytes;
-  return L.ent_bytes < ((size_t)1 << 32);  // 32-bit buffer offsets
-}
-
-static bool desc_layout(const aqlm_hip_packed_desc* d, PackedLayout& L) {
-  return d && d->magic == PK_MAGIC && d->version == PK_VERSION && d->slices_log2 == PK_S_LOG &&
-         packed_layout(d->out_features, d->in_features, d->waves, d->steps, L, (int)d->x_copies, d->entry_bytes, d->slice_groups,
-                       (d->flags & AQLM_HIP_PACKED_RELABELLED) != 0) &&
-         L.used == d->used_bytes && d->rows_per_group == L.RG && ((d->flags & AQLM_HIP_PACKED_VARGEOM) != 0) == (L.G.vg != 0);
-}
-
-// Wave-steps of work in the longest stream -> waves per workgroup.
-// Long streams (>= 13 steps per wave at 16 waves: the 28672-row / 28672-wide layers) are bound by the entry stream and want
-// every wave the CU can hold: 16 (8192 -> 28672 with 14 / 12 waves: 30.9 / 30.7 us against 25.1; r03_mb_packed_variants.log).
-// Mid-size layers are bound by the LDS and run as fast or faster on 14 waves (single-kernel regime, same box: 8192 -> 8192
-// 10.6 vs 10.9 us, 14336 -> 4096 10.3 vs 10.5, 4096 -> 14336 10.45 vs 10.55, 4096 -> 11008 9.10 vs 9.09) -- and 14 waves
-// leave room for the two DMA waves of the pipelined shared-input kernel, whose fill then hides completely (2 x 4096 ->
-// 14336 in one launch: 18.85 us packed for 14 waves, 19.75 for 16).  (Round 2's "13-15 waves are 10-18 % slower" was
-// measured with the two-kernel finalize and no longer holds.)  Small layers (< 48 wave-steps per workgroup): the wave
-// ranges have T = ceil(q / NW) steps each, so the capacity NW * T overshoots the content by up to NW - 1 steps, a large
-// share of such a layer: pick 4..8 waves with the least overshoot.
-static int choose_waves(uint32_t max_lane_steps) {
-  const int q = (int)((max_lane_steps + 63) / 64);
-  if (tuning().packed_waves >= 1 && tuning().packed_waves <= PK_MAX_NW) return tuning().packed_waves;
-  if (q >= 48) return (q + 15) / 16 >= 13 ? 16 : 14;
-  // ... and a step count that is a multiple of the ring depth (3): a remainder of one or two steps runs through the
-  // kernel's tail code and leaves late requests behind (measured, profiles/r02_mb_wave_counts.log: 4096x4096 with
-  // 6 waves x 6 steps 6.09 us, 7 x 5 6.23 us, 5 x 7 6.22 us; 8192->1024 with 6 x 3 = 7 x 3 5.23 us, 5 x 4 5.55 us)
-  int best = 8, best_cost = 1 << 30;
-  for (int nw = 8; nw >= (PK_NST > 256 ? 2 : 4); --nw) {  // many small workgroups per CU: fewer waves each
-    const int t = (q + nw - 1) / nw;
-    const int cost = (nw * t - q) * 8 + (8 - nw) + ((t >= 3 && t % 3 != 0) ? 12 : 0);
-    if (cost < best_cost) { best_cost = cost; best = nw; }
-  }
-  return best;
-}
+#include "packed_format.h"  // constants, stream geometry, buffer layout, wave-count choice
 
 // ------------------------------------------------------------------------------------------------ prepack
 // K0: how often every codebook entry is used (the relabelling plan is made from it on the host).
@@ -1049,844 +854,7 @@ __global__ __launch_bounds__(64) void pk_dequant_kernel(const uint8_t* __restric
   }
 }
 
-// ------------------------------------------------------------------------------------------------ gemv
-struct PackedGemvParams {
-  const uint32_t* ent;
-  const uint32_t* winfo;
-  const uint32_t* rowstart;  // [nst][RG + 1]
-  const uint8_t* codebook;
-  const uint16_t* x;
-  float* partial;  // [S][B][M]
-  long x_row_stride;
-  int M, in_groups, RG, NW, T, XC;
-  uint32_t ent_bytes;
-  // fused finalize (acc != nullptr): the 16 slice workgroups of a row meet in ONE 64-bit cell per (input row, output row)
-  unsigned long long* acc;  // [B][M], zero at rest
-  float cb_absmax;          // largest |codebook entry| of the layer (bounds the slice sums)
-  const uint16_t* scales;
-  const uint16_t* bias;
-  uint16_t* y;
-  long y_row_stride;
-  // chain prefetch (optional): the layer that runs NEXT on this stream.  NPW extra waves of every workgroup pull the
-  // next layer's stream of the same workgroup index (same XCD under the observed block % 8 placement) and a share of
-  // its codebook slice towards this XCD's L2 while the other waves compute -- the next launch then starts L2-warm.
-  // row-parallel shards (one-shot all-reduce over xGMI, xgmi_reduce.hip): instead of writing y, the workgroup that owns
-  // a row's total PUBLISHES it -- fp32, system-scope store -- in this rank's pub buffer, and the last workgroup of the
-  // launch raises the rank's flag.  nullptr: ordinary launch.
-  float* pub;                    // this rank's pub[2][max_elems]
-  uint32_t* pub_flag;            // this rank's flag[2]
-  uint32_t* pub_epoch;           // [0] epoch, [4..11] arrival counters of the 8 workgroup shards, [12] top counter
-  uint32_t pub_max_elems;
-  const uint8_t* next_ent;       // entry area of the next layer's packed buffer (nullptr: no prefetch)
-  const uint8_t* next_codebook;
-  uint32_t next_block_bytes;     // bytes of one workgroup's stream in the next layer (NW' * T' KiB)
-  int NPW;                       // prefetch waves in this launch (workgroup = NW + NPW waves)
-  int fill_rotate;               // 1: workgroup g starts its slice fill at piece g * (pieces / row groups)
-#ifdef AQLM_PACKED_TRACE
-  unsigned long long* trace;  // [256 workgroups][8] wall-clock stamps (100 MHz), profiling builds only
-  int dbg;                    // bit 0: skip the LDS reads + dot products, bit 1: no entry stream (out-of-range loads)
-#endif
-};
-
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-typedef __attribute__((address_space(3))) const u32x4* lds_u32x4_ptr;
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef __attribute__((address_space(1))) const void* gbl_void_ptr;
-typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;  // constant address space: uniform loads go through s_load
-
-template <int WORD>
-__device__ __forceinline__ uint32_t half_and(uint32_t w, uint32_t mask) {
-  uint32_t d;  // d = ((w >> 16*WORD) & 0xffff) & mask in one instruction (sub-dword operand select)
-  if constexpr (WORD == 0)
-    asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(d) : "v"(mask), "v"(w));
-  else
-    asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(d) : "v"(mask), "v"(w));
-  return d;
-}
-
-__device__ __forceinline__ void lds_store_f32(uint32_t byte_addr, float v) {
-  asm volatile("ds_write_b32 %0, %1" : : "v"(byte_addr), "v"(v) : "memory");
-}
-// LDS reads hipcc does not see (pipelined kernel's epilogue): while LDS-DMA requests are in flight the compiler guards every
-// LDS read it knows of with vmcnt(0) -- it cannot tell which addresses the DMA writes.  The caller waits (lds_asm_wait)
-// before it uses the values.
-__device__ __forceinline__ uint32_t lds_asm_load_b32(uint32_t byte_addr) {
-  uint32_t v;
-  asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(byte_addr));  // no "memory" clobber: with one hipcc treats the asm as a possible LDS reader and puts vmcnt(0) in front
-  return v;
-}
-__device__ __forceinline__ u32x4 lds_asm_load_b128(uint32_t byte_addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
-  return v;
-}
-// the wait names the registers it guards ("+v"): a bare `s_waitcnt` asm orders nothing for the compiler's scheduler, which
-// is free to move a USE of an asm-loaded value in front of it (it happened: wrong row sums in one build, right ones in the next)
-__device__ __forceinline__ void lds_asm_wait(uint32_t& a) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a)); }
-__device__ __forceinline__ void lds_asm_wait(uint32_t& a, uint32_t& b, uint32_t& c, u32x4& d0, u32x4& d1, u32x4& d2, u32x4& d3) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
-}
-
-// LDS map (byte offsets from the start of the workgroup's LDS, which is address 0: the kernel has no static LDS).
-//   B == 1: x at 0 (XWIN bytes reserved), slice at XWIN, bookkeeping behind the slice   (x-first: both reads cost one op)
-//   B  > 1: slice at 0, then B planes x[b][j] of XP = (in_groups + 1) * 16 bytes (a plane keeps the bank pattern of
-//           the single-row case: slot j -> bank group j % 16; interleaving the rows would leave 16 / B groups), bookkeeping
-//   bookkeeping: rowstart[RG + 1] u32 (LDS-DMA copy of the stream's row starts), rowval[B][RG + 1] f32 (sum of the
-//   lane-steps of a row from the start of the column that holds its LAST lane-step), colend[B][16 * 64] f32 (what a
-//   column accumulated after its last row end: the head of a row that continues in the next column)
-template <int B, uint32_t XWIN>
-struct PackedLds {
-  static constexpr bool XFIRST = (B == 1) && AQLM_PK_XFIRST && XWIN != 0u;  // XWIN == 0: slice first also for one row (tall layers)
-  static constexpr uint32_t SLICE = XFIRST ? XWIN : 0u;
-  static constexpr uint32_t X = XFIRST ? 0u : PK_SLICE_BYTES;
-  __host__ __device__ static uint32_t plane(int in_groups) { return (uint32_t)(in_groups + 1) * PK_VB; }
-  __host__ __device__ static uint32_t rowstart(int in_groups) {
-    return XFIRST ? XWIN + PK_SLICE_BYTES : PK_SLICE_BYTES + plane(in_groups) * B;
-  }
-  __host__ __device__ static uint32_t rs_bytes(int RG) { return ((uint32_t)(RG + 1) * 4u + 1023u) & ~1023u; }  // whole DMA pieces
-  __host__ __device__ static uint32_t rowval(int in_groups, int RG) { return rowstart(in_groups) + rs_bytes(RG); }
-  __host__ __device__ static uint32_t colend(int in_groups, int RG) { return rowval(in_groups, RG) + (uint32_t)B * (RG + 1) * 4u; }
-  __host__ __device__ static uint32_t xmax(int in_groups, int RG) {  // 16-B aligned: read with ds_read_b128
-    return (colend(in_groups, RG) + (uint32_t)B * PK_MAX_NW * 64 * 4 + 15u) & ~15u;
-  }
-  __host__ __device__ static uint32_t dump(int in_groups, int RG) {  // 1 KiB landing zone per prefetch wave (LDS-DMA needs a destination)
-    return (xmax(in_groups, RG) + (uint32_t)B * PK_MAX_NW * 4u + 15u) & ~15u;
-  }
-  __host__ __device__ static size_t total(int in_groups, int RG, int npw = 0) {
-    return npw ? (size_t)dump(in_groups, RG) + (size_t)npw * 1024
-               : (size_t)xmax(in_groups, RG) + (size_t)B * PK_MAX_NW * 4;  // xmax[B][16 waves] u32: largest |x| seen by each wave (fused finalize)
-  }
-};
-
-// `block` in [0, 256): the workgroup's index within its own layer (== blockIdx.x for a single-layer launch).
-// PUB: the row-parallel shard's variant (the last arrival publishes the fp32 total for the peers instead of writing y).  A
-// template parameter, not a run-time test of p.pub: carrying the publish branches in the ordinary kernel cost 0.15 us per
-// launch (same box, profiles/r03_mb_ab_commits.log).
-// VG: variable geometry (format v7): `ns` = the first stream of each of the 16 slices, one byte each; the workgroup finds its
-// slice, row range and stream from them with a handful of instructions (no table in memory: a dependent load in front of the
-// slice fill would cost more than the imbalance it repairs).
-struct PackedVgArgs {
-  uint32_t ns[4];
-};
-
-// NOPF: the launch has no prefetch waves (p.NPW == 0 by construction: the expert-routed launch) -- their branches go away at
-// compile time.  (A run-time p.NPW == 0 leaves them in, and with them a path on which hipcc sees the LDS-DMA still in flight.)
-template <class T_, int B, int PD, uint32_t XWIN, int EB, bool PUB = false, bool VG = false, bool NOPF = false>
-__device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p, const int block, const int NWB,
-                                                      const PackedVgArgs& vg = PackedVgArgs{}) {
-  using LDS = PackedLds<B, XWIN>;
-  using ring_t = typename std::conditional<EB == 3, u32x3, u32x4>::type;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int NT = NWB << 6;  // NWB = waves in the workgroup (>= p.NW); passed in: blockDim lives in the hidden kernel arguments
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef AQLM_PACKED_TRACE
-  unsigned long long tr[8];
-  uint32_t tr_wait = 0, tr_work = 0;
-  tr[0] = wall_clock64();
-  const unsigned long long cyc0 = __builtin_readcyclecounter();  // s_memtime: shader clock
-#define AQLM_TRACE(i) tr[i] = wall_clock64()
-#else
-#define AQLM_TRACE(i)
-#endif
-  // slice = block % 16: blocks are observed to land on XCD block % 8, so each XCD's L2 serves two 64 KiB slices
-  // (speed only; any placement is correct).
-  int slice, group, row_begin, nrows, stream_ix;
-  if constexpr (VG) {
-    static_assert(PK_S == 16 && PK_NST == 256, "variable geometry: 16 slices, 256 workgroups");
-    // workgroups land on XCD block % 8: XCD x serves streams [32 x, 32 x + 32) -- consecutive streams share their slice
-    stream_ix = ((block & 7) << 5) | (block >> 3);
-    // ns = the first stream of slices 0..15, one byte each (slice 0 starts at 0, the last slice ends at 256).  Lane i < 16
-    // looks at slice i: the slices that start at or before this stream answer the ballot, the last of them owns it.
-    // (A scalar walk over the 16 bytes was ~280 dependent instructions in front of the first load: 0.5 us.)
-    const uint32_t w = lane < 4 ? vg.ns[0] : (lane < 8 ? vg.ns[1] : (lane < 12 ? vg.ns[2] : vg.ns[3]));
-    const uint32_t start_v = (w >> ((lane & 3) * 8)) & 255u;
-    const unsigned long long m = __ballot((uint32_t)stream_ix >= start_v) & 0xffffull;
-    const int s = __popcll(m) - 1;
-    const int start = __builtin_amdgcn_readlane((int)start_v, s);
-    const int end = s == PK_S - 1 ? PK_NST : __builtin_amdgcn_readlane((int)start_v, s < PK_S - 1 ? s + 1 : s);
-    int n = end - start;
-    n = n < 1 ? 1 : n;
-    slice = s;
-    group = stream_ix - start;
-    const int base = p.M / n, extra = p.M - base * n;
-    row_begin = group * base + (group < extra ? group : extra);
-    nrows = base + (group < extra ? 1 : 0);
-  } else {
-    stream_ix = block;
-    slice = block & (PK_S - 1);
-    group = block >> PK_S_LOG;
-    row_begin = group * p.RG;
-    nrows = p.M - row_begin;
-    nrows = nrows < 0 ? 0 : (nrows < p.RG ? nrows : p.RG);
-  }
-  if ((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_raw != 0u) __builtin_trap();  // LDS map above
-
-  const int RG1 = p.RG + 1;
-  const uint32_t rowstart_off = LDS::rowstart(p.in_groups);
-  const uint32_t rowval_off = LDS::rowval(p.in_groups, p.RG);
-  const uint32_t colend_off = LDS::colend(p.in_groups, p.RG);
-
-  // ---- prologue: everything that needs no other data is issued first, in one burst -------------------------------
-  const uint32_t XP = LDS::plane(p.in_groups);
-  const uint32_t xstride16 = (uint32_t)pk_x_stride(p.in_groups) * PK_VB;
-  __amdgpu_buffer_rsrc_t rs_ent = __builtin_amdgcn_make_buffer_rsrc((void*)p.ent, 0, p.ent_bytes, 0x00020000);
-  const int wv = wave < p.NW ? wave : p.NW - 1;  // waves beyond the stream's wave count (shared-input launches) idle
-  const uint32_t wbase = (uint32_t)(((size_t)stream_ix * p.NW + wv) * p.T) * (EB == 3 ? (uint32_t)PK_WREG3 : 1024u);
-  const int Tm1 = p.T - 1;
-  // (0) 3-byte entries: the row-end flag words of this wave range, word t in lane t -- the OLDEST load of the queue, so
-  // it has landed whenever the wait of (5) returns
-  u32x2 flagw = {0u, 0u};
-  if constexpr (EB == 3)
-    flagw = __builtin_amdgcn_raw_buffer_load_b64(rs_ent, (uint32_t)(lane < Tm1 ? lane : Tm1) * 8u, wbase, 0);
-  // Chain prefetch: the last p.NPW waves of the workgroup take no part in the fill or the loop.  They ask for the NEXT
-  // layer's bytes (LDS-DMA into a 1 KiB dump zone each: no registers, nothing to wait for before the fill barrier) and
-  // meet the others at the barriers.
-  const int NWD = NWB - p.NPW;  // waves that fill and compute
-  const bool pfw = !NOPF && wave >= NWD;
-  if (pfw) {
-    const int pw = wave - NWD;
-    const uint32_t dump = LDS::dump(p.in_groups, p.RG) + (uint32_t)pw * 1024u;
-    const uint8_t* nsrc = p.next_ent + (size_t)block * p.next_block_bytes;
-    for (uint32_t off = (uint32_t)pw * 1024u; off < p.next_block_bytes; off += (uint32_t)p.NPW * 1024u)
-      __builtin_amdgcn_global_load_lds((gbl_void_ptr)(nsrc + off + lane * 16), (lds_void_ptr)(size_t)dump, 16, 0, AUX_NT);
-    constexpr uint32_t SHARE = PK_SLICE_BYTES / PK_NG;  // the PK_NG workgroups of a slice split its next-layer image
-    const uint8_t* csrc = p.next_codebook + (size_t)slice * PK_SLICE_BYTES + (size_t)group * SHARE;
-    for (uint32_t off = (uint32_t)pw * 1024u; off < SHARE; off += (uint32_t)p.NPW * 1024u)
-      __builtin_amdgcn_global_load_lds((gbl_void_ptr)(csrc + off + lane * 16), (lds_void_ptr)(size_t)dump, 16, 0, 0);
-  }
-  // (1) LDS-DMA: the 64 KiB slice (shared by the 16 workgroups of the XCD that hold it -> L2 hits) and x
-  if (!pfw) {
-    const uint8_t* src = p.codebook + (size_t)slice * PK_SLICE_BYTES;
-    // rotated start: the PK_NG workgroups that fill the same slice from the same L2 walk it from different pieces, so at
-    // any moment they ask different L2 channels (and, cold, each pulls a different part from HBM first)
-    constexpr int PIECES = (int)(PK_SLICE_BYTES / 1024);
-    const int rot = p.fill_rotate ? (group & (PK_NG - 1)) * (PIECES / PK_NG) : 0;
-    for (int i0 = wave; i0 < PIECES; i0 += NWD) {
-      const int i = (i0 + rot) & (PIECES - 1);
-      __builtin_amdgcn_global_load_lds((gbl_void_ptr)(src + i * 1024 + lane * 16),
-                                       (lds_void_ptr)(size_t)(LDS::SLICE + (uint32_t)i * 1024u), 16, 0, 0);
-    }
-    const int x16 = p.in_groups * (int)(PK_VB / 16);  // 16-byte units of a row of x
-    const int nchunk = (x16 + 63) >> 6;              // KiB pieces per row of x
-    // B == 1: XC rotated copies of the row (copy c at slot c * xstride); B > 1: one plane per row
-    const int ncopy = B == 1 ? p.XC : B;
-    for (int c = wave; c < nchunk * ncopy; c += NWD) {
-      const int b = c / nchunk, i = c - b * nchunk;
-      const int idx = i * 64 + lane;
-      const uint32_t dst = LDS::X + (uint32_t)b * (B == 1 ? xstride16 : XP) + (uint32_t)i * 1024u;
-      if (idx < x16)
-        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(p.x + (B == 1 ? (size_t)0 : (size_t)b * p.x_row_stride) + (size_t)idx * 8),
-                                         (lds_void_ptr)(size_t)dst, 16, 0, 0);
-    }
-    // the stream's row starts (needed by the epilogue only; as an LDS-DMA they are older than the ring loads, see (5)).
-    // Rows of the table are only 4-B aligned -> dword DMA, 256 B per wave-instruction.
-    const uint32_t* rs_src = p.rowstart + (size_t)stream_ix * RG1;
-    for (int i = wave; i * 64 < RG1; i += NWD) {
-      const int idx = i * 64 + lane;
-      if (idx < RG1)
-        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(rs_src + idx), (lds_void_ptr)(size_t)(rowstart_off + (uint32_t)i * 256u), 4, 0, 0);
-    }
-  }
-  // (2) the entry stream of this wave: fixed addresses, PD steps ahead in a register ring with compile-time slots
-  const uint32_t voff = (uint32_t)lane * (EB == 3 ? 12u : 16u);
-  const uint32_t ebase = EB == 3 ? wbase + (uint32_t)p.T * 8u : wbase;
-  auto fetch = [&](int t) -> ring_t {  // unconditional (a load under a branch derails hipcc's wait counts); steps past the
-    // end of the range get an out-of-range offset: the buffer unit answers them with zeros and touches no memory
-#ifdef AQLM_PACKED_TRACE
-    const uint32_t vo = (t <= Tm1 && !(p.dbg & 2)) ? voff : 0xfffffff0u;
-#else
-    const uint32_t vo = t <= Tm1 ? voff : 0xfffffff0u;
-#endif
-    if constexpr (EB == 3) return __builtin_amdgcn_raw_buffer_load_b96(rs_ent, vo, ebase + (uint32_t)t * (uint32_t)PK_STEP3, AUX_NT);
-    else return __builtin_amdgcn_raw_buffer_load_b128(rs_ent, vo, ebase + (uint32_t)t * 1024u, AUX_NT);
-  };
-  ring_t ring[PD];
-#pragma unroll
-  for (int k = 0; k < PD; ++k) ring[k] = fetch(pfw ? 0x7fffffff : k);  // prefetch waves: out-of-range requests (zeros, no memory traffic)
-  // (3) steps of this wave through the scalar cache (not a VMEM op: it must not sit in the vmcnt queue, see (5))
-  // 4-byte entries need neither: the start rows ride in the entries, and every wave range runs all T steps (the tail of a
-  // stream is padded with null entries up to T steps -- the workgroup waits for its full ranges anyway)
-  int steps = wave < p.NW ? p.T : 0;
-  [[maybe_unused]] uint32_t wave_start_row = 0u;
-  if constexpr (EB == 3) {
-    const const_u32_ptr wi = (const_u32_ptr)(uintptr_t)(p.winfo + ((size_t)stream_ix * p.NW + wv) * 4);
-    steps = wave < p.NW ? (int)wi[2] : 0;
-    wave_start_row = wi[3];
-  }
-  // (4) LDS that needs no data: the zero vectors the null entries point at
-  if (tid < B * (int)(PK_VB / 16))  // the null entries' x: PK_VB zero bytes per row of x
-    *reinterpret_cast<u32x4*>(smem_raw + LDS::X + (uint32_t)(tid / (int)(PK_VB / 16)) * XP + (uint32_t)p.in_groups * PK_VB +
-                              (uint32_t)(tid % (int)(PK_VB / 16)) * 16u) = u32x4{0u, 0u, 0u, 0u};
-  const uint32_t xmax_off = LDS::xmax(p.in_groups, p.RG);
-  if (tid < B * PK_MAX_NW) *reinterpret_cast<uint32_t*>(smem_raw + xmax_off + (uint32_t)tid * 4u) = 0u;  // slots of absent waves
-  AQLM_TRACE(1);  // every load of the prologue has been issued
-  // (5) the slice and x are older in the VMEM queue than the PD ring loads: wait for everything BUT the ring, so the
-  // stream keeps flowing while the loop starts (a __syncthreads() here would emit vmcnt(0) and drain it)
-  // (the builtin, not an asm string: hipcc's wait-count pass must learn that the LDS-DMA ops have retired, or it guards
-  // the first use of the ring with vmcnt(0))
-  // the parameters of the epilogue (the non-preloaded tail of the kernel arguments) are fetched NOW, under the LDS fill:
-  // left to the compiler their s_load sits at the first use, behind the loop, with its whole latency exposed (0.3 us)
-  asm volatile("" : : "s"(p.acc), "s"(p.partial), "s"(p.scales), "s"(p.bias), "s"(p.y), "s"(p.y_row_stride), "s"(p.cb_absmax));
-  // ... and so are scale and bias of the row this thread finalizes (cold they are an HBM round trip: requested behind the
-  // last-arrival test they sat at the very end of the kernel's critical path).  Unconditional, always-valid addresses
-  // (a branch around a load ends in a vmcnt(0) at the join); younger than the ring, so the wait below lets them fly too.
-  uint16_t scale_h, bias_h;
-  {
-    const int r = tid < nrows ? tid : (nrows > 0 ? nrows - 1 : 0);
-    const uint16_t* sp = p.scales ? p.scales : reinterpret_cast<const uint16_t*>(p.rowstart);  // partials mode: unused
-    const uint16_t* bp = p.bias ? p.bias : sp;
-    scale_h = sp[row_begin + r];
-    bias_h = bp[row_begin + r];
-  }
-  constexpr int PDW = PD + 2;
-  if (!pfw) __builtin_amdgcn_s_waitcnt((PDW & 15) | (7 << 4) | (0 << 8) | ((PDW >> 4) << 14));  // vmcnt(PD + 2) lgkmcnt(0)
-  else __builtin_amdgcn_s_waitcnt(63 | (7 << 4) | (0 << 8) | (3 << 14));                          // prefetch waves: lgkmcnt(0) only
-  __builtin_amdgcn_s_barrier();
-  AQLM_TRACE(2);
-
-  uint32_t mask = PK_HMASK;
-  asm volatile("" : "+v"(mask));  // the SDWA operand must sit in a VGPR
-  // One accumulator chain per row of x for every batch size: a row's result must not depend on how many rows share the
-  // launch (tested bit for bit).  Several independent chains per row were measured: no gain (the loop is not bound by
-  // the dependent latency of v_dot2c).
-  constexpr int NA = 1;
-  float acc[B][NA];
-#pragma unroll
-  for (int b = 0; b < B; ++b)
-#pragma unroll
-    for (int a = 0; a < NA; ++a) acc[b][a] = 0.f;
-  uint32_t row_addr = 0;  // LDS byte address of rowval[0][current row of this column]
-
-  // One lane-step = 4 entries.  Per entry: a_cb / a_x = LDS byte offsets of the codebook vector (inside the slice) and of
-  // x[j] (inside the x area; for B > 1 `copy` is the x copy the entry names -- the planes hold one, so its offset is
-  // taken out again).  ALL LDS reads of a group of entries are issued before the first dot product: with 2 waves per SIMD
-  // the loop is bound by LDS latency, not bandwidth (traced: 0.3 us per step with two entries in flight per wave).
-  constexpr int NV = (int)(PK_VB / 16);  // 16-byte reads per vector: 1 (8 elements) or 2 (16 elements)
-  constexpr int EG0 = B <= 2 ? 4 : (B <= 4 ? 2 : 1);
-  constexpr int EG = NV > 1 && EG0 > 1 && B > 1 ? EG0 / 2 : EG0;  // entries per read batch (registers: EG * NV * (1 + B) * 4)
-  auto entries = [&](const uint32_t (&a_cb)[4], const uint32_t (&a_x)[4], const uint32_t (&copy)[4]) {
-#ifdef AQLM_PACKED_TRACE
-    if (p.dbg & 1) { acc[0][0] += __uint_as_float(a_cb[0] ^ a_x[1] ^ a_cb[2] ^ a_x[3]); return; }
-#endif
-#pragma unroll
-    for (int g0 = 0; g0 < 4; g0 += EG) {
-      u32x4 ev[EG][NV], xv[EG][B][NV];
-#ifdef AQLM_PACKED_TRACE
-      if (p.dbg & 8) {  // no LDS reads: the dot products run on register garbage (what does the VALU part cost alone?)
-#pragma unroll
-        for (int k = 0; k < EG; ++k)
-#pragma unroll
-          for (int h = 0; h < NV; ++h) {
-            ev[k][h] = u32x4{a_cb[g0 + k], a_x[g0 + k], a_cb[g0 + k] ^ 0x3c00u, a_x[g0 + k] ^ 0x3c00u};
-#pragma unroll
-            for (int b = 0; b < B; ++b) xv[k][b][h] = u32x4{a_x[g0 + k], a_cb[g0 + k], a_x[g0 + k] ^ 0x3c00u, a_cb[g0 + k]};
-          }
-      } else
-#endif
-#pragma unroll
-      for (int k = 0; k < EG; ++k) {
-#pragma unroll
-        for (int h = 0; h < NV; ++h) ev[k][h] = *(lds_u32x4_ptr)(size_t)((a_cb[g0 + k] ^ ((uint32_t)h * 16u)) + LDS::SLICE);
-        if constexpr (B == 1) {
-#pragma unroll
-          for (int h = 0; h < NV; ++h) xv[k][0][h] = *(lds_u32x4_ptr)(size_t)((a_x[g0 + k] ^ ((uint32_t)h * 16u)) + LDS::X);
-        } else {
-#pragma unroll
-          for (int h = 0; h < NV; ++h) {
-            const uint32_t ax = (a_x[g0 + k] ^ ((uint32_t)h * 16u)) + LDS::X - copy[g0 + k] * xstride16;
-#pragma unroll
-            for (int b = 0; b < B; ++b) xv[k][b][h] = *(lds_u32x4_ptr)(size_t)(ax + (uint32_t)b * XP);
-          }
-        }
-      }
-#ifdef AQLM_PACKED_TRACE
-      if (p.dbg & 4) {  // LDS reads but no dot products: one op per entry keeps the reads alive
-#pragma unroll
-        for (int k = 0; k < EG; ++k) acc[0][0] += __uint_as_float((ev[k][NV - 1].x ^ xv[k][0][NV - 1].w) & 0x007fffffu);
-        continue;
-      }
-#endif
-#pragma unroll
-      for (int k = 0; k < EG; ++k)
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-#pragma unroll
-          for (int h = 0; h < NV; ++h) acc[b][(g0 + k) % NA] = dot8<T_>(ev[k][h], xv[k][b][h], acc[b][(g0 + k) % NA]);
-    }
-  };
-  auto total = [&](int b) -> float {  // fixed summation order of the chains
-    float v = acc[b][0];
-#pragma unroll
-    for (int a = 1; a < NA; ++a) v += acc[b][a];
-    return v;
-  };
-  auto flush = [&]() {  // a row ends here: exactly one lane-step per row does, so the store has a unique writer
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      lds_store_f32(row_addr + (uint32_t)(b * RG1) * 4u, total(b));
-#pragma unroll
-      for (int a = 0; a < NA; ++a) acc[b][a] = 0.f;
-    }
-    row_addr += 4u;
-  };
-  uint32_t cmask = 0u;  // 3-byte entries: bit t = this column's lane-step t ends a row
-  [[maybe_unused]] uint32_t xrecip = 0u;
-  if constexpr (EB == 3 && B > 1) xrecip = 0xffffffffu / (xstride16 >> 4) + 1u;  // slot / stride == mulhi(slot, xrecip) for slot < 2^16
-  auto step = [&](const ring_t& e) {
-    uint32_t a_cb[4], a_x[4], copy[4] = {0u, 0u, 0u, 0u};
-    if constexpr (EB == 4) {
-      const uint32_t w[4] = {e.x, e.y, e.z, e.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        a_cb[k] = half_and<0>(w[k], mask);  // (plain v_and / v_lshrrev instead of the two SDWA ops: measured, no change)
-        a_x[k] = half_and<1>(w[k], mask);
-        if constexpr (B > 1) copy[k] = (w[k] >> 16) & 3u;
-      }
-      entries(a_cb, a_x, copy);
-      if (e.x & 1u) flush();
-    } else {
-      // 96 bits = 4 x (slot:12 | code:12), entry k at bit 24 k
-      const uint32_t w0 = e.x, w1 = e.y, w2 = e.z;
-      const uint32_t t1 = __builtin_amdgcn_alignbit(w1, w0, 24);   // bits 24.. : code 1 in [11:0]
-      const uint32_t t2 = __builtin_amdgcn_alignbit(w2, w1, 28);   // bits 60.. : slot 2 in [11:0]
-      a_cb[0] = (w0 << 4) & 0xfff0u;   a_x[0] = (w0 >> 8) & 0xfff0u;
-      a_cb[1] = (t1 << 4) & 0xfff0u;   a_x[1] = w1 & 0xfff0u;
-      a_cb[2] = (w1 >> 12) & 0xfff0u;  a_x[2] = (t2 << 4) & 0xfff0u;
-      a_cb[3] = (w2 >> 4) & 0xfff0u;   a_x[3] = half_and<1>(w2, mask);
-      if constexpr (B > 1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) copy[k] = __umulhi(a_x[k] >> 4, xrecip);
-      }
-      entries(a_cb, a_x, copy);
-      if (cmask & 1u) flush();
-      cmask >>= 1;
-    }
-  };
-
-  if (steps > 0) {
-    if constexpr (EB == 4) {  // the column's starting row rides in the spare bits of its first lane-step
-      const uint32_t f = pk_get_start_row(ring[0].x, ring[0].y, ring[0].z, ring[0].w);
-      row_addr = rowval_off + f * 4u;
-    } else {  // flag word t sits in lane t: collect this lane's bit of every word, and count the row ends of the columns before it
-      uint32_t pre = 0u;
-      const uint32_t l31 = (uint32_t)lane & 31u;
-      for (int t = 0; t < steps; ++t) {
-        const uint32_t slo = (uint32_t)__builtin_amdgcn_readlane((int)flagw.x, t), shi = (uint32_t)__builtin_amdgcn_readlane((int)flagw.y, t);
-        const uint32_t sel = lane >= 32 ? shi : slo;
-        cmask |= ((sel >> l31) & 1u) << t;
-        pre = __builtin_amdgcn_mbcnt_hi(shi, __builtin_amdgcn_mbcnt_lo(slo, pre));
-      }
-      row_addr = rowval_off + (wave_start_row + pre) * 4u;
-    }
-    int t = 0;
-    for (; t + PD <= steps; t += PD) {
-#pragma unroll
-      for (int k = 0; k < PD; ++k) {  // single back-edge, static ring slots: no in-flight register is ever copied
-#ifdef AQLM_PACKED_TRACE
-        // profiling build: split a step into "waiting for its entries" and "LDS reads + dot products" (shader cycles)
-        const unsigned long long c0 = __builtin_amdgcn_s_memtime();
-        __builtin_amdgcn_s_waitcnt(((PD - 1) & 15) | (7 << 4) | (15 << 8));
-        const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-        step(ring[k]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long c2 = __builtin_amdgcn_s_memtime();
-        tr_wait += (uint32_t)(c1 - c0);
-        tr_work += (uint32_t)(c2 - c1);
-#else
-        step(ring[k]);                 // the slot's words are dead once their addresses are formed ...
-#endif
-        ring[k] = fetch(t + PD + k);   // ... so the refill lands in the same registers (no copy at the back-edge)
-      }
-    }
-    const int rem = steps - t;
-#pragma unroll
-    for (int k = 0; k < PD - 1; ++k)
-      if (k < rem) step(ring[k]);
-  }
-  // Fused finalize: the largest |x| of every input row, as the 15-bit magnitude pattern of the storage type (integer
-  // order == magnitude order; a NaN compares above Inf, so it surfaces).  x sits in LDS and every workgroup of the layer
-  // sees the same x, so all of them derive the same fixed-point scale from it in the epilogue.  Done AFTER the loop: the
-  // waves finish it at different times (the SIMDs favour their older waves), so for most of them this is idle time, and
-  // right behind the fill barrier it would stand between every wave and its first lane-step (measured: 0.35 us).
-  if (p.acc != nullptr) {
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      us2 m = {0, 0};
-      for (int idx = tid; idx < p.in_groups * (int)(PK_VB / 16); idx += NT) {
-        const u32x4 v = *(lds_u32x4_ptr)(size_t)(LDS::X + (uint32_t)b * (B == 1 ? 0u : XP) + (uint32_t)idx * 16u);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m = __builtin_elementwise_max(m, __builtin_bit_cast(us2, w[k] & 0x7fff7fffu));
-      }
-      // wave maximum on the VALU (DPP), one slot per wave: no LDS atomics, no shuffle round trips on the way to the loop
-      const uint32_t mm = wave_max_u32(m.x > m.y ? (uint32_t)m.x : (uint32_t)m.y);
-      if (lane == 0) *reinterpret_cast<uint32_t*>(smem_raw + xmax_off + (uint32_t)(b * PK_MAX_NW + wave) * 4u) = mm;
-    }
-  }
-
-  // what the column gathered after its last row end belongs to a row that continues in the next column (0 otherwise)
-  if (wave < p.NW) {
-#pragma unroll
-    for (int b = 0; b < B; ++b) lds_store_f32(colend_off + (uint32_t)((b * PK_MAX_NW + wave) * 64 + lane) * 4u, total(b));
-  }
-  AQLM_TRACE(4);
-  asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");  // the asm LDS stores above are invisible to the compiler's counters
-  __syncthreads();
-  AQLM_TRACE(5);
-  // ---- epilogue: row r = rowval[r] + the column remainders of the columns it crosses, in column order -------------
-  float* pub_half = nullptr;
-  uint32_t pub_e = 0u;
-  if (PUB && p.pub != nullptr && p.acc != nullptr) {  // row-parallel shard: publish instead of writing y (epoch parity picks the half)
-    pub_e = __hip_atomic_load(p.pub_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    pub_half = p.pub + (size_t)(pub_e & 1u) * p.pub_max_elems;
-  }
-  {
-    const uint32_t* rs = reinterpret_cast<const uint32_t*>(smem_raw + rowstart_off);
-    const float* rowval = reinterpret_cast<const float*>(smem_raw + rowval_off);
-    const float* colend = reinterpret_cast<const float*>(smem_raw + colend_off);
-    const uint32_t T = (uint32_t)p.T;
-    for (int r = tid; r < nrows; r += NT) {
-      const uint32_t q0 = rs[r], q1 = rs[r + 1];
-      const uint32_t c0 = q0 / T, c1 = (q1 - 1u) / T;  // first / last column the row touches (column = wave * 64 + lane)
-      float v[B];
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        v[b] = rowval[b * RG1 + r];
-        for (uint32_t c = c0; c < c1; ++c) v[b] += colend[(size_t)b * PK_MAX_NW * 64 + c];
-      }
-      if (p.acc == nullptr) {
-#pragma unroll
-        for (int b = 0; b < B; ++b) p.partial[((size_t)slice * B + b) * p.M + row_begin + r] = v[b];
-      } else {
-        // Fused finalize.  The slice sum goes into the row's cell as a fixed-point number in bits 63..10 (integer adds
-        // commute: the total does not depend on the order the 16 workgroups arrive in), together with +1 in the arrival
-        // counter (bits 4..0) and +1 in bits 9..5 if the value is not finite.  The unit 2^-sh comes from a bound every
-        // workgroup of the layer computes identically: |slice sum| <= in_features * max|codebook| * max|x| < 2^e, so
-        // with sh = 47 - e sixteen addends stay below 2^52 -- no overflow whatever the data, and ~2^-47 of the bound as
-        // resolution (fp32 partials carry 2^-24 of their own magnitude).  ONE returning atomic per cell is the whole
-        // hand-shake: whoever reads 15 earlier arrivals owns the total, applies scale and bias, rounds once, writes y and
-        // puts the cell back to zero for the next launch.
-        const int row = row_begin + r;
-        unsigned long long old[B], mine[B];
-        int sh[B];
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          uint32_t xm = 0u;  // every wave of the workgroup left the maximum of its share of x
-          {                  // (16 slots = four 16-B reads in flight together)
-            static_assert(PK_MAX_NW == 16, "four 16-byte reads cover the slots");
-            u32x4 sl[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sl[q] = *(lds_u32x4_ptr)(size_t)(xmax_off + (uint32_t)(b * PK_MAX_NW + q * 4) * 4u);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const uint32_t a = sl[q].x > sl[q].y ? sl[q].x : sl[q].y, c = sl[q].z > sl[q].w ? sl[q].z : sl[q].w;
-              const uint32_t d = a > c ? a : c;
-              xm = d > xm ? d : xm;
-            }
-          }
-          const float bound = (float)p.in_groups * (float)PK_G * p.cb_absmax * T_::to_float((uint16_t)xm);
-          int e = 0;
-          (void)frexpf(bound, &e);                               // bound < 2^e (e = 0 for bound == 0)
-          const bool finite = bound < __builtin_inff() && fabsf(v[b]) <= 2.f * bound;  // false for NaN / Inf anywhere
-          sh[b] = PK_FIX_BITS - e;
-          const long long q = finite ? __float2ll_rn(ldexpf(v[b], sh[b])) : 0ll;
-          mine[b] = ((unsigned long long)q << PK_VAL_SHIFT) + (finite ? 1ull : 1ull + (1ull << PK_CNT_BITS));
-          old[b] = __hip_atomic_fetch_add(p.acc + (size_t)b * p.M + row, mine[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        const bool first = r == tid;  // this thread's first (usually only) row: scale and bias were requested in the prologue
-        const float scale = pub_half ? 1.f : T_::to_float(first ? scale_h : p.scales[row]);
-        const float bias = (pub_half || !p.bias) ? 0.f : T_::to_float(first ? bias_h : p.bias[row]);
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          if ((old[b] & PK_CNT_MASK) == (unsigned long long)(PK_S - 1)) {
-            const unsigned long long cell = old[b] + mine[b];
-            const long long sum = (long long)cell >> PK_VAL_SHIFT;
-            float sv = (float)ldexp((double)sum, -sh[b]);
-            if ((cell >> PK_CNT_BITS) & PK_CNT_MASK) sv = __builtin_nanf("");
-            if (pub_half)  // the shard's fp32 total, visible to the peers (write-through, system scope); scale / bias later
-              __hip_atomic_store(pub_half + (size_t)b * p.M + row, sv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            else
-              p.y[(size_t)b * p.y_row_stride + row] = T_::from_float(__builtin_fmaf(sv, scale, bias));
-            __hip_atomic_store(p.acc + (size_t)b * p.M + row, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-    }
-  }
-  if (pub_half) {
-    // Every row total of this launch is published by exactly one workgroup before that workgroup arrives here: when all
-    // PK_NST workgroups have arrived (8 sharded counters of PK_NST / 8 arrivals, then one of 8 -- a single counter would
-    // serialise 256 device-scope atomics), everything is out and the rank's flag goes up.  Stores are drained first
-    // (write-through + vmcnt(0) == published, cdna_hip_programming.md Guideline 16 R1).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t* shard = p.pub_epoch + 4 + (block & 7);
-      const uint32_t a = __hip_atomic_fetch_add(shard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a + 1u == (uint32_t)(PK_NST / 8)) {
-        __hip_atomic_store(shard, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t t = __hip_atomic_fetch_add(p.pub_epoch + 12, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t + 1u == 8u) {
-          __hip_atomic_store(p.pub_epoch + 12, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __hip_atomic_store(p.pub_flag + (pub_e & 1u), pub_e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-    }
-  }
-#ifdef AQLM_PACKED_TRACE
-  AQLM_TRACE(6);
-  if (p.trace && lane == 0) {
-    unsigned long long* o = p.trace + ((size_t)block * PK_MAX_NW + wave) * 8;
-    tr[3] = __builtin_readcyclecounter() - cyc0;  // shader cycles from entry to end (slot 3 is not a time stamp)
-    tr[7] = ((unsigned long long)tr_wait << 32) | tr_work;  // steps of the main loop: cycles waiting for entries | cycles in LDS reads + dots
-    for (int i = 0; i < 8; ++i) o[i] = tr[i];
-  }
-#endif
-}
-
-// What the prologue needs before it can issue its first load comes as individual leading arguments: with
-// -amdgpu-kernarg-preload-count (Makefile) the command processor delivers those 14 dwords in SGPRs at wave launch, and
-// the cold s_load round trip of the kernel-argument segment leaves the head of the critical path.  Struct arguments
-// are not preloaded; the rest of the parameters (needed after the LDS fill) stay in one.
-struct PackedGemvRest {
-  const uint32_t* winfo;
-  float* partial;
-  long x_row_stride;
-  unsigned long long* acc;
-  const uint16_t* scales;
-  const uint16_t* bias;
-  uint16_t* y;
-  long y_row_stride;
-  float cb_absmax;
-  const uint8_t* next_ent;
-  const uint8_t* next_codebook;
-  uint32_t next_block_bytes;
-  float* pub;
-  uint32_t* pub_flag;
-  uint32_t* pub_epoch;
-  uint32_t pub_max_elems;
-#ifdef AQLM_PACKED_TRACE
-  unsigned long long* trace;
-  int dbg;
-#endif
-};
-
-template <class T_, int B, int PD, uint32_t XWIN, int EB, bool PUB = false>
-__global__ __launch_bounds__(1024) void gemv_1x16_packed_kernel(const uint8_t* codebook, const uint16_t* x, const uint32_t* ent,
-                                                                const uint32_t* rowstart, int in_groups, uint32_t geom, int RG,
-                                                                uint32_t ent_bytes, int M, const PackedGemvRest rest) {
-  // geom: waves 0..7 | x copies 8..11 | prefetch waves 12..14 | rotated fill 15 | steps 16..31
-  const int NW = (int)(geom & 0xffu), XC = (int)((geom >> 8) & 0xfu), NPW = (int)((geom >> 12) & 7u), T = (int)(geom >> 16);
-  PackedGemvParams p;
-  p.NPW = NPW;
-  p.fill_rotate = (int)((geom >> 15) & 1u);
-  p.next_ent = rest.next_ent;
-  p.next_codebook = rest.next_codebook;
-  p.next_block_bytes = rest.next_block_bytes;
-  p.pub = rest.pub;
-  p.pub_flag = rest.pub_flag;
-  p.pub_epoch = rest.pub_epoch;
-  p.pub_max_elems = rest.pub_max_elems;
-  p.ent = ent;
-  p.winfo = rest.winfo;
-  p.rowstart = rowstart;
-  p.codebook = codebook;
-  p.x = x;
-  p.partial = rest.partial;
-  p.acc = rest.acc;
-  p.cb_absmax = rest.cb_absmax;
-  p.scales = rest.scales;
-  p.bias = rest.bias;
-  p.y = rest.y;
-  p.y_row_stride = rest.y_row_stride;
-  p.x_row_stride = rest.x_row_stride;
-  p.M = M;
-  p.in_groups = in_groups;
-  p.RG = RG;
-  p.NW = NW;
-  p.T = T;
-  p.XC = XC;
-  p.ent_bytes = ent_bytes;
-#ifdef AQLM_PACKED_TRACE
-  p.trace = rest.trace;
-  p.dbg = rest.dbg;
-#endif
-  gemv_1x16_packed_body<T_, B, PD, XWIN, EB, PUB>(p, blockIdx.x, NW + NPW);
-}
-
-#if AQLM_PK_G == 8
-// Variable-geometry twin (format v7, flag AQLM_HIP_PACKED_VARGEOM): same body; the 14 preloaded dwords now also carry the row
-// groups of the 16 slices, so three of the ordinary kernel's arguments travel compressed: the row-start table as its distance
-// in front of the entries, in_groups and the row-table size in one word, and the entry bytes are derived (4-byte entries only).
-template <class T_, int B, int PD, uint32_t XWIN>
-__global__ __launch_bounds__(1024) void gemv_1x16_packed_vg_kernel(const uint8_t* codebook, const uint16_t* x, const uint32_t* ent,
-                                                                   uint32_t rowstart_back, uint32_t ig_rg, uint32_t geom, int M,
-                                                                   uint32_t ns0, uint32_t ns1, uint32_t ns2, uint32_t ns3,
-                                                                   const PackedGemvRest rest) {
-  // geom: waves 0..7 | x copies 8..11 | rotated fill 15 | steps 16..31;  ig_rg: in_groups 0..11 | rows per group 12..27
-  const int NW = (int)(geom & 0xffu), XC = (int)((geom >> 8) & 0xfu), T = (int)(geom >> 16);
-  PackedGemvParams p;
-  p.NPW = 0;
-  p.fill_rotate = (int)((geom >> 15) & 1u);
-  p.next_ent = nullptr;
-  p.next_codebook = nullptr;
-  p.next_block_bytes = 0;
-  p.pub = nullptr;
-  p.pub_flag = nullptr;
-  p.pub_epoch = nullptr;
-  p.pub_max_elems = 0;
-  p.ent = ent;
-  p.winfo = rest.winfo;
-  p.rowstart = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ent) - rowstart_back);
-  p.codebook = codebook;
-  p.x = x;
-  p.partial = rest.partial;
-  p.acc = rest.acc;
-  p.cb_absmax = rest.cb_absmax;
-  p.scales = rest.scales;
-  p.bias = rest.bias;
-  p.y = rest.y;
-  p.y_row_stride = rest.y_row_stride;
-  p.x_row_stride = rest.x_row_stride;
-  p.M = M;
-  p.in_groups = (int)(ig_rg & 0xfffu);
-  p.RG = (int)(ig_rg >> 12);
-  p.NW = NW;
-  p.T = T;
-  p.XC = XC;
-  p.ent_bytes = (uint32_t)PK_NST * (uint32_t)NW * (uint32_t)T * 1024u;
-#ifdef AQLM_PACKED_TRACE
-  p.trace = rest.trace;
-  p.dbg = rest.dbg;
-#endif
-  const PackedVgArgs vg{{ns0, ns1, ns2, ns3}};
-  gemv_1x16_packed_body<T_, B, PD, XWIN, 4, false, true>(p, blockIdx.x, NW, vg);
-}
-#endif
-
-// Several prepacked layers that multiply the same x (q/k/v, gate/up) in one launch of 256 workgroups per layer; the
-// next layer's workgroups start as CUs free up, so one layer's tail and the next one's LDS fill overlap.
-struct PackedSegment {
-  const uint32_t* ent;
-  const uint32_t* winfo;
-  const uint32_t* rowstart;
-  const uint8_t* codebook;
-  float* partial;
-  int M, RG, NW, T, XC;
-  uint32_t ent_bytes;
-  // fused finalize (acc != nullptr)
-  unsigned long long* acc;
-  const uint16_t* scales;
-  const uint16_t* bias;
-  uint16_t* y;
-  long y_row_stride;
-  float cb_absmax;
-};
-
-struct PackedMultiParams {
-  const uint16_t* x;
-  long x_row_stride;
-  int in_groups, nseg;
-  PackedSegment seg[AQLM_HIP_MAX_SEGMENTS];
-};
-
-template <class T_, int B, int PD, uint32_t XWIN, int EB>
-__global__ __launch_bounds__(1024) void gemv_1x16_packed_multi_kernel(const PackedMultiParams mp) {
-  const int sidx = (int)blockIdx.x / PK_NST;
-  PackedGemvParams p{};
-  p.x = mp.x;
-  p.x_row_stride = mp.x_row_stride;
-  p.in_groups = mp.in_groups;
-#pragma unroll
-  for (int k = 0; k < AQLM_HIP_MAX_SEGMENTS; ++k) {
-    if (k == 0 || sidx == k) {  // scalar select chain (no dynamic indexing of the kernel-argument struct)
-      p.ent = mp.seg[k].ent;
-      p.winfo = mp.seg[k].winfo;
-      p.rowstart = mp.seg[k].rowstart;
-      p.codebook = mp.seg[k].codebook;
-      p.partial = mp.seg[k].partial;
-      p.M = mp.seg[k].M;
-      p.RG = mp.seg[k].RG;
-      p.NW = mp.seg[k].NW;
-      p.T = mp.seg[k].T;
-      p.XC = mp.seg[k].XC;
-      p.ent_bytes = mp.seg[k].ent_bytes;
-      p.acc = mp.seg[k].acc;
-      p.scales = mp.seg[k].scales;
-      p.bias = mp.seg[k].bias;
-      p.y = mp.seg[k].y;
-      p.y_row_stride = mp.seg[k].y_row_stride;
-      p.cb_absmax = mp.seg[k].cb_absmax;
-    }
-  }
-  gemv_1x16_packed_body<T_, B, PD, XWIN, EB>(p, (int)blockIdx.x % PK_NST, (int)blockDim.x >> 6);
-}
-
-struct PackedFinalizeParams {
-  const float* partial;  // [S][B][M]
-  const uint16_t* scales;
-  const uint16_t* bias;
-  uint16_t* y;
-  long y_row_stride;
-  int M, B;
-};
-
-template <class T_>
-__device__ __forceinline__ void packed_finalize_row(const PackedFinalizeParams& p, int row) {
-  if (row >= p.M) return;
-  const float scale = T_::to_float(p.scales[row]);
-  const float bias = p.bias ? T_::to_float(p.bias[row]) : 0.f;
-  for (int b = 0; b < p.B; ++b) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < PK_S; ++k) s += p.partial[((size_t)k * p.B + b) * p.M + row];
-    p.y[(size_t)b * p.y_row_stride + row] = T_::from_float(__builtin_fmaf(s, scale, bias));
-  }
-}
-
-// scalar arguments: preloaded into SGPRs at wave launch (see gemv_1x16_packed_kernel); this kernel is one dependent load
-// round trip long, the kernel-argument fetch would be a second one
-template <class T_>
-__global__ __launch_bounds__(256) void gemv_1x16_packed_finalize(const float* partial, const uint16_t* scales, const uint16_t* bias,
-                                                                 uint16_t* y, long y_row_stride, int M, int B) {
-  PackedFinalizeParams p;
-  p.partial = partial;
-  p.scales = scales;
-  p.bias = bias;
-  p.y = y;
-  p.y_row_stride = y_row_stride;
-  p.M = M;
-  p.B = B;
-  packed_finalize_row<T_>(p, blockIdx.x * 256 + threadIdx.x);
-}
-
-struct PackedFinalizeSegment {
-  PackedFinalizeParams f;
-  int block_begin;
-};
-
-struct PackedFinalizeMultiParams {
-  int nseg;
-  PackedFinalizeSegment seg[AQLM_HIP_MAX_SEGMENTS];
-};
-
-template <class T_>
-__global__ __launch_bounds__(256) void gemv_1x16_packed_finalize_multi(const PackedFinalizeMultiParams mp) {
-  PackedFinalizeParams p = mp.seg[0].f;
-  int begin = 0;
-#pragma unroll
-  for (int k = 1; k < AQLM_HIP_MAX_SEGMENTS; ++k) {
-    if (k < mp.nseg && (int)blockIdx.x >= mp.seg[k].block_begin) {
-      p = mp.seg[k].f;
-      begin = mp.seg[k].block_begin;
-    }
-  }
-  packed_finalize_row<T_>(p, ((int)blockIdx.x - begin) * 256 + threadIdx.x);
-}
+#include "packed_gemv_kernels.h"  // matvec: params, LDS maps, body, kernel wrappers, finalize kernels
 
 
 // ---------------------------------------------------------------------------------------------- pipelined shared-input launch
@@ -2374,140 +1342,13 @@ static bool pipe_eligible(const PackedLayout* Ls, int n, int in_groups, int& max
   return pipe_lds(max_rg, xwin, oneb).total <= 160u * 1024u;
 }
 
-// ---------------------------------------------------------------------------------------------- host launch helpers
-static int pick_pd(const PackedLayout& L) {
-  const int t = tuning().packed_prefetch;
-  if (t == 3 || t == 4 || t == 8) return t;
-  // measured (profiles/r02_mb_packed_variants.log): 3 steps in flight per wave are best or within 1 % of best on every
-  // shape; 8 are 5-10 % slower (the bigger burst of the prologue delays the codebook slice, which gates the loop)
-  return 3;
-}
-
-// Instantiations: (dtype, B, PD, entry bytes).  Only the batch-1 kernels come with the deeper ring (PD = 8): with more
-// rows the loop is LDS-bound and 4 steps in flight cover the stream.
-// slice_first: the one-row image with the slice in front (no 64 KiB x window): for layers whose row tables do not fit
-// behind the window (packed_b1_slice_first).
-template <class KP, class Launch>
-static int dispatch_packed(int dtype, int batch, int pd, int eb, bool slice_first, Launch&& launch) {
-#define AQLM_PK_GO(TT, BB, PP, EE) launch(KP::template get<TT, BB, PP, EE, PK_XWIN_FULL>(), PackedLds<BB, PK_XWIN_FULL>{})
-#define AQLM_PK_GO0(TT, PP, EE) launch(KP::template get<TT, 1, PP, EE, 0u>(), PackedLds<1, 0u>{})
-#define AQLM_PK_CASE(BB)                                                                                      \
-  case BB:                                                                                                    \
-    if (dtype == AQLM_HIP_F16) return eb == 3 ? AQLM_PK_GO(F16, BB, 4, 3) : AQLM_PK_GO(F16, BB, 4, 4);          \
-    return eb == 3 ? AQLM_PK_GO(BF16, BB, 4, 3) : AQLM_PK_GO(BF16, BB, 4, 4);
-  switch (batch) {
-    case 1:
-#define AQLM_PK_B1(TT, EE) (pd == 8 ? AQLM_PK_GO(TT, 1, 8, EE) : (pd == 4 ? AQLM_PK_GO(TT, 1, 4, EE) : AQLM_PK_GO(TT, 1, 3, EE)))
-      if (slice_first) {  // (ring depth 3, the default, only)
-        if (dtype == AQLM_HIP_F16) return eb == 3 ? AQLM_PK_GO0(F16, 3, 3) : AQLM_PK_GO0(F16, 3, 4);
-        return eb == 3 ? AQLM_PK_GO0(BF16, 3, 3) : AQLM_PK_GO0(BF16, 3, 4);
-      }
-      if (dtype == AQLM_HIP_F16) return eb == 3 ? AQLM_PK_B1(F16, 3) : AQLM_PK_B1(F16, 4);
-      return eb == 3 ? AQLM_PK_B1(BF16, 3) : AQLM_PK_B1(BF16, 4);
-#undef AQLM_PK_B1
-    AQLM_PK_CASE(2)
-    AQLM_PK_CASE(3)
-    AQLM_PK_CASE(4)
-    AQLM_PK_CASE(5)
-    AQLM_PK_CASE(6)
-    AQLM_PK_CASE(7)
-    AQLM_PK_CASE(8)
-  }
-#undef AQLM_PK_CASE
-#undef AQLM_PK_GO
-#undef AQLM_PK_GO0
-  return AQLM_HIP_E_INVALID;
-}
-
-struct SingleKernels {
-  template <class T_, int B, int PD, int EB, uint32_t XW>
-  static auto get() { return gemv_1x16_packed_kernel<T_, B, PD, XW, EB>; }
-};
-struct PublishKernels {  // row-parallel shards (aqlm_hip_gemv_1x16_packed_publish)
-  template <class T_, int B, int PD, int EB, uint32_t XW>
-  static auto get() { return gemv_1x16_packed_kernel<T_, B, PD, XW, EB, true>; }
-};
-struct MultiKernels {
-  template <class T_, int B, int PD, int EB, uint32_t XW>
-  static auto get() { return gemv_1x16_packed_multi_kernel<T_, B, PD, XW, EB>; }
-};
-
-// largest batch whose LDS image fits the CU
-template <int BB>
-static size_t packed_lds_total(int in_groups, int RG) { return PackedLds<BB, PK_XWIN_FULL>::total(in_groups, RG); }
-// one row: x first (a 64 KiB window, both reads without an address add) where that fits, else slice first
-static bool packed_b1_slice_first(int in_groups, int RG) { return packed_lds_total<1>(in_groups, RG) > 160 * 1024; }
-static size_t packed_lds_need(int b, int in_groups, int RG) {
-  switch (b) {
-    case 1: return std::min(packed_lds_total<1>(in_groups, RG), PackedLds<1, 0u>::total(in_groups, RG));
-    case 2: return packed_lds_total<2>(in_groups, RG);
-    case 3: return packed_lds_total<3>(in_groups, RG);
-    case 4: return packed_lds_total<4>(in_groups, RG);
-    case 5: return packed_lds_total<5>(in_groups, RG);
-    case 6: return packed_lds_total<6>(in_groups, RG);
-    case 7: return packed_lds_total<7>(in_groups, RG);
-    default: return packed_lds_total<8>(in_groups, RG);
-  }
-}
-static int packed_max_batch(int in_groups, int RG) {
-  // (the single-row image is not always the smallest: x first keeps a 64 KiB window in front of the slice)
-  if (packed_lds_need(1, in_groups, RG) > 160 * 1024) return 0;
-  int b = AQLM_HIP_MAX_GEMV_BATCH;
-  while (b > 1 && packed_lds_need(b, in_groups, RG) > 160 * 1024) --b;
-  return packed_lds_need(b, in_groups, RG) <= 160 * 1024 ? b : 0;
-}
+#include "packed_launch.h"  // host launch helpers: kernel dispatch, LDS budget
 
 }  // namespace PK_NS
 }  // namespace aqlm
 
 using namespace aqlm;
 using namespace aqlm::PK_NS;
-
-#if AQLM_PK_G == 8
-// the 16-element twin of this file (same signatures; hidden symbols of this library)
-#pragma GCC visibility push(hidden)
-extern "C" {
-size_t aqlm_hip_g16_prepack_1x16_bytes(int, int, int);
-int aqlm_hip_g16_prepack_1x16(const void*, int, int, int, void*, size_t, aqlm_hip_packed_desc*, void*);
-int aqlm_hip_g16_prepack_1x16_ex(const void*, int, int, int, void*, size_t, aqlm_hip_packed_desc*, int, void*);
-int aqlm_hip_g16_packed_set_codebook(aqlm_hip_packed_desc*, void*, const void*, void*);
-int aqlm_hip_g16_packed_plan_relabel(const uint32_t*, int, uint16_t*);
-int aqlm_hip_g16_packed_plan_relabel_ex(const uint32_t*, int, int, uint16_t*);
-int aqlm_hip_g16_packed_plan_geometry(const uint64_t*, int, int, int, uint8_t*);
-int aqlm_hip_g16_packed_desc_read(const void*, size_t, aqlm_hip_packed_desc*);
-int aqlm_hip_g16_unpack_1x16(const aqlm_hip_packed_desc*, const void*, void*, void*);
-int aqlm_hip_g16_dequant_1x16_packed(const aqlm_hip_packed_desc*, const void*, const void*, const void*, void*, int, void*);
-int aqlm_hip_g16_gemv_1x16_packed_cells(const aqlm_hip_packed_desc*, const void*, const void*, const void*, const void*, const void*, void*, int,
-                                        long, long, int, void*, size_t, void*);
-int aqlm_hip_g16_gemv_1x16_packed(const aqlm_hip_packed_desc*, void*, const void*, const void*, const void*, const void*, void*, int, long, long,
-                                  int, void*, size_t, void*);
-int aqlm_hip_g16_gemv_1x16_packed_chain(const aqlm_hip_packed_desc*, void*, const void*, const void*, const void*, const void*, void*, int, long,
-                                        long, int, void*, size_t, const aqlm_hip_packed_desc*, const void*, const void*, void*);
-int aqlm_hip_g16_gemv_1x16_packed_partials(const aqlm_hip_packed_desc*, const void*, const void*, const void*, int, long, int, void*, size_t, void*);
-int aqlm_hip_g16_gemv_1x16_packed_publish(const aqlm_hip_packed_desc*, void*, const void*, const void*, int, long, int, const aqlm_hip_xgmi*, void*,
-                                          void*, void*);
-int aqlm_hip_g16_gemv_1x16_packed_multi(const aqlm_hip_segment*, const aqlm_hip_packed_desc* const*, int, const void*, int, int, long, int, void*,
-                                        size_t, void*);
-int aqlm_hip_g16_gemv_1x16_packed_multi_cells(const aqlm_hip_segment*, const aqlm_hip_packed_desc* const*, int, const void*, int, int, long, int,
-                                              void*, size_t, void*);
-size_t aqlm_hip_g16_gemv_1x16_routed_packed_lds_bytes(int, int, int);
-int aqlm_hip_g16_routed_packed_entry_fill(const aqlm_hip_packed_desc*, const void*, const void*, const void*, const void*,
-                                          aqlm_hip_routed_packed_entry*);
-int aqlm_hip_g16_gemv_1x16_routed_packed_geometry(const aqlm_hip_packed_desc* const*, int, aqlm_hip_routed_packed_geometry*);
-int aqlm_hip_g16_gemv_1x16_routed_packed(const aqlm_hip_routed_packed_entry*, const aqlm_hip_routed_packed_geometry*, int, int, const void*,
-                                         int, int, int, const void*, long, int, void*, int, void*, size_t, void*);
-}
-#pragma GCC visibility pop
-// a descriptor of the twin's format (32 slices)
-static inline bool pk_is_g16(const aqlm_hip_packed_desc* d) { return d && d->slices_log2 == 5; }
-#define PK_G16_FORWARD(desc_expr, call) \
-  if (pk_is_g16(desc_expr)) return call
-#define PK_G16_FORWARD_IF(cond, call) \
-  if (cond) return call
-#else
-#define PK_G16_FORWARD(desc_expr, call)
-#define PK_G16_FORWARD_IF(cond, call)
-#endif
 
 // ---- planning steps of the repack (host, pure functions) -----------------------------------------------------------------
 // Relabelling: deal the 65536 entries to the PK_S slices, heaviest first, each to the lightest slice that still has room
@@ -2586,10 +1427,8 @@ static int plan_geometry(const unsigned long long* slice_steps, int M, int in_fe
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_packed_plan_relabel(const uint32_t* usage, int slices_log2, uint16_t* new_of_old) {
-#if AQLM_PK_G == 8
-  if (slices_log2 == 5) return aqlm_hip_g16_packed_plan_relabel(usage, slices_log2, new_of_old);
-#endif
+extern "C" PK_API int PK_ENTRY(packed_plan_relabel)(const uint32_t* usage, int slices_log2, uint16_t* new_of_old) {
+  PK_G16_FORWARD_IF(slices_log2 == 5, packed_plan_relabel, usage, slices_log2, new_of_old);
   if (!usage || !new_of_old || slices_log2 != PK_S_LOG) {
     set_last_error("aqlm_hip_packed_plan_relabel: null pointer or slices_log2 not 4 / 5");
     return AQLM_HIP_E_INVALID;
@@ -2597,10 +1436,8 @@ extern "C" PK_API int aqlm_hip_packed_plan_relabel(const uint32_t* usage, int sl
   return plan_relabel(usage, new_of_old);
 }
 
-extern "C" PK_API int aqlm_hip_packed_plan_relabel_ex(const uint32_t* usage, int slices_log2, int force, uint16_t* new_of_old) {
-#if AQLM_PK_G == 8
-  if (slices_log2 == 5) return aqlm_hip_g16_packed_plan_relabel_ex(usage, slices_log2, force, new_of_old);
-#endif
+extern "C" PK_API int PK_ENTRY(packed_plan_relabel_ex)(const uint32_t* usage, int slices_log2, int force, uint16_t* new_of_old) {
+  PK_G16_FORWARD_IF(slices_log2 == 5, packed_plan_relabel_ex, usage, slices_log2, force, new_of_old);
   if (!usage || !new_of_old || slices_log2 != PK_S_LOG) {
     set_last_error("aqlm_hip_packed_plan_relabel_ex: null pointer or slices_log2 not 4 / 5");
     return AQLM_HIP_E_INVALID;
@@ -2608,11 +1445,9 @@ extern "C" PK_API int aqlm_hip_packed_plan_relabel_ex(const uint32_t* usage, int
   return plan_relabel(usage, new_of_old, force != 0);
 }
 
-extern "C" PK_API int aqlm_hip_packed_plan_geometry(const uint64_t* slice_steps, int slices_log2, int out_features, int in_features,
-                                                    uint8_t* slice_groups) {
-#if AQLM_PK_G == 8
-  if (slices_log2 == 5) return aqlm_hip_g16_packed_plan_geometry(slice_steps, slices_log2, out_features, in_features, slice_groups);
-#endif
+extern "C" PK_API int PK_ENTRY(packed_plan_geometry)(const uint64_t* slice_steps, int slices_log2, int out_features, int in_features,
+                                                     uint8_t* slice_groups) {
+  PK_G16_FORWARD_IF(slices_log2 == 5, packed_plan_geometry, slice_steps, slices_log2, out_features, in_features, slice_groups);
   if (!slice_steps || !slice_groups || slices_log2 != PK_S_LOG) {
     set_last_error("aqlm_hip_packed_plan_geometry: null pointer or slices_log2 not 4 / 5");
     return AQLM_HIP_E_INVALID;
@@ -2637,8 +1472,8 @@ static PkScratch pk_scratch(int M) {
   return sc;
 }
 
-extern "C" PK_API size_t aqlm_hip_prepack_1x16_bytes(int out_features, int in_features, int in_group_size) {
-  PK_G16_FORWARD_IF(in_group_size == 16, aqlm_hip_g16_prepack_1x16_bytes(out_features, in_features, in_group_size));
+extern "C" PK_API size_t PK_ENTRY(prepack_1x16_bytes)(int out_features, int in_features, int in_group_size) {
+  PK_G16_FORWARD_IF(in_group_size == 16, prepack_1x16_bytes, out_features, in_features, in_group_size);
   if (!packed_shape_ok(out_features, in_features, in_group_size)) return 0;
   // capacity for streams up to 1.5 x the balanced length (the repack balances the slices; what is left is the difference
   // between the rows of one slice), plus the permutation + codebook image of a relabelled buffer and the repack's scratch;
@@ -2656,9 +1491,9 @@ extern "C" PK_API size_t aqlm_hip_prepack_1x16_bytes(int out_features, int in_fe
   return align_up(meta + ent + ent * PK_WREG3 / 1024 + image + pk_scratch(out_features).bytes + 4096, 1024);
 }
 
-extern "C" PK_API int aqlm_hip_prepack_1x16_ex(const void* codes, int out_features, int in_features, int in_group_size,
-                                               void* packed, size_t packed_bytes, aqlm_hip_packed_desc* desc, int flags, void* stream_) {
-  PK_G16_FORWARD_IF(in_group_size == 16, aqlm_hip_g16_prepack_1x16_ex(codes, out_features, in_features, in_group_size, packed, packed_bytes, desc, flags, stream_));
+extern "C" PK_API int PK_ENTRY(prepack_1x16_ex)(const void* codes, int out_features, int in_features, int in_group_size,
+                                                void* packed, size_t packed_bytes, aqlm_hip_packed_desc* desc, int flags, void* stream_) {
+  PK_G16_FORWARD_IF(in_group_size == 16, prepack_1x16_ex, codes, out_features, in_features, in_group_size, packed, packed_bytes, desc, flags, stream_);
   hipStream_t stream = (hipStream_t)stream_;
   if (!codes || !packed || !desc) {
     set_last_error("aqlm_hip_prepack_1x16: null pointer argument");
@@ -2669,7 +1504,7 @@ extern "C" PK_API int aqlm_hip_prepack_1x16_ex(const void* codes, int out_featur
                    in_group_size, in_features, out_features);
     return AQLM_HIP_E_UNSUPPORTED;
   }
-  const size_t cap = aqlm_hip_prepack_1x16_bytes(out_features, in_features, in_group_size);
+  const size_t cap = PK_ENTRY(prepack_1x16_bytes)(out_features, in_features, in_group_size);
   if (packed_bytes < cap || !aligned16(packed)) {
     set_last_error("aqlm_hip_prepack_1x16: packed buffer needs %zu bytes (16-B aligned), got %zu", cap, packed_bytes);
     return AQLM_HIP_E_INVALID;
@@ -2826,9 +1661,9 @@ extern "C" PK_API int aqlm_hip_prepack_1x16_ex(const void* codes, int out_featur
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_prepack_1x16(const void* codes, int out_features, int in_features, int in_group_size,
-                                     void* packed, size_t packed_bytes, aqlm_hip_packed_desc* desc, void* stream_) {
-  return aqlm_hip_prepack_1x16_ex(codes, out_features, in_features, in_group_size, packed, packed_bytes, desc, 0, stream_);
+extern "C" PK_API int PK_ENTRY(prepack_1x16)(const void* codes, int out_features, int in_features, int in_group_size,
+                                      void* packed, size_t packed_bytes, aqlm_hip_packed_desc* desc, void* stream_) {
+  return PK_ENTRY(prepack_1x16_ex)(codes, out_features, in_features, in_group_size, packed, packed_bytes, desc, 0, stream_);
 }
 
 // codebook image of a relabelled buffer: image[new] = codebook[old_of_new[new]], one 16-B piece per thread
@@ -2843,8 +1678,8 @@ __global__ __launch_bounds__(256) void pk_codebook_image_kernel(const uint16_t* 
 }  // namespace PK_NS
 }  // namespace aqlm
 
-extern "C" PK_API int aqlm_hip_packed_set_codebook(aqlm_hip_packed_desc* desc, void* packed, const void* codebook, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_packed_set_codebook(desc, packed, codebook, stream_));
+extern "C" PK_API int PK_ENTRY(packed_set_codebook)(aqlm_hip_packed_desc* desc, void* packed, const void* codebook, void* stream_) {
+  PK_G16_FORWARD(desc, packed_set_codebook, desc, packed, codebook, stream_);
   PackedLayout L;
   if (!packed || !codebook || !desc_layout(desc, L) || !aligned16(packed) || !aligned16(codebook)) {
     set_last_error("aqlm_hip_packed_set_codebook: null / misaligned pointer or invalid descriptor");
@@ -2859,14 +1694,12 @@ extern "C" PK_API int aqlm_hip_packed_set_codebook(aqlm_hip_packed_desc* desc, v
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_packed_desc_read(const void* header_host, size_t header_bytes, aqlm_hip_packed_desc* desc) {
-#if AQLM_PK_G == 8
+extern "C" PK_API int PK_ENTRY(packed_desc_read)(const void* header_host, size_t header_bytes, aqlm_hip_packed_desc* desc) {
   if (header_host && desc && header_bytes >= sizeof(aqlm_hip_packed_desc)) {
     aqlm_hip_packed_desc h;
     memcpy(&h, header_host, sizeof(h));
-    if (pk_is_g16(&h)) return aqlm_hip_g16_packed_desc_read(header_host, header_bytes, desc);
+    PK_G16_FORWARD(&h, packed_desc_read, header_host, header_bytes, desc);
   }
-#endif
   if (!header_host || !desc || header_bytes < sizeof(aqlm_hip_packed_desc)) {
     set_last_error("aqlm_hip_packed_desc_read: need the first %zu bytes of the packed buffer", sizeof(aqlm_hip_packed_desc));
     return AQLM_HIP_E_INVALID;
@@ -2882,8 +1715,8 @@ extern "C" PK_API int aqlm_hip_packed_desc_read(const void* header_host, size_t 
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_unpack_1x16(const aqlm_hip_packed_desc* desc, const void* packed, void* codes, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_unpack_1x16(desc, packed, codes, stream_));
+extern "C" PK_API int PK_ENTRY(unpack_1x16)(const aqlm_hip_packed_desc* desc, const void* packed, void* codes, void* stream_) {
+  PK_G16_FORWARD(desc, unpack_1x16, desc, packed, codes, stream_);
   hipStream_t stream = (hipStream_t)stream_;
   PackedLayout L;
   if (!packed || !codes || !desc_layout(desc, L)) {
@@ -2903,9 +1736,9 @@ extern "C" PK_API int aqlm_hip_unpack_1x16(const aqlm_hip_packed_desc* desc, con
 
 // W from the packed buffer (pk_dequant_kernel).  Reads the entries, the permutation stored behind them and the CALLER's codebook:
 // never the permuted codebook image, whose flag and the descriptor's codebook range are not looked at.
-extern "C" PK_API int aqlm_hip_dequant_1x16_packed(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
-                                                   const void* scales, void* W, int dtype, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_dequant_1x16_packed(desc, packed, codebook, scales, W, dtype, stream_));
+extern "C" PK_API int PK_ENTRY(dequant_1x16_packed)(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                                    const void* scales, void* W, int dtype, void* stream_) {
+  PK_G16_FORWARD(desc, dequant_1x16_packed, desc, packed, codebook, scales, W, dtype, stream_);
   hipStream_t stream = (hipStream_t)stream_;
   PackedLayout L;
   if (!packed || !codebook || !W || !desc_layout(desc, L)) {
@@ -2970,42 +1803,32 @@ struct PackedNext {
 static int packed_launch_main(const PackedLayout& L, const void* packed, const void* codebook, const uint16_t* x, int nb,
                               long x_row_stride, int dtype, void* workspace, size_t workspace_bytes, hipStream_t stream,
                               const char* who, const PackedFused& fused = PackedFused{}, const PackedNext& next = PackedNext{}) {
-  const size_t need = (fused.y || fused.pub) ? 0 : (size_t)PK_S * nb * L.M * sizeof(float);
+  const bool finalizes = fused.y || fused.pub;
+  const size_t need = finalizes ? 0 : (size_t)PK_S * nb * L.M * sizeof(float);
   if (need && (!workspace || workspace_bytes < need)) {
     set_last_error("%s: workspace of %zu bytes required, got %zu", who, need, workspace_bytes);
     return AQLM_HIP_E_INVALID;
   }
   const uint8_t* base = (const uint8_t*)packed;
-  PackedGemvParams p{};
-  p.ent = (const uint32_t*)(base + L.off_ent);
-  p.winfo = (const uint32_t*)(base + L.off_winfo);
-  p.rowstart = (const uint32_t*)(base + L.off_rowstart);
-  p.codebook = L.relabel ? base + L.off_cb : (const uint8_t*)codebook;  // relabelled: the permuted image (aqlm_hip_packed_set_codebook)
-  p.x = x;
-  p.partial = (float*)workspace;
-  if (fused.y || fused.pub) {
-    p.pub = fused.pub;
-    p.pub_flag = fused.pub_flag;
-    p.pub_epoch = fused.pub_epoch;
-    p.pub_max_elems = fused.pub_max_elems;
-    p.acc = fused.cells ? (unsigned long long*)fused.cells : (unsigned long long*)(const_cast<uint8_t*>(base) + L.off_acc);
-    p.cb_absmax = fused.cb_absmax;
-    p.scales = (const uint16_t*)fused.scales;
-    p.bias = (const uint16_t*)fused.bias;
-    p.y = (uint16_t*)fused.y;
-    p.y_row_stride = fused.y_row_stride;
+  const uint32_t* ent = (const uint32_t*)(base + L.off_ent);
+  const uint32_t* rowstart = (const uint32_t*)(base + L.off_rowstart);
+  const uint8_t* cb = L.relabel ? base + L.off_cb : (const uint8_t*)codebook;  // relabelled: the permuted image (aqlm_hip_packed_set_codebook)
+  // the trailing kernel argument as both launches below pass it; the ordinary one adds the publish and next-layer fields
+  PackedGemvRest rest{};
+  rest.winfo = (const uint32_t*)(base + L.off_winfo);
+  rest.partial = (float*)workspace;
+  rest.x_row_stride = x_row_stride;
+  if (finalizes) {
+    rest.acc = fused.cells ? (unsigned long long*)fused.cells : (unsigned long long*)(const_cast<uint8_t*>(base) + L.off_acc);
+    rest.cb_absmax = fused.cb_absmax;
+    rest.scales = (const uint16_t*)fused.scales;
+    rest.bias = (const uint16_t*)fused.bias;
+    rest.y = (uint16_t*)fused.y;
+    rest.y_row_stride = fused.y_row_stride;
   }
-  p.x_row_stride = x_row_stride;
-  p.M = L.M;
-  p.in_groups = L.in_groups;
-  p.RG = L.RG;
-  p.NW = L.NW;
-  p.T = L.T;
-  p.XC = L.XC;
-  p.ent_bytes = (uint32_t)L.ent_bytes;
 #ifdef AQLM_PACKED_TRACE
-  p.trace = workspace && workspace_bytes >= need + (size_t)PK_NST * PK_MAX_NW * 8 * 8 ? (unsigned long long*)((uint8_t*)workspace + need) : nullptr;
-  p.dbg = tuning().packed_debug;
+  rest.trace = workspace && workspace_bytes >= need + (size_t)PK_NST * PK_MAX_NW * 8 * 8 ? (unsigned long long*)((uint8_t*)workspace + need) : nullptr;
+  rest.dbg = tuning().packed_debug;
 #endif
   // chain prefetch: up to `packed_prefetch_waves` extra waves per workgroup (default 2) when a next layer is named
   int npw = 0;
@@ -3019,38 +1842,25 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     if (lds > 160 * 1024) { npw = 0; }
     const size_t lds_final = decltype(lds_map)::total(L.in_groups, L.RG, npw);
     if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_final)) return e;
-    PackedGemvRest rest{};
-    rest.pub = p.pub;
-    rest.pub_flag = p.pub_flag;
-    rest.pub_epoch = p.pub_epoch;
-    rest.pub_max_elems = p.pub_max_elems;
+    PackedGemvRest r = rest;
+    r.pub = fused.pub;
+    r.pub_flag = fused.pub_flag;
+    r.pub_epoch = fused.pub_epoch;
+    r.pub_max_elems = fused.pub_max_elems;
     if (npw) {
-      rest.next_ent = next.ent;
-      rest.next_codebook = next.codebook;
-      rest.next_block_bytes = next.block_bytes;
+      r.next_ent = next.ent;
+      r.next_codebook = next.codebook;
+      r.next_block_bytes = next.block_bytes;
     }
-    rest.winfo = p.winfo;
-    rest.partial = p.partial;
-    rest.x_row_stride = p.x_row_stride;
-    rest.acc = p.acc;
-    rest.cb_absmax = p.cb_absmax;
-    rest.scales = p.scales;
-    rest.bias = p.bias;
-    rest.y = p.y;
-    rest.y_row_stride = p.y_row_stride;
-#ifdef AQLM_PACKED_TRACE
-    rest.trace = p.trace;
-    rest.dbg = p.dbg;
-#endif
-    hipLaunchKernelGGL(kern, dim3(PK_NST), dim3((L.NW + npw) * 64), lds_final, stream, p.codebook, p.x, p.ent, p.rowstart, p.in_groups,
-                       (uint32_t)p.NW | ((uint32_t)p.XC << 8) | ((uint32_t)npw << 12) | (rotate << 15) | ((uint32_t)p.T << 16), p.RG,
-                       p.ent_bytes, p.M, rest);
+    hipLaunchKernelGGL(kern, dim3(PK_NST), dim3((L.NW + npw) * 64), lds_final, stream, cb, x, ent, rowstart, L.in_groups,
+                       (uint32_t)L.NW | ((uint32_t)L.XC << 8) | ((uint32_t)npw << 12) | (rotate << 15) | ((uint32_t)L.T << 16), L.RG,
+                       (uint32_t)L.ent_bytes, L.M, r);
     return check_hip(hipGetLastError(), "gemv_1x16_packed launch");
   };
   const bool sf = nb == 1 && packed_b1_slice_first(L.in_groups, L.RG);
 #if AQLM_PK_G == 8
   if (L.G.vg) {  // variable geometry: its own kernels (4-byte entries, ring depth 3 / 4, no chain prefetch, no publish)
-    if (p.pub != nullptr || L.EB != 4) {
+    if (fused.pub != nullptr || L.EB != 4) {
       set_last_error("%s: a variable-geometry buffer runs on the single-layer matvec entries only (repack with "
                      "AQLM_HIP_PREPACK_UNIFORM_ONLY for the publish form)", who);
       return AQLM_HIP_E_UNSUPPORTED;
@@ -3060,23 +1870,9 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     auto launch_vg = [&](auto kern, auto lds_map) -> int {
       const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, 0);
       if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
-      PackedGemvRest rest{};
-      rest.winfo = p.winfo;
-      rest.partial = p.partial;
-      rest.x_row_stride = p.x_row_stride;
-      rest.acc = p.acc;
-      rest.cb_absmax = p.cb_absmax;
-      rest.scales = p.scales;
-      rest.bias = p.bias;
-      rest.y = p.y;
-      rest.y_row_stride = p.y_row_stride;
-#ifdef AQLM_PACKED_TRACE
-      rest.trace = p.trace;
-      rest.dbg = p.dbg;
-#endif
-      hipLaunchKernelGGL(kern, dim3(PK_NST), dim3(L.NW * 64), lds, stream, p.codebook, p.x, p.ent, (uint32_t)(L.off_ent - L.off_rowstart),
-                         (uint32_t)p.in_groups | ((uint32_t)p.RG << 12), (uint32_t)p.NW | ((uint32_t)p.XC << 8) | (rotate << 15) | ((uint32_t)p.T << 16),
-                         p.M, ns[0], ns[1], ns[2], ns[3], rest);
+      hipLaunchKernelGGL(kern, dim3(PK_NST), dim3(L.NW * 64), lds, stream, cb, x, ent, (uint32_t)(L.off_ent - L.off_rowstart),
+                         (uint32_t)L.in_groups | ((uint32_t)L.RG << 12), (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16),
+                         L.M, ns[0], ns[1], ns[2], ns[3], rest);
       return check_hip(hipGetLastError(), "gemv_1x16_packed (variable geometry) launch");
     };
 #define AQLM_PK_VG(TT, BB, PP, XW) launch_vg(gemv_1x16_packed_vg_kernel<TT, BB, PP, XW>, PackedLds<BB, XW>{})
@@ -3100,7 +1896,7 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     return AQLM_HIP_E_INVALID;
   }
 #endif
-  if (p.pub != nullptr) return dispatch_packed<PublishKernels>(dtype, nb, pick_pd(L), L.EB, sf, launch);
+  if (fused.pub != nullptr) return dispatch_packed<PublishKernels>(dtype, nb, pick_pd(L), L.EB, sf, launch);
   return dispatch_packed<SingleKernels>(dtype, nb, pick_pd(L), L.EB, sf, launch);
 }
 
@@ -3141,62 +1937,7 @@ static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed,
                                  const void* scales, const void* bias, const void* x, void* y, int batch,
                                  long x_row_stride, long y_row_stride, int dtype, void* workspace,
                                  size_t workspace_bytes, void* stream_, const PackedNext& next, void* cells = nullptr,
-                                 size_t cells_bytes = 0);
-
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed_cells(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
-                                               const void* scales, const void* bias, const void* x, void* y, int batch,
-                                               long x_row_stride, long y_row_stride, int dtype, void* cells,
-                                               size_t cells_bytes, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_gemv_1x16_packed_cells(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, cells, cells_bytes, stream_));
-  if (!cells || !desc || !(desc->codebook_absmax > 0.f) || cells_bytes < (size_t)std::min(batch, AQLM_HIP_MAX_GEMV_BATCH) * desc->out_features * 8 ||
-      (reinterpret_cast<uintptr_t>(cells) & 7u)) {
-    set_last_error("aqlm_hip_gemv_1x16_packed_cells: needs a descriptor with the codebook range and %zu bytes of 8-B aligned, "
-                   "zero-filled cells", desc ? (size_t)std::min(batch, AQLM_HIP_MAX_GEMV_BATCH) * desc->out_features * 8 : (size_t)0);
-    return AQLM_HIP_E_INVALID;
-  }
-  if (!tuning().packed_fused_finalize) {
-    set_last_error("aqlm_hip_gemv_1x16_packed_cells: the fused finalize is switched off (tuning knob packed_fused_finalize)");
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  return gemv_1x16_packed_impl(desc, const_cast<void*>(packed), codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype,
-                               nullptr, 0, stream_, PackedNext{}, cells, cells_bytes);
-}
-
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
-                                         const void* scales, const void* bias, const void* x, void* y, int batch,
-                                         long x_row_stride, long y_row_stride, int dtype, void* workspace,
-                                         size_t workspace_bytes, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_gemv_1x16_packed(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace, workspace_bytes, stream_));
-  return gemv_1x16_packed_impl(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace,
-                               workspace_bytes, stream_, PackedNext{});
-}
-
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed_chain(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
-                                               const void* scales, const void* bias, const void* x, void* y, int batch,
-                                               long x_row_stride, long y_row_stride, int dtype, void* workspace,
-                                               size_t workspace_bytes, const aqlm_hip_packed_desc* next_desc,
-                                               const void* next_packed, const void* next_codebook, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_gemv_1x16_packed_chain(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace, workspace_bytes, next_desc, next_packed, next_codebook, stream_));
-  PackedNext next;
-  PackedLayout LN;
-  if (next_desc && next_packed && next_codebook) {
-    if (!desc_layout(next_desc, LN) || !aligned16(next_packed) || !aligned16(next_codebook)) {
-      set_last_error("aqlm_hip_gemv_1x16_packed_chain: invalid descriptor / misaligned buffer of the next layer");
-      return AQLM_HIP_E_INVALID;
-    }
-    next.ent = (const uint8_t*)next_packed + LN.off_ent;
-    next.codebook = LN.relabel ? (const uint8_t*)next_packed + LN.off_cb : (const uint8_t*)next_codebook;
-    next.block_bytes = (uint32_t)(LN.ent_bytes / LN.nst);
-    if (LN.G.vg) next = PackedNext{};  // the hint assumes workgroup b of both layers sits on one XCD with the same slice: uniform geometry only
-  }
-  return gemv_1x16_packed_impl(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace,
-                               workspace_bytes, stream_, next);
-}
-
-static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
-                                 const void* scales, const void* bias, const void* x, void* y, int batch,
-                                 long x_row_stride, long y_row_stride, int dtype, void* workspace,
-                                 size_t workspace_bytes, void* stream_, const PackedNext& next, void* cells, size_t cells_bytes) {
+                                 size_t cells_bytes = 0) {
   hipStream_t stream = (hipStream_t)stream_;
   PackedLayout L;
   int max_b = 0;
@@ -3243,10 +1984,60 @@ static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed,
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed_partials(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
-                                                  const void* x, int batch, long x_row_stride, int dtype, void* workspace,
-                                                  size_t workspace_bytes, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_gemv_1x16_packed_partials(desc, packed, codebook, x, batch, x_row_stride, dtype, workspace, workspace_bytes, stream_));
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_cells)(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                                const void* scales, const void* bias, const void* x, void* y, int batch,
+                                                long x_row_stride, long y_row_stride, int dtype, void* cells,
+                                                size_t cells_bytes, void* stream_) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed_cells, desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, cells, cells_bytes, stream_);
+  if (!cells || !desc || !(desc->codebook_absmax > 0.f) || cells_bytes < (size_t)std::min(batch, AQLM_HIP_MAX_GEMV_BATCH) * desc->out_features * 8 ||
+      (reinterpret_cast<uintptr_t>(cells) & 7u)) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_cells: needs a descriptor with the codebook range and %zu bytes of 8-B aligned, "
+                   "zero-filled cells", desc ? (size_t)std::min(batch, AQLM_HIP_MAX_GEMV_BATCH) * desc->out_features * 8 : (size_t)0);
+    return AQLM_HIP_E_INVALID;
+  }
+  if (!tuning().packed_fused_finalize) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_cells: the fused finalize is switched off (tuning knob packed_fused_finalize)");
+    return AQLM_HIP_E_UNSUPPORTED;
+  }
+  return gemv_1x16_packed_impl(desc, const_cast<void*>(packed), codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype,
+                               nullptr, 0, stream_, PackedNext{}, cells, cells_bytes);
+}
+
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed)(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
+                                          const void* scales, const void* bias, const void* x, void* y, int batch,
+                                          long x_row_stride, long y_row_stride, int dtype, void* workspace,
+                                          size_t workspace_bytes, void* stream_) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed, desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace, workspace_bytes, stream_);
+  return gemv_1x16_packed_impl(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace,
+                               workspace_bytes, stream_, PackedNext{});
+}
+
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_chain)(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
+                                                const void* scales, const void* bias, const void* x, void* y, int batch,
+                                                long x_row_stride, long y_row_stride, int dtype, void* workspace,
+                                                size_t workspace_bytes, const aqlm_hip_packed_desc* next_desc,
+                                                const void* next_packed, const void* next_codebook, void* stream_) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed_chain, desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace, workspace_bytes, next_desc, next_packed, next_codebook, stream_);
+  PackedNext next;
+  PackedLayout LN;
+  if (next_desc && next_packed && next_codebook) {
+    if (!desc_layout(next_desc, LN) || !aligned16(next_packed) || !aligned16(next_codebook)) {
+      set_last_error("aqlm_hip_gemv_1x16_packed_chain: invalid descriptor / misaligned buffer of the next layer");
+      return AQLM_HIP_E_INVALID;
+    }
+    next.ent = (const uint8_t*)next_packed + LN.off_ent;
+    next.codebook = LN.relabel ? (const uint8_t*)next_packed + LN.off_cb : (const uint8_t*)next_codebook;
+    next.block_bytes = (uint32_t)(LN.ent_bytes / LN.nst);
+    if (LN.G.vg) next = PackedNext{};  // the hint assumes workgroup b of both layers sits on one XCD with the same slice: uniform geometry only
+  }
+  return gemv_1x16_packed_impl(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace,
+                               workspace_bytes, stream_, next);
+}
+
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_partials)(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                                   const void* x, int batch, long x_row_stride, int dtype, void* workspace,
+                                                   size_t workspace_bytes, void* stream_) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed_partials, desc, packed, codebook, x, batch, x_row_stride, dtype, workspace, workspace_bytes, stream_);
   PackedLayout L;
   int max_b = 0;
   if (int e = packed_check_args("aqlm_hip_gemv_1x16_packed_partials", desc, packed, codebook, x, batch, x_row_stride, dtype, L, max_b))
@@ -3260,15 +2051,10 @@ extern "C" PK_API int aqlm_hip_gemv_1x16_packed_partials(const aqlm_hip_packed_d
                             (hipStream_t)stream_, "aqlm_hip_gemv_1x16_packed_partials");
 }
 
-static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const aqlm_hip_packed_desc* const* descs,
-                                       int num_segments, const void* x, int in_features, int batch, long x_row_stride,
-                                       int dtype, void* workspace, size_t workspace_bytes, void* cells, size_t cells_bytes,
-                                       void* stream_);
-
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed_publish(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
-                                                 const void* x, int batch, long x_row_stride, int dtype,
-                                                 const aqlm_hip_xgmi* xg, void* pub_own, void* flag_own, void* stream_) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_gemv_1x16_packed_publish(desc, packed, codebook, x, batch, x_row_stride, dtype, xg, pub_own, flag_own, stream_));
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_publish)(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
+                                                  const void* x, int batch, long x_row_stride, int dtype,
+                                                  const aqlm_hip_xgmi* xg, void* pub_own, void* flag_own, void* stream_) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed_publish, desc, packed, codebook, x, batch, x_row_stride, dtype, xg, pub_own, flag_own, stream_);
   PackedLayout L;
   int max_b = 0;
   if (int e = packed_check_args("aqlm_hip_gemv_1x16_packed_publish", desc, packed, codebook, x, batch, x_row_stride, dtype, L, max_b))
@@ -3287,28 +2073,6 @@ extern "C" PK_API int aqlm_hip_gemv_1x16_packed_publish(const aqlm_hip_packed_de
   fz.pub_max_elems = (uint32_t)xg->max_elems;
   return packed_launch_main(L, packed, codebook, (const uint16_t*)x, batch, x_row_stride, dtype, nullptr, 0, (hipStream_t)stream_,
                             "aqlm_hip_gemv_1x16_packed_publish", fz);
-}
-
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed_multi(const aqlm_hip_segment* segments, const aqlm_hip_packed_desc* const* descs,
-                                               int num_segments, const void* x, int in_features, int batch,
-                                               long x_row_stride, int dtype, void* workspace, size_t workspace_bytes,
-                                               void* stream_) {
-  PK_G16_FORWARD(descs && num_segments >= 1 ? descs[0] : nullptr, aqlm_hip_g16_gemv_1x16_packed_multi(segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, workspace, workspace_bytes, stream_));
-  return gemv_1x16_packed_multi_impl(segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, workspace,
-                                     workspace_bytes, nullptr, 0, stream_);
-}
-
-extern "C" PK_API int aqlm_hip_gemv_1x16_packed_multi_cells(const aqlm_hip_segment* segments, const aqlm_hip_packed_desc* const* descs,
-                                                     int num_segments, const void* x, int in_features, int batch,
-                                                     long x_row_stride, int dtype, void* cells, size_t cells_bytes,
-                                                     void* stream_) {
-  PK_G16_FORWARD(descs && num_segments >= 1 ? descs[0] : nullptr, aqlm_hip_g16_gemv_1x16_packed_multi_cells(segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, cells, cells_bytes, stream_));
-  if (!cells || (reinterpret_cast<uintptr_t>(cells) & 7u) || !tuning().packed_fused_finalize) {
-    set_last_error("aqlm_hip_gemv_1x16_packed_multi_cells: needs 8-B aligned, zero-filled cells and the fused finalize switched on");
-    return AQLM_HIP_E_INVALID;
-  }
-  return gemv_1x16_packed_multi_impl(segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, nullptr, 0,
-                                     cells, cells_bytes, stream_);
 }
 
 static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const aqlm_hip_packed_desc* const* descs,
@@ -3498,6 +2262,28 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
   else
     hipLaunchKernelGGL(gemv_1x16_packed_finalize_multi<BF16>, dim3(fblocks), dim3(256), 0, stream, fm);
   return check_hip(hipGetLastError(), "gemv_1x16_packed_finalize_multi launch");
+}
+
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_multi)(const aqlm_hip_segment* segments, const aqlm_hip_packed_desc* const* descs,
+                                                int num_segments, const void* x, int in_features, int batch,
+                                                long x_row_stride, int dtype, void* workspace, size_t workspace_bytes,
+                                                void* stream_) {
+  PK_G16_FORWARD(descs && num_segments >= 1 ? descs[0] : nullptr, gemv_1x16_packed_multi, segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, workspace, workspace_bytes, stream_);
+  return gemv_1x16_packed_multi_impl(segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, workspace,
+                                     workspace_bytes, nullptr, 0, stream_);
+}
+
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_multi_cells)(const aqlm_hip_segment* segments, const aqlm_hip_packed_desc* const* descs,
+                                                      int num_segments, const void* x, int in_features, int batch,
+                                                      long x_row_stride, int dtype, void* cells, size_t cells_bytes,
+                                                      void* stream_) {
+  PK_G16_FORWARD(descs && num_segments >= 1 ? descs[0] : nullptr, gemv_1x16_packed_multi_cells, segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, cells, cells_bytes, stream_);
+  if (!cells || (reinterpret_cast<uintptr_t>(cells) & 7u) || !tuning().packed_fused_finalize) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_multi_cells: needs 8-B aligned, zero-filled cells and the fused finalize switched on");
+    return AQLM_HIP_E_INVALID;
+  }
+  return gemv_1x16_packed_multi_impl(segments, descs, num_segments, x, in_features, batch, x_row_stride, dtype, nullptr, 0,
+                                     cells, cells_bytes, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------- expert-routed launch (MoE decode)

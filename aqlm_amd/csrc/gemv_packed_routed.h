@@ -1,5 +1,6 @@
 // Expert-routed launch of the prepacked 1x16 matvec (Mixtral decode on prepacked experts), gfx950, wave64.
-// Included at the end of gemv_packed.hip, so it is built twice like the rest of that file (8- and 16-element vectors).
+// Included at the end of gemv_packed.hip, so it is built twice like the rest of that file (8- and 16-element vectors).  Needs the
+// matvec body and LDS maps (packed_gemv_kernels.h), the layout (packed_format.h), packed_launch.h and that file's packed_fused.
 //
 // One launch computes every (token, expert) pair of one projection of a mixture-of-experts block -- or of the two that read the
 // same rows (w1 and w3) -- on the experts' PACKED buffers, with the routing read on the device only:
@@ -124,16 +125,16 @@ static bool routed_packed_desc_ok(const aqlm_hip_packed_desc* d, PackedLayout& L
 using namespace aqlm;
 using namespace aqlm::PK_NS;
 
-extern "C" PK_API size_t aqlm_hip_gemv_1x16_routed_packed_lds_bytes(int out_features, int in_features, int in_group_size) {
-  PK_G16_FORWARD_IF(in_group_size == 16, aqlm_hip_g16_gemv_1x16_routed_packed_lds_bytes(out_features, in_features, in_group_size));
+extern "C" PK_API size_t PK_ENTRY(gemv_1x16_routed_packed_lds_bytes)(int out_features, int in_features, int in_group_size) {
+  PK_G16_FORWARD_IF(in_group_size == 16, gemv_1x16_routed_packed_lds_bytes, out_features, in_features, in_group_size);
   if (!packed_shape_ok(out_features, in_features, in_group_size)) return 0;
   const int in_groups = in_features / PK_G, RG = (out_features + PK_NG - 1) / PK_NG;
   return routed_packed_lds(in_groups, RG, packed_b1_slice_first(in_groups, RG));
 }
 
-extern "C" PK_API int aqlm_hip_routed_packed_entry_fill(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
-                                                        const void* scales, const void* bias, aqlm_hip_routed_packed_entry* entry) {
-  PK_G16_FORWARD(desc, aqlm_hip_g16_routed_packed_entry_fill(desc, packed, codebook, scales, bias, entry));
+extern "C" PK_API int PK_ENTRY(routed_packed_entry_fill)(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
+                                                         const void* scales, const void* bias, aqlm_hip_routed_packed_entry* entry) {
+  PK_G16_FORWARD(desc, routed_packed_entry_fill, desc, packed, codebook, scales, bias, entry);
   static const char* who = "aqlm_hip_routed_packed_entry_fill";
   if (!desc || !packed || !codebook || !scales || !entry) {
     set_last_error("%s: null pointer argument", who);
@@ -171,9 +172,9 @@ extern "C" PK_API int aqlm_hip_routed_packed_entry_fill(const aqlm_hip_packed_de
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_gemv_1x16_routed_packed_geometry(const aqlm_hip_packed_desc* const* descs, int n,
-                                                                aqlm_hip_routed_packed_geometry* geom) {
-  PK_G16_FORWARD(descs && n >= 1 ? descs[0] : nullptr, aqlm_hip_g16_gemv_1x16_routed_packed_geometry(descs, n, geom));
+extern "C" PK_API int PK_ENTRY(gemv_1x16_routed_packed_geometry)(const aqlm_hip_packed_desc* const* descs, int n,
+                                                                 aqlm_hip_routed_packed_geometry* geom) {
+  PK_G16_FORWARD(descs && n >= 1 ? descs[0] : nullptr, gemv_1x16_routed_packed_geometry, descs, n, geom);
   static const char* who = "aqlm_hip_gemv_1x16_routed_packed_geometry";
   if (!descs || n < 1 || n > AQLM_HIP_MAX_ROUTED_EXPERTS * 2 || !geom) {
     set_last_error("%s: 1..%d descriptors and a geometry to fill required (got %d)", who, AQLM_HIP_MAX_ROUTED_EXPERTS * 2, n);
@@ -210,19 +211,18 @@ extern "C" PK_API int aqlm_hip_gemv_1x16_routed_packed_geometry(const aqlm_hip_p
   return 0;
 }
 
-extern "C" PK_API int aqlm_hip_gemv_1x16_routed_packed_supported(const aqlm_hip_packed_desc* const* descs, int n) {
+extern "C" PK_API int PK_ENTRY(gemv_1x16_routed_packed_supported)(const aqlm_hip_packed_desc* const* descs, int n) {
   aqlm_hip_routed_packed_geometry g;
-  return aqlm_hip_gemv_1x16_routed_packed_geometry(descs, n, &g) == 0 ? 1 : 0;
+  return PK_ENTRY(gemv_1x16_routed_packed_geometry)(descs, n, &g) == 0 ? 1 : 0;
 }
 
-extern "C" PK_API int aqlm_hip_gemv_1x16_routed_packed(const aqlm_hip_routed_packed_entry* table,
-                                                       const aqlm_hip_routed_packed_geometry* geom, int num_experts,
-                                                       int num_segments, const void* expert_ids, int ids_int64, int num_pairs,
-                                                       int top_k, const void* x, long x_row_stride, int x_per_pair, void* y,
-                                                       int dtype, void* cells, size_t cells_bytes, void* stream_) {
-  PK_G16_FORWARD_IF(geom && geom->in_group_size == 16,
-                    aqlm_hip_g16_gemv_1x16_routed_packed(table, geom, num_experts, num_segments, expert_ids, ids_int64, num_pairs, top_k, x,
-                                                         x_row_stride, x_per_pair, y, dtype, cells, cells_bytes, stream_));
+extern "C" PK_API int PK_ENTRY(gemv_1x16_routed_packed)(const aqlm_hip_routed_packed_entry* table,
+                                                        const aqlm_hip_routed_packed_geometry* geom, int num_experts,
+                                                        int num_segments, const void* expert_ids, int ids_int64, int num_pairs,
+                                                        int top_k, const void* x, long x_row_stride, int x_per_pair, void* y,
+                                                        int dtype, void* cells, size_t cells_bytes, void* stream_) {
+  PK_G16_FORWARD_IF(geom && geom->in_group_size == 16, gemv_1x16_routed_packed, table, geom, num_experts, num_segments, expert_ids,
+                    ids_int64, num_pairs, top_k, x, x_row_stride, x_per_pair, y, dtype, cells, cells_bytes, stream_);
   static const char* who = "aqlm_hip_gemv_1x16_routed_packed";
   if (int e = check_not_null(who, table && geom && expert_ids && x && y && cells)) return e;
   if (int e = check_aligned(who, "table / expert_ids", aligned8(table) && ids_aligned(expert_ids, ids_int64))) return e;

@@ -1,4 +1,4 @@
-"""numpy model of the packed 1x16 g8 format v7 (aqlm_amd/csrc/gemv_packed.hip): the specification that
+"""numpy model of the packed 1x16 g8 format v7 (aqlm_amd/csrc/packed_format.h, described at the head of gemv_packed.hip): the specification that
 aqlm_hip_prepack_1x16 is held to, plus a straight-line simulation of the kernel's traversal (column walk, flag masks,
 LDS slots, carries).  Test infrastructure only.
 

@@ -31,6 +31,17 @@ def test_header_and_binding_agree(native):
         assert hasattr(raw, s), f"libaqlm_hip.so does not export {s}"
 
 
+def test_g16_twins_of_the_packed_entries_stay_hidden(native):
+    """The packed 1x16 entries are built a second time for 16-element vectors as aqlm_hip_g16_*: reached through the public
+    entries only, never exported."""
+    packed = [s for s in native.SIGNATURES if "pack" in s]
+    assert len(packed) >= 22
+    raw = ctypes.CDLL(native.LIB_PATH)
+    for s in packed:
+        twin = "aqlm_hip_g16_" + s[len("aqlm_hip_"):]
+        assert not hasattr(raw, twin), f"libaqlm_hip.so exports {twin}"
+
+
 def test_abi_version_and_error_string(native):
     assert native.lib.aqlm_hip_abi_version() == native.ABI_VERSION == 9
     assert isinstance(native.last_error(), str)
