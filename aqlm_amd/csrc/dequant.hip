@@ -113,7 +113,12 @@ __global__ __launch_bounds__(256) void dequant_generic_kernel(const DequantGener
         code &= mask;
         f += T::to_float(p.codebooks[((long)c * cbsize + code) * p.G + e]);
       }
-      p.W[t * p.G + e] = T::from_float(f * scale);
+      // The product has to exist as an fp32 value before it is rounded, as in dequant_kernel: left alone, the compiler folds
+      // fptrunc(fmul) into v_fma_mixlo_f16 f, scale, +0 -- a zero sum times a negative scale then comes out +0 instead of -0, and
+      // the exact product is rounded once instead of fp32-then-fp16 (a last-place difference from the tuned instances).
+      float w = f * scale;
+      asm volatile("" : "+v"(w));
+      p.W[t * p.G + e] = T::from_float(w);
     }
   }
 }

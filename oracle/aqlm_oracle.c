@@ -35,9 +35,13 @@
 #include <omp.h>
 #endif
 
-static inline uint32_t load_code(const void* codes, size_t idx, int code_bytes) {
-  if (code_bytes == 1) return ((const uint8_t*)codes)[idx];
-  return ((const uint16_t*)codes)[idx];
+/* The containers are signed (utils.py:23-26): an index >= 2**(nbits-1) is stored negative, so for nbits below the
+ * container width its unsigned view carries ones above bit nbits-1.  utils.py:29-31 takes `% 2**nbits`; the mask is that. */
+static inline uint32_t code_mask(int nbits) { return nbits >= 32 ? 0xffffffffu : ((uint32_t)1 << nbits) - 1u; }
+
+static inline uint32_t load_code(const void* codes, size_t idx, int code_bytes, uint32_t mask) {
+  if (code_bytes == 1) return ((const uint8_t*)codes)[idx] & mask;
+  return ((const uint16_t*)codes)[idx] & mask;
 }
 
 /* returns bytes of LUT scratch needed by aqlm_oracle_lut_gemv_f32 */
@@ -60,6 +64,7 @@ void aqlm_oracle_lut_gemv_f32(const float* x, const float* codebooks, const void
   const int g = in_group_size, K = num_codebooks;
   const int in_groups = in_features / g;
   const size_t cbsize = (size_t)1 << nbits;
+  const uint32_t mask = code_mask(nbits);
 #ifdef _OPENMP
   if (nthreads > 0) omp_set_num_threads(nthreads);
 #endif
@@ -91,7 +96,7 @@ void aqlm_oracle_lut_gemv_f32(const float* x, const float* codebooks, const void
       const size_t rowbase = (size_t)j * out_features * K;
       for (int i = i0; i < i1; ++i) {
         float s = y[i];
-        for (int c = 0; c < K; ++c) s += lj[(size_t)c * cbsize + load_code(codes_alt, rowbase + (size_t)i * K + c, code_bytes)];
+        for (int c = 0; c < K; ++c) s += lj[(size_t)c * cbsize + load_code(codes_alt, rowbase + (size_t)i * K + c, code_bytes, mask)];
         y[i] = s;
       }
     }
@@ -106,6 +111,7 @@ void aqlm_oracle_dequant_gemv_f32(const float* x, const float* codebooks, const 
   const int g = in_group_size, K = num_codebooks;
   const int in_groups = in_features / g;
   const size_t cbsize = (size_t)1 << nbits;
+  const uint32_t mask = code_mask(nbits);
 #ifdef _OPENMP
   if (nthreads > 0) omp_set_num_threads(nthreads);
 #endif
@@ -116,7 +122,7 @@ void aqlm_oracle_dequant_gemv_f32(const float* x, const float* codebooks, const 
     for (int j = 0; j < in_groups; ++j) {
       const float* xj = x + (size_t)j * g;
       for (int c = 0; c < K; ++c) {
-        const uint32_t v = load_code(codes, rowbase + (size_t)j * K + c, code_bytes);
+        const uint32_t v = load_code(codes, rowbase + (size_t)j * K + c, code_bytes, mask);
         const float* e = codebooks + ((size_t)c * cbsize + v) * g;
         float s = 0.f;
         for (int t = 0; t < g; ++t) s += e[t] * xj[t];
@@ -136,6 +142,7 @@ void aqlm_oracle_dequant_weight_f32(const float* codebooks, const void* codes, i
   const int g = in_group_size, K = num_codebooks;
   const int in_groups = in_features / g;
   const size_t cbsize = (size_t)1 << nbits;
+  const uint32_t mask = code_mask(nbits);
 #pragma omp parallel for schedule(static)
   for (int i = 0; i < out_features; ++i) {
     const size_t rowbase = (size_t)i * in_groups * K;
@@ -143,7 +150,7 @@ void aqlm_oracle_dequant_weight_f32(const float* codebooks, const void* codes, i
       float* w = W + (size_t)i * in_features + (size_t)j * g;
       for (int t = 0; t < g; ++t) w[t] = 0.f;
       for (int c = 0; c < K; ++c) {
-        const uint32_t v = load_code(codes, rowbase + (size_t)j * K + c, code_bytes);
+        const uint32_t v = load_code(codes, rowbase + (size_t)j * K + c, code_bytes, mask);
         const float* e = codebooks + ((size_t)c * cbsize + v) * g;
         for (int t = 0; t < g; ++t) w[t] += e[t];
       }

@@ -33,6 +33,9 @@ __all__ = [
     "pack_int_data",
     "unpack_int_data",
     "dequantize_weight",
+    "dequantize_weight_storage",
+    "storage_bits_to_float64",
+    "round_to_storage_bits",
     "dequantize_gemm",
     "dequantize_gemm_transposed",
     "permute_codes_for_lut",
@@ -104,6 +107,70 @@ def dequantize_weight(
         acc = acc * np.asarray(scales).astype(acc_dtype)
     # [og, ig, o, i] -> [og, o, ig, i] -> [out, in]
     return acc.swapaxes(-3, -2).reshape(num_out_groups * out_group_size, num_in_groups * in_group_size)
+
+
+def dequantize_weight_storage(
+    codes_unsigned: np.ndarray,
+    codebooks: np.ndarray,
+    scales: Optional[np.ndarray],
+    float_dtype,
+) -> np.ndarray:
+    """The arithmetic contract of the dequantise kernels, as bit patterns of the storage type.
+
+    Per weight, in float32: start from zero and add the selected entry of every codebook in codebook order; multiply by the
+    row's scale (nothing is multiplied when ``scales`` is None); round once, to nearest-even, into the storage type.  This is
+    ``_dequantize_weight`` (utils.py:43-70) carried out in float32 on operands of the storage type, followed by one cast.
+
+    codes_unsigned, codebooks, scales: as for ``dequantize_weight``; codebooks and scales hold values of the storage type.
+    float_dtype: ``np.float16`` or the string "bfloat16" (as for ``make_layer``).
+    returns: uint16 [out, in].  A NaN comes back as the canonical quiet NaN (0x7e00 / 0x7fc0)."""
+    codes_unsigned = np.asarray(codes_unsigned)
+    num_out_groups, num_in_groups, num_codebooks = codes_unsigned.shape[-3:]
+    K, codebook_size, out_group_size, in_group_size = codebooks.shape
+    assert K == num_codebooks
+    cb = np.asarray(codebooks).astype(np.float32)
+    acc = np.zeros((num_out_groups, num_in_groups, out_group_size, in_group_size), dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for c in range(num_codebooks):
+            acc += cb[c][codes_unsigned[..., c]]
+        if scales is not None:
+            acc *= np.asarray(scales).astype(np.float32)
+        assert acc.dtype == np.float32
+        w = acc.swapaxes(-3, -2).reshape(num_out_groups * out_group_size, num_in_groups * in_group_size)
+        if isinstance(float_dtype, str) and float_dtype == "bfloat16":
+            bits = bf16_bits(round_to_bf16(w))
+            bits[np.isnan(w)] = 0x7FC0  # the integer rounding of round_to_bf16 is for numbers
+            return bits
+        assert np.dtype(float_dtype) == np.float16, float_dtype
+        bits = np.ascontiguousarray(w.astype(np.float16)).view(np.uint16)
+        bits[np.isnan(w)] = 0x7E00
+        return bits
+
+
+def storage_bits_to_float64(bits: np.ndarray, float_dtype) -> np.ndarray:
+    """uint16 bit patterns of the storage type -> the values they denote, as float64."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint16)
+    if isinstance(float_dtype, str) and float_dtype == "bfloat16":
+        return bf16_from_bits(bits).astype(np.float64)
+    return bits.view(np.float16).astype(np.float64)
+
+
+def round_to_storage_bits(a: np.ndarray, float_dtype) -> np.ndarray:
+    """float64 (or float32) values -> uint16 bit patterns of the storage type, ONE round-to-nearest-even from the given precision
+    (fp16: numpy's own cast; bf16: on the 64-bit pattern, so a float64 value is not rounded twice)."""
+    a = np.ascontiguousarray(a)
+    with np.errstate(over="ignore"):
+        if not (isinstance(float_dtype, str) and float_dtype == "bfloat16"):
+            return np.ascontiguousarray(a.astype(np.float16)).view(np.uint16)
+        if a.dtype == np.float32:
+            return bf16_bits(round_to_bf16(a))
+        assert a.dtype == np.float64 and np.isfinite(a).all()
+        # float64 -> bf16: below the bf16 normal range the spacing is fixed at 2**-133, above it is 2**(e-7)
+        mant, expo = np.frexp(a)                      # a = mant * 2**expo, 0.5 <= |mant| < 1
+        q = np.maximum(expo - 8, -133)                # exponent of the unit in the last place of the result
+        r = np.ldexp(np.rint(np.ldexp(a, -q)), q)     # np.rint rounds half to even; the scaling is exact
+        r = np.where(np.abs(r) >= 2.0**128, np.copysign(np.inf, a), r)
+        return bf16_bits(r.astype(np.float32))        # exact: r is a bf16 value (or inf)
 
 
 def _nbits_of(codebooks: np.ndarray) -> int:

@@ -135,6 +135,9 @@ def test_golden_forward_dequant_backward(hk, golden, name):
     Wref = golden[f"{name}/W_ref32"]
     rt = 2.0**-10 if dt == torch.float16 else 2.0**-7
     np.testing.assert_allclose(W.float().cpu().numpy(), Wref, rtol=rt, atol=1e-6)
+    # ... and bit for bit the kernels' arithmetic contract (fp32 sum in codebook order, * scale, one rounding)
+    bits = orc.dequantize_weight_storage(L["codes_unsigned"], L["codebooks"], L["scales"], np.float16 if dt == torch.float16 else "bfloat16")
+    assert torch.equal(W.view(torch.int16), torch.from_numpy(bits.view(np.int16)).to(DEV)), f"{name}: W differs from the contract's bits"
     # backward operator
     gout = torch.from_numpy(golden[f"{name}/gout"]).to(dt).to(DEV)
     fn = hk.code1x16_matmat_dequant_transposed if nbits == 16 else hk.code2x8_matmat_dequant_transposed
