@@ -1,6 +1,6 @@
 // Expert-routed launch of the prepacked 1x16 matvec (Mixtral decode on prepacked experts), gfx950, wave64.
 // Included at the end of gemv_packed.hip, so it is built twice like the rest of that file (8- and 16-element vectors).  Needs the
-// matvec body and LDS maps (packed_gemv_kernels.h), the layout (packed_format.h), packed_launch.h and that file's packed_fused.
+// matvec body and LDS maps (packed_gemv_kernels.h), the layout (packed_format.h), packed_launch.h and packed_gemv_entries.h's packed_fused.
 //
 // One launch computes every (token, expert) pair of one projection of a mixture-of-experts block -- or of the two that read the
 // same rows (w1 and w3) -- on the experts' PACKED buffers, with the routing read on the device only:

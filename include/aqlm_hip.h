@@ -282,7 +282,8 @@ int aqlm_hip_gemm_1x16_scan(const void* codes_i16, const void* codebook, const v
 
 /*
  * Load-time repack of 1x16 codes (g 8 or 16) into the slice-bucketed format v7 consumed by aqlm_hip_gemv_1x16_packed (layout:
- * aqlm_amd/csrc/packed_format.h and the head of gemv_packed.hip, specification tests/packed_model.py; 4 bytes per code + ~6 bytes
+ * aqlm_amd/csrc/packed_format.h and the head of gemv_packed.hip, specification tests/packed_model.py, the repack itself
+ * packed_repack_kernels.h and packed_repack_entries.h; 4 bytes per code + ~6 bytes
  * per (row, slice), plus 64 bytes per output row of zero-at-rest accumulator cells for the fused finalize).
  * The reference does the analogous thing for its CPU kernel: a one-off permutation of `codes` at first use
  * (inference.py:78-83).

@@ -78,6 +78,12 @@ def test_argument_validation_without_gpu(native):
         native.check(native.E_INVALID)
 
 
+def good_packed_desc(native):
+    """A valid descriptor of a 512 -> 64 layer: 4 waves x 1 step of 4-byte entries, 4 copies of x, |codebook| <= 1.5."""
+    uniform = (ctypes.c_uint8 * 32)(*([16] * 16))
+    return native.PackedDesc(0x37505141, 7, 64, 512, 4, 4, 1, 4, 1024 * (74 + 1024), 4, 1.5, 0, 4, uniform)
+
+
 def test_segment_struct_and_multi_validation(native):
     # aqlm_hip_segment: 5 pointers + long + 2 ints, no padding surprises
     assert ctypes.sizeof(native.Segment) == 56
@@ -113,8 +119,7 @@ def test_segment_struct_and_multi_validation(native):
     assert rc == native.E_INVALID and "descriptor" in native.last_error()
     # 64 rows -> 4 per row group; winfo (sized for 16 waves) + row starts (256 x 5 u32) + the accumulator cells of the
     # fused finalize (8 x 64 u64) end at 74 KiB, then 256 x 4 x 1 KiB of entries
-    uniform = (ctypes.c_uint8 * 32)(*([16] * 16))
-    good = native.PackedDesc(0x37505141, 7, 64, 512, 4, 4, 1, 4, 1024 * (74 + 1024), 4, 1.5, 0, 4, uniform)   # ... 4 copies of x, |codebook| <= 1.5
+    good = good_packed_desc(native)
     back = native.PackedDesc.from_ints(good.as_ints())
     assert bytes(back) == bytes(good)
     rc = L.aqlm_hip_gemv_1x16_packed(ctypes.byref(good), p, p, p, None, p, p, 9, 512, 64, native.F16, p, 1 << 20, None)
@@ -137,6 +142,117 @@ def test_segment_struct_and_multi_validation(native):
     odd.slice_groups[3] = 17
     rc = L.aqlm_hip_gemv_1x16_packed(ctypes.byref(odd), p, p, p, None, p, p, 1, 512, 64, native.F16, p, 1 << 20, None)
     assert rc == native.E_INVALID and "descriptor" in native.last_error()
+
+
+def packed_multi_malformed_calls(native, p):
+    """-> [(name, call)]: malformed calls of aqlm_hip_gemv_1x16_packed_multi / _multi_cells of two segments; `p`: 16-B aligned host
+    memory that stands for every buffer.  Every one of them is refused by a check that stands in front of the first launch (read
+    in packed_gemv_entries.h), so none needs a GPU."""
+    from tests import packed_model as pm
+
+    L = native.lib
+
+    def variant(out=64, entry_bytes=4, groups=None, flags=0, absmax=1.5):
+        d = good_packed_desc(native)
+        lay = pm.layout(out, 512 // 8, 4, 1, entry_bytes, groups, bool(flags & native.PACKED_RELABELLED))
+        d.out_features, d.entry_bytes, d.flags, d.codebook_absmax = out, entry_bytes, flags, absmax
+        d.rows_per_group, d.used_bytes = lay["RG"], lay["used"]
+        if groups:
+            d.slice_groups = (ctypes.c_uint8 * 32)(*groups)
+        return d
+
+    good = good_packed_desc(native)
+    assert bytes(variant()) == bytes(good)
+    norange = variant(absmax=0.0)                                   # no codebook range: two-kernel finalize, needs the workspace
+    relab = variant(flags=native.PACKED_RELABELLED)                 # relabelled, codebook image never written
+    three = variant(entry_bytes=3)
+    vg = variant(out=512, groups=[17, 15] + [16] * 14, flags=native.PACKED_VARGEOM)   # 512 rows: the fewest with variable geometry
+
+    def segs(*outs, **null):
+        a = (native.Segment * len(outs))()
+        for k, (s, out) in enumerate(zip(a, outs)):
+            s.codes = s.codebook = s.scales = s.y = p
+            s.out_features, s.y_row_stride = out, out
+            if null.get("codes") == k:
+                s.codes = None
+        return a
+
+    def descs(*ds):
+        return (native._descp * len(ds))(*[ctypes.pointer(d) if d is not None else native._descp() for d in ds])
+
+    def multi(sg, ds, n=2, x=p, in_features=512, batch=1, xs=512, dtype=native.F16, ws=p, ws_bytes=1 << 20):
+        return lambda: L.aqlm_hip_gemv_1x16_packed_multi(sg, ds, n, x, in_features, batch, xs, dtype, ws, ws_bytes, None)
+
+    def cells(sg, ds, c=p, c_bytes=1 << 20):
+        return lambda: L.aqlm_hip_gemv_1x16_packed_multi_cells(sg, ds, 2, p, 512, 1, 512, native.F16, c, c_bytes, None)
+
+    two, gg = segs(64, 64), descs(good, good)
+    return [
+        ("null segments", multi(None, gg)),
+        ("null descs", multi(two, None)),
+        ("0 segments", multi(two, gg, n=0)),
+        ("MAX_SEGMENTS + 1 segments", multi(two, gg, n=native.MAX_SEGMENTS + 1)),
+        ("dtype 7", multi(two, gg, dtype=7)),
+        ("batch 0", multi(two, gg, batch=0)),
+        ("batch 9", multi(two, gg, batch=9)),
+        ("x misaligned by 2", multi(two, gg, x=p + 2)),
+        ("batch 2, x_row_stride 12", multi(two, gg, batch=2, xs=12)),
+        ("null descriptor in slot 1", multi(two, descs(good, None))),
+        ("in_features differs from the argument", multi(two, gg, in_features=1024)),
+        ("out_features differs from the segment's", multi(segs(64, 128), gg)),
+        ("null codes in slot 1", multi(segs(64, 64, codes=1), gg)),
+        ("null codes in slot 0, null descriptor in slot 1", multi(segs(64, 64, codes=0), descs(good, None))),
+        ("null codes and null descriptor in slot 1", multi(segs(64, 64, codes=1), descs(good, None))),
+        ("relabelled without its codebook image in slot 1", multi(two, descs(good, relab))),
+        ("3- and 4-byte entries mixed", multi(two, descs(good, three))),
+        ("no codebook range, workspace one byte short", multi(two, descs(norange, norange), ws_bytes=2 * 16 * 64 * 4 - 1)),
+        ("cells: null cells", cells(two, gg, c=None)),
+        ("cells: misaligned by 4", cells(two, gg, c=p + 4)),
+        ("cells: descriptor without the range", cells(two, descs(good, norange))),
+        ("cells: cells_bytes one short", cells(two, gg, c_bytes=2 * 64 * 8 - 1)),
+        # a variable-geometry descriptor sends the call down the one-launch-per-segment path, which checks segment k only after
+        # it has launched segment k - 1: the mismatch stands in slot 0, the descriptor that selects the path behind it
+        ("variable geometry in slot 1, out_features mismatch in slot 0", multi(segs(128, 512), descs(good, vg))),
+        ("variable geometry in slot 1, null descriptor in slot 0", multi(segs(64, 512), descs(None, vg))),
+    ]
+
+
+def test_packed_multi_rejections_are_unchanged(native):
+    """Which malformed call of the shared-input packed entries is refused with which code and message: recorded from the library
+    as it was before gemv_1x16_packed_multi_impl began to compute its segments' layouts once, up front."""
+    multi, cells = "aqlm_hip_gemv_1x16_packed_multi: ", "aqlm_hip_gemv_1x16_packed_multi_cells: "
+    expected = {
+        "null segments": (-1, multi + "1..4 segments, their descriptors and a non-null x required (got 2)"),
+        "null descs": (-1, multi + "1..4 segments, their descriptors and a non-null x required (got 2)"),
+        "0 segments": (-1, multi + "1..4 segments, their descriptors and a non-null x required (got 0)"),
+        "MAX_SEGMENTS + 1 segments": (-1, multi + "1..4 segments, their descriptors and a non-null x required (got 5)"),
+        "dtype 7": (-2, multi + "AQLM HIP kernels only support float16 and bfloat16 (dtype id 7)"),
+        "batch 0": (-1, multi + "batch must be 1..8 with 16-B aligned rows (batch 0)"),
+        "batch 9": (-1, multi + "batch must be 1..8 with 16-B aligned rows (batch 9)"),
+        "x misaligned by 2": (-1, multi + "batch must be 1..8 with 16-B aligned rows (batch 1)"),
+        "batch 2, x_row_stride 12": (-1, multi + "batch must be 1..8 with 16-B aligned rows (batch 2)"),
+        "null descriptor in slot 1": (-1, multi + "segment 1: invalid descriptor, or it does not match in_features 512 / out_features 64"),
+        "in_features differs from the argument": (-1, multi + "segment 0: invalid descriptor, or it does not match in_features 1024 / out_features 64"),
+        "out_features differs from the segment's": (-1, multi + "segment 1: invalid descriptor, or it does not match in_features 512 / out_features 128"),
+        "null codes in slot 1": (-1, multi + "null pointer in segment 1"),
+        "null codes in slot 0, null descriptor in slot 1": (-1, multi + "null pointer in segment 0"),
+        "null codes and null descriptor in slot 1": (-1, multi + "null pointer in segment 1"),
+        "relabelled without its codebook image in slot 1": (-1, multi + "segment 1: a relabelled buffer needs its codebook image (aqlm_hip_packed_set_codebook)"),
+        "3- and 4-byte entries mixed": (-2, multi + "segments mix 3- and 4-byte entry formats"),
+        "no codebook range, workspace one byte short": (-1, multi + "workspace of 8192 bytes required, got 8191"),
+        "cells: null cells": (-1, cells + "needs 8-B aligned, zero-filled cells and the fused finalize switched on"),
+        "cells: misaligned by 4": (-1, cells + "needs 8-B aligned, zero-filled cells and the fused finalize switched on"),
+        "cells: descriptor without the range": (-1, cells + "every descriptor must carry the codebook range"),
+        "cells: cells_bytes one short": (-1, cells + "1024 bytes of cells required, got 1023"),
+        "variable geometry in slot 1, out_features mismatch in slot 0": (-1, multi + "segment 0: descriptor does not match in_features 512 / out_features 128"),
+        "variable geometry in slot 1, null descriptor in slot 0": (-1, multi + "segment 0: descriptor does not match in_features 512 / out_features 64"),
+    }
+    buf = ctypes.create_string_buffer(4096 + 16)
+    calls = packed_multi_malformed_calls(native, (ctypes.addressof(buf) + 15) & ~15)
+    assert len(calls) == len(expected) >= 16
+    for name, call in calls:
+        rc = call()
+        assert (rc, native.last_error()) == expected[name], name
 
 
 def test_workspace_bytes(native):

@@ -1,4 +1,4 @@
-"""How far is the bank-aware entry order of the packed 1x16 format (pk_arrange_kernel, aqlm_amd/csrc/gemv_packed.hip) from
+"""How far is the bank-aware entry order of the packed 1x16 format (pk_arrange_kernel, aqlm_amd/csrc/packed_repack_kernels.h) from
 what any order could reach?  CPU-only study on one synthetic wave range (random codes):
 
   * `greedy`      restates the device algorithm (slot by slot, rotating priority inside a 16-lane LDS service group);
