@@ -129,6 +129,7 @@ class LoraEntry(ctypes.Structure):
 LORA_ENTRY_WORDS = ctypes.sizeof(LoraEntry) // 8   # 64-bit words of a table entry
 MAX_LORA_ROWS = 256      # aqlm_hip_lora_bgmv: rows per call
 MAX_LORA_SGMV_ROWS = 65536   # aqlm_hip_lora_sgmv: rows per call
+MAX_LORA_SGMV_ROUTED_PAIRS = 65536   # aqlm_hip_lora_sgmv_routed: (token, expert) pairs per call
 MAX_LORA_RANK = 128
 
 _rpep = ctypes.POINTER(RoutedPackedEntry)
@@ -164,6 +165,10 @@ SIGNATURES = {
     "aqlm_hip_lora_sgmv_workspace_bytes": (_sz, [_ci, _ci, _ci]),
     "aqlm_hip_lora_sgmv_supported": (_ci, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_lora_sgmv": (_ci, [_vp, _ci, _ci, _vp, _ci, _ci, _vp, _cl, _vp, _cl, _ci, _ci, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_lora_sgmv_routed_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_sgmv_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_sgmv_routed": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _vp,
+                                  _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

@@ -1,6 +1,6 @@
 // What the LoRA launches share (lora_bgmv.hip: per-row matvec; lora_bgmv_routed.hip: the same per (token, expert) pair of a
-// mixture-of-experts block; lora_sgmv.hip: segmented MFMA GEMM): the device contract of
-// the adapter table and the ids, and the argument checks of the entry points.
+// mixture-of-experts block; lora_sgmv.hip: segmented MFMA GEMM; lora_sgmv_routed.hip: the same on pair tiles of one expert): the
+// device contract of the adapter table and the ids, and the argument checks of the entry points.
 //
 // The contract: an id selects a table entry, so it is range-checked BEFORE it forms an address -- a row whose id lies outside
 // [0, num_adapters) touches no table slot and its y row is never written -- and an entry whose rank is no multiple of 8 in

@@ -1,5 +1,6 @@
 // The bucket of the expert-grouped launches: the one statement of its layout.  moe_bucket_kernel (moe_grouped.hip) writes it; the
-// grouped GEMM (moe_grouped.hip) and its transposed product (moe_grouped_bwd.hip) read it through the accessors below.
+// grouped GEMM (moe_grouped.hip), its transposed product (moe_grouped_bwd.hip) and the routed segmented adapter GEMM
+// (lora_sgmv_routed.hip, tiles of 16) read it through the accessors below.
 //
 // int32 words: [0] tiles, [1] pairs with an id outside [0, E), [2] pairs with a valid id, [3] 0;
 // then max_tiles x {expert, first, count, 0}; then the pair list [num_pairs]: the valid pairs by expert, in ascending pair

@@ -740,16 +740,8 @@ def lora_bgmv_routed_supported(out_features: int, in_features: int, max_rank: in
                                                          int(num_experts), int(num_segments)))
 
 
-def lora_bgmv_routed_(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair) -> None:
-    """``y[p, s] += scaling * B (A x_row(p))`` with the adapter of ``table`` entry (adapter_ids[p // top_k], expert_ids[p], s), in
-    place, for every (token, expert) pair and projection of a mixture-of-experts launch in two launches (include/aqlm_hip.h,
-    aqlm_hip_lora_bgmv_routed; bit-identical per row to ``lora_bgmv_`` with that entry as a one-slot table).
-    geometry = [num_adapters, num_experts, num_segments, max_rank, out_features, in_features, top_k]; ``y`` contiguous
-    [T * top_k, num_segments, out] (or [T * top_k, out] with one segment), the output of the routed / grouped ops; ``x`` [T, in]
-    (token rows, ``x_per_pair`` False) or [T * top_k, in] (pair rows) with a unit inner stride; ``adapter_ids`` [T] int64 / int32 on
-    the device or None = adapter 0; ``expert_ids`` [T, top_k] int64 / int32 on the device; both are read on the device only, and a
-    pair with either id out of range is left as it is.  ``table`` from ``lora_routed_table``.  At most MAX_LORA_ROWS pairs per
-    call.  The fp32 workspace comes from the caching allocator, so the call can be captured."""
+def _check_lora_routed(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair):
+    """The argument checks of ``lora_bgmv_routed_`` / ``lora_sgmv_routed_`` -> (P, rows, dtype id, contiguous adapter ids)."""
     n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
     dt = _dtype_id(y)
     if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
@@ -771,6 +763,21 @@ def lora_bgmv_routed_(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair
             raise ValueError(f"adapter_ids must be [{T}] int64 / int32 on {y.device}, got {tuple(adapter_ids.shape)} "
                              f"{adapter_ids.dtype} on {adapter_ids.device}")
         adapter_ids = _c(adapter_ids)
+    return P, rows, dt, adapter_ids
+
+
+def lora_bgmv_routed_(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair) -> None:
+    """``y[p, s] += scaling * B (A x_row(p))`` with the adapter of ``table`` entry (adapter_ids[p // top_k], expert_ids[p], s), in
+    place, for every (token, expert) pair and projection of a mixture-of-experts launch in two launches (include/aqlm_hip.h,
+    aqlm_hip_lora_bgmv_routed; bit-identical per row to ``lora_bgmv_`` with that entry as a one-slot table).
+    geometry = [num_adapters, num_experts, num_segments, max_rank, out_features, in_features, top_k]; ``y`` contiguous
+    [T * top_k, num_segments, out] (or [T * top_k, out] with one segment), the output of the routed / grouped ops; ``x`` [T, in]
+    (token rows, ``x_per_pair`` False) or [T * top_k, in] (pair rows) with a unit inner stride; ``adapter_ids`` [T] int64 / int32 on
+    the device or None = adapter 0; ``expert_ids`` [T, top_k] int64 / int32 on the device; both are read on the device only, and a
+    pair with either id out of range is left as it is.  ``table`` from ``lora_routed_table``.  At most MAX_LORA_ROWS pairs per
+    call.  The fp32 workspace comes from the caching allocator, so the call can be captured."""
+    n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
+    P, rows, dt, adapter_ids = _check_lora_routed(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair)
     if P == 0:
         return
     x = _flat_rows(x)
@@ -783,6 +790,41 @@ def lora_bgmv_routed_(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair
             int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
     if rc:
         _native.check(rc, "aqlm lora bgmv routed")
+
+
+SGMV_ROUTED_TILE_PAIRS = 16  # pairs per tile of the bucket aqlm_hip_lora_sgmv_routed reads: the rows of one matrix instruction
+
+
+def lora_sgmv_routed_supported(out_features: int, in_features: int, max_rank: int, num_pairs: int, num_experts: int,
+                               num_segments: int) -> bool:
+    return bool(_lib.aqlm_hip_lora_sgmv_routed_supported(int(out_features), int(in_features), int(max_rank), int(num_pairs),
+                                                         int(num_experts), int(num_segments)))
+
+
+def lora_sgmv_routed_(y, x, adapter_ids, expert_ids, bucket, table, geometry, x_per_pair) -> None:
+    """``lora_bgmv_routed_`` at any number of pairs (prefill, large batches): the segmented adapter GEMM on the matrix unit over
+    row tiles gathered through the expert bucket (include/aqlm_hip.h, aqlm_hip_lora_sgmv_routed; bit-identical per row to
+    ``lora_sgmv_`` with that entry as a one-slot table).  Same arguments as ``lora_bgmv_routed_`` plus ``bucket``:
+    ``moe_bucket(expert_ids, num_experts, 16)`` of the same ``expert_ids``.  ``out_features`` must be a multiple of 4 (y rows are
+    written in groups of 4 outputs).  At most MAX_LORA_SGMV_ROUTED_PAIRS pairs per call."""
+    n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
+    P, rows, dt, adapter_ids = _check_lora_routed(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair)
+    if P == 0:
+        return
+    if (bucket.dtype != torch.int32 or bucket.device != y.device or not bucket.is_contiguous()
+            or bucket.numel() != _bucket_words(P, E, SGMV_ROUTED_TILE_PAIRS)):
+        raise ValueError(f"bucket must come from moe_bucket(expert_ids, {E}, {SGMV_ROUTED_TILE_PAIRS}) on {y.device}")
+    x = _flat_rows(x)
+    eids = _c(expert_ids)
+    ws = _workspace(y.device, max(_lib.aqlm_hip_lora_sgmv_routed_workspace_bytes(P, S, max_rank, in_features), 16))
+    with _device_guard(y.device):
+        rc = _lib.aqlm_hip_lora_sgmv_routed(
+            table.data_ptr(), n, E, S, max_rank, _ptr(adapter_ids), int(adapter_ids is not None and adapter_ids.element_size() == 8),
+            eids.data_ptr(), int(eids.element_size() == 8), bucket.data_ptr(), P, top_k, x.data_ptr(),
+            x.stride(0) if rows > 1 else in_features, int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, dt,
+            ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
+    if rc:
+        _native.check(rc, "aqlm lora sgmv routed")
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1965,6 +2007,12 @@ torch.library.register_fake("aqlm::lora_bgmv_routed_")(lambda y, x, adapter_ids,
 _LIB.define("lora_sgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
 _LIB.impl("lora_sgmv_", lora_sgmv_, "CUDA")
 torch.library.register_fake("aqlm::lora_sgmv_")(_fake_lora_bgmv)
+
+_LIB.define("lora_sgmv_routed_(Tensor(a!) y, Tensor x, Tensor? adapter_ids, Tensor expert_ids, Tensor bucket, Tensor table, "
+            "int[] geometry, bool x_per_pair) -> ()")
+_LIB.impl("lora_sgmv_routed_", lora_sgmv_routed_, "CUDA")
+torch.library.register_fake("aqlm::lora_sgmv_routed_")(
+    lambda y, x, adapter_ids, expert_ids, bucket, table, geometry, x_per_pair: None)
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

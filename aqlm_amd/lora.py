@@ -20,7 +20,10 @@ decline -- runs the adapters as torch ops, differentiable in x, A and B, so the 
 Adapters on the ROUTED EXPERTS of a Mixtral block ride on whichever launches the block takes: for up to
 ``ROUTED_BGMV_MAX_PAIRS`` (token, expert) pairs ``aqlm_hip_lora_bgmv_routed`` (aqlm_amd/csrc/lora_bgmv_routed.hip) adds them in place to
 the output of the gate / up launch and of the down launch -- two launches each, adapter ids and expert ids read on the device only,
-capturable --; every other call (more pairs, a gradient needed, host tensors, ``torch.compile``) runs PEFT's formula per (adapter,
+capturable --; calls of ``ROUTED_SGMV_MIN_PAIRS`` .. ``ROUTED_SGMV_MAX_PAIRS`` pairs (prefill) have ``aqlm_hip_lora_sgmv_routed``
+(aqlm_amd/csrc/lora_sgmv_routed.hip), the segmented adapter GEMM on row tiles gathered through an expert bucket of 16-pair tiles that
+the provider builds once per forward (one small launch, no sync, capturable), for the pair counts at which it was measured to
+win; every other call (a gradient needed, host tensors, ``torch.compile``, shapes the kernels decline) runs PEFT's formula per (adapter,
 expert) as masked torch ops in fp32 without a host sync, differentiable in x, A and B, so expert adapters serve prefill and train.  Their
 ``state_dict()`` keys are ``<block>.base_layer.<e>.<w>.codes``, ``<block>.lora_A.<name>.<e>.<w>.weight`` and
 ``<block>.lora_B.<name>.<e>.<w>.weight`` (PEFT has no per-expert module convention for fused experts to follow); adapter FILES name
@@ -71,6 +74,21 @@ SGMV_MAX_ROWS = AQLM_HIP_MAX_LORA_SGMV_ROWS
 # over 128 tokens: 1707 against 6203 us), so the constant is the launch's own limit.  0 switches the route off.
 ROUTED_BGMV_MAX_PAIRS = 256
 
+AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS = 65536  # include/aqlm_hip.h: pairs one aqlm_hip_lora_sgmv_routed call takes
+
+# Calls of ROUTED_SGMV_MIN_PAIRS .. ROUTED_SGMV_MAX_PAIRS pairs on the routed experts run aqlm_hip_lora_sgmv_routed; up to 256
+# pairs every call keeps the route it had (the torch path included, when ROUTED_BGMV_MAX_PAIRS is lowered).  ROUTED_SGMV_MAX_PAIRS
+# is a measured route constant (profiles/lora_moe_prefill.json, written by `python tools/lora_moe_benchmark.py
+# --prefill`): the largest of the pair counts 512 / 1024 / 2048 / 4096 / 8192 (T = 256 .. 4096 at top_k 2) up to which the captured
+# block with the HIP route replayed faster than the captured block with the torch path at that count and every smaller one in all
+# three adapter mixes (one adapter; four adapters as four contiguous sequences; four adapters interleaved per token), on a
+# Mixtral-8x7B-shaped prepacked block with rank-16 adapters on w1 / w2 / w3 of all experts; the launch's own limit when it won at
+# every measured count.  Measured: it won at every count in all three mixes (four sequences over 1024 tokens: 4963 against 17090 us
+# captured, bare block 4496; four adapters interleaved over 4096 tokens: 19055 against 59975 us, bare block 16351), so the constant
+# is the launch's own limit.  0 switches the route off.
+ROUTED_SGMV_MIN_PAIRS = 257
+ROUTED_SGMV_MAX_PAIRS = AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS
+
 _PREFIX = "base_model.model."
 _DTYPES_OK = (torch.float16, torch.bfloat16)
 
@@ -95,6 +113,14 @@ def takes_routed_bgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, co
     of ``takes_bgmv_route`` with 1..ROUTED_BGMV_MAX_PAIRS (token, expert) pairs (never more than one launch takes)."""
     return bool(is_cuda and dtype_ok and not grad_needed and not compiling
                 and 1 <= pairs <= min(ROUTED_BGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_ROWS) and supported)
+
+
+def takes_routed_sgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling: bool, pairs: int, supported: bool) -> bool:
+    """Whether a call on the routed experts that did not take the BGMV route runs the two launches of aqlm_hip_lora_sgmv_routed
+    (else the torch path): the conditions of ``takes_routed_bgmv_route`` with ROUTED_SGMV_MIN_PAIRS..ROUTED_SGMV_MAX_PAIRS
+    (token, expert) pairs (never more than one launch takes)."""
+    return bool(is_cuda and dtype_ok and not grad_needed and not compiling
+                and ROUTED_SGMV_MIN_PAIRS <= pairs <= min(ROUTED_SGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS) and supported)
 
 
 class AdapterBank:
@@ -426,6 +452,7 @@ class _ExpertAdapters:
     def __init__(self, layer: LoraQuantizedMixtralExperts, sel, ids: Optional[torch.Tensor]):
         self.layer, self.ids = layer, ids
         self._tables = None  # the layer's device tables, looked up (and their key compared) once per forward
+        self._bucket = None  # the 16-pair expert bucket of the SGMV route, built once per forward and read by both calls
         self.names = [sel] if isinstance(sel, str) else [n for n in layer.bank.names if n in layer.lora_A]
 
     def on_pairs(self, out: torch.Tensor, x: torch.Tensor, top_k_index: torch.Tensor, segments, x_per_pair: bool) -> torch.Tensor:
@@ -442,8 +469,10 @@ class _ExpertAdapters:
         dtype_ok = x.dtype in _DTYPES_OK and out.dtype == x.dtype and all(a.dtype == x.dtype and b.dtype == x.dtype for a, b, _ in weights)
         grad_needed = torch.is_grad_enabled() and (x.requires_grad or out.requires_grad
                                                    or any(a.requires_grad or b.requires_grad for a, b, _ in weights))
+        bgmv = 1 <= P <= min(ROUTED_BGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_ROWS)
+        sgmv = ROUTED_SGMV_MIN_PAIRS <= P <= min(ROUTED_SGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS)
         fast = (x.is_cuda and dtype_ok and not grad_needed and not compiling and top_k_index.dim() == 2 and out.is_contiguous()
-                and 1 <= P <= min(ROUTED_BGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_ROWS))
+                and (bgmv or sgmv))
         if fast:
             from .inference_kernels import hip_kernel
 
@@ -456,10 +485,17 @@ class _ExpertAdapters:
                 table, n, max_rank = table[a * words:(a + 1) * words], 1, max_ranks[a]
             else:
                 n, max_rank = len(max_ranks), max(max_ranks)
-            supported = ranks_ok and hip_kernel.lora_bgmv_routed_supported(M, x.shape[1], max_rank, P, layer.num_experts, S)
+            geometry = [n, layer.num_experts, S, max_rank, M, x.shape[1], top_k_index.shape[1]]
+            supported = bgmv and ranks_ok and hip_kernel.lora_bgmv_routed_supported(M, x.shape[1], max_rank, P, layer.num_experts, S)
             if takes_routed_bgmv_route(x.is_cuda, dtype_ok, grad_needed, compiling, P, supported):
-                hip_kernel.lora_bgmv_routed_(out, x, self.ids, top_k_index, table,
-                                             [n, layer.num_experts, S, max_rank, M, x.shape[1], top_k_index.shape[1]], x_per_pair)
+                hip_kernel.lora_bgmv_routed_(out, x, self.ids, top_k_index, table, geometry, x_per_pair)
+                return out
+            supported = (sgmv and ranks_ok and out.data_ptr() % 8 == 0
+                         and hip_kernel.lora_sgmv_routed_supported(M, x.shape[1], max_rank, P, layer.num_experts, S))
+            if takes_routed_sgmv_route(x.is_cuda, dtype_ok, grad_needed, compiling, P, supported):
+                if self._bucket is None:
+                    self._bucket = torch.ops.aqlm.moe_bucket(top_k_index, layer.num_experts, hip_kernel.SGMV_ROUTED_TILE_PAIRS)
+                hip_kernel.lora_sgmv_routed_(out, x, self.ids, top_k_index, self._bucket, table, geometry, x_per_pair)
                 return out
         return self._torch_pairs(out, x, top_k_index, segments, x_per_pair)
 

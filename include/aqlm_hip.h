@@ -607,6 +607,50 @@ int aqlm_hip_lora_sgmv(const aqlm_hip_lora_entry* table, int num_adapters, int m
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The segmented adapter GEMM on the ROUTED experts of a mixture-of-experts block (prefill, large batches): aqlm_hip_lora_sgmv
+ * on row tiles gathered through the expert bucket of the grouped launches, the counterpart of aqlm_hip_lora_bgmv_routed above
+ * AQLM_HIP_MAX_LORA_ROWS pairs (no reference counterpart).  `table`, adapter_ids, expert_ids, x, x_per_pair, y and top_k are
+ * aqlm_hip_lora_bgmv_routed's.  `bucket`: DEVICE, 16-byte aligned, written by aqlm_hip_moe_bucket from the SAME expert_ids with
+ * the same num_pairs and num_experts and tile_pairs 16.  For every pair p of a tile of the bucket, with a = adapter_ids[p / top_k]
+ * (NULL: adapter 0) and e the tile's expert, and every segment s, with the entry [(a * num_experts + e) * num_segments + s],
+ * x_row(p) = x + (x_per_pair ? p : p / top_k) * x_row_stride and yrow = y + (p * num_segments + s) * out_features, T the storage
+ * type:
+ *     t[r]    = sum_k A[r, k] * x_row(p)[k]                                    r < rank   (fp32)
+ *     hi = round_T(t),  lo = round_T(t - float(hi))
+ *     yrow[i] = round_T(float(yrow[i]) + scaling * sum_r B[i, r] * (hi[r] + lo[r]))
+ * A pair keeps its y rows bit for bit, and nothing is loaded through its table slot, when its adapter id is out of range, its
+ * expert id is out of range (such pairs sit in the bucket's tail and belong to no tile), its entry has rank 0 or its entry's rank
+ * is no multiple of 8 in 8..max_rank.  One workgroup row tile is one slot of the bucket: up to 16 pairs of one expert, read through
+ * the pair list, served in one pass per DISTINCT valid adapter among them, every row written exactly once; pairs stay in ascending
+ * order inside an expert, so per-sequence adapter ids cost one pass per tile and two at a seam.  Both grids have
+ * ceil(num_pairs / 16) + min(num_experts, num_pairs) row tiles x num_segments -- the sizes only, never the routing --, and a slot
+ * at or past the bucket's tile count exits after reading that one word.  A tile record is dropped before it forms an address when
+ * its expert lies outside [0, num_experts), its count outside [1, 16], its first outside [0, num_pairs - count] or an entry of its
+ * list outside [0, num_pairs) (a foreign bucket, or one with larger tiles); a listed pair whose expert id is not the tile's
+ * expert (a bucket of other ids) counts as a pair without an adapter.  The sum over in_features is cut as aqlm_hip_lora_sgmv
+ * cuts it, by a function of in_features alone, and every sum runs in aqlm_hip_lora_sgmv's order: a pair's y row is BIT-IDENTICAL
+ * to aqlm_hip_lora_sgmv called on that one row with that entry as a one-slot table, so it does not depend on the other pairs,
+ * their number or their order.  `workspace`: fp32 [num_pairs][num_segments][splits][max_rank],
+ * aqlm_hip_lora_sgmv_routed_workspace_bytes bytes, 16-byte aligned.  No atomics, no inter-workgroup communication;
+ * stream-ordered, no allocation, no synchronisation (hipGraph-capturable; both id arrays may be rewritten in place between
+ * replays when the aqlm_hip_moe_bucket launch is part of the captured step).
+ * Argument checks as aqlm_hip_lora_bgmv_routed, in the same order, with num_pairs up to AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS;
+ * then a null or misaligned bucket (AQLM_HIP_E_INVALID); AQLM_HIP_E_UNSUPPORTED in addition for num_experts >
+ * AQLM_HIP_MAX_ROUTED_EXPERTS, num_segments > 2, and out_features % 4 != 0 or y not 8-byte aligned (y rows are written in 8-byte
+ * groups at a stride of out_features); last the workspace size.  aqlm_hip_lora_sgmv_routed_supported answers for the six sizes
+ * beforehand.
+ */
+#define AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS 65536
+
+size_t aqlm_hip_lora_sgmv_routed_workspace_bytes(int num_pairs, int num_segments, int max_rank, int in_features); /* 0 when unsupported */
+int aqlm_hip_lora_sgmv_routed_supported(int out_features, int in_features, int max_rank, int num_pairs, int num_experts,
+                                        int num_segments);
+int aqlm_hip_lora_sgmv_routed(const aqlm_hip_lora_entry* table, int num_adapters, int num_experts, int num_segments, int max_rank,
+                              const void* adapter_ids, int adapter_ids_int64, const void* expert_ids, int expert_ids_int64,
+                              const void* bucket, int num_pairs, int top_k, const void* x, long x_row_stride, int x_per_pair, void* y,
+                              int out_features, int in_features, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the

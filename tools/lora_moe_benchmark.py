@@ -17,6 +17,18 @@ adapter mixes at every measured count -- every round of (c) below the smallest r
 ``aqlm_amd.lora.ROUTED_BGMV_MAX_PAIRS`` is set to (0 when it wins nowhere).  Writes --out (default profiles/lora_moe.json).
 
     python tools/lora_moe_benchmark.py [--tokens 1,2,4,8,16,32,64,128] [--iters 30] [--repeats 3]
+
+``--prefill`` measures the prefill route instead, on the same block and with the same protocol: T = 256 / 512 / 1024 / 2048 / 4096
+tokens (512 .. 8192 pairs, the grouped base launches under capture), three adapter mixes (one adapter; 4 adapters as 4 contiguous
+sequences; 4 adapters interleaved per token), (b) with ``ROUTED_SGMV_MAX_PAIRS = 0`` against (c) the two launches of
+aqlm_hip_lora_sgmv_routed per projection group plus the 16-pair bucket launch.  ``routed_sgmv_max_pairs`` in the output is the
+largest pair count up to which (c) beat (b) at that count and every smaller one in all three mixes, the launch's own limit when it
+won at every measured count, and is what ``aqlm_amd.lora.ROUTED_SGMV_MAX_PAIRS`` is set to.  As data only, ``eager_rows`` holds
+eager calls at 1024 / 2048 / 4096 pairs: the per-expert loop with ``on_rows`` (what an eager call of that size runs) against the
+grouped base launches with the new route (``moe.GROUPED_EAGER_MAX_PAIRS`` raised for the measurement).  Writes --out (default
+profiles/lora_moe_prefill.json).
+
+    python tools/lora_moe_benchmark.py --prefill [--tokens 256,512,1024,2048,4096] [--iters 20] [--repeats 3]
 """
 import argparse
 import json
@@ -50,16 +62,169 @@ def adapter(seed):
     return state, {"peft_type": "LORA", "r": RANK, "lora_alpha": 2 * RANK, "bias": "none", "target_modules": ["w1", "w2", "w3"]}
 
 
+PREFILL_TOKENS = "256,512,1024,2048,4096"
+EAGER_PAIRS = (1024, 2048, 4096)
+
+
+def timed_eager(fns, iters, warmup):
+    """median per call of each of the eager `fns`, interleaved; a host clock around work that ends in a device synchronise (the
+    per-expert loop syncs with the host, so device events alone would miss its waits)"""
+    import time
+
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(iters):
+        for i, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[i].append((time.perf_counter() - t0) * 1e6)
+    return [round(sorted(t)[len(t) // 2], 2) for t in times]
+
+
+def prefill(args):
+    """--prefill: base / torch path / routed sgmv at prefill pair counts, three adapter mixes; writes profiles/lora_moe_prefill.json."""
+    import aqlm_amd.lora as lora
+    import aqlm_amd.moe as moe
+    from aqlm_amd import _native
+
+    dev = torch.device("cuda:0")
+    q, _ = build(dev, False)
+    report = moe.prepack_experts(q)
+    holder = Holder(q)
+    bank = lora.attach_adapters(holder, {f"ad{i}": adapter(100 + i) for i in range(ADAPTERS)})
+    block = holder.experts
+    gen = torch.Generator(device=dev).manual_seed(1)
+    names = ["base_graph_us", "torch_graph_us", "hip_graph_us"]
+    token_counts = [int(t) for t in args.tokens.split(",")]
+    limit = _native.MAX_LORA_SGMV_ROUTED_PAIRS
+    table, eager_rows = [], []
+    with torch.no_grad():
+        for T in token_counts:
+            if T % ADAPTERS:
+                raise SystemExit(f"--prefill: {T} tokens do not split into {ADAPTERS} sequences")
+            sets = [torch.randn((T, H), generator=gen, device=dev).half() for _ in range(SETS)]
+            logits = torch.randn((T, E), generator=gen, device=dev)
+            w, idx = torch.topk(torch.softmax(logits, -1), K, dim=-1)
+            w = w / w.sum(-1, keepdim=True)
+            seq_ids = torch.arange(ADAPTERS, device=dev, dtype=torch.int64)
+            tok_ids = (torch.arange(T, device=dev) % ADAPTERS).to(torch.int64)
+            mixes = (("one adapter", "ad0"), (f"{ADAPTERS} adapters, contiguous sequences", seq_ids),
+                     (f"{ADAPTERS} adapters interleaved per token", tok_ids))
+            for mix, selection in mixes:
+                static = sets[0].clone()
+                graphs, outs = [], []
+                for which, max_pairs in ((None, 0), (selection, 0), (selection, limit)):
+                    bank.select(which)
+                    lora.ROUTED_SGMV_MAX_PAIRS = max_pairs  # the route is decided when the call is captured
+                    g, out = captured(lambda: block(static, idx, w))
+                    graphs.append(g)
+                    outs.append(out)
+                turn = [0] * len(graphs)
+
+                def replay(i):
+                    static.copy_(sets[turn[i] % SETS])
+                    turn[i] += 1
+                    graphs[i].replay()
+
+                fns = [lambda i=i: replay(i) for i in range(len(graphs))]
+                runs = [timed_alternating(fns, args.iters, args.warmup) for _ in range(args.repeats)]
+                row = {"tokens": T, "pairs": T * K, "adapters": mix}
+                for i, name in enumerate(names):
+                    vals = sorted(r[i] for r in runs)
+                    row[name] = vals[len(vals) // 2]
+                    row[name.replace("_us", "_runs_us")] = [r[i] for r in runs]
+                    row[name.replace("_us", "_spread_us")] = round(vals[-1] - vals[0], 2)
+                row["hip_wins"] = bool(max(r[2] for r in runs) < min(r[1] for r in runs) - row["torch_graph_spread_us"])
+                static.copy_(sets[0])
+                for g in graphs:
+                    g.replay()
+                torch.cuda.synchronize()
+                row["rel_diff_hip_vs_torch"] = float(((outs[2].float() - outs[1].float()).abs().mean()
+                                                      / outs[1].float().abs().mean()).item())
+                row["rel_size_of_the_adapter_term"] = float(((outs[1].float() - outs[0].float()).abs().mean()
+                                                             / outs[0].float().abs().mean()).item())
+                del graphs, outs
+                table.append(row)
+                print(json.dumps(row), flush=True)
+                if T * K in EAGER_PAIRS:  # data only: what an eager call of this size runs against the grouped base + new route
+                    bank.select(selection)
+                    x0 = sets[0]
+                    keep = moe.GROUPED_EAGER_MAX_PAIRS
+
+                    def loop():
+                        moe.GROUPED_EAGER_MAX_PAIRS = keep
+                        return block(x0, idx, w)
+
+                    def grouped():
+                        moe.GROUPED_EAGER_MAX_PAIRS = moe.MAX_GROUPED_PAIRS
+                        try:
+                            return block(x0, idx, w)
+                        finally:
+                            moe.GROUPED_EAGER_MAX_PAIRS = keep
+
+                    lora.ROUTED_SGMV_MAX_PAIRS = limit
+                    assert not q.takes_grouped_path(x0, idx), "an eager call of this size was expected to run the per-expert loop"
+                    eruns = [timed_eager([loop, grouped], max(args.iters // 2, 3), 2) for _ in range(args.repeats)]
+                    erow = {"tokens": T, "pairs": T * K, "adapters": mix}
+                    for i, name in enumerate(("eager_loop_on_rows_us", "eager_grouped_sgmv_us")):
+                        vals = sorted(r[i] for r in eruns)
+                        erow[name] = vals[len(vals) // 2]
+                        erow[name.replace("_us", "_runs_us")] = [r[i] for r in eruns]
+                    erow["rel_diff"] = float(((grouped().float() - loop().float()).abs().mean() / loop().float().abs().mean()).item())
+                    eager_rows.append(erow)
+                    print(json.dumps(erow), flush=True)
+    best, all_won = 0, True
+    for T in token_counts:  # the largest pair count UP TO which the new route wins in all three mixes
+        if not all(r["hip_wins"] for r in table if r["tokens"] == T):
+            all_won = False
+            break
+        best = T * K
+    result = {"block": {"hidden": H, "intermediate": I, "experts": E, "top_k": K, "scheme": "1x16g8", "dtype": "float16",
+                        "rank": RANK, "adapters": ADAPTERS, "projections": ["w1", "w3", "w2"]},
+              "device": torch.cuda.get_device_name(dev), "iters": args.iters, "repeats": args.repeats, "warmup": args.warmup,
+              "prepack_experts": report,
+              "what": "one block forward captured in a hipGraph and replayed, the copy of the next of three input sets included; "
+                      "median over the repeats of the median replay (device events), spread = max - min over the repeats; "
+                      "eager_rows (data only): eager calls, host clock around a call that ends in a device synchronise, the "
+                      "per-expert loop + on_rows against the grouped base launches + aqlm_hip_lora_sgmv_routed",
+              "rows": table, "eager_rows": eager_rows, "hip_won_at_every_count": all_won, "largest_count_won_up_to": best,
+              "routed_sgmv_max_pairs": limit if all_won else best,
+              "rule": "hip_wins: every repeat of hip_graph_us below the smallest torch_graph_us minus its spread over the repeats; "
+                      "routed_sgmv_max_pairs: the largest pair count up to which all three adapter mixes win at that count and "
+                      "every smaller one; the launch's own limit when it won at every measured count; 0 when it never won",
+              "command": f"python tools/lora_moe_benchmark.py --prefill --tokens {args.tokens} --iters {args.iters} "
+                         f"--repeats {args.repeats}"}
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps({k: v for k, v in result.items() if k not in ("rows", "eager_rows")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tokens", default="1,2,4,8,16,32,64,128")
-    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--prefill", action="store_true",
+                    help=f"measure the prefill route (aqlm_hip_lora_sgmv_routed) at {PREFILL_TOKENS} tokens against the torch path; "
+                         "writes profiles/lora_moe_prefill.json")
+    ap.add_argument("--tokens", default=None, help="default 1,2,4,8,16,32,64,128; with --prefill " + PREFILL_TOKENS)
+    ap.add_argument("--iters", type=int, default=None, help="default 30; with --prefill 20")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join("profiles", "lora_moe.json"))
+    ap.add_argument("--out", default=None, help="default profiles/lora_moe.json; with --prefill profiles/lora_moe_prefill.json")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/lora_moe_benchmark.py measures on the GPU; none found")
+    if args.prefill:
+        args.tokens = args.tokens or PREFILL_TOKENS
+        args.iters = args.iters or 20
+        args.out = args.out or os.path.join("profiles", "lora_moe_prefill.json")
+        return prefill(args)
+    args.tokens = args.tokens or "1,2,4,8,16,32,64,128"
+    args.iters = args.iters or 30
+    args.out = args.out or os.path.join("profiles", "lora_moe.json")
 
     import aqlm_amd.lora as lora
     import aqlm_amd.moe as moe
