@@ -169,6 +169,12 @@ SIGNATURES = {
     "aqlm_hip_lora_sgmv_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci]),
     "aqlm_hip_lora_sgmv_routed": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _cl, _ci, _vp, _ci, _ci, _ci, _vp,
                                   _sz, _vp]),
+    "aqlm_hip_lora_transpose_routed_bytes": (_sz, [_ci, _ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_transpose_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_transpose_routed": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_lora_grad_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_lora_grad_routed": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _cl, _cl, _ci, _ci, _vp, _cl,
+                                  _cl, _ci, _cl, _vp, _sz, _ci, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

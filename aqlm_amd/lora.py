@@ -23,7 +23,10 @@ the output of the gate / up launch and of the down launch -- two launches each, 
 capturable --; calls of ``ROUTED_SGMV_MIN_PAIRS`` .. ``ROUTED_SGMV_MAX_PAIRS`` pairs (prefill) have ``aqlm_hip_lora_sgmv_routed``
 (aqlm_amd/csrc/lora_sgmv_routed.hip), the segmented adapter GEMM on row tiles gathered through an expert bucket of 16-pair tiles that
 the provider builds once per forward (one small launch, no sync, capturable), for the pair counts at which it was measured to
-win; every other call (a gradient needed, host tensors, ``torch.compile``, shapes the kernels decline) runs PEFT's formula per (adapter,
+win; a call that needs a GRADIENT (``ROUTED_TRAIN_MIN_PAIRS`` .. ``ROUTED_TRAIN_MAX_PAIRS`` pairs) runs that same launch inside an autograd
+function whose backward is device launches only -- the launch again on a transposed table for grad_x, ``aqlm_hip_lora_grad_routed``
+(aqlm_amd/csrc/lora_routed_bwd.hip) for grad_A and grad_B; no host sync, no atomics, capturable, bit-reproducible --; every other call
+(host tensors, ``torch.compile``, shapes the kernels decline) runs PEFT's formula per (adapter,
 expert) as masked torch ops in fp32 without a host sync, differentiable in x, A and B, so expert adapters serve prefill and train.  Their
 ``state_dict()`` keys are ``<block>.base_layer.<e>.<w>.codes``, ``<block>.lora_A.<name>.<e>.<w>.weight`` and
 ``<block>.lora_B.<name>.<e>.<w>.weight`` (PEFT has no per-expert module convention for fused experts to follow); adapter FILES name
@@ -89,6 +92,21 @@ AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS = 65536  # include/aqlm_hip.h: pairs one aql
 ROUTED_SGMV_MIN_PAIRS = 257
 ROUTED_SGMV_MAX_PAIRS = AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS
 
+# Calls on the routed experts that NEED A GRADIENT (of x, of the launch's output or of an adapter weight) and have
+# ROUTED_TRAIN_MIN_PAIRS .. ROUTED_TRAIN_MAX_PAIRS pairs run aqlm_hip_lora_sgmv_routed inside an autograd function whose backward is
+# device launches only (the same launch on a transposed table for grad_x, aqlm_hip_lora_grad_routed for grad_A / grad_B; DESIGN.md
+# 4.8k); beyond it, the torch path.  The launch serves every pair count, so one kernel family trains at every size: the BGMV route
+# stays out of training.  ROUTED_TRAIN_MAX_PAIRS is a measured route constant (profiles/lora_moe_train.json, written by `python
+# tools/lora_moe_benchmark.py --train`): the largest of the pair counts 16 / 512 / 2048 / 8192 up to which forward + backward on
+# this route beat the torch path of the same commit at that count and every smaller one in all three adapter mixes (one adapter;
+# four contiguous sequences; four adapters interleaved per token), on a Mixtral-8x7B-shaped prepacked block with rank-16 adapters
+# on w1 / w2 / w3 of all experts, one of them trained; the launch's own limit when it won at every measured count.  Measured: it
+# won at every count in all three mixes and on the skewed routing, eager and captured (four sequences over 1024 tokens: 9442
+# against 32444 us captured, bare block's step 8292; one adapter over 4096 tokens: 31007 against 51332 us, bare block 26914; 8
+# tokens, four adapters: 2551 against 10213 us), so the constant is the launch's own limit.  0 switches the route off.
+ROUTED_TRAIN_MIN_PAIRS = 1
+ROUTED_TRAIN_MAX_PAIRS = AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS
+
 _PREFIX = "base_model.model."
 _DTYPES_OK = (torch.float16, torch.bfloat16)
 
@@ -121,6 +139,15 @@ def takes_routed_sgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, co
     (token, expert) pairs (never more than one launch takes)."""
     return bool(is_cuda and dtype_ok and not grad_needed and not compiling
                 and ROUTED_SGMV_MIN_PAIRS <= pairs <= min(ROUTED_SGMV_MAX_PAIRS, AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS) and supported)
+
+
+def takes_routed_train_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling: bool, pairs: int, supported: bool) -> bool:
+    """Whether a call on the routed experts that needs a gradient runs the device route (aqlm_hip_lora_sgmv_routed under autograd,
+    backward on launches only; else the torch path): tensors on the device, one fp16 / bf16 dtype throughout, a gradient needed,
+    not being traced by torch.compile, ROUTED_TRAIN_MIN_PAIRS..ROUTED_TRAIN_MAX_PAIRS (token, expert) pairs (never more than one
+    launch takes), and shapes the launches accept."""
+    return bool(is_cuda and dtype_ok and grad_needed and not compiling
+                and ROUTED_TRAIN_MIN_PAIRS <= pairs <= min(ROUTED_TRAIN_MAX_PAIRS, AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS) and supported)
 
 
 class AdapterBank:
@@ -400,9 +427,12 @@ class LoraQuantizedMixtralExperts(nn.Module):
         return [wt for n in names for e in range(self.num_experts) for w in ("w1", "w3", "w2")
                 for wt in (self._weights(n, e, w),) if wt is not None]
 
-    def _device_tables(self, device: torch.device):
+    def _device_tables(self, device: torch.device, transposed=None):
         """The device tables of the two launches over ALL adapters of the bank ([bank][E][S]; what this block lacks is a zero
-        entry), keyed on data_ptr and version of every A and B and rebuilt on an eager call when one of them moved or was written."""
+        entry), keyed on data_ptr and version of every A and B and rebuilt on an eager call when one of them moved or was written.
+        ``transposed``: the projection group whose TRANSPOSED side the caller needs as well (the training route): the buffer of
+        the B^T / A^T copies and the table [S][bank][E] over it, built here under the same key the first time it is asked for
+        (its copies are written by a launch at the start of every backward, not here)."""
         names = list(self.bank.names)
         key = (device, tuple(names), tuple((a.data_ptr(), tensor_version(a), b.data_ptr(), tensor_version(b), s)
                                            for a, b, s in self._all_weights(names)))
@@ -418,8 +448,20 @@ class LoraQuantizedMixtralExperts(nn.Module):
                 ranks = [[wt[0].shape[0] for per in pa for wt in per if wt is not None] for pa in entries]
                 tables[segments] = (hip_kernel.lora_routed_table(entries, device), [max(r, default=0) for r in ranks],
                                     all(v % 8 == 0 for r in ranks for v in r))
-            self._tables = (key, tables)
+            self._tables = (key, tables, {})
+        if transposed is not None and transposed not in self._tables[2]:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LoraQuantizedMixtralExperts: the transposed adapter table is built by a host-to-device copy; run "
+                                   "one eager training step before capturing (and again after moving or rewriting an adapter)")
+            from .inference_kernels import hip_kernel
+
+            entries = [[[self._weights(n, e, w) for w in transposed] for e in range(self.num_experts)] for n in names]
+            self._tables[2][transposed] = hip_kernel.lora_routed_transposed_table(entries, device)[:2]
         return self._tables[1]
+
+    def _transposed_tables(self, segments):
+        """(buffer, transposed device table) of projection group ``segments``, as ``_device_tables(..., transposed=segments)`` built it."""
+        return self._tables[2][segments]
 
     def _token_ids(self, sel: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         """The selection as one id per row of the [T, H] input; per-sequence ids are broadcast over T / n consecutive rows."""
@@ -439,6 +481,14 @@ class LoraQuantizedMixtralExperts(nn.Module):
         if sel is None or len(self.lora_A) == 0 or (isinstance(sel, str) and sel not in self.lora_A):
             return self.base_layer(hidden_states, top_k_index, top_k_weights)  # bits and launches of the bare block
         ids = None if isinstance(sel, str) else self._token_ids(sel, hidden_states)
+        if torch.is_grad_enabled() and not hidden_states.requires_grad:
+            # The base block chooses raw ops (no autograd) by ``hidden_states.requires_grad`` alone: with a frozen input -- the
+            # first block over a frozen embedding -- its w2 launch would cut the adapters of w1 / w3 off the graph.  So an input that
+            # requires grad whenever a selected adapter trains; nothing flows back into the caller's tensor.
+            names = [sel] if isinstance(sel, str) else [n for n in self.bank.names if n in self.lora_A]
+            trained = next((t for a, b, _ in self._all_weights(names) for t in (a, b) if t.requires_grad), None)
+            if trained is not None:
+                hidden_states = _AsTrainedInput.apply(hidden_states, trained)
         return self.base_layer(hidden_states, top_k_index, top_k_weights, adapters=_ExpertAdapters(self, sel, ids))
 
     def extra_repr(self) -> str:
@@ -457,7 +507,8 @@ class _ExpertAdapters:
 
     def on_pairs(self, out: torch.Tensor, x: torch.Tensor, top_k_index: torch.Tensor, segments, x_per_pair: bool) -> torch.Tensor:
         """``out`` [P, S, M], the output of a pair-batched launch on projections ``segments``; ``x`` [T, K] token rows or [P, K] pair
-        rows.  -> ``out`` with every pair's adapter term added: the very tensor (HIP route, in place) or a new one (torch path)."""
+        rows.  -> ``out`` with every pair's adapter term added: the very tensor (HIP routes, in place; with a gradient needed, as
+        the output of ``_RoutedAdapterFunction``) or a new one (torch path)."""
         layer = self.layer
         segments = tuple(segments)
         P, S, M = out.shape
@@ -497,6 +548,34 @@ class _ExpertAdapters:
                     self._bucket = torch.ops.aqlm.moe_bucket(top_k_index, layer.num_experts, hip_kernel.SGMV_ROUTED_TILE_PAIRS)
                 hip_kernel.lora_sgmv_routed_(out, x, self.ids, top_k_index, self._bucket, table, geometry, x_per_pair)
                 return out
+        train = (x.is_cuda and dtype_ok and grad_needed and not compiling and top_k_index.dim() == 2 and out.is_contiguous()
+                 and ROUTED_TRAIN_MIN_PAIRS <= P <= min(ROUTED_TRAIN_MAX_PAIRS, AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS))
+        if train:
+            from .inference_kernels import hip_kernel
+
+            E, Kin = layer.num_experts, x.shape[1]
+            if self._tables is None:
+                self._tables = layer._device_tables(x.device)
+            table, max_ranks, ranks_ok = self._tables[segments]
+            a0 = None if self.ids is not None else layer.bank.index(self.names[0])
+            n, max_rank = (len(max_ranks), max(max_ranks)) if a0 is None else (1, max_ranks[a0])
+            supported = (ranks_ok and out.data_ptr() % 8 == 0 and M % 8 == 0
+                         and hip_kernel.lora_sgmv_routed_supported(M, Kin, max_rank, P, E, S)
+                         and hip_kernel.lora_sgmv_routed_supported(Kin, M, max_rank, P, E, 1)
+                         and hip_kernel.lora_transpose_routed_supported(M, Kin, max(max_ranks), E, S)
+                         and hip_kernel.lora_grad_routed_supported(M, max_rank, P, E, S)
+                         and hip_kernel.lora_grad_routed_supported(Kin, max_rank, P, E, S))
+            if takes_routed_train_route(x.is_cuda, dtype_ok, grad_needed, compiling, P, supported):
+                if segments not in layer._tables[2]:
+                    layer._device_tables(x.device, transposed=segments)
+                if self._bucket is None:
+                    self._bucket = torch.ops.aqlm.moe_bucket(top_k_index, E, hip_kernel.SGMV_ROUTED_TILE_PAIRS)
+                # the weights autograd has to see: A and B of every live entry of the adapters in play, in table order
+                who = [(layer.bank.index(name), e, s, t) for name in self.names for e in range(E) for s, w in enumerate(segments)
+                       for wt in (layer._weights(name, e, w),) if wt is not None for t in (0, 1)]
+                flat = [layer._weights(layer.bank.names[a], e, segments[s])[t] for a, e, s, t in who]
+                call = _RoutedCall(layer, segments, self.ids, top_k_index, self._bucket, table, a0, n, max_rank, x_per_pair, who)
+                return _RoutedAdapterFunction.apply(out, x, call, *flat)
         return self._torch_pairs(out, x, top_k_index, segments, x_per_pair)
 
     def _torch_pairs(self, out, x, top_k_index, segments, x_per_pair):
@@ -559,6 +638,117 @@ class _ExpertAdapters:
                 delta = torch.where((ids == layer.bank.index(name))[:, None], delta, torch.zeros((), dtype=delta.dtype, device=delta.device))
             total = delta if total is None else total + delta
         return out if total is None else (out.float() + total).to(out.dtype)
+
+
+class _AsTrainedInput(torch.autograd.Function):
+    """``x`` as a tensor that requires grad because ``trained`` does (``LoraQuantizedMixtralExperts.forward``); no gradient flows
+    back into either."""
+
+    @staticmethod
+    def forward(ctx, x, trained):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return None, None
+
+
+class _RoutedCall:
+    """What one training call of ``on_pairs`` hands to its autograd function besides the tensors autograd differentiates."""
+
+    def __init__(self, layer, segments, ids, top_k_index, bucket, table, adapter0, n, max_rank, x_per_pair, who):
+        self.layer, self.segments, self.ids, self.top_k_index, self.bucket, self.table = layer, segments, ids, top_k_index, bucket, table
+        self.adapter0, self.n, self.max_rank, self.x_per_pair, self.who = adapter0, n, max_rank, x_per_pair, who
+
+
+class _RoutedAdapterFunction(torch.autograd.Function):
+    """``out += adapters(x)`` on the routed experts with a backward on device launches only.  Forward:
+    ``aqlm_hip_lora_sgmv_routed`` in place -- the bits of the serving route -- into a workspace this call owns (the cached one
+    would be overwritten by the next layer): it keeps t = A x of every pair.  Backward, with gy the gradient of ``out``:
+    the transposed copies of the weights as they are now (one launch), per projection the same launch on the transposed table
+    with x := gy[:, s] (its workspace then holds u = B^T gy, its output scaling * A^T u = grad_x per pair), and per trained
+    adapter one ``aqlm_hip_lora_grad_routed`` for grad_A (V = x, w = u) and one for grad_B^T (V = gy, w = t).  No host
+    synchronisation, no atomics, capturable, bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, out, x, call, *weights):
+        from .inference_kernels import hip_kernel
+
+        P, S, M = out.shape
+        K = x.shape[1]
+        E = call.layer.num_experts
+        k = call.top_k_index.shape[1]
+        geometry = [call.n, E, S, call.max_rank, M, K, k]
+        table = call.table
+        if call.adapter0 is not None:
+            words = table.shape[0] // len(call.layer.bank.names)
+            table = table[call.adapter0 * words:(call.adapter0 + 1) * words]
+        t = torch.empty((hip_kernel.lora_sgmv_routed_workspace_floats(P, S, call.max_rank, K),), dtype=torch.float32, device=x.device)
+        hip_kernel.lora_sgmv_routed_(out, x, call.ids, call.top_k_index, call.bucket, table, geometry, call.x_per_pair, workspace=t)
+        ctx.mark_dirty(out)
+        ctx.call, ctx.geometry = call, geometry
+        ctx.save_for_backward(x, t, table, call.bucket, call.top_k_index, *(() if call.ids is None else (call.ids,)))
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        from .inference_kernels import hip_kernel
+
+        call = ctx.call
+        x, t, table, bucket, top_k_index = ctx.saved_tensors[:5]
+        ids = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        n, E, S, max_rank, M, K, k = ctx.geometry
+        P = gy.shape[0]
+        gy = gy.contiguous()
+        x = hip_kernel._flat_rows(x)  # rows the launches can address, as the forward's launch saw them
+        layer, segments = call.layer, call.segments
+        need_x = ctx.needs_input_grad[1]
+        need_w = [ctx.needs_input_grad[3 + i] for i in range(len(call.who))]
+        need_a = any(nd for nd, (_, _, _, which) in zip(need_w, call.who) if which == 0)
+        grads = [None] * len(call.who)
+        gx = None
+        if need_x or need_a:
+            # u = B^T gy and grad_x per pair: the forward's launch on the transposed table, a segment at a time
+            full = layer._device_tables(x.device, transposed=segments)[segments][0]
+            buffer, ttable = layer._transposed_tables(segments)
+            names = len(layer.bank.names)
+            hip_kernel.lora_transpose_routed_(buffer, full, ttable, [names, E, S, max(layer._tables[1][segments][1]), M, K])
+            splits_m = hip_kernel.lora_sgmv_splits(M)
+            u = torch.empty((S, P, splits_m, max_rank), dtype=torch.float32, device=x.device)
+            words = ttable.shape[0] // (S * names)  # one adapter of one segment: [E] entries
+            total = None
+            for s in range(S):
+                a_first = 0 if call.adapter0 is None else call.adapter0
+                tt = ttable[(s * names + a_first) * words:(s * names + a_first + n) * words]
+                gxs = torch.zeros((P, 1, K), dtype=gy.dtype, device=x.device)
+                hip_kernel.lora_sgmv_routed_(gxs, gy[:, s, :], ids, top_k_index, bucket, tt, [n, E, 1, max_rank, K, M, k], True,
+                                             workspace=u[s].view(-1))
+                if need_x:
+                    total = gxs.view(P, K).float() if total is None else total + gxs.view(P, K).float()
+            if need_x:
+                if not call.x_per_pair:
+                    total = total.view(P // k, k, K).sum(dim=1)  # the token's pairs in ascending order
+                gx = total.to(x.dtype)
+        for a in sorted({a for nd, (a, _, _, _) in zip(need_w, call.who) if nd}):
+            a_local = a if call.adapter0 is None else 0
+            mine = [(i, e, s, which) for i, (a_, e, s, which) in enumerate(call.who) if a_ == a and need_w[i]]
+            # (every entry read below is live -- the route needs every rank a multiple of 8 -- and the kernel writes all of a live
+            # entry, so the outputs need no memset)
+            if any(which == 0 for _, _, _, which in mine):
+                ga = hip_kernel.lora_grad_routed(x, u, ids, top_k_index, bucket, table, [n, E, S, max_rank, K, k, a_local],
+                                                 [x.stride(0) if x.shape[0] > 1 else K, 0, int(call.x_per_pair),
+                                                  u.stride(1), u.stride(0), u.shape[2], max_rank],
+                                                 out=torch.empty((E, S, max_rank, K), dtype=torch.float32, device=x.device))
+            if any(which == 1 for _, _, _, which in mine):
+                splits_k = t.numel() // (P * S * max_rank)
+                gb = hip_kernel.lora_grad_routed(gy, t, ids, top_k_index, bucket, table, [n, E, S, max_rank, M, k, a_local],
+                                                 [S * M, M, 1, S * splits_k * max_rank, splits_k * max_rank, splits_k, max_rank],
+                                                 out=torch.empty((E, S, max_rank, M), dtype=torch.float32, device=x.device))
+            for i, e, s, which in mine:
+                w = layer._weights(layer.bank.names[a], e, segments[s])[which]
+                r = w.shape[1] if which else w.shape[0]
+                grads[i] = ga[e, s, :r].to(w.dtype) if which == 0 else gb[e, s, :r].t().to(w.dtype)
+        return (gy, gx, None, *grads)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -651,6 +651,61 @@ int aqlm_hip_lora_sgmv_routed(const aqlm_hip_lora_entry* table, int num_adapters
                               int out_features, int in_features, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The BACKWARD of the adapters on the routed experts (training; no reference counterpart).  With grad_y the gradient arriving
+ * for y [num_pairs][num_segments][out_features], t = A x_row(p) the forward's workspace and u[p, s] = B^T grad_y[p, s] (fp32):
+ *     grad_x_row(p) += scaling * A^T u[p, s]
+ *     grad_A[a, e, s] = scaling * sum over the pairs p of (a, e) of  u[p, s] (x) x_row(p)          [rank][in_features]
+ *     grad_B[a, e, s] = scaling * sum over the pairs p of (a, e) of  grad_y[p, s] (x) t[p, s]      [out_features][rank]
+ *
+ * grad_x is aqlm_hip_lora_sgmv_routed itself on a TRANSPOSED table: num_segments one-segment tables laid out
+ * [num_segments][num_adapters][num_experts], the entry of (s, a, e) = {a: B^T [rank][out_features], b: A^T [in_features][rank],
+ * rank, scaling} (a zero entry where the forward entry is none or has a rank that is no multiple of 8), called per segment with
+ * x := grad_y[:, s, :] (pair rows, row stride num_segments * out_features), a zeroed y [num_pairs][1][in_features], in_features
+ * := out_features and out_features := in_features (so both must be multiples of 8); its workspace then holds u[:, s] in
+ * sgmv slices of out_features.  aqlm_hip_lora_transpose_routed fills the storage-type `buffer` that the transposed entries point
+ * into: ONE launch over all entries of the forward `table`, which copies A and B of every entry whose rank is a multiple of 8 in
+ * 8..max_rank and equals the rank of its transposed entry, and whose two copies lie inside [buffer, buffer + buffer_bytes) --
+ * checked on the device before an address is formed; every other entry leaves the buffer as it is.  Stream-ordered, no
+ * allocation, no synchronisation.  aqlm_hip_lora_transpose_routed_bytes: the buffer size when every entry has max_rank,
+ * num_adapters * num_experts * num_segments * max_rank * (out_features + in_features) * 2; 0 when unsupported.
+ * Checks, in order: null table / transposed / buffer, then table or transposed not 8-byte or buffer not 16-byte aligned, then a
+ * size below 1 (AQLM_HIP_E_INVALID); then AQLM_HIP_E_UNSUPPORTED for max_rank no multiple of 8 in 8..128, in_features or
+ * out_features no multiple of 8, num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS, num_segments > 2 or more than 65535 entries.
+ *
+ * aqlm_hip_lora_grad_routed is the reduction over pairs that both weight gradients are: for ONE adapter index `adapter` (adapter_ids
+ * NULL: every pair has adapter 0) and every expert e and segment s, with scaling that of the entry [(adapter * E + e) * S + s],
+ *     g[e][s][r][i] = scaling * sum over the pairs p of expert e whose adapter id is `adapter`, in bucket order (ascending p), of
+ *                     w[p, s][r] * V[p, s][i]                                  r < max_rank, i < dim      (fp32, fused multiply-add)
+ * V[p, s] = v + (v_per_pair ? p : p / top_k) * v_row_stride + s * v_seg_stride: storage-type rows of `dim` elements (elements;
+ * 16-byte aligned rows).  w[p, s][r] = sum over k < w_splits, in ascending k, of
+ * w[p * w_pair_stride + s * w_seg_stride + k * w_split_stride + r]: fp32, the workspace of a shrink launch.  grad_A: V = x,
+ * v_seg_stride 0, w = u; grad_B^T: V = grad_y, w = the forward's workspace.  An entry that is live (rank a multiple of 8 in
+ * 8..max_rank) has ALL its max_rank x dim elements written -- zeros when no pair has it, and for r >= rank --, so nothing needs
+ * a memset; an entry that is not live is not touched.  `bucket`, the ids and their checks are aqlm_hip_lora_sgmv_routed's: tile
+ * records, list entries and both ids are range-checked before they form an address, and a pair with an id out of range, or listed
+ * under another expert than its own, contributes nothing.  No atomics, no inter-workgroup communication: the result is a function
+ * of the inputs alone, bit for bit.  Stream-ordered, no allocation, no synchronisation (hipGraph-capturable).
+ * Checks, in order: a null pointer (adapter_ids may be NULL), misalignment (table 8, ids their size, bucket and g 16, w 4 bytes),
+ * a size below 1 / num_pairs no multiple of top_k / adapter outside [0, num_adapters), strides shorter than the rows or negative
+ * (AQLM_HIP_E_INVALID); the dtype, then max_rank no multiple of 8 in 8..128, dim no multiple of 8, num_pairs >
+ * AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS, num_experts > AQLM_HIP_MAX_ROUTED_EXPERTS, num_segments > 2, w_splits > 8, v not 16-byte
+ * aligned or a V stride no multiple of 8 (AQLM_HIP_E_UNSUPPORTED); last g_bytes < num_experts * num_segments * max_rank * dim * 4
+ * (AQLM_HIP_E_INVALID).  aqlm_hip_lora_grad_routed_supported answers for the five sizes beforehand.
+ */
+size_t aqlm_hip_lora_transpose_routed_bytes(int num_adapters, int num_experts, int num_segments, int max_rank, int out_features,
+                                            int in_features); /* 0 when unsupported */
+int aqlm_hip_lora_transpose_routed_supported(int out_features, int in_features, int max_rank, int num_experts, int num_segments);
+int aqlm_hip_lora_transpose_routed(const aqlm_hip_lora_entry* table, const aqlm_hip_lora_entry* transposed, int num_adapters,
+                                   int num_experts, int num_segments, int max_rank, int out_features, int in_features, void* buffer,
+                                   size_t buffer_bytes, void* stream);
+int aqlm_hip_lora_grad_routed_supported(int dim, int max_rank, int num_pairs, int num_experts, int num_segments);
+int aqlm_hip_lora_grad_routed(const aqlm_hip_lora_entry* table, int num_adapters, int num_experts, int num_segments, int max_rank,
+                              int adapter, const void* adapter_ids, int adapter_ids_int64, const void* expert_ids,
+                              int expert_ids_int64, const void* bucket, int num_pairs, int top_k, const void* v, long v_row_stride,
+                              long v_seg_stride, int v_per_pair, int dim, const float* w, long w_pair_stride, long w_seg_stride,
+                              int w_splits, long w_split_stride, float* g, size_t g_bytes, int dtype, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the

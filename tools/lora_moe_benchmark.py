@@ -29,6 +29,20 @@ grouped base launches with the new route (``moe.GROUPED_EAGER_MAX_PAIRS`` raised
 profiles/lora_moe_prefill.json).
 
     python tools/lora_moe_benchmark.py --prefill [--tokens 256,512,1024,2048,4096] [--iters 20] [--repeats 3]
+
+``--train`` measures a TRAINING step -- forward + backward, hidden_states requiring grad, adapter ``ad0`` trainable, the other
+three frozen, a fixed grad-output -- on the same block at T = 8 / 256 / 1024 / 4096 tokens (16 .. 8192 pairs) in the three mixes of
+``--prefill``, plus one skewed routing at 2048 pairs (three tokens in four on experts 0 and 1): (a) the bare block's step
+(``bank.select(None)``), (b) the torch path of the same commit (``ROUTED_TRAIN_MAX_PAIRS = 0``), (c) the device route
+(aqlm_hip_lora_sgmv_routed under autograd, its backward on the transposed table plus aqlm_hip_lora_grad_routed).  Each both eager
+(host clock around a step that ends in a device synchronise) and captured in a hipGraph and replayed (device events); median
+over --repeats rounds of the median of --iters steps, spread = max - min over the rounds; the peak-memory delta of one eager step
+(``torch.cuda.max_memory_allocated`` over the memory allocated before it).  ``routed_train_max_pairs`` in the output is the
+largest pair count up to which (c) beat (b), eager AND captured, at that count and every smaller one in every mix, the launch's
+own limit when it won at every measured count, and is what ``aqlm_amd.lora.ROUTED_TRAIN_MAX_PAIRS`` is set to.  Writes --out
+(default profiles/lora_moe_train.json).
+
+    python tools/lora_moe_benchmark.py --train [--tokens 8,256,1024,4096] [--iters 20] [--repeats 3]
 """
 import argparse
 import json
@@ -204,8 +218,128 @@ def prefill(args):
     print(json.dumps({k: v for k, v in result.items() if k not in ("rows", "eager_rows")}))
 
 
+TRAIN_TOKENS = "8,256,1024,4096"
+SKEWED_TOKENS = 1024
+
+
+def train(args):
+    """--train: forward + backward of base / torch path / device route, eager and captured; writes profiles/lora_moe_train.json."""
+    import aqlm_amd.lora as lora
+    import aqlm_amd.moe as moe
+    from aqlm_amd import _native
+
+    dev = torch.device("cuda:0")
+    q, _ = build(dev, False)
+    report = moe.prepack_experts(q)
+    holder = Holder(q)
+    bank = lora.attach_adapters(holder, {f"ad{i}": adapter(100 + i) for i in range(ADAPTERS)})
+    block = holder.experts
+    trained = [p for store in (block.lora_A, block.lora_B) for p in store["ad0"].parameters()]
+    for p in trained:
+        p.requires_grad_(True)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    limit = _native.MAX_LORA_SGMV_ROUTED_PAIRS
+    routes = (("base", None, 0), ("torch", "selection", 0), ("hip", "selection", limit))
+    token_counts = [int(t) for t in args.tokens.split(",")]
+    cases = [(T, False) for T in token_counts] + ([(SKEWED_TOKENS, True)] if SKEWED_TOKENS in token_counts else [])
+    table = []
+    for T, skewed in cases:
+        if T % ADAPTERS:
+            raise SystemExit(f"--train: {T} tokens do not split into {ADAPTERS} sequences")
+        x = torch.randn((T, H), generator=gen, device=dev).half().requires_grad_()
+        logits = torch.randn((T, E), generator=gen, device=dev)
+        if skewed:
+            logits[torch.arange(T, device=dev) % 4 != 3, :2] += 20.0
+        w, idx = torch.topk(torch.softmax(logits, -1), K, dim=-1)
+        w = w / w.sum(-1, keepdim=True)
+        r = torch.randn((T, H), generator=gen, device=dev)
+        seq_ids = torch.arange(ADAPTERS, device=dev, dtype=torch.int64)
+        tok_ids = (torch.arange(T, device=dev) % ADAPTERS).to(torch.int64)
+        mixes = (("one adapter", "ad0"), (f"{ADAPTERS} adapters, contiguous sequences", seq_ids),
+                 (f"{ADAPTERS} adapters interleaved per token", tok_ids))
+        for mix, selection in (mixes[2:] if skewed else mixes):
+
+            def step():
+                x.grad = None
+                for p in trained:
+                    p.grad = None
+                (block(x, idx, w).float() * r).sum().backward()
+
+            def eager(which, max_pairs):
+                bank.select(selection if which else None)
+                lora.ROUTED_TRAIN_MAX_PAIRS = max_pairs
+                step()
+
+            graphs, grads, peaks = [], [], []
+            for name, which, max_pairs in routes:
+                bank.select(selection if which else None)
+                lora.ROUTED_TRAIN_MAX_PAIRS = max_pairs  # the route is decided when the step is captured
+                step()
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                step()
+                torch.cuda.synchronize()
+                peaks.append(round((torch.cuda.max_memory_allocated() - before) / 2 ** 20, 1))
+                g, _ = captured(step)
+                graphs.append(g)
+                g.replay()
+                torch.cuda.synchronize()
+                grads.append([x.grad.float().clone()] + [p.grad.float().clone() for p in trained if p.grad is not None])
+            fns_graph = [g.replay for g in graphs]
+            fns_eager = [lambda which=which, max_pairs=max_pairs: eager(which, max_pairs) for _, which, max_pairs in routes]
+            runs_g = [timed_alternating(fns_graph, args.iters, args.warmup) for _ in range(args.repeats)]
+            runs_e = [timed_eager(fns_eager, args.iters, 2) for _ in range(args.repeats)]
+            row = {"tokens": T, "pairs": T * K, "adapters": mix, "routing": "skewed" if skewed else "router-like",
+                   "pairs_per_expert": torch.bincount(idx.reshape(-1), minlength=E).tolist()}
+            for kind, runs in (("graph", runs_g), ("eager", runs_e)):
+                for i, (name, _, _) in enumerate(routes):
+                    vals = sorted(rr[i] for rr in runs)
+                    row[f"{name}_{kind}_us"] = vals[len(vals) // 2]
+                    row[f"{name}_{kind}_runs_us"] = [rr[i] for rr in runs]
+                    row[f"{name}_{kind}_spread_us"] = round(vals[-1] - vals[0], 2)
+                row[f"hip_wins_{kind}"] = bool(max(rr[2] for rr in runs) < min(rr[1] for rr in runs) - row[f"torch_{kind}_spread_us"])
+            row["hip_wins"] = row["hip_wins_graph"] and row["hip_wins_eager"]
+            for (name, _, _), peak in zip(routes, peaks):
+                row[f"{name}_peak_delta_mb"] = peak
+            rel = lambda a, b: float(((a - b).abs().mean() / b.abs().mean()).item())  # noqa: E731
+            row["rel_diff_x_grad_hip_vs_torch"] = rel(grads[2][0], grads[1][0])
+            row["rel_diff_weight_grads_hip_vs_torch"] = max(rel(a, b) for a, b in zip(grads[2][1:], grads[1][1:]) if float(b.abs().max()))
+            del graphs, grads
+            table.append(row)
+            print(json.dumps(row), flush=True)
+    best, all_won = 0, True
+    for T in token_counts:  # the largest pair count UP TO which the device route wins in every mix
+        if not all(row["hip_wins"] for row in table if row["tokens"] == T):
+            all_won = False
+            break
+        best = T * K
+    result = {"block": {"hidden": H, "intermediate": I, "experts": E, "top_k": K, "scheme": "1x16g8", "dtype": "float16",
+                        "rank": RANK, "adapters": ADAPTERS, "trained": ["ad0"], "projections": ["w1", "w3", "w2"]},
+              "device": torch.cuda.get_device_name(dev), "iters": args.iters, "repeats": args.repeats, "warmup": args.warmup,
+              "prepack_experts": report,
+              "what": "one training step of the block (forward + backward, hidden_states and adapter ad0 requiring grad): *_graph_us "
+                      "captured in a hipGraph and replayed (device events), *_eager_us eager (host clock, ends in a device "
+                      "synchronise); median over the repeats of the median step, spread = max - min over the repeats; "
+                      "*_peak_delta_mb: torch.cuda.max_memory_allocated of one eager step over the memory allocated before it",
+              "rows": table, "hip_won_at_every_count": all_won, "largest_count_won_up_to": best,
+              "routed_train_max_pairs": limit if all_won else best,
+              "rule": "hip_wins_{graph,eager}: every repeat of hip below the smallest torch minus its spread over the repeats; "
+                      "hip_wins: both; routed_train_max_pairs: the largest pair count up to which every mix wins at that count and "
+                      "every smaller one; the launch's own limit when it won at every measured count; 0 when it never won",
+              "command": f"python tools/lora_moe_benchmark.py --train --tokens {args.tokens} --iters {args.iters} "
+                         f"--repeats {args.repeats}"}
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true",
+                    help=f"measure a training step (forward + backward) at {TRAIN_TOKENS} tokens, the device route against the torch "
+                         "path; writes profiles/lora_moe_train.json")
     ap.add_argument("--prefill", action="store_true",
                     help=f"measure the prefill route (aqlm_hip_lora_sgmv_routed) at {PREFILL_TOKENS} tokens against the torch path; "
                          "writes profiles/lora_moe_prefill.json")
@@ -217,6 +351,11 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/lora_moe_benchmark.py measures on the GPU; none found")
+    if args.train:
+        args.tokens = args.tokens or TRAIN_TOKENS
+        args.iters = args.iters or 20
+        args.out = args.out or os.path.join("profiles", "lora_moe_train.json")
+        return train(args)
     if args.prefill:
         args.tokens = args.tokens or PREFILL_TOKENS
         args.iters = args.iters or 20
