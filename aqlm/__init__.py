@@ -52,3 +52,4 @@ checkpoint = importlib.import_module(__name__ + ".checkpoint")
 fusion = importlib.import_module(__name__ + ".fusion")
 moe = importlib.import_module(__name__ + ".moe")
 lora = importlib.import_module(__name__ + ".lora")
+tuning = importlib.import_module(__name__ + ".tuning")

@@ -9,6 +9,7 @@ from .inference import QuantizedLinear
 from .inference_kernels import get_backward_pass_kernel, get_forward_pass_kernel, optimize_for_training
 from .moe import QuantizedMixtralExperts, quantized_experts, replace_moe_experts
 from . import lora  # noqa: E402  (LoRA adapters on quantized layers: attach_adapters, AdapterBank)
+from . import tuning  # noqa: E402  (training codebooks / scales / biases: make_trainable, prepare)
 
 __version__ = "1.1.7"
 
@@ -26,4 +27,5 @@ __all__ = [
     "quantized_experts",
     "replace_moe_experts",
     "lora",
+    "tuning",
 ]

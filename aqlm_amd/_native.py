@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("AQLM_AMD_HIP_LIB") or os.path.join(_HERE, "libaqlm_hi
 ABI_VERSION = 9
 
 F16, BF16 = 0, 1
+F32 = 2   # dW and the outputs of the gradient entries only (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16)
 E_INVALID, E_UNSUPPORTED = -1, -2
 MAX_GEMV_BATCH = 8
 OP_GEMM_1X16_MFMA = 1
@@ -175,6 +176,13 @@ SIGNATURES = {
     "aqlm_hip_lora_grad_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
     "aqlm_hip_lora_grad_routed": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _cl, _cl, _ci, _ci, _vp, _cl,
                                   _cl, _ci, _cl, _vp, _sz, _ci, _vp]),
+    "aqlm_hip_codebook_grad_chunk": (_ci, []),
+    "aqlm_hip_codebook_grad_1x16_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_codebook_grad_1x16_max_chunks": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_codebook_grad_1x16_workspace_bytes": (_sz, [_ci, _ci, _ci]),
+    "aqlm_hip_codebook_grad_1x16": (_ci, [_vp, _cl, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_scales_grad_1x16_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_scales_grad_1x16": (_ci, [_vp, _cl, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

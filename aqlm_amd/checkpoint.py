@@ -100,11 +100,13 @@ def validate_quantized_state_dict(state_dict: Mapping[str, torch.Tensor], config
 
 def memory_report(model: torch.nn.Module) -> Dict[str, float]:
     """Bytes held by the QuantizedLinear modules of ``model``: checkpoint tensors and the derived prepacked buffers,
-    plus the resulting bits per weight of the code storage (canonical 1x16 g8 = 2.0) and of everything."""
+    plus the resulting bits per weight of the code storage (canonical 1x16 g8 = 2.0) and of everything.  ``codebook_grad_index``:
+    the inverted indices of trainable 1x16 layers (aqlm_amd/tuning.py) -- 4 bytes per code plus ~0.5 MB of tables per layer, next to
+    the 2 bytes per code of the codes themselves; training state, not counted in the bits per weight."""
     from .inference import QuantizedLinear
 
     rep = {"quantized_linears": 0, "codes": 0, "codebooks": 0, "scales_bias": 0, "prepacked_layers": 0, "prepacked": 0,
-           "codes_dropped_layers": 0, "weights": 0}
+           "codes_dropped_layers": 0, "weights": 0, "codebook_grad_index_layers": 0, "codebook_grad_index": 0}
     for m in model.modules():
         if isinstance(m, QuantizedLinear):
             rep["quantized_linears"] += 1
@@ -119,6 +121,10 @@ def memory_report(model: torch.nn.Module) -> Dict[str, float]:
                 rep["prepacked"] += m._packed_codes.numel()
             if m._codes_dropped:
                 rep["codes_dropped_layers"] += 1
+            if m._grad_index is not None:
+                # the inverted index of a trainable 1x16 layer (aqlm_amd/tuning.py): 4 bytes per code + tables, next to the codes' 2
+                rep["codebook_grad_index_layers"] += 1
+                rep["codebook_grad_index"] += m._grad_index[1].nbytes()
     if rep["weights"]:
         rep["code_bits_per_weight"] = 8.0 * (rep["codes"] + rep["prepacked"]) / rep["weights"]
         rep["total_bits_per_weight"] = 8.0 * (rep["codes"] + rep["prepacked"] + rep["codebooks"] + rep["scales_bias"]) / rep["weights"]

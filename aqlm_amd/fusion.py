@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from .derived import tensor_version
 from .inference import GEMV_MAX_ROWS, QuantizedLinear
+from .tuning import param_grad_needed
 
 DEFAULT_PATTERNS: Tuple[Tuple[str, ...], ...] = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))
 MAX_MEMBERS = 4  # AQLM_HIP_MAX_SEGMENTS
@@ -69,6 +70,8 @@ class SharedInputGroup:
             return False
         if torch.is_grad_enabled() and input.requires_grad:
             return False
+        if torch.is_grad_enabled() and any(param_grad_needed(m) for m in self.members):
+            return False  # a member's codebooks / scales / bias train: every member runs alone, under autograd (aqlm_amd/tuning.py)
         if torch.compiler.is_compiling():
             return False
         first = self.members[0]

@@ -133,14 +133,15 @@ class QuantizedLinear(nn.Module):
     # prepacked / planar codes of the GPU decode kernels (`_packed_codes`, keyed on `_packed_fingerprint`) with their codebook
     # range, the permuted codes of the host LUT kernel, the dense W (`_dense`: (fingerprint, W)), the compiled fast lane of the
     # decode call (`_fast`, aqlm_amd/_front.py: a pybind11 object that cannot be pickled) and the checksums of the parameters it
-    # was all built from (`_derived_checks`, see DERIVED_CHECK_EVERY).  `_prepack_deferred`: a transition inside a hipGraph
+    # was all built from (`_derived_checks`, see DERIVED_CHECK_EVERY), and the inverted index of the codes that the codebook
+    # gradient of a trainable 1x16 layer is summed through (`_grad_index`: (fingerprint of the codes, CodebookGradIndex)).  `_prepack_deferred`: a transition inside a hipGraph
     # capture or a trace left its last step (`_settle`, and the repack if that waited too) to the first eager forward.  None of it is saved, copied or pickled:
     # `copy.deepcopy(model)`, `torch.save(model)` and `pickle` work at any time (EMA copies, PEFT `modules_to_save`, draft-model
     # clones), and the copy rebuilds its derived state at its first forward.  A module whose canonical codes were dropped hands
     # them back to the copy.
     _DERIVED_DEFAULTS = {"gemv_op": None, "gemm_op": None, "use_gemv_rule": None, "_fast": None, "_packed_codes": None,
                          "_packed_fingerprint": None, "_cpu_codes_alt": None, "_prepack_deferred": False, "_dense": None,
-                         "_derived_checks": None, "_calls_since_check": 0}
+                         "_derived_checks": None, "_calls_since_check": 0, "_grad_index": None}
 
     def _reset_derived(self) -> None:
         """Forget everything derived from the parameters.  With the canonical codes dropped the packed buffer IS the weights: it
@@ -199,7 +200,8 @@ class QuantizedLinear(nn.Module):
         # staggered start: the modules of a model were all built at the same forward; without an offset every 256th decode step would
         # verify all of them at once (one multi-millisecond spike per 256 tokens instead of one module's ~40 us now and then)
         self._calls_since_check = (id(self) >> 4) % DERIVED_CHECK_EVERY if DERIVED_CHECK_EVERY else 0
-        if not DERIVED_CHECK_EVERY or (self._packed_codes is None and self._cpu_codes_alt is None and self._dense is None):
+        if not DERIVED_CHECK_EVERY or (self._packed_codes is None and self._cpu_codes_alt is None and self._dense is None
+                                       and self._grad_index is None):
             return
         checks = {}
         if not self._codes_dropped:
@@ -237,6 +239,10 @@ class QuantizedLinear(nn.Module):
                     self.prepare_matmul_op(input)
                 else:
                     self._settle()
+        if torch.is_grad_enabled() and (self.codebooks.requires_grad or self.scales.requires_grad
+                                        or (self.bias is not None and self.bias.requires_grad)):
+            # a parameter of this layer trains: none of the routes below (they read derived copies or skip autograd)
+            return self._forward_trainable(input)
         group = self._shared_input_group
         if group is not None and group.applicable(input):
             return group.forward(self, input)  # one launch for all projections of this input (fusion.py)
@@ -294,6 +300,62 @@ class QuantizedLinear(nn.Module):
                 kernel = op.forward_pass_kernel
                 return _MatmulFromPacked.apply(input, self, lambda x: kernel(x, self._canonical_codes(), self.codebooks, self.scales, self.bias))
         return op.apply(input, self._codes_for_ops(), self.codebooks, self.scales, self.bias)
+
+    def _takes_codebook_grad_kernel(self, input: Optional[torch.Tensor]) -> bool:
+        """`tuning.takes_codebook_grad_kernel` for this layer and this input (None: any input in the parameters' dtype)."""
+        from . import tuning
+
+        cb, dt = self.codebooks, self.codebooks.dtype
+        scheme = (self.num_codebooks == 1 and self.nbits_per_codebook == 16 and self.out_group_size == 1
+                  and self.in_group_size in (8, 16))
+        on_gpu = cb.is_cuda and self.scales.is_cuda and (input is None or input.is_cuda)
+        dtypes_ok = (dt in (torch.float16, torch.bfloat16) and self.scales.dtype == dt
+                     and (self.bias is None or self.bias.dtype == dt) and (input is None or input.dtype == dt))
+        supported = False
+        if scheme and on_gpu and tuning.CODEBOOK_GRAD_KERNEL:
+            from .inference_kernels import hip_kernel
+
+            supported = hip_kernel.codebook_grad_supported(self.out_features, self.in_features, self.in_group_size)
+        return tuning.takes_codebook_grad_kernel(self.num_codebooks, self.nbits_per_codebook, self.out_group_size, self.in_group_size,
+                                                 on_gpu, dtypes_ok, supported, torch.compiler.is_compiling())
+
+    def codebook_grad_index(self):
+        """The inverted index of this layer's codes (hip_kernel.CodebookGradIndex) that the codebook gradient is summed through:
+        derived state like the packed codes -- keyed on ``codes_fingerprint(self.codes)``, forgotten by ``_reset_derived()`` /
+        ``invalidate_derived_state()``, covered by the periodic checksum of the codes, never saved, copied or pickled.  It costs 4
+        bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves.  Built at the first training step, or
+        by ``aqlm.tuning.prepare(model)``; never inside a hipGraph capture (the build sorts and allocates): there it must exist.
+        A layer whose canonical codes were dropped (``prepack_model``) builds it from ``_canonical_codes()`` -- one transient
+        unpack, which does not undo the drop.  The training calls themselves read the canonical codes (forward kernel, scale
+        gradient): after a non-strict drop (``prepack_model``'s default) the first of them restores the codes for good, after a
+        strict one every call unpacks them for its forward and keeps that copy until its backward has run."""
+        fp = codes_fingerprint(self.codes)
+        cached = self._grad_index
+        if cached is not None and cached[0] == fp:
+            return cached[1]
+        if self.codebooks.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("QuantizedLinear: a trainable layer needs the inverted index of its codes, and it cannot be built "
+                               "inside a hipGraph capture; call aqlm.tuning.prepare(model) before capturing")
+        from .inference_kernels import hip_kernel
+
+        index = hip_kernel.build_codebook_grad_index(self._canonical_codes(), self.in_group_size)
+        self._grad_index = (fp, index)
+        if not torch.compiler.is_compiling():
+            self._record_derived_checks()
+        return index
+
+    def _forward_trainable(self, input: torch.Tensor) -> torch.Tensor:
+        """A call that must produce gradients for codebooks / scales / bias (module docstring of aqlm_amd/tuning.py)."""
+        if self._takes_codebook_grad_kernel(input):
+            index = self.codebook_grad_index()  # (first: inside a capture a missing index raises before any launch)
+            return _TrainableMatmul1x16.apply(input, self.codebooks, self.scales, self.bias, self._codes_for_ops(), index)
+        from .utils import _dequantize_weight
+
+        # the reference's definition under autograd; the arithmetic on the codes outside inference mode (`unpack_int_data` runs
+        # inside it, and its result could not be saved for the backward)
+        with torch.inference_mode(False):
+            unsigned = self._codes_for_ops().detach().to(torch.int64) % self.codebook_size
+        return torch.nn.functional.linear(input, _dequantize_weight(unsigned, self.codebooks, self.scales), self.bias)
 
     def _serves_from_packed(self, input: torch.Tensor) -> bool:
         """A call the packed-dequant routes can take: a 1x16 layer on slice-bucketed codes, input on the GPU in the codebook dtype."""
@@ -544,6 +606,52 @@ def _get_autograd_matmul_op(forward_pass_kernel, backward_pass_kernel):
 
     _QuantizedMatmul.forward_pass_kernel = staticmethod(forward_pass_kernel)
     return _QuantizedMatmul
+
+
+class _TrainableMatmul1x16(torch.autograd.Function):
+    """A 1x16 layer on the GPU with trainable codebooks / scales / bias.  Forward: the kernel the frozen layer runs for that row
+    count on the canonical codes and the live parameters (the direct matvec up to GEMV_MAX_ROWS rows, the large-batch op above).
+    Backward, in this order: grad_input by the frozen layer's backward kernel (only if needed; its W is released before the next
+    step, so the two [out, in] transients never coexist), dbias, ``dW = grad_y^T @ x`` by the library GEMM (storage dtype, as the
+    reference's autograd produces it; fp32 with ``tuning.CODEBOOK_GRAD_FP32_DW``), then the two reductions of dW
+    (aqlm_hip_codebook_grad_1x16 through the inverted index, aqlm_hip_scales_grad_1x16).  Gradients in each parameter's dtype."""
+
+    @staticmethod
+    def forward(ctx, input, codebooks, scales, bias, codes, index):
+        from .inference_kernels import hip_kernel
+
+        ctx.save_for_backward(input, codes, codebooks, scales)
+        ctx.index = index
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        if math.prod(input.shape[:-1]) <= GEMV_MAX_ROWS:
+            return hip_kernel._gemv(input, codes, codebooks, scales, bias, "1x16")
+        return hip_kernel.code1x16_matmat_dequant(input, codes, codebooks, scales, bias)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import tuning
+        from .inference_kernels import hip_kernel
+
+        input, codes, codebooks, scales = ctx.saved_tensors
+        grad_output = grad_output.contiguous()
+        need_input, need_codebooks, need_scales, need_bias = ctx.needs_input_grad[:4]
+        grad_input = grad_codebooks = grad_scales = grad_bias = None
+        if need_input:
+            grad_input = torch.ops.aqlm.code1x16_matmat_dequant_transposed(grad_output, codes, codebooks, scales, None)
+        gy = grad_output.reshape(-1, grad_output.shape[-1])
+        if need_bias and ctx.bias_dtype is not None:
+            grad_bias = gy.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+        if need_codebooks or need_scales:
+            x = input.reshape(-1, input.shape[-1])
+            if tuning.CODEBOOK_GRAD_FP32_DW:
+                dw = torch.mm(gy.t(), x, out_dtype=torch.float32)
+            else:
+                dw = torch.mm(gy.t(), x)
+            if need_codebooks:
+                grad_codebooks = hip_kernel.codebook_grad_1x16(dw, scales, ctx.index, out_dtype=codebooks.dtype).reshape(codebooks.shape)
+            if need_scales:
+                grad_scales = hip_kernel.scales_grad_1x16(dw, codes, codebooks, out_dtype=scales.dtype).reshape(scales.shape)
+        return grad_input, grad_codebooks, grad_scales, grad_bias, None, None
 
 
 class _MatmulFromPacked(torch.autograd.Function):

@@ -992,6 +992,147 @@ def lora_grad_routed(v, w, adapter_ids, expert_ids, bucket, table, geometry, lay
 
 
 # ------------------------------------------------------------------------------------------------------
+# gradients of the codebook and the scales of a 1x16 layer (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16)
+# ------------------------------------------------------------------------------------------------------
+CODEBOOK_GRAD_CHUNK = int(_lib.aqlm_hip_codebook_grad_chunk())  # positions per chunk of an entry's list (a constant of the library)
+CODEBOOK_GRAD_ENTRIES = 65536
+_GRAD_DT = {torch.float16: _native.F16, torch.bfloat16: _native.BF16, torch.float32: _native.F32}
+
+
+def codebook_grad_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
+    return bool(_lib.aqlm_hip_codebook_grad_1x16_supported(int(out_features), int(in_features), int(in_group_size))
+                and _lib.aqlm_hip_scales_grad_1x16_supported(int(out_features), int(in_features), int(in_group_size)))
+
+
+def codebook_grad_max_chunks(out_features: int, in_features: int, in_group_size: int) -> int:
+    return int(_lib.aqlm_hip_codebook_grad_1x16_max_chunks(int(out_features), int(in_features), int(in_group_size)))
+
+
+class CodebookGradIndex:
+    """The inverted index of a 1x16 layer's codes (include/aqlm_hip.h, aqlm_hip_codebook_grad_1x16): per codebook entry the
+    ascending list of the positions ``o * (in_features / g) + j`` that use it (``order`` int32 [n_codes], ``starts`` int32 [65537]),
+    every list cut into chunks of at most ``CODEBOOK_GRAD_CHUNK`` positions (``chunks`` int32 [max_chunks, 3]: entry, begin, end;
+    rows past the last chunk hold entry -1; ``chunk_starts`` int32 [65537]).  4 bytes per code plus ~0.5 MB of tables."""
+
+    __slots__ = ("order", "starts", "chunks", "chunk_starts", "out_features", "in_features", "in_group_size")
+
+    def __init__(self, order, starts, chunks, chunk_starts, out_features, in_features, in_group_size):
+        self.order, self.starts, self.chunks, self.chunk_starts = order, starts, chunks, chunk_starts
+        self.out_features, self.in_features, self.in_group_size = int(out_features), int(in_features), int(in_group_size)
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.order, self.starts, self.chunks, self.chunk_starts))
+
+    def geometry(self):
+        return [self.out_features, self.in_features, self.in_group_size]
+
+
+def build_codebook_grad_index(codes: torch.Tensor, in_group_size: int) -> CodebookGradIndex:
+    """The index from canonical ``codes`` [out, in / g, 1] int16, with torch ops on the codes' device: one stable sort by the
+    unsigned code value and binary searches for the tables.  No host synchronisation (the chunk table has its upper bound
+    ``min(n_codes, 65536) + n_codes // CHUNK`` of rows, the unused ones marked -1) and no kernel of this library: it runs once per
+    layer.  Works on host tensors too (the tests model it in numpy)."""
+    if codes.dim() != 3 or codes.shape[2] != 1 or codes.dtype != torch.int16:
+        raise ValueError(f"codes must be int16 [out, in / g, 1], got {codes.dtype} {tuple(codes.shape)}")
+    out_features, nj = int(codes.shape[0]), int(codes.shape[1])
+    g, n, chunk = int(in_group_size), out_features * nj, CODEBOOK_GRAD_CHUNK
+    max_chunks = codebook_grad_max_chunks(out_features, nj * g, g)
+    if max_chunks == 0:
+        raise NotImplementedError(f"no codebook-gradient index for a layer of {out_features} x {nj * g}, g = {g}")
+    dev = codes.device
+    with torch.inference_mode(False), torch.no_grad():
+        values = codes.detach().reshape(-1).to(torch.int32) & 0xFFFF  # the unsigned index a two's-complement container holds
+        sorted_values, order = torch.sort(values, stable=True)        # stable: every entry's list ascends
+        entries = torch.arange(CODEBOOK_GRAD_ENTRIES + 1, dtype=torch.int32, device=dev)
+        starts = torch.searchsorted(sorted_values, entries)           # [65537]; starts[65536] == n
+        counts = starts[1:] - starts[:-1]
+        chunk_starts = torch.zeros_like(starts)
+        chunk_starts[1:] = torch.cumsum((counts + (chunk - 1)) // chunk, 0)
+        k = torch.arange(max_chunks, dtype=torch.int64, device=dev)
+        entry = torch.searchsorted(chunk_starts[1:], k, right=True)   # the entry whose chunk rows hold k; 65536: past the last chunk
+        valid = entry < CODEBOOK_GRAD_ENTRIES
+        e = entry.clamp(max=CODEBOOK_GRAD_ENTRIES - 1)
+        begin = starts[e] + (k - chunk_starts[e]) * chunk
+        end = torch.minimum(begin + chunk, starts[e + 1])
+        zero = torch.zeros_like(k)
+        chunks = torch.stack((torch.where(valid, entry, zero - 1), torch.where(valid, begin, zero), torch.where(valid, end, zero)), 1)
+        return CodebookGradIndex(order.to(torch.int32), starts.to(torch.int32), chunks.to(torch.int32).contiguous(),
+                                 chunk_starts.to(torch.int32), out_features, nj * g, g)
+
+
+def _check_dw(dw, out_features, in_features, what):
+    if dw.dim() != 2 or tuple(dw.shape) != (out_features, in_features) or dw.stride(1) != 1 or dw.dtype not in _GRAD_DT or not dw.is_cuda:
+        raise ValueError(f"{what}: dW must be a GPU fp16 / bf16 / fp32 [{out_features}, {in_features}] with a unit inner stride, got "
+                         f"{dw.dtype} {tuple(dw.shape)} strides {tuple(dw.stride())} on {dw.device}")
+
+
+def _codebook_grad_op(dw, scales, starts, order, chunks, chunk_starts, geometry):
+    out_features, in_features, g, out_dt = (int(x) for x in geometry)
+    _check_dw(dw, out_features, in_features, "codebook_grad_1x16")
+    n = out_features * (in_features // max(g, 1))
+    max_chunks = codebook_grad_max_chunks(out_features, in_features, g)
+    want = ((starts, (CODEBOOK_GRAD_ENTRIES + 1,)), (order, (n,)), (chunks, (max_chunks, 3)), (chunk_starts, (CODEBOOK_GRAD_ENTRIES + 1,)))
+    for t, shape in want:
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dw.device:
+            raise ValueError(f"codebook_grad_1x16: index tensors must be contiguous int32 {[s for _, s in want]} on {dw.device} "
+                             "(build_codebook_grad_index)")
+    dt = _native.F16
+    if scales is not None:
+        if scales.numel() != out_features or scales.device != dw.device:
+            raise ValueError(f"codebook_grad_1x16: scales must hold {out_features} elements on {dw.device}")
+        dt = _dtype_id(scales)
+        scales = _c(scales)
+    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
+    out = torch.empty((CODEBOOK_GRAD_ENTRIES, g), dtype=out_dtype, device=dw.device)
+    ws_bytes = int(_lib.aqlm_hip_codebook_grad_1x16_workspace_bytes(out_features, in_features, g))
+    ws = _workspace(dw.device, max(ws_bytes, 16))
+    with _device_guard(dw.device):
+        rc = _lib.aqlm_hip_codebook_grad_1x16(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], _ptr(scales), dt, starts.data_ptr(),
+                                              order.data_ptr(), chunks.data_ptr(), chunk_starts.data_ptr(), out_features, in_features,
+                                              g, out.data_ptr(), out_dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(dw.device))
+    if rc:
+        _native.check(rc, "aqlm codebook grad")
+    return out
+
+
+def codebook_grad_1x16(dw, scales, index: CodebookGradIndex, out_dtype: Optional[torch.dtype] = None):
+    """dC [65536, g] (``out_dtype``, default dW's dtype) = for every entry the sum of ``scales[o] * dW[o, j*g : j*g + g]`` over the
+    positions of its list, fp32, in the fixed order of the index (include/aqlm_hip.h); ``scales`` None = 1.  Every element is
+    written (+0 for unused entries).  Two launches on the current stream, the fp32 partials in the cached per-stream workspace (a
+    fresh one inside a hipGraph capture)."""
+    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
+    return _codebook_grad_op(dw, scales, index.starts, index.order, index.chunks, index.chunk_starts, index.geometry() + [out_dt])
+
+
+def _scales_grad_op(dw, codes, codebooks, geometry):
+    out_features, in_features, g, out_dt = (int(x) for x in geometry)
+    _check_dw(dw, out_features, in_features, "scales_grad_1x16")
+    if (codes.dtype != torch.int16 or codes.numel() != out_features * (in_features // max(g, 1)) or not codes.is_contiguous()
+            or codes.device != dw.device):
+        raise ValueError(f"scales_grad_1x16: codes must be contiguous int16 [{out_features}, {in_features // max(g, 1)}, 1] on {dw.device}")
+    if tuple(codebooks.shape) != (1, CODEBOOK_GRAD_ENTRIES, 1, g) or codebooks.device != dw.device:
+        raise ValueError(f"scales_grad_1x16: codebooks must be [1, 65536, 1, {g}] on {dw.device}, got {tuple(codebooks.shape)}")
+    dt = _dtype_id(codebooks)
+    codebooks = _c(codebooks)
+    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
+    out = torch.empty((out_features,), dtype=out_dtype, device=dw.device)
+    with _device_guard(dw.device):
+        rc = _lib.aqlm_hip_scales_grad_1x16(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], codes.data_ptr(), codebooks.data_ptr(), dt,
+                                            out_features, in_features, g, out.data_ptr(), out_dt, _stream_ptr(dw.device))
+    if rc:
+        _native.check(rc, "aqlm scales grad")
+    return out
+
+
+def scales_grad_1x16(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = None):
+    """ds [out] (``out_dtype``, default dW's dtype): ``sum over j, t of dW[o, j*g + t] * codebooks[0, code(o, j), 0, t]`` -- the
+    unscaled codebook, the canonical codes; fp32 in a fixed order, one rounding (include/aqlm_hip.h)."""
+    g = int(codebooks.shape[3])
+    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
+    return _scales_grad_op(dw, codes, codebooks, [int(codes.shape[0]), int(codes.shape[1]) * g, g, out_dt])
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
@@ -2195,6 +2336,20 @@ _LIB.impl("lora_grad_routed", _lora_grad_routed_op, "CUDA")
 torch.library.register_fake("aqlm::lora_grad_routed")(
     lambda v, w, adapter_ids, expert_ids, bucket, table, geometry, layout: v.new_empty(
         (int(geometry[1]), int(geometry[2]), int(geometry[3]), int(geometry[4])), dtype=torch.float32))
+
+
+# gradients of the codebook and the scales of a 1x16 layer; geometry = [out_features, in_features, g, output dtype id]
+_GRAD_FAKE_DT = {_native.F16: torch.float16, _native.BF16: torch.bfloat16, _native.F32: torch.float32}
+_LIB.define("codebook_grad_1x16(Tensor dw, Tensor? scales, Tensor starts, Tensor order, Tensor chunks, Tensor chunk_starts, "
+            "int[] geometry) -> Tensor")
+_LIB.impl("codebook_grad_1x16", _codebook_grad_op, "CUDA")
+torch.library.register_fake("aqlm::codebook_grad_1x16")(
+    lambda dw, scales, starts, order, chunks, chunk_starts, geometry: dw.new_empty(
+        (CODEBOOK_GRAD_ENTRIES, int(geometry[2])), dtype=_GRAD_FAKE_DT[int(geometry[3])]))
+_LIB.define("scales_grad_1x16(Tensor dw, Tensor codes, Tensor codebooks, int[] geometry) -> Tensor")
+_LIB.impl("scales_grad_1x16", _scales_grad_op, "CUDA")
+torch.library.register_fake("aqlm::scales_grad_1x16")(
+    lambda dw, codes, codebooks, geometry: dw.new_empty((int(geometry[0]),), dtype=_GRAD_FAKE_DT[int(geometry[3])]))
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

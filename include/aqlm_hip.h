@@ -40,6 +40,7 @@ extern "C" {
 
 #define AQLM_HIP_F16 0
 #define AQLM_HIP_BF16 1
+#define AQLM_HIP_F32 2 /* dW and the outputs of the gradient entries (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16) only */
 
 #define AQLM_HIP_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, misaligned buffer) */
 #define AQLM_HIP_E_UNSUPPORTED (-2) /* shape / scheme outside what the entry point implements */
@@ -704,6 +705,51 @@ int aqlm_hip_lora_grad_routed(const aqlm_hip_lora_entry* table, int num_adapters
                               int expert_ids_int64, const void* bucket, int num_pairs, int top_k, const void* v, long v_row_stride,
                               long v_seg_stride, int v_per_pair, int dim, const float* w, long w_pair_stride, long w_seg_stride,
                               int w_splits, long w_split_stride, float* g, size_t g_bytes, int dtype, void* stream);
+
+/*
+ * Gradients of the continuous parameters of a 1x16 layer (one codebook of 65536 entries, out_group_size 1, in_group_size g = 8
+ * or 16) from dW = grad_y^T @ x, [out_features][in_features] with a row stride in elements, fp16 / bf16 / fp32 (dw_dtype; 16-byte
+ * aligned rows).  The reference gets them from autograd through its dequantisation (an embedding_bag backward: sort or atomics);
+ * here the codes, which do not change while codebooks and scales train, are turned round once per layer into an inverted index:
+ *     order        int32 [n_codes]     positions o * (in_features / g) + j, sorted stably by code value (codes % 65536), so that
+ *                                      every entry's list is in ascending position order          (n_codes = out * in / g)
+ *     starts       int32 [65537]       entry c owns order[starts[c] .. starts[c + 1])
+ *     chunks       int32 [max_chunks][3]  (entry, begin, end): every list cut into pieces of at most
+ *                                      AQLM_HIP_CODEBOOK_GRAD_CHUNK positions, in entry order then list order, unused entries absent;
+ *                                      rows past the last chunk hold entry -1.  max_chunks = min(n_codes, 65536) + n_codes / CHUNK
+ *                                      (aqlm_hip_codebook_grad_1x16_max_chunks; 0: shape refused) bounds the count for any codes
+ *     chunk_starts int32 [65537]       entry c owns the chunk rows chunk_starts[c] .. chunk_starts[c + 1]
+ * aqlm_hip_codebook_grad_1x16:  out[c][t] = sum over the positions (o, j) of entry c of s[o] * dW[o, j * g + t], s = scales
+ * [out_features] in `dtype` (fp16 / bf16) or NULL for 1; out [65536][g] in out_dtype (fp16 / bf16 / fp32), 16-byte aligned.
+ * Summation, a function of the index and of CHUNK alone: a chunk is summed in fp32 by 16 lanes -- lane l adds the chunk's
+ * positions l, l + 16, ... in that order (fused multiply-add by s), then a fixed butterfly adds the lanes --; an entry of one
+ * chunk writes that sum, an entry of several has its partials (`workspace`, fp32 [max_chunks][g], 16-byte aligned,
+ * aqlm_hip_codebook_grad_1x16_workspace_bytes) added in chunk order by a second launch; one rounding to out_dtype.  EVERY one of
+ * the 65536 x g outputs is written by every call (+0 for an entry without positions): no memset, no dependence on what out or
+ * workspace held.  No atomics.  Index values are range-checked before they form an address: a chunk row with an entry outside
+ * [0, 65536), a range outside [0, n_codes] or longer than CHUNK is skipped, a position outside [0, n_codes) contributes nothing.
+ * aqlm_hip_scales_grad_1x16:  out[o] = sum over j, t of dW[o, j * g + t] * C[code(o, j)][t] with the canonical codes
+ * [out][in / g] int16 and the UNSCALED codebook [65536][g] in `dtype`; one wave per row -- lane l adds the products of the
+ * groups l, l + 64, ... in order (fp32, fused multiply-add), a fixed tree adds the lanes --, one rounding to out_dtype.
+ * Both: stream-ordered, no allocation, no synchronisation (hipGraph-capturable), no scratch.  Checks, in order: a null pointer
+ * (scales may be NULL), misalignment (dw / out of the codebook gradient / workspace / codebook 16 bytes, the index arrays and the
+ * output of the scales gradient 4, scales and codes 2), non-positive sizes or in_features % g != 0, a row stride below in_features
+ * or a workspace that is too small (AQLM_HIP_E_INVALID); then dw_dtype / out_dtype outside fp16 / bf16 / fp32, dtype outside
+ * fp16 / bf16, g outside {8, 16}, more than AQLM_HIP_CODEBOOK_GRAD_MAX_CODES codes or dW rows not 16-byte aligned
+ * (AQLM_HIP_E_UNSUPPORTED).  Nothing is launched on bad arguments.  The ..._supported queries answer for the three sizes.
+ */
+#define AQLM_HIP_CODEBOOK_GRAD_CHUNK 256
+#define AQLM_HIP_CODEBOOK_GRAD_MAX_CODES (1 << 30)
+int aqlm_hip_codebook_grad_chunk(void); /* AQLM_HIP_CODEBOOK_GRAD_CHUNK of the loaded library */
+int aqlm_hip_codebook_grad_1x16_supported(int out_features, int in_features, int in_group_size);
+int aqlm_hip_codebook_grad_1x16_max_chunks(int out_features, int in_features, int in_group_size);
+size_t aqlm_hip_codebook_grad_1x16_workspace_bytes(int out_features, int in_features, int in_group_size);
+int aqlm_hip_codebook_grad_1x16(const void* dw, long dw_row_stride, int dw_dtype, const void* scales, int dtype, const void* starts,
+                                const void* order, const void* chunks, const void* chunk_starts, int out_features, int in_features,
+                                int in_group_size, void* out, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
+int aqlm_hip_scales_grad_1x16_supported(int out_features, int in_features, int in_group_size);
+int aqlm_hip_scales_grad_1x16(const void* dw, long dw_row_stride, int dw_dtype, const void* codes, const void* codebook, int dtype,
+                              int out_features, int in_features, int in_group_size, void* out, int out_dtype, void* stream);
 
 /*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
