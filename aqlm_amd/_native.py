@@ -226,6 +226,7 @@ SIGNATURES = {
     "aqlm_hip_checksum": (_ci, [_vp, _sz, _vp, _vp]),
     "aqlm_hip_set_tuning": (_ci, [ctypes.c_char_p, _ci]),
     "aqlm_hip_get_tuning": (_ci, [ctypes.c_char_p, ctypes.POINTER(_ci)]),
+    "aqlm_hip_capture_overlap_stats": (_ci, [ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 
@@ -288,3 +289,16 @@ def get_tuning(key: str) -> int:
     v = _ci(0)
     check(lib.aqlm_hip_get_tuning(key.encode(), ctypes.byref(v)), "get_tuning")
     return v.value
+
+
+CAPTURE_OVERLAP_FIELDS = ("seen", "relaxed", "kept_conflict", "kept_window", "runs_broken", "api_failures")
+
+
+def capture_overlap_stats(reset: bool = False) -> dict:
+    """Counters of the packed matvec launches made on a stream under capture (aqlm_hip_capture_overlap_stats);
+    `reset` zeroes them after reading."""
+    out = (ctypes.c_uint64 * 6)()
+    check(lib.aqlm_hip_capture_overlap_stats(out), "capture_overlap_stats")
+    if reset:
+        check(lib.aqlm_hip_capture_overlap_stats(None), "capture_overlap_stats")
+    return dict(zip(CAPTURE_OVERLAP_FIELDS, (int(v) for v in out)))

@@ -76,11 +76,149 @@ static int* tuning_slot(const char* key) {
   if (!strcmp(key, "packed_entry_bytes")) return &t.packed_entry_bytes;
   if (!strcmp(key, "packed_debug")) return &t.packed_debug;
   if (!strcmp(key, "packed_fill_rotate")) return &t.packed_fill_rotate;
+  if (!strcmp(key, "packed_capture_window")) return &t.packed_capture_window;
+  if (!strcmp(key, "packed_capture_min_run")) return &t.packed_capture_min_run;
   if (!strcmp(key, "packed_pipe")) return &t.packed_pipe;
   if (!strcmp(key, "packed_prefetch_waves")) return &t.packed_prefetch_waves;
   if (!strcmp(key, "packed_dequant_by_xcd")) return &t.packed_dequant_by_xcd;
   if (!strcmp(key, "lut_waves")) return &t.lut_waves;
   return nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Capture overlap: the HIP side of capture_overlap.h.  One planner for the process (both builds of the packed entries launch
+// through it), behind one mutex that is never held across a launch.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct CaptureOverlapState {
+  std::mutex mu;
+  capture_overlap::Planner planner;
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};  // seen, relaxed, kept for a conflict, kept for the window, runs broken, API failures
+  bool off = false;                        // a capture call failed once: every launch as issued from then on
+};
+CaptureOverlapState& capture_state() {
+  static CaptureOverlapState s;
+  return s;
+}
+hipError_t set_capture_deps(hipStream_t stream, const std::vector<capture_overlap::NodeId>& nodes) {
+  static_assert(sizeof(hipGraphNode_t) == sizeof(capture_overlap::NodeId), "a graph node handle is carried as a 64-bit id");
+  std::vector<hipGraphNode_t> d;
+  for (capture_overlap::NodeId n : nodes) d.push_back(reinterpret_cast<hipGraphNode_t>(static_cast<uintptr_t>(n)));
+  return hipStreamUpdateCaptureDependencies(stream, d.empty() ? nullptr : d.data(), d.size(), hipStreamSetCaptureDependencies);
+}
+bool same_nodes(const std::vector<capture_overlap::NodeId>& a, const std::vector<capture_overlap::NodeId>& b) {
+  return a.size() == b.size() && std::is_permutation(a.begin(), a.end(), b.begin());
+}
+// the stream's capture status; false (and the error) when the query itself failed
+bool read_capture(hipStream_t stream, bool& capturing, unsigned long long& id, std::vector<capture_overlap::NodeId>& deps, hipError_t& err) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  const hipGraphNode_t* d = nullptr;
+  size_t n = 0;
+  hipGraph_t graph = nullptr;
+  err = hipStreamGetCaptureInfo_v2(stream, &st, &id, &graph, &d, &n);
+  if (err != hipSuccess) return false;
+  capturing = st == hipStreamCaptureStatusActive;
+  deps.clear();
+  if (capturing)
+    for (size_t i = 0; i < n; ++i) deps.push_back(static_cast<capture_overlap::NodeId>(reinterpret_cast<uintptr_t>(d[i])));
+  return true;
+}
+}  // namespace
+
+void CaptureRelax::fail(const char* what, hipError_t e) {
+  (void)hipGetLastError();  // the launch that follows checks the sticky error: this one is ours
+  CaptureOverlapState& s = capture_state();
+  s.off = true;
+  ++s.stats[5];
+  set_last_error("capture overlap switched off for this process: %s: %s (%d)", what, hipGetErrorString(e), (int)e);
+}
+
+CaptureRelax::CaptureRelax(hipStream_t stream) : stream_(stream) {
+  if (!stream) return;  // the null stream cannot be captured
+  CaptureOverlapState& s = capture_state();
+  {
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (s.off) return;
+  }
+  bool capturing = false;
+  hipError_t err = hipSuccess;
+  if (!read_capture(stream, capturing, id_, before_, err)) {
+    std::lock_guard<std::mutex> lock(s.mu);
+    fail("hipStreamGetCaptureInfo_v2", err);
+    return;
+  }
+  if (!capturing) return;
+  const int window = tuning().packed_capture_window;
+  std::lock_guard<std::mutex> lock(s.mu);
+  ++s.stats[0];
+  if (window <= 1) ++s.stats[3];  // exactly the graph as issued: nothing to plan
+  else active_ = true;
+}
+
+void CaptureRelax::begin() {
+  if (!active_ || begun_) return;
+  begun_ = true;
+  CaptureOverlapState& s = capture_state();
+  std::lock_guard<std::mutex> lock(s.mu);
+  plan_ = s.planner.run(id_).plan(before_.data(), before_.size(), fp, tuning().packed_capture_window, tuning().packed_capture_min_run);
+  ++s.stats[plan_.kind == capture_overlap::kBroken ? 4 : (int)plan_.kind];
+  if (plan_.kind == capture_overlap::kBroken || same_nodes(plan_.deps, before_)) return;
+  const hipError_t e = set_capture_deps(stream_, plan_.deps);
+  if (e == hipSuccess) {
+    changed_ = true;
+    return;
+  }
+  // the stream still waits for everything it did: launch as issued
+  fail("hipStreamUpdateCaptureDependencies", e);
+  s.planner.run(id_).reset();
+  active_ = false;
+}
+
+int CaptureRelax::launched() {
+  if (!active_ || !begun_ || done_) return 0;
+  done_ = true;
+  CaptureOverlapState& s = capture_state();
+  std::lock_guard<std::mutex> lock(s.mu);
+  capture_overlap::Run& run = s.planner.run(id_);
+  bool capturing = false;
+  unsigned long long id = 0;
+  std::vector<capture_overlap::NodeId> now;
+  hipError_t err = hipSuccess;
+  const bool read = read_capture(stream_, capturing, id, now, err);
+  std::vector<capture_overlap::NodeId> want;
+  if (read && capturing && id == id_ && now.size() == 1 && run.commit(plan_, now[0], std::move(fp))) {
+    want = run.tail();
+  } else {
+    // the new node is not known: everything the call found, and whatever the stream names now
+    if (!read) fail("hipStreamGetCaptureInfo_v2", err);
+    run.reset();
+    if (!changed_) return 0;  // the launch was chained as issued
+    want = before_;
+    for (capture_overlap::NodeId n : now)
+      if (std::find(want.begin(), want.end(), n) == want.end()) want.push_back(n);
+    if (!read || !capturing) {
+      set_last_error("capture overlap: the stream's capture state was lost after a launch that had been moved");
+      return AQLM_HIP_E_INVALID;
+    }
+  }
+  if (same_nodes(want, now)) return 0;
+  const hipError_t e = set_capture_deps(stream_, want);
+  if (e == hipSuccess) return 0;
+  run.reset();
+  const bool moved = changed_ || want.size() > 1;
+  fail("hipStreamUpdateCaptureDependencies", e);
+  return moved ? (int)e : 0;
+}
+
+CaptureRelax::~CaptureRelax() {
+  if (!active_ || !begun_ || done_) return;
+  // the call ends without its launch: the stream waits for what it waited for before
+  CaptureOverlapState& s = capture_state();
+  std::lock_guard<std::mutex> lock(s.mu);
+  s.planner.run(id_).reset();
+  if (!changed_) return;
+  const hipError_t e = set_capture_deps(stream_, before_);
+  if (e != hipSuccess) fail("hipStreamUpdateCaptureDependencies", e);
 }
 
 // position-sensitive checksum (include/aqlm_hip.h): per-thread partial sums, wave reduction through the atomics' return path is
@@ -121,6 +259,16 @@ extern "C" int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2
   const unsigned blocks = (unsigned)std::min<size_t>(2048, (nwords + 255) / 256);
   hipLaunchKernelGGL(aqlm::checksum_kernel, dim3(blocks), dim3(256), 0, stream, (const uint8_t*)data, bytes, (unsigned long long*)out_u64x2);
   return aqlm::check_hip(hipGetLastError(), "checksum launch");
+}
+
+extern "C" int aqlm_hip_capture_overlap_stats(uint64_t out[6]) {
+  aqlm::CaptureOverlapState& s = aqlm::capture_state();
+  std::lock_guard<std::mutex> lock(s.mu);
+  for (int i = 0; i < 6; ++i) {
+    if (out) out[i] = s.stats[i];
+    else s.stats[i] = 0;
+  }
+  return 0;
 }
 
 extern "C" int aqlm_hip_abi_version(void) { return AQLM_HIP_ABI_VERSION; }

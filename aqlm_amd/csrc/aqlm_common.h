@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/aqlm_hip.h"
+#include "capture_overlap.h"
 
 namespace aqlm {
 
@@ -175,9 +176,39 @@ struct Tuning {
   int packed_fill_rotate = 1;    // packed 1x16 kernel: 1 = the workgroups that share a codebook slice start their LDS fill at different pieces
   int lut_waves = 0;             // 8 x 8 look-up-table matvec: waves per workgroup (8 / 16); 0 = default
   int packed_prefetch_waves = 0; // chain prefetch: extra waves per workgroup that pull the next layer towards L2 (0 = 2, -1 = off)
+  int packed_capture_window = capture_overlap::kDefaultWindow;  // packed 1x16 matvecs captured into a graph: consecutive launches that share no memory and may run side by side (1..8; capture_overlap.h); 1 = every launch after the previous one
+  int packed_capture_min_run = capture_overlap::kDefaultMinRun;  // ... launches an uninterrupted run of them must hold before any is relaxed (a graph with branches costs host time per node: capture_overlap.h); 1 = from the second launch on
   int packed_dequant_by_xcd = 1; // aqlm_hip_dequant_1x16_packed, grid order: 1 = by the measured rule (16-B vectors: the streams that run together on an XCD are the slices of one row group, so their partial-line stores meet in one L2; 32-B vectors: stream-major like the unpack kernel), 0 = always stream-major, 2 = always by XCD (A/B runs)
 };
 Tuning& tuning();
+
+// The first kernel of a packed matvec call on a stream that is being captured: ordered by the memory the call touches, not
+// by the order of issue (capture_overlap.h has the rule, api.hip the state shared by both builds of the packed entries).
+//   CaptureRelax relax(stream);
+//   if (relax.capturing()) { relax.fp.add(...); ...; relax.begin(); }
+//   <launch>;  relax.launched();
+// Outside a capture it costs the one status query.  A call that returns without launched() leaves the stream as it found it.
+class CaptureRelax {
+ public:
+  explicit CaptureRelax(hipStream_t stream);
+  ~CaptureRelax();
+  CaptureRelax(const CaptureRelax&) = delete;
+  CaptureRelax& operator=(const CaptureRelax&) = delete;
+  bool capturing() const { return active_; }
+  capture_overlap::Footprint fp;
+  void begin();
+  // After the launch (later launches of the call: no effect).  0, or the error when the stream could not be made to wait
+  // for the launches that ran beside this one: the capture would be wrong, so the call fails.
+  int launched();
+
+ private:
+  void fail(const char* what, hipError_t e);
+  hipStream_t stream_;
+  bool active_ = false, begun_ = false, done_ = false, changed_ = false;
+  unsigned long long id_ = 0;
+  std::vector<capture_overlap::NodeId> before_;  // the stream's dependency set as the call found it
+  capture_overlap::Plan plan_;
+};
 
 // slice-scan MFMA kernel of the 1x16 g8 scheme at 2+ rows (gemm_1x16_scan.hip); the large-batch op of gemm_mfma.hip routes to it
 namespace scan {

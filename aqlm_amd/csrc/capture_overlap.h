@@ -1,0 +1,219 @@
+// Capture overlap: which earlier launches a launch captured into a graph really has to wait for.  Plain C++17, no HIP: the
+// launch side (aqlm_common.h: CaptureRelax, api.hip) hands in opaque node ids and byte ranges and installs what comes back;
+// tests/capture_overlap_host.cpp drives the same code on the CPU.
+//
+// A stream under capture only describes a dependency graph, and whoever adds a node may choose its dependencies.  The library
+// knows the memory every packed matvec reads and writes, so consecutive launches that share none of it need no edge between
+// them: the next layer's workgroups start on CUs as the previous layer's leave them, instead of after its last one.
+//
+// Per capture id the planner keeps the RUN of library launches it has added: the dependency set the run started from (base)
+// and a TAIL of at most W launches that nothing captured so far waits for, each with its footprint.  For a new launch, given
+// the stream's current dependency set D:
+//   1. D is not exactly the tail (a foreign node, an event wait, another capture, the first launch): the run is broken;
+//      base := D, the launch depends on D, tail := {launch}.
+//   2. otherwise it depends on every tail launch whose footprint overlaps its own with a write on either side (RAW, WAR, WAW);
+//      with no such launch and a full tail, on the oldest tail launch (W chains, never more than W launches in flight); with
+//      neither, on base alone.  Every tail launch is ordered after base, so base is named only when no tail launch is.
+//      The tail launches it depends on leave the tail, the new launch joins it -- and answers for them from then on: a tail
+//      entry's footprint is its launch's own plus those of the launches that left the tail through it, because a later launch
+//      that touches the memory of one of those can only be ordered after it by waiting for the entry.  (Comparing with the
+//      launch's own footprint alone loses exactly that hazard: A, B in the tail; C waits for A; D touches A's memory but not
+//      C's.)  A footprint that would outgrow kMaxRanges is handled like a broken run: the launch waits for the whole tail.
+//   3. after the launch the caller sets the stream's dependency set to the tail: whatever is captured next, by anyone, waits
+//      for every launch it could observe.
+#ifndef AQLM_CAPTURE_OVERLAP_H_
+#define AQLM_CAPTURE_OVERLAP_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace aqlm {
+namespace capture_overlap {
+
+using NodeId = uint64_t;
+
+constexpr int kMaxWindow = 8;
+// Every branch of a replayed graph wants a hardware queue of its own, and a process opens 4 by default, which the capturing
+// stream and every other stream share.  Measured on the 64-layer decode step (profiles/capture_overlap.json): 2 branches
+// 391-396 us in every placement of the streams tried; 3 and 4 branches 397-411 us, or 450-455 us (stream order: 470) when two
+// branches land on one queue, which depends on how many streams the process created before.  Two is faster and does not
+// depend on that.
+constexpr int kDefaultWindow = 2;
+// A graph with branches leaves the runtime's single-stream replay and pays about 2 us of host time per node, for EVERY node of
+// the graph (64 nodes: 20 -> 157 us of enqueue per replay).  Where the library's launches are the graph, as in a stack of
+// linears, the kernels are longer than that and the overlap wins; in a decoder's graph of thousands of short framework nodes
+// the replay becomes host-bound (Llama-3-8B decode loop: 5.84 -> 7.90 ms per token with q/k/v relaxed).  Nothing the planner
+// sees tells the two apart except how long the library's launches go uninterrupted: a run relaxes nothing until it is this
+// long, which q/k/v, gate/up and the like never are.
+constexpr int kDefaultMinRun = 8;
+constexpr size_t kMaxRanges = 256;  // of one tail entry's footprint (a packed matvec brings 6 to 9)
+
+struct Range {
+  uintptr_t begin, end;  // [begin, end) in bytes
+  bool writes;
+};
+
+struct Footprint {
+  std::vector<Range> ranges;
+  void add(const void* p, size_t bytes, bool writes) {
+    if (!p || !bytes) return;
+    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+    ranges.push_back(Range{b, b + bytes, writes});
+  }
+  // `rows` rows of `row_bytes` each, `stride_bytes` apart (any sign): one range when they touch, else one per row
+  void add_rows(const void* p, int rows, long stride_bytes, size_t row_bytes, bool writes) {
+    if (rows > 1 && stride_bytes == (long)row_bytes) return add(p, (size_t)rows * row_bytes, writes);
+    for (int r = 0; r < rows; ++r) add(reinterpret_cast<const char*>(p) + (ptrdiff_t)r * stride_bytes, row_bytes, writes);
+  }
+};
+
+inline bool hazard(const Footprint& a, const Footprint& b) {
+  for (const Range& x : a.ranges)
+    for (const Range& y : b.ranges)
+      if ((x.writes || y.writes) && x.begin < y.end && y.begin < x.end) return true;
+  return false;
+}
+
+enum Kind { kBroken = 0, kRelaxed = 1, kConflict = 2, kWindow = 3 };
+
+struct Plan {
+  Kind kind = kBroken;
+  std::vector<NodeId> deps;   // what the launch depends on
+  std::vector<size_t> leave;  // ascending tail positions of the launches among them
+  bool restart = false;       // the launch starts a run: base := deps, tail := {launch}
+  uint64_t generation = 0;    // of the run when it was planned: commit() takes only the latest plan
+};
+
+class Run {
+ public:
+  uint64_t capture_id = 0;
+
+  // Steps 1 and 2 for a launch with footprint `fp`; `deps` / `num_deps` = D.  Nothing is recorded until commit().
+  // A run relaxes nothing until it holds `min_run` launches: until then every launch waits for the whole tail, as issued.
+  Plan plan(const NodeId* deps, size_t num_deps, const Footprint& fp, int window, int min_run = 1) {
+    window = std::min(std::max(window, 1), kMaxWindow);
+    Plan p;
+    p.generation = ++generation_;
+    if (!is_tail(deps, num_deps)) {
+      p.kind = kBroken;
+      p.restart = true;
+      p.deps.assign(deps, deps + num_deps);
+      return p;
+    }
+    for (size_t i = 0; i < tail_.size(); ++i)
+      if (hazard(tail_[i].fp, fp)) p.leave.push_back(i);
+    if (!p.leave.empty()) {
+      p.kind = kConflict;
+    } else if (length_ < (size_t)std::max(min_run, 1)) {
+      p.kind = kWindow;
+      for (size_t i = 0; i < tail_.size(); ++i) p.leave.push_back(i);
+    } else if ((int)tail_.size() >= window) {
+      p.kind = kWindow;
+      p.leave.push_back(0);  // the oldest
+    } else {
+      p.kind = kRelaxed;
+      p.deps = base_;
+      return p;
+    }
+    size_t ranges = fp.ranges.size();
+    for (size_t i : p.leave) ranges += tail_[i].fp.ranges.size();
+    if (ranges > kMaxRanges) {  // too much to answer for: wait for the whole tail (= D) and start over from there
+      p.restart = true;
+      p.leave.clear();
+      p.deps.assign(deps, deps + num_deps);
+      return p;
+    }
+    for (size_t i : p.leave) p.deps.push_back(tail_[i].node);
+    return p;
+  }
+
+  // The launch of plan `p` became `node`: step 2's bookkeeping, after which tail() is what step 3 installs.  False (and
+  // nothing recorded) when `p` is not the run's latest plan.
+  bool commit(const Plan& p, NodeId node, Footprint fp) {
+    if (p.generation != generation_) return false;
+    if (p.restart) {
+      base_ = p.deps;
+      tail_.clear();
+      length_ = 0;
+    } else {
+      for (size_t k = p.leave.size(); k-- > 0;) {
+        const Footprint& gone = tail_[p.leave[k]].fp;
+        fp.ranges.insert(fp.ranges.end(), gone.ranges.begin(), gone.ranges.end());
+        tail_.erase(tail_.begin() + (ptrdiff_t)p.leave[k]);
+      }
+    }
+    ++generation_;
+    ++length_;
+    tail_.push_back(Entry{node, std::move(fp)});
+    return true;
+  }
+
+  // Forget the run (its launch failed, or the new node could not be read): the next launch starts a new one.
+  void reset() {
+    ++generation_;
+    base_.clear();
+    tail_.clear();
+    length_ = 0;
+  }
+
+  std::vector<NodeId> tail() const {
+    std::vector<NodeId> t;
+    for (const Entry& e : tail_) t.push_back(e.node);
+    return t;
+  }
+  const std::vector<NodeId>& base() const { return base_; }
+
+ private:
+  struct Entry {
+    NodeId node;
+    Footprint fp;
+  };
+  bool is_tail(const NodeId* deps, size_t n) const {
+    if (tail_.empty() || n != tail_.size()) return false;
+    for (size_t i = 0; i < n; ++i) {
+      bool found = false;
+      for (const Entry& e : tail_) found = found || e.node == deps[i];
+      if (!found) return false;
+      for (size_t j = 0; j < i; ++j)
+        if (deps[j] == deps[i]) return false;
+    }
+    return true;
+  }
+  std::vector<NodeId> base_;
+  std::vector<Entry> tail_;  // oldest first
+  size_t length_ = 0;        // launches of the run so far
+  uint64_t generation_ = 0;
+};
+
+// The runs of the captures in progress: a few at most (one per capturing stream), the least recently used one makes room.
+class Planner {
+ public:
+  Run& run(uint64_t capture_id) {
+    ++clock_;
+    size_t lru = 0;
+    for (size_t i = 0; i < kSlots; ++i) {
+      if (used_[i] && runs_[i].capture_id == capture_id) {
+        used_[i] = clock_;
+        return runs_[i];
+      }
+      if (used_[i] < used_[lru]) lru = i;
+    }
+    runs_[lru].reset();
+    runs_[lru].capture_id = capture_id;
+    used_[lru] = clock_;
+    return runs_[lru];
+  }
+
+ private:
+  static constexpr size_t kSlots = 4;
+  Run runs_[kSlots];
+  uint64_t used_[kSlots] = {0, 0, 0, 0};
+  uint64_t clock_ = 0;
+};
+
+}  // namespace capture_overlap
+}  // namespace aqlm
+#endif  // AQLM_CAPTURE_OVERLAP_H_

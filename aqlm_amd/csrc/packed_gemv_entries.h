@@ -177,6 +177,21 @@ static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed,
   }
   if (int e = packed_check_args("aqlm_hip_gemv_1x16_packed", desc, packed, codebook, x, batch, x_row_stride, dtype, L, max_b)) return e;
   const bool fused = packed_fused(desc);
+  // On a stream under capture the first kernel of the call waits only for the earlier packed matvecs whose memory it shares
+  // (capture_overlap.h); the call's later kernels follow it as issued.  The footprint is everything the call reads or writes.
+  CaptureRelax relax(stream);
+  if (relax.capturing()) {
+    relax.fp.add_rows(x, batch, x_row_stride * 2, (size_t)desc->in_features * 2, false);
+    relax.fp.add(packed, L.used, false);
+    if (fused && !cells) relax.fp.add((const uint8_t*)packed + L.off_acc, L.off_ent - L.off_acc, true);
+    relax.fp.add(codebook, (size_t)65536 * PK_VB, false);
+    relax.fp.add(scales, (size_t)L.M * 2, false);
+    relax.fp.add(bias, (size_t)L.M * 2, false);
+    relax.fp.add_rows(y, batch, y_row_stride * 2, (size_t)L.M * 2, true);
+    if (fused && cells) relax.fp.add(cells, (size_t)batch * L.M * 8, true);
+    if (!fused) relax.fp.add(workspace, (size_t)PK_S * std::min(batch, max_b) * L.M * sizeof(float), true);
+    relax.begin();
+  }
   for (int b0 = 0; b0 < batch; b0 += max_b) {  // rows that do not fit one LDS image go in several launches
     const int nb = std::min(max_b, batch - b0);
     uint16_t* yb = (uint16_t*)y + (size_t)b0 * y_row_stride;
@@ -193,6 +208,7 @@ static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed,
                                    workspace, workspace_bytes, stream, "aqlm_hip_gemv_1x16_packed", fz,
                                    fused && b0 + nb >= batch ? next : PackedNext{}))
       return e;
+    if (int e = relax.launched()) return e;
     if (fused) continue;
     if (dtype == AQLM_HIP_F16)
       hipLaunchKernelGGL(gemv_1x16_packed_finalize<F16>, dim3((L.M + 255) / 256), dim3(256), 0, stream, (const float*)workspace,
@@ -436,6 +452,23 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
     set_last_error("aqlm_hip_gemv_1x16_packed_multi: %d rows of %d features do not fit the LDS image", batch, in_features);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  // under capture: the first kernel below is ordered by the memory of all segments (as in gemv_1x16_packed_impl)
+  CaptureRelax relax(stream);
+  if (relax.capturing()) {
+    relax.fp.add_rows(x, batch, x_row_stride * 2, (size_t)in_features * 2, false);
+    for (int k = 0; k < num_segments; ++k) {
+      const aqlm_hip_segment& sg = segments[k];
+      relax.fp.add(sg.codes, Ls[k].used, false);
+      if (fused && !cells) relax.fp.add((const uint8_t*)sg.codes + Ls[k].off_acc, Ls[k].off_ent - Ls[k].off_acc, true);
+      relax.fp.add(sg.codebook, (size_t)65536 * PK_VB, false);
+      relax.fp.add(sg.scales, (size_t)sg.out_features * 2, false);
+      relax.fp.add(sg.bias, (size_t)sg.out_features * 2, false);
+      relax.fp.add_rows(sg.y, batch, sg.y_row_stride * 2, (size_t)sg.out_features * 2, true);
+    }
+    if (fused && cells) relax.fp.add(cells, cells_need, true);
+    if (!fused) relax.fp.add(workspace, need, true);
+    relax.begin();
+  }
   // batch 1 with the single-kernel finalize: one workgroup per CU walks all segments, slices double-buffered (pipe kernel)
   if (fused && batch == 1 && tuning().packed_pipe) {
     int prg = 0, nwc = 0, dmaw = 0;
@@ -455,7 +488,8 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
       auto go = [&](auto kern) -> int {
         if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
         hipLaunchKernelGGL(kern, dim3(PK_NST), dim3((nwc + dmaw) * 64), lds, stream, pp);
-        return check_hip(hipGetLastError(), "gemv_1x16_packed_pipe launch");
+        if (int e = check_hip(hipGetLastError(), "gemv_1x16_packed_pipe launch")) return e;
+        return relax.launched();
       };
 #define AQLM_PP_GO(SELF, XWV, OB) \
   (dtype == AQLM_HIP_F16 ? go(gemv_1x16_packed_pipe_kernel<F16, SELF, XWV, OB>) : go(gemv_1x16_packed_pipe_kernel<BF16, SELF, XWV, OB>))
@@ -472,7 +506,8 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
     const size_t lds = decltype(lds_map)::total(mp.in_groups, max_rg);
     if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
     hipLaunchKernelGGL(kern, dim3(PK_NST * num_segments), dim3(nw * 64), lds, stream, mp);
-    return check_hip(hipGetLastError(), "gemv_1x16_packed_multi launch");
+    if (int e = check_hip(hipGetLastError(), "gemv_1x16_packed_multi launch")) return e;
+    return relax.launched();
   };
   if (int e = dispatch_packed<MultiKernels>(dtype, batch, pd, eb, batch == 1 && packed_b1_slice_first(mp.in_groups, max_rg), launch)) return e;
   if (fused) return 0;

@@ -11,7 +11,8 @@
  *   - raw device pointers, caller-owned, never retained; inputs are never written (one documented exception: the
  *     accumulator cells inside a prepacked buffer, see aqlm_hip_gemv_1x16_packed; the *_cells entries avoid it);
  *   - stream-ordered on `stream` (a hipStream_t passed as void*; NULL = the null stream), asynchronous,
- *     no allocation, no synchronisation -> hipGraph-capturable and re-entrant;
+ *     no allocation, no synchronisation -> hipGraph-capturable and re-entrant (the packed 1x16 matvec entries order
+ *     themselves by data flow inside a capture: "Capture overlap" below);
  *   - tensors use the reference's checkpoint layout unchanged:
  *       codes      [out_features][in_features/in_group_size][num_codebooks]  int8 (nbits<=8) / int16 (nbits<=16)
  *                  two's-complement containers holding UNSIGNED indices (utils.py:11-31)
@@ -936,6 +937,39 @@ size_t aqlm_hip_workspace_bytes(int op, int batch, int out_features, int in_feat
  * (aqlm_amd/inference.py, DERIVED_CHECK_EVERY) and rebuilds what no longer matches.
  */
 int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2, void* stream);
+
+/*
+ * Capture overlap -- the ordering contract of aqlm_hip_gemv_1x16_packed, _cells, _chain, _multi and _multi_cells.
+ * Outside a stream capture nothing differs from every other entry: stream-ordered.  On a stream that is being captured
+ * (hipStreamBeginCapture / torch.cuda.graph) the first kernel of such a call is ordered after everything captured before it
+ * EXCEPT earlier calls of these same entries in an unbroken run whose argument footprints it does not touch; everything
+ * captured after it, by this library or by anyone else, is ordered after all of them.
+ *   - footprint of a call, from its arguments and descriptor: the rows of x it uses, the packed buffer(s), codebook, scales,
+ *     bias (read); the rows of y, the accumulator cells (those inside the packed buffer, or the caller's) and the workspace
+ *     when used (written).  Two calls touch when two of their ranges overlap and at least one is written.  Memory a call
+ *     reaches in no other way than through these arguments is all it may assume about: a caller that aliases buffers the
+ *     arguments do not show (none of the entries allows that) gets no ordering for them.
+ *   - a run is broken by any other node or wait on the capturing stream between two calls: another entry of this library, a
+ *     kernel of the framework, a memcpy, an event wait, a change of the dependency set by the caller.
+ *   - at most `packed_capture_window` (tuning key, 1..8, default 2) calls of a run are left unordered among themselves; the
+ *     next one waits for the oldest.  1 = every call after the previous one, exactly the graph that stream order gives.
+ *     Every branch of the replayed graph wants a hardware queue of its own out of the 4 a process opens by default; with 3 or
+ *     4 branches two of them can land on one queue, depending on the streams the process created before, and most of the
+ *     gain is lost.  Two branches were the fastest in every placement measured.
+ *   - a run leaves nothing unordered until it holds `packed_capture_min_run` calls (tuning key, default 8; 1 = from the second
+ *     call on).  A graph with branches is replayed at about 2 us of host time per node, for every node of the graph; that pays
+ *     where these calls are most of the graph (a stack of linears) and not in a decoder's graph of thousands of short framework
+ *     kernels, whose runs of these calls (q/k/v, gate/up) are short.  Below the threshold the graph is the one stream order gives.
+ *   - results are the same bits either way.  A graph captured this way has parallel branches: replay it with at least the
+ *     default number of hardware queues.
+ *   - should the runtime refuse the capture calls (hipStreamGetCaptureInfo_v2, hipStreamUpdateCaptureDependencies), the
+ *     launch goes out stream-ordered, the feature switches itself off for the process and aqlm_hip_last_error() says so;
+ *     the call fails only if a launch that was already moved can no longer be joined to the stream.
+ * aqlm_hip_capture_overlap_stats: out[0..5] = calls seen on a capturing stream, relaxed (no edge to any call of the run), kept
+ * for a conflict, kept for the window, runs started or broken, capture-call failures; process-wide, since the last reset.
+ * NULL resets the counters.  Returns 0.
+ */
+int aqlm_hip_capture_overlap_stats(uint64_t out[6]);
 
 /*
  * Tuning / experiment knobs (process-wide, not part of the reference surface; defaults are the shipped
