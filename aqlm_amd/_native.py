@@ -196,6 +196,8 @@ SIGNATURES = {
     "aqlm_hip_unpack_1x16": (_ci, [_descp, _vp, _vp, _vp]),
     "aqlm_hip_dequant_1x16_packed": (_ci, [_descp, _vp, _vp, _vp, _vp, _ci, _vp]),
     "aqlm_hip_gemv_1x16_packed": (_ci, [_descp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _cl, _cl, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_gemv_1x16_packed_image": (_ci, [_descp, _ci, _ci, _sz, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(_ci)]),
     "aqlm_hip_gemv_1x16_packed_cells": (_ci, [_descp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _cl, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_chain": (_ci, [_descp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _cl, _cl, _ci, _vp, _sz, _descp, _vp, _vp, _vp]),
     "aqlm_hip_gemv_1x16_packed_partials": (_ci, [_descp, _vp, _vp, _vp, _ci, _cl, _ci, _vp, _sz, _vp]),
@@ -302,3 +304,21 @@ def capture_overlap_stats(reset: bool = False) -> dict:
     if reset:
         check(lib.aqlm_hip_capture_overlap_stats(None), "capture_overlap_stats")
     return dict(zip(CAPTURE_OVERLAP_FIELDS, (int(v) for v in out)))
+
+
+def packed_image(desc: "PackedDesc", rows: int = 1, dtype: int = F16):
+    """-> (dynamic LDS bytes, x window) of the packed 1x16 launch for `rows` input rows of the layer `desc` describes, under the
+    current tuning (aqlm_hip_gemv_1x16_packed_image); window 8208 = compact, 65520 = full, 0 = slice first.  No device needed."""
+    lds, win = _sz(0), ctypes.c_uint32(0)
+    check(lib.aqlm_hip_gemv_1x16_packed_image(ctypes.byref(desc), int(rows), int(dtype), 0, ctypes.byref(lds), ctypes.byref(win), None),
+          "packed_image")
+    return int(lds.value), int(win.value)
+
+
+def packed_image_blocks_per_cu(desc: "PackedDesc", rows: int = 1, dtype: int = F16, probe_lds_bytes: int = 0) -> int:
+    """Workgroups of that launch's kernel the runtime lets share a CU (hipOccupancyMaxActiveBlocksPerMultiprocessor at the launch's
+    block size) at `probe_lds_bytes` of dynamic LDS, 0 = the launch's own.  Needs the current device."""
+    n = _ci(0)
+    check(lib.aqlm_hip_gemv_1x16_packed_image(ctypes.byref(desc), int(rows), int(dtype), int(probe_lds_bytes), None, None, ctypes.byref(n)),
+          "packed_image")
+    return n.value

@@ -76,6 +76,7 @@ static int* tuning_slot(const char* key) {
   if (!strcmp(key, "packed_entry_bytes")) return &t.packed_entry_bytes;
   if (!strcmp(key, "packed_debug")) return &t.packed_debug;
   if (!strcmp(key, "packed_fill_rotate")) return &t.packed_fill_rotate;
+  if (!strcmp(key, "packed_compact_window")) return &t.packed_compact_window;
   if (!strcmp(key, "packed_capture_window")) return &t.packed_capture_window;
   if (!strcmp(key, "packed_capture_min_run")) return &t.packed_capture_min_run;
   if (!strcmp(key, "packed_pipe")) return &t.packed_pipe;

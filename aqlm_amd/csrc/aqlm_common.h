@@ -174,6 +174,7 @@ struct Tuning {
   int packed_prefetch = 0;       // packed 1x16 kernel: steps of the entry stream in flight per wave (4 / 8); 0 = heuristic
   int packed_pipe = 1;           // shared-input launches of batch 1: 1 = one workgroup per CU walks the segments with double-buffered slices
   int packed_fill_rotate = 1;    // packed 1x16 kernel: 1 = the workgroups that share a codebook slice start their LDS fill at different pieces
+  int packed_compact_window = 0; // packed 1x16 kernel, one-row launches whose x fits 8208 bytes (<= 4096 features): 0 = the compact x window (two layers' workgroups share a CU), 1 = always the 64 KiB window (A/B runs)
   int lut_waves = 0;             // 8 x 8 look-up-table matvec: waves per workgroup (8 / 16); 0 = default
   int packed_prefetch_waves = 0; // chain prefetch: extra waves per workgroup that pull the next layer towards L2 (0 = 2, -1 = off)
   int packed_capture_window = capture_overlap::kDefaultWindow;  // packed 1x16 matvecs captured into a graph: consecutive launches that share no memory and may run side by side (1..8; capture_overlap.h); 1 = every launch after the previous one

@@ -85,7 +85,7 @@
   X(gemv_1x16_packed_cells) X(gemv_1x16_packed) X(gemv_1x16_packed_chain) X(gemv_1x16_packed_partials)                         \
   X(gemv_1x16_packed_publish) X(gemv_1x16_packed_multi) X(gemv_1x16_packed_multi_cells) X(gemv_1x16_routed_packed_lds_bytes)   \
   X(routed_packed_entry_fill) X(gemv_1x16_routed_packed_geometry) X(gemv_1x16_routed_packed_supported)                         \
-  X(gemv_1x16_routed_packed)
+  X(gemv_1x16_routed_packed) X(gemv_1x16_packed_image)
 #define PK_TWIN_DECLARE(name) extern "C" __attribute__((visibility("hidden"))) decltype(aqlm_hip_##name) aqlm_hip_g16_##name;
 PK_TWIN_ENTRIES(PK_TWIN_DECLARE)
 #undef PK_TWIN_DECLARE

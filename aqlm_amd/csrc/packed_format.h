@@ -28,6 +28,10 @@ constexpr int PK_VERSION = 7;
 constexpr int PK_MIN_GROUPS = PK_NG / 2;     // variable geometry: workgroups of a slice (its rows per group stay <= 2 x the uniform count)
 constexpr int PK_VG_MIN_ROWS = 512;          // ... and only layers of at least this many rows (every group owns >= 1 row)
 constexpr uint32_t PK_XWIN_FULL = 65520;     // x window of the batch-1 kernel (x first, slice behind it)
+// ... and the compact one: the window is reserved address space, not data, and with 64 KiB of it no second workgroup fits the
+// CU.  The x image of a one-row launch is in_groups vectors (the fill is guarded by idx < x16) plus the null slot behind them,
+// so (4096 / 8 + 1) * 16 bytes hold inputs of <= 4096 features exactly; then two layers' workgroups share a CU.
+constexpr uint32_t PK_XWIN_COMPACT = (4096u / 8u + 1u) * 16u;  // 8208
 // accumulator cell of the fused finalize: [arrivals : CNT bits][non-finite contributions : CNT bits][fixed-point sum]
 constexpr int PK_CNT_BITS = PK_S_LOG + 1;                       // counts 0 .. PK_S
 constexpr unsigned long long PK_CNT_MASK = (1ull << PK_CNT_BITS) - 1ull;
@@ -43,6 +47,10 @@ static_assert(PK_FIX_BITS + 1 + PK_S_LOG <= 63 - 2 * (PK_S_LOG + 1), "PK_S adden
 // pattern is rotated by 4 c: an entry can read the copy whose bank group is still free in its service group.
 __host__ __device__ static inline int pk_x_stride(int in_groups) { return ((in_groups + 1 + 11) & ~15) + 4; }  // >= in_groups + 1
 static inline int pk_max_x_copies(int in_groups) { return std::max(1, std::min(4, 4095 / pk_x_stride(in_groups))); }
+// bytes of the x image of a one-row launch: the last copy's in_groups vectors and its null slot end it
+static inline uint32_t pk_x_image_bytes(int in_groups, int XC) {
+  return ((uint32_t)(XC - 1) * (uint32_t)pk_x_stride(in_groups) + (uint32_t)in_groups + 1u) * PK_VB;
+}
 // start row of a column: 15 bits over the low nibbles of its first lane-step (entry 0: bits 1-3, entries 1-3: bits 0-3)
 __host__ __device__ static inline uint32_t pk_get_start_row(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3) {
   return ((e0 >> 1) & 7u) | ((e1 & 15u) << 3) | ((e2 & 15u) << 7) | ((e3 & 15u) << 11);

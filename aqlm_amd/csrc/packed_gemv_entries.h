@@ -68,9 +68,9 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
   }
   const uint32_t rotate = tuning().packed_fill_rotate ? 1u : 0u;
   auto launch = [&](auto kern, auto lds_map) -> int {
-    const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, npw);
+    const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, npw, L.NW);
     if (lds > 160 * 1024) { npw = 0; }
-    const size_t lds_final = decltype(lds_map)::total(L.in_groups, L.RG, npw);
+    const size_t lds_final = decltype(lds_map)::total(L.in_groups, L.RG, npw, L.NW);
     if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_final)) return e;
     PackedGemvRest r = rest;
     r.pub = fused.pub;
@@ -88,6 +88,7 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     return check_hip(hipGetLastError(), "gemv_1x16_packed launch");
   };
   const bool sf = nb == 1 && packed_b1_slice_first(L.in_groups, L.RG);
+  const bool compact = nb == 1 && packed_b1_compact(L, packed_b1_pd(L));
 #if AQLM_PK_G == 8
   if (L.G.vg) {  // variable geometry: its own kernels (4-byte entries, ring depth 3 / 4, no chain prefetch, no publish)
     if (fused.pub != nullptr || L.EB != 4) {
@@ -98,36 +99,18 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     uint32_t ns[4] = {0u, 0u, 0u, 0u};
     for (int i = 0; i < PK_S; ++i) ns[i >> 2] |= (uint32_t)L.G.first[i] << ((i & 3) * 8);  // first stream of every slice (< 256)
     auto launch_vg = [&](auto kern, auto lds_map) -> int {
-      const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, 0);
+      const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, 0, L.NW);
       if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
       hipLaunchKernelGGL(kern, dim3(PK_NST), dim3(L.NW * 64), lds, stream, cb, x, ent, (uint32_t)(L.off_ent - L.off_rowstart),
                          (uint32_t)L.in_groups | ((uint32_t)L.RG << 12), (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16),
                          L.M, ns[0], ns[1], ns[2], ns[3], rest);
       return check_hip(hipGetLastError(), "gemv_1x16_packed (variable geometry) launch");
     };
-#define AQLM_PK_VG(TT, BB, PP, XW) launch_vg(gemv_1x16_packed_vg_kernel<TT, BB, PP, XW>, PackedLds<BB, XW>{})
-#define AQLM_PK_VG_CASE(BB) \
-  case BB:                  \
-    return dtype == AQLM_HIP_F16 ? AQLM_PK_VG(F16, BB, 4, PK_XWIN_FULL) : AQLM_PK_VG(BF16, BB, 4, PK_XWIN_FULL);
-    switch (nb) {
-      case 1:
-        if (sf) return dtype == AQLM_HIP_F16 ? AQLM_PK_VG(F16, 1, 3, 0u) : AQLM_PK_VG(BF16, 1, 3, 0u);
-        return dtype == AQLM_HIP_F16 ? AQLM_PK_VG(F16, 1, 3, PK_XWIN_FULL) : AQLM_PK_VG(BF16, 1, 3, PK_XWIN_FULL);
-      AQLM_PK_VG_CASE(2)
-      AQLM_PK_VG_CASE(3)
-      AQLM_PK_VG_CASE(4)
-      AQLM_PK_VG_CASE(5)
-      AQLM_PK_VG_CASE(6)
-      AQLM_PK_VG_CASE(7)
-      AQLM_PK_VG_CASE(8)
-    }
-#undef AQLM_PK_VG_CASE
-#undef AQLM_PK_VG
-    return AQLM_HIP_E_INVALID;
+    return dispatch_packed_vg(dtype, nb, sf, compact, launch_vg);
   }
 #endif
-  if (fused.pub != nullptr) return dispatch_packed<PublishKernels>(dtype, nb, pick_pd(L), L.EB, sf, launch);
-  return dispatch_packed<SingleKernels>(dtype, nb, pick_pd(L), L.EB, sf, launch);
+  if (fused.pub != nullptr) return dispatch_packed<PublishKernels>(dtype, nb, pick_pd(L), L.EB, sf, false, launch);
+  return dispatch_packed<SingleKernels>(dtype, nb, pick_pd(L), L.EB, sf, compact, launch);
 }
 
 static int packed_check_args(const char* who, const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
@@ -286,6 +269,42 @@ extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_partials)(const aqlm_hip_packed_
   }
   return packed_launch_main(L, packed, codebook, (const uint16_t*)x, batch, x_row_stride, dtype, workspace, workspace_bytes,
                             (hipStream_t)stream_, "aqlm_hip_gemv_1x16_packed_partials");
+}
+
+// What packed_launch_main would launch for `rows` rows (ordinary form: no publish, no prefetch waves), read off the kernel
+// instance and the LDS map its dispatch picks -- no second copy of the rule.
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_image)(const aqlm_hip_packed_desc* desc, int rows, int dtype, size_t probe_lds_bytes,
+                                                size_t* lds_bytes, uint32_t* x_window, int* blocks_per_cu) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed_image, desc, rows, dtype, probe_lds_bytes, lds_bytes, x_window, blocks_per_cu);
+  PackedLayout L;
+  if (!desc_layout(desc, L) || rows < 1 || rows > AQLM_HIP_MAX_GEMV_BATCH || (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16)) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_image: invalid packed descriptor, rows outside 1..%d or a dtype other than float16 / "
+                   "bfloat16", AQLM_HIP_MAX_GEMV_BATCH);
+    return AQLM_HIP_E_INVALID;
+  }
+  const int max_b = packed_max_batch(L.in_groups, L.RG);
+  if (max_b == 0) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_image: layer does not fit the LDS image (in_features %d)", desc->in_features);
+    return AQLM_HIP_E_UNSUPPORTED;
+  }
+  const int nb = std::min(rows, max_b);
+  auto visit = [&](auto kern, auto lds_map) -> int {
+    using Map = decltype(lds_map);
+    const size_t lds = Map::total(L.in_groups, L.RG, 0, L.NW);
+    if (lds_bytes) *lds_bytes = lds;
+    if (x_window) *x_window = Map::XFIRST ? Map::SLICE : 0u;
+    if (!blocks_per_cu) return 0;
+    const size_t ask = probe_lds_bytes ? probe_lds_bytes : lds;
+    if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ask)) return e;
+    return check_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kern, L.NW * 64, ask),
+                     "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+  };
+  const bool sf = nb == 1 && packed_b1_slice_first(L.in_groups, L.RG);
+  const bool compact = nb == 1 && packed_b1_compact(L, packed_b1_pd(L));
+#if AQLM_PK_G == 8
+  if (L.G.vg) return dispatch_packed_vg(dtype, nb, sf, compact, visit);
+#endif
+  return dispatch_packed<SingleKernels>(dtype, nb, pick_pd(L), L.EB, sf, compact, visit);
 }
 
 extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_publish)(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
@@ -509,7 +528,7 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
     if (int e = check_hip(hipGetLastError(), "gemv_1x16_packed_multi launch")) return e;
     return relax.launched();
   };
-  if (int e = dispatch_packed<MultiKernels>(dtype, batch, pd, eb, batch == 1 && packed_b1_slice_first(mp.in_groups, max_rg), launch)) return e;
+  if (int e = dispatch_packed<MultiKernels>(dtype, batch, pd, eb, batch == 1 && packed_b1_slice_first(mp.in_groups, max_rg), false, launch)) return e;
   if (fused) return 0;
   if (dtype == AQLM_HIP_F16)
     hipLaunchKernelGGL(gemv_1x16_packed_finalize_multi<F16>, dim3(fblocks), dim3(256), 0, stream, fm);

@@ -81,6 +81,10 @@ __device__ __forceinline__ void lds_asm_wait(uint32_t& a, uint32_t& b, uint32_t&
 
 // LDS map (byte offsets from the start of the workgroup's LDS, which is address 0: the kernel has no static LDS).
 //   B == 1: x at 0 (XWIN bytes reserved), slice at XWIN, bookkeeping behind the slice   (x-first: both reads cost one op)
+//           XWIN = PK_XWIN_FULL (65520): any x the format allows; image 135-140 KiB, one workgroup per CU
+//           XWIN = PK_XWIN_COMPACT (8208): x of <= 4096 features; with the bookkeeping sized by the launch (TIGHT) the image is
+//           76-83 KiB, so a workgroup of ANOTHER layer fits the CU beside it (4096->4096 + 4096->11008: 160 640 of 163 840 bytes)
+//           XWIN = 0: slice first, as for B > 1 (layers whose row tables do not fit behind a window)
 //   B  > 1: slice at 0, then B planes x[b][j] of XP = (in_groups + 1) * 16 bytes (a plane keeps the bank pattern of
 //           the single-row case: slot j -> bank group j % 16; interleaving the rows would leave 16 / B groups), bookkeeping
 //   bookkeeping: rowstart[RG + 1] u32 (LDS-DMA copy of the stream's row starts), rowval[B][RG + 1] f32 (sum of the
@@ -95,18 +99,26 @@ struct PackedLds {
   __host__ __device__ static uint32_t rowstart(int in_groups) {
     return XFIRST ? XWIN + PK_SLICE_BYTES : PK_SLICE_BYTES + plane(in_groups) * B;
   }
-  __host__ __device__ static uint32_t rs_bytes(int RG) { return ((uint32_t)(RG + 1) * 4u + 1023u) & ~1023u; }  // whole DMA pieces
+  // TIGHT (the compact window): the image is meant to share the CU with another layer's, so the bookkeeping is sized by what
+  // the launch uses -- the row-start table in the 256-byte pieces its dword DMA is issued in (a piece's lanes are guarded by
+  // idx < RG + 1), colend for the `nw` waves of the stream (columns >= nw * 64 are neither written nor read) -- not by the
+  // worst case.  Every other image ignores `nw` and keeps the map it had.
+  static constexpr bool TIGHT = XFIRST && XWIN < PK_XWIN_FULL;
+  __host__ __device__ static uint32_t rs_bytes(int RG) {  // whole DMA pieces
+    return TIGHT ? ((uint32_t)(RG + 1) * 4u + 255u) & ~255u : ((uint32_t)(RG + 1) * 4u + 1023u) & ~1023u;
+  }
   __host__ __device__ static uint32_t rowval(int in_groups, int RG) { return rowstart(in_groups) + rs_bytes(RG); }
   __host__ __device__ static uint32_t colend(int in_groups, int RG) { return rowval(in_groups, RG) + (uint32_t)B * (RG + 1) * 4u; }
-  __host__ __device__ static uint32_t xmax(int in_groups, int RG) {  // 16-B aligned: read with ds_read_b128
-    return (colend(in_groups, RG) + (uint32_t)B * PK_MAX_NW * 64 * 4 + 15u) & ~15u;
+  __host__ __device__ static uint32_t xmax(int in_groups, int RG, int nw) {  // 16-B aligned: read with ds_read_b128
+    return (colend(in_groups, RG) + (uint32_t)B * (TIGHT ? (uint32_t)nw : (uint32_t)PK_MAX_NW) * 64 * 4 + 15u) & ~15u;
   }
-  __host__ __device__ static uint32_t dump(int in_groups, int RG) {  // 1 KiB landing zone per prefetch wave (LDS-DMA needs a destination)
-    return (xmax(in_groups, RG) + (uint32_t)B * PK_MAX_NW * 4u + 15u) & ~15u;
+  __host__ __device__ static uint32_t dump(int in_groups, int RG, int nw) {  // 1 KiB landing zone per prefetch wave (LDS-DMA needs a destination)
+    return (xmax(in_groups, RG, nw) + (uint32_t)B * PK_MAX_NW * 4u + 15u) & ~15u;
   }
-  __host__ __device__ static size_t total(int in_groups, int RG, int npw = 0) {
-    return npw ? (size_t)dump(in_groups, RG) + (size_t)npw * 1024
-               : (size_t)xmax(in_groups, RG) + (size_t)B * PK_MAX_NW * 4;  // xmax[B][16 waves] u32: largest |x| seen by each wave (fused finalize)
+  // nw: the waves of the stream (PackedLayout::NW; for the multi launch, whose images are never TIGHT, any value)
+  __host__ __device__ static size_t total(int in_groups, int RG, int npw = 0, int nw = PK_MAX_NW) {
+    return npw ? (size_t)dump(in_groups, RG, nw) + (size_t)npw * 1024
+               : (size_t)xmax(in_groups, RG, nw) + (size_t)B * PK_MAX_NW * 4;  // xmax[B][16 waves] u32: largest |x| seen by each wave (fused finalize)
   }
 };
 
@@ -198,7 +210,7 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   const bool pfw = !NOPF && wave >= NWD;
   if (pfw) {
     const int pw = wave - NWD;
-    const uint32_t dump = LDS::dump(p.in_groups, p.RG) + (uint32_t)pw * 1024u;
+    const uint32_t dump = LDS::dump(p.in_groups, p.RG, p.NW) + (uint32_t)pw * 1024u;
     const uint8_t* nsrc = p.next_ent + (size_t)block * p.next_block_bytes;
     for (uint32_t off = (uint32_t)pw * 1024u; off < p.next_block_bytes; off += (uint32_t)p.NPW * 1024u)
       __builtin_amdgcn_global_load_lds((gbl_void_ptr)(nsrc + off + lane * 16), (lds_void_ptr)(size_t)dump, 16, 0, AUX_NT);
@@ -270,7 +282,7 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   if (tid < B * (int)(PK_VB / 16))  // the null entries' x: PK_VB zero bytes per row of x
     *reinterpret_cast<u32x4*>(smem_raw + LDS::X + (uint32_t)(tid / (int)(PK_VB / 16)) * XP + (uint32_t)p.in_groups * PK_VB +
                               (uint32_t)(tid % (int)(PK_VB / 16)) * 16u) = u32x4{0u, 0u, 0u, 0u};
-  const uint32_t xmax_off = LDS::xmax(p.in_groups, p.RG);
+  const uint32_t xmax_off = LDS::xmax(p.in_groups, p.RG, p.NW);
   if (tid < B * PK_MAX_NW) *reinterpret_cast<uint32_t*>(smem_raw + xmax_off + (uint32_t)tid * 4u) = 0u;  // slots of absent waves
   AQLM_TRACE(1);  // every load of the prologue has been issued
   // (5) the slice and x are older in the VMEM queue than the PD ring loads: wait for everything BUT the ring, so the

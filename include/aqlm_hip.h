@@ -402,6 +402,20 @@ int aqlm_hip_gemv_1x16_packed(const aqlm_hip_packed_desc* desc, void* packed, co
                               void* stream);
 
 /*
+ * The LDS image of the launch that aqlm_hip_gemv_1x16_packed / _cells makes for `rows` input rows of this layer under the current
+ * tuning (no launch, no device needed): *lds_bytes = its dynamic LDS (of one launch: more rows than fit one image go out in
+ * several), *x_window = the bytes reserved for x in front of the codebook slice -- 8208 (the compact window: one row, inputs of
+ * <= 4096 features, tuning key packed_compact_window at 0), 65520 (the full window) or 0 (slice first: two and more rows, tall
+ * layers).  A compact image leaves room on the CU for a workgroup of another layer, which is what lets captured launches
+ * (capture overlap, below) run side by side.  With `blocks_per_cu` the runtime is asked as well (this needs a device):
+ * hipOccupancyMaxActiveBlocksPerMultiprocessor for the kernel instance that launch would run, at its block size (desc->waves x 64)
+ * and at `probe_lds_bytes` of dynamic LDS (0: the launch's own *lds_bytes) -- how many such workgroups the runtime lets share a CU.
+ * Every output pointer may be NULL.  0, AQLM_HIP_E_INVALID / _UNSUPPORTED, or the HIP error.
+ */
+int aqlm_hip_gemv_1x16_packed_image(const aqlm_hip_packed_desc* desc, int rows, int dtype, size_t probe_lds_bytes, size_t* lds_bytes,
+                                    uint32_t* x_window, int* blocks_per_cu);
+
+/*
  * Re-entrant form of the single-kernel finalize: the accumulator cells are the CALLER's -- `cells` = at least
  * batch * out_features * 8 bytes, 8-B aligned, zero-filled once; every call leaves them zero.  The packed buffer is only
  * read, so the same layer may run on several streams / from several host threads at once, like the reference's stateless
