@@ -229,6 +229,7 @@ SIGNATURES = {
     "aqlm_hip_set_tuning": (_ci, [ctypes.c_char_p, _ci]),
     "aqlm_hip_get_tuning": (_ci, [ctypes.c_char_p, ctypes.POINTER(_ci)]),
     "aqlm_hip_capture_overlap_stats": (_ci, [ctypes.POINTER(ctypes.c_uint64)]),
+    "aqlm_hip_capture_overlap_stats_ex": (_ci, [ctypes.POINTER(ctypes.c_uint64), _ci]),
 }
 
 
@@ -293,16 +294,17 @@ def get_tuning(key: str) -> int:
     return v.value
 
 
-CAPTURE_OVERLAP_FIELDS = ("seen", "relaxed", "kept_conflict", "kept_window", "runs_broken", "api_failures")
+CAPTURE_OVERLAP_FIELDS = ("seen", "relaxed", "kept_conflict", "kept_window", "runs_broken", "api_failures",
+                          "merged", "merge_refused", "nodes_added")
 
 
 def capture_overlap_stats(reset: bool = False) -> dict:
     """Counters of the packed matvec launches made on a stream under capture (aqlm_hip_capture_overlap_stats);
     `reset` zeroes them after reading."""
-    out = (ctypes.c_uint64 * 6)()
-    check(lib.aqlm_hip_capture_overlap_stats(out), "capture_overlap_stats")
+    out = (ctypes.c_uint64 * len(CAPTURE_OVERLAP_FIELDS))()
+    check(lib.aqlm_hip_capture_overlap_stats_ex(out, len(out)), "capture_overlap_stats")
     if reset:
-        check(lib.aqlm_hip_capture_overlap_stats(None), "capture_overlap_stats")
+        check(lib.aqlm_hip_capture_overlap_stats_ex(None, 0), "capture_overlap_stats")
     return dict(zip(CAPTURE_OVERLAP_FIELDS, (int(v) for v in out)))
 
 

@@ -79,6 +79,7 @@ static int* tuning_slot(const char* key) {
   if (!strcmp(key, "packed_compact_window")) return &t.packed_compact_window;
   if (!strcmp(key, "packed_capture_window")) return &t.packed_capture_window;
   if (!strcmp(key, "packed_capture_min_run")) return &t.packed_capture_min_run;
+  if (!strcmp(key, "packed_capture_merge")) return &t.packed_capture_merge;
   if (!strcmp(key, "packed_pipe")) return &t.packed_pipe;
   if (!strcmp(key, "packed_prefetch_waves")) return &t.packed_prefetch_waves;
   if (!strcmp(key, "packed_dequant_by_xcd")) return &t.packed_dequant_by_xcd;
@@ -94,7 +95,9 @@ namespace {
 struct CaptureOverlapState {
   std::mutex mu;
   capture_overlap::Planner planner;
-  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};  // seen, relaxed, kept for a conflict, kept for the window, runs broken, API failures
+  // seen, relaxed, kept for a conflict, kept for the window, runs broken, API failures; then: launches that joined a node
+  // (also counted as kept for the window), rewrites of a node the runtime refused, launches that added a node of their own
+  uint64_t stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool off = false;                        // a capture call failed once: every launch as issued from then on
 };
 CaptureOverlapState& capture_state() {
@@ -152,16 +155,14 @@ CaptureRelax::CaptureRelax(hipStream_t stream) : stream_(stream) {
   const int window = tuning().packed_capture_window;
   std::lock_guard<std::mutex> lock(s.mu);
   ++s.stats[0];
-  if (window <= 1) ++s.stats[3];  // exactly the graph as issued: nothing to plan
+  ++s.stats[8];  // (a launch that joins a node takes it back)
+  if (window <= 1 && tuning().packed_capture_merge <= 1) ++s.stats[3];  // exactly the graph as issued: nothing to plan
   else active_ = true;
 }
 
-void CaptureRelax::begin() {
-  if (!active_ || begun_) return;
-  begun_ = true;
+// counts the plan and makes the stream wait for what it names (an ordinary launch follows); caller holds the mutex
+void CaptureRelax::apply_plan() {
   CaptureOverlapState& s = capture_state();
-  std::lock_guard<std::mutex> lock(s.mu);
-  plan_ = s.planner.run(id_).plan(before_.data(), before_.size(), fp, tuning().packed_capture_window, tuning().packed_capture_min_run);
   ++s.stats[plan_.kind == capture_overlap::kBroken ? 4 : (int)plan_.kind];
   if (plan_.kind == capture_overlap::kBroken || same_nodes(plan_.deps, before_)) return;
   const hipError_t e = set_capture_deps(stream_, plan_.deps);
@@ -173,6 +174,49 @@ void CaptureRelax::begin() {
   fail("hipStreamUpdateCaptureDependencies", e);
   s.planner.run(id_).reset();
   active_ = false;
+}
+
+int CaptureRelax::begin(uint64_t key, const void* member, size_t member_bytes) {
+  if (!active_ || begun_) return 0;
+  begun_ = true;
+  const int merge = std::min(std::max(tuning().packed_capture_merge, 1), capture_overlap::kMaxMerge);
+  if (merge > 1 && key != 0 && member) {
+    key_ = key;
+    member_.assign(static_cast<const unsigned char*>(member), static_cast<const unsigned char*>(member) + member_bytes);
+  }
+  CaptureOverlapState& s = capture_state();
+  std::lock_guard<std::mutex> lock(s.mu);
+  plan_ = s.planner.run(id_).plan(before_.data(), before_.size(), fp, tuning().packed_capture_window, tuning().packed_capture_min_run,
+                                  key_, merge);
+  if (plan_.merge) return plan_.member;  // counted by join()
+  apply_plan();
+  return 0;
+}
+
+bool CaptureRelax::join(const hipKernelNodeParams* node) {
+  if (!active_ || !begun_ || done_ || !plan_.merge) return false;
+  CaptureOverlapState& s = capture_state();
+  std::lock_guard<std::mutex> lock(s.mu);
+  capture_overlap::Run& run = s.planner.run(id_);
+  // The node has no dependents (it is in the tail) and stays where it is in the graph: only what it launches changes, and
+  // the runtime copies the arguments.  The stream's dependency set is the tail before and after.
+  // (A plan that another launch of this capture has overtaken is not acted on: the node is only touched when the commit holds.)
+  const hipError_t e = node && run.latest(plan_)
+                           ? hipGraphKernelNodeSetParams(reinterpret_cast<hipGraphNode_t>(static_cast<uintptr_t>(plan_.target)), node)
+                           : hipErrorInvalidValue;
+  if (e == hipSuccess && run.commit(plan_, plan_.target, fp, member_.data(), member_.size())) {
+    ++s.stats[3];
+    ++s.stats[6];
+    --s.stats[8];
+    done_ = true;
+    return true;
+  }
+  // refused (the node is as it was: the call changes it or fails), or the plan went stale: today's edge instead
+  (void)hipGetLastError();
+  ++s.stats[7];
+  plan_ = run.plan(before_.data(), before_.size(), fp, tuning().packed_capture_window, tuning().packed_capture_min_run, key_, 1);
+  apply_plan();
+  return false;
 }
 
 int CaptureRelax::launched() {
@@ -187,7 +231,7 @@ int CaptureRelax::launched() {
   hipError_t err = hipSuccess;
   const bool read = read_capture(stream_, capturing, id, now, err);
   std::vector<capture_overlap::NodeId> want;
-  if (read && capturing && id == id_ && now.size() == 1 && run.commit(plan_, now[0], std::move(fp))) {
+  if (read && capturing && id == id_ && now.size() == 1 && run.commit(plan_, now[0], std::move(fp), member_.data(), member_.size())) {
     want = run.tail();
   } else {
     // the new node is not known: everything the call found, and whatever the stream names now
@@ -262,14 +306,24 @@ extern "C" int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2
   return aqlm::check_hip(hipGetLastError(), "checksum launch");
 }
 
-extern "C" int aqlm_hip_capture_overlap_stats(uint64_t out[6]) {
+static int capture_overlap_stats(uint64_t* out, int n) {
   aqlm::CaptureOverlapState& s = aqlm::capture_state();
   std::lock_guard<std::mutex> lock(s.mu);
-  for (int i = 0; i < 6; ++i) {
-    if (out) out[i] = s.stats[i];
-    else s.stats[i] = 0;
+  for (int i = 0; i < 9; ++i) {
+    if (!out) s.stats[i] = 0;
+    else if (i < n) out[i] = s.stats[i];
   }
   return 0;
+}
+
+extern "C" int aqlm_hip_capture_overlap_stats(uint64_t out[6]) { return capture_overlap_stats(out, 6); }
+
+extern "C" int aqlm_hip_capture_overlap_stats_ex(uint64_t* out, int count) {
+  if (out && (count < 0 || count > 9)) {
+    aqlm::set_last_error("aqlm_hip_capture_overlap_stats_ex: count must be 0..9 (got %d)", count);
+    return AQLM_HIP_E_INVALID;
+  }
+  return capture_overlap_stats(out, count);
 }
 
 extern "C" int aqlm_hip_abi_version(void) { return AQLM_HIP_ABI_VERSION; }

@@ -179,6 +179,7 @@ struct Tuning {
   int packed_prefetch_waves = 0; // chain prefetch: extra waves per workgroup that pull the next layer towards L2 (0 = 2, -1 = off)
   int packed_capture_window = capture_overlap::kDefaultWindow;  // packed 1x16 matvecs captured into a graph: consecutive launches that share no memory and may run side by side (1..8; capture_overlap.h); 1 = every launch after the previous one
   int packed_capture_min_run = capture_overlap::kDefaultMinRun;  // ... launches an uninterrupted run of them must hold before any is relaxed (a graph with branches costs host time per node: capture_overlap.h); 1 = from the second launch on
+  int packed_capture_merge = capture_overlap::kDefaultMerge;  // ... launches of one kernel instance that may share a graph node, run by the grouped kernel (1..8; capture_overlap.h, "Grouped launches"); 1 = every launch a node of its own
   int packed_dequant_by_xcd = 1; // aqlm_hip_dequant_1x16_packed, grid order: 1 = by the measured rule (16-B vectors: the streams that run together on an XCD are the slices of one row group, so their partial-line stores meet in one L2; 32-B vectors: stream-major like the unpack kernel), 0 = always stream-major, 2 = always by XCD (A/B runs)
 };
 Tuning& tuning();
@@ -197,15 +198,25 @@ class CaptureRelax {
   CaptureRelax& operator=(const CaptureRelax&) = delete;
   bool capturing() const { return active_; }
   capture_overlap::Footprint fp;
-  void begin();
-  // After the launch (later launches of the call: no effect).  0, or the error when the stream could not be made to wait
-  // for the launches that ran beside this one: the capture would be wrong, so the call fails.
+  // `key` != 0: the launch is one grid of a kernel whose grouped form can run several such launches as one (capture_overlap.h,
+  // "Grouped launches"); the key names the kernel instance, block size and LDS bytes, `member` is what the grouped launch needs
+  // to know of this one.  When begin() returns n > 0 the launch may join a node that holds n launches already: group() is
+  // their members in order, and the caller builds the node for n + 1 and hands it to join().  join() false: the runtime
+  // refused the rewrite (counted, not an error); the stream is set up for an ordinary launch and the caller makes one.
+  int begin(uint64_t key = 0, const void* member = nullptr, size_t member_bytes = 0);
+  const std::vector<unsigned char>& group() const { return plan_.payload; }
+  bool join(const hipKernelNodeParams* node);  // (null: the caller cannot build the node)
+  // After the launch (later launches of the call: no effect; nor after a join()).  0, or the error when the stream could not
+  // be made to wait for the launches that ran beside this one: the capture would be wrong, so the call fails.
   int launched();
 
  private:
   void fail(const char* what, hipError_t e);
+  void apply_plan();
   hipStream_t stream_;
   bool active_ = false, begun_ = false, done_ = false, changed_ = false;
+  uint64_t key_ = 0;
+  std::vector<unsigned char> member_;
   unsigned long long id_ = 0;
   std::vector<capture_overlap::NodeId> before_;  // the stream's dependency set as the call found it
   capture_overlap::Plan plan_;

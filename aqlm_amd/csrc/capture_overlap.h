@@ -21,6 +21,18 @@
 //      C's.)  A footprint that would outgrow kMaxRanges is handled like a broken run: the launch waits for the whole tail.
 //   3. after the launch the caller sets the stream's dependency set to the tail: whatever is captured next, by anyone, waits
 //      for every launch it could observe.
+//
+// Grouped launches.  Every node of a replayed graph pays a dependent-launch boundary, and the next node of a chain starts only
+// when the last workgroup of the previous one has left; inside one launch the dispatcher backfills a CU the moment a workgroup
+// leaves it.  So a launch may JOIN the node of a tail entry instead of adding one, when the caller can run both as one grid: it
+// hands in a KEY (kernel instance, block size, LDS bytes; 0 = launches alone) and only equal keys share a node, at most
+// `merge_max` launches each.  Where step 2 would answer "no hazard, tail full: wait for the oldest entry", the oldest entry
+// with the launch's key and room left takes the launch in: no node is added, the entry's footprint absorbs the launch's (it
+// has been checked against every tail entry's footprint, that entry's included, so it may run beside all of them and after
+// everything the entry's node waits for), and the entry becomes the youngest of the tail, so that the next launch of another
+// key finds its own partner first.  The caller rewrites the node (Plan::target, Plan::member); the members' launch parameters
+// travel with the entry as an opaque payload.  A full group, another key, a footprint that would outgrow kMaxRanges: the
+// answers of step 2 as they were.  The stream's dependency set after a joined launch is the tail, the same nodes as before.
 #ifndef AQLM_CAPTURE_OVERLAP_H_
 #define AQLM_CAPTURE_OVERLAP_H_
 
@@ -49,6 +61,11 @@ constexpr int kDefaultWindow = 2;
 // sees tells the two apart except how long the library's launches go uninterrupted: a run relaxes nothing until it is this
 // long, which q/k/v, gate/up and the like never are.
 constexpr int kDefaultMinRun = 8;
+constexpr int kMaxMerge = 8;  // launches that may share one node (the grouped kernel's segments)
+// Measured on the 64-layer decode step at a window of 2 (profiles/capture_merge.json): 1 launch per node 357-359 us, 2: 377,
+// 3: 361, 4: 345, 5: 336, 6: 334, 8: 338.  Small groups lose: two workgroups of the SAME launch may share a CU where before a
+// workgroup of the other chain sat, and the longer chain waits for its place; from 4 on the saved boundaries and tails win.
+constexpr int kDefaultMerge = 6;
 constexpr size_t kMaxRanges = 256;  // of one tail entry's footprint (a packed matvec brings 6 to 9)
 
 struct Range {
@@ -85,6 +102,13 @@ struct Plan {
   std::vector<size_t> leave;  // ascending tail positions of the launches among them
   bool restart = false;       // the launch starts a run: base := deps, tail := {launch}
   uint64_t generation = 0;    // of the run when it was planned: commit() takes only the latest plan
+  uint64_t key = 0;           // of the launch (0: it shares no node)
+  // the launch joins the node of a tail entry (kind stays kWindow; deps / leave are empty: no node is added)
+  bool merge = false;
+  size_t merge_pos = 0;                // tail position of that entry
+  NodeId target = 0;                   // its node
+  int member = 0;                      // the launch's index among the node's launches (>= 1)
+  std::vector<unsigned char> payload;  // what the entry's launches left with commit(), in order
 };
 
 class Run {
@@ -93,9 +117,13 @@ class Run {
 
   // Steps 1 and 2 for a launch with footprint `fp`; `deps` / `num_deps` = D.  Nothing is recorded until commit().
   // A run relaxes nothing until it holds `min_run` launches: until then every launch waits for the whole tail, as issued.
-  Plan plan(const NodeId* deps, size_t num_deps, const Footprint& fp, int window, int min_run = 1) {
+  // `key` / `merge_max`: the launch may join a tail entry of the same non-zero key that holds fewer than `merge_max` launches.
+  Plan plan(const NodeId* deps, size_t num_deps, const Footprint& fp, int window, int min_run = 1, uint64_t key = 0,
+            int merge_max = 1) {
     window = std::min(std::max(window, 1), kMaxWindow);
+    merge_max = std::min(merge_max, kMaxMerge);
     Plan p;
+    p.key = key;
     p.generation = ++generation_;
     if (!is_tail(deps, num_deps)) {
       p.kind = kBroken;
@@ -112,6 +140,20 @@ class Run {
       for (size_t i = 0; i < tail_.size(); ++i) p.leave.push_back(i);
     } else if ((int)tail_.size() >= window) {
       p.kind = kWindow;
+      for (size_t i = 0; key != 0 && i < tail_.size(); ++i) {
+        if (tail_[i].key != key || tail_[i].members >= merge_max) continue;
+        if (fp.ranges.size() + tail_[i].fp.ranges.size() > kMaxRanges) {  // too much for one entry: wait for the whole tail
+          p.restart = true;
+          p.deps.assign(deps, deps + num_deps);
+          return p;
+        }
+        p.merge = true;
+        p.merge_pos = i;
+        p.target = tail_[i].node;
+        p.member = tail_[i].members;
+        p.payload = tail_[i].payload;
+        return p;
+      }
       p.leave.push_back(0);  // the oldest
     } else {
       p.kind = kRelaxed;
@@ -132,8 +174,22 @@ class Run {
 
   // The launch of plan `p` became `node`: step 2's bookkeeping, after which tail() is what step 3 installs.  False (and
   // nothing recorded) when `p` is not the run's latest plan.
-  bool commit(const Plan& p, NodeId node, Footprint fp) {
+  // `payload`: the launch's parameters, opaque here; a later launch that joins the node gets them back (Plan::payload).
+  bool commit(const Plan& p, NodeId node, Footprint fp, const void* payload = nullptr, size_t payload_bytes = 0) {
     if (p.generation != generation_) return false;
+    const unsigned char* pb = static_cast<const unsigned char*>(payload);
+    if (p.merge) {  // `node` is the entry's node (the caller rewrote it, or replaced it by a node with the same dependencies)
+      Entry e = std::move(tail_[p.merge_pos]);
+      tail_.erase(tail_.begin() + (ptrdiff_t)p.merge_pos);
+      e.node = node;
+      e.fp.ranges.insert(e.fp.ranges.end(), fp.ranges.begin(), fp.ranges.end());
+      if (pb) e.payload.insert(e.payload.end(), pb, pb + payload_bytes);
+      ++e.members;
+      ++generation_;
+      ++length_;
+      tail_.push_back(std::move(e));  // the youngest now
+      return true;
+    }
     if (p.restart) {
       base_ = p.deps;
       tail_.clear();
@@ -147,9 +203,11 @@ class Run {
     }
     ++generation_;
     ++length_;
-    tail_.push_back(Entry{node, std::move(fp)});
+    tail_.push_back(Entry{node, std::move(fp), p.key, 1, std::vector<unsigned char>(pb, pb + (pb ? payload_bytes : 0))});
     return true;
   }
+
+  bool latest(const Plan& p) const { return p.generation == generation_; }
 
   // Forget the run (its launch failed, or the new node could not be read): the next launch starts a new one.
   void reset() {
@@ -170,6 +228,9 @@ class Run {
   struct Entry {
     NodeId node;
     Footprint fp;
+    uint64_t key;  // of its launches (0: nothing joins it)
+    int members;   // launches that share the node
+    std::vector<unsigned char> payload;
   };
   bool is_tail(const NodeId* deps, size_t n) const {
     if (tail_.empty() || n != tail_.size()) return false;

@@ -32,7 +32,8 @@ struct PackedNext {
 
 static int packed_launch_main(const PackedLayout& L, const void* packed, const void* codebook, const uint16_t* x, int nb,
                               long x_row_stride, int dtype, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                              const char* who, const PackedFused& fused = PackedFused{}, const PackedNext& next = PackedNext{}) {
+                              const char* who, const PackedFused& fused = PackedFused{}, const PackedNext& next = PackedNext{},
+                              CaptureRelax* relax = nullptr) {
   const bool finalizes = fused.y || fused.pub;
   const size_t need = finalizes ? 0 : (size_t)PK_S * nb * L.M * sizeof(float);
   if (need && (!workspace || workspace_bytes < need)) {
@@ -67,6 +68,47 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     npw = std::min(std::min(want, 7), PK_MAX_NW - L.NW);
   }
   const uint32_t rotate = tuning().packed_fill_rotate ? 1u : 0u;
+#if AQLM_PK_G == 8
+  // Capture overlap, grouped launches (capture_overlap.h): a one-row launch of a compact-window instance that finalizes into y
+  // is one grid of 256 workgroups, and gemv_1x16_packed_group_kernel runs up to PK_GROUP_MAX such grids of one instance, block
+  // size and LDS image as one.  When the planner lets this launch join a node, the node is rewritten to the grouped kernel
+  // with this layer as one more segment and nothing is launched.  `joined` false: launch as usual (begin() has been called).
+  auto try_join = [&](bool vg, const PackedGroupSegment& me, unsigned threads, size_t lds, bool& joined) -> int {
+    joined = false;
+    if (tuning().packed_capture_merge <= 1) {
+      if (relax) relax->begin();
+      return 0;
+    }
+    const void* gk = vg ? (dtype == AQLM_HIP_F16 ? (const void*)gemv_1x16_packed_group_kernel<F16, 3, PK_XWIN_COMPACT, 4, true>
+                                                 : (const void*)gemv_1x16_packed_group_kernel<BF16, 3, PK_XWIN_COMPACT, 4, true>)
+                        : (dtype == AQLM_HIP_F16 ? (const void*)gemv_1x16_packed_group_kernel<F16, 3, PK_XWIN_COMPACT, 4, false>
+                                                 : (const void*)gemv_1x16_packed_group_kernel<BF16, 3, PK_XWIN_COMPACT, 4, false>);
+    if (int e = ensure_dynamic_lds(gk, lds)) return e;  // on eager launches too: the attribute is in place before a capture needs it
+    if (!relax) return 0;
+    uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(gk) * 0x9E3779B97F4A7C15ull ^ ((uint64_t)threads << 32) ^ (uint64_t)lds;
+    if (key == 0) key = 1;
+    const int n = relax->begin(key, &me, sizeof me);
+    if (n <= 0) return 0;
+    const std::vector<unsigned char>& members = relax->group();
+    if (n >= PK_GROUP_MAX || members.size() != (size_t)n * sizeof(PackedGroupSegment)) {
+      relax->join(nullptr);
+      return 0;
+    }
+    PackedGroupParams gp{};
+    memcpy(gp.seg, members.data(), members.size());
+    gp.seg[n] = me;
+    void* args[1] = {&gp};
+    hipKernelNodeParams node{};
+    node.func = const_cast<void*>(gk);
+    node.gridDim = dim3((unsigned)(n + 1) * PK_NST);
+    node.blockDim = dim3(threads);
+    node.sharedMemBytes = (unsigned)lds;
+    node.kernelParams = args;
+    node.extra = nullptr;
+    joined = relax->join(&node);
+    return 0;
+  };
+#endif
   auto launch = [&](auto kern, auto lds_map) -> int {
     const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, npw, L.NW);
     if (lds > 160 * 1024) { npw = 0; }
@@ -82,6 +124,25 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
       r.next_codebook = next.codebook;
       r.next_block_bytes = next.block_bytes;
     }
+    bool joined = false;
+#if AQLM_PK_G == 8
+    if (decltype(lds_map)::TIGHT && nb == 1 && npw == 0 && fused.y && !fused.pub) {
+      PackedGroupSegment me{};
+      me.codebook = cb;
+      me.x = x;
+      me.ent = ent;
+      me.rowstart = rowstart;
+      me.in_groups = L.in_groups;
+      me.RG = L.RG;
+      me.M = L.M;
+      me.geom = (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16);
+      me.ent_bytes = (uint32_t)L.ent_bytes;
+      me.rest = r;
+      if (int e = try_join(false, me, (unsigned)L.NW * 64u, lds_final, joined)) return e;
+    } else
+#endif
+    if (relax) relax->begin();
+    if (joined) return 0;
     hipLaunchKernelGGL(kern, dim3(PK_NST), dim3((L.NW + npw) * 64), lds_final, stream, cb, x, ent, rowstart, L.in_groups,
                        (uint32_t)L.NW | ((uint32_t)L.XC << 8) | ((uint32_t)npw << 12) | (rotate << 15) | ((uint32_t)L.T << 16), L.RG,
                        (uint32_t)L.ent_bytes, L.M, r);
@@ -101,6 +162,25 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     auto launch_vg = [&](auto kern, auto lds_map) -> int {
       const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, 0, L.NW);
       if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
+      bool joined = false;
+      if (decltype(lds_map)::TIGHT && nb == 1 && fused.y) {
+        PackedGroupSegment me{};
+        me.codebook = cb;
+        me.x = x;
+        me.ent = ent;
+        me.rowstart = rowstart;
+        me.in_groups = L.in_groups;
+        me.RG = L.RG;
+        me.M = L.M;
+        me.geom = (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16);
+        me.ent_bytes = (uint32_t)PK_NST * (uint32_t)L.NW * (uint32_t)L.T * 1024u;  // as the variable-geometry kernel derives it
+        for (int i = 0; i < 4; ++i) me.ns[i] = ns[i];
+        me.rest = rest;
+        if (int e = try_join(true, me, (unsigned)L.NW * 64u, lds, joined)) return e;
+      } else if (relax) {
+        relax->begin();
+      }
+      if (joined) return 0;
       hipLaunchKernelGGL(kern, dim3(PK_NST), dim3(L.NW * 64), lds, stream, cb, x, ent, (uint32_t)(L.off_ent - L.off_rowstart),
                          (uint32_t)L.in_groups | ((uint32_t)L.RG << 12), (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16),
                          L.M, ns[0], ns[1], ns[2], ns[3], rest);
@@ -173,8 +253,7 @@ static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed,
     relax.fp.add_rows(y, batch, y_row_stride * 2, (size_t)L.M * 2, true);
     if (fused && cells) relax.fp.add(cells, (size_t)batch * L.M * 8, true);
     if (!fused) relax.fp.add(workspace, (size_t)PK_S * std::min(batch, max_b) * L.M * sizeof(float), true);
-    relax.begin();
-  }
+  }  // (packed_launch_main plans the first launch: relax.begin(), or a place in a grouped launch)
   for (int b0 = 0; b0 < batch; b0 += max_b) {  // rows that do not fit one LDS image go in several launches
     const int nb = std::min(max_b, batch - b0);
     uint16_t* yb = (uint16_t*)y + (size_t)b0 * y_row_stride;
@@ -189,7 +268,7 @@ static int gemv_1x16_packed_impl(const aqlm_hip_packed_desc* desc, void* packed,
     }
     if (int e = packed_launch_main(L, packed, codebook, (const uint16_t*)x + (size_t)b0 * x_row_stride, nb, x_row_stride, dtype,
                                    workspace, workspace_bytes, stream, "aqlm_hip_gemv_1x16_packed", fz,
-                                   fused && b0 + nb >= batch ? next : PackedNext{}))
+                                   fused && b0 + nb >= batch ? next : PackedNext{}, b0 == 0 ? &relax : nullptr))
       return e;
     if (int e = relax.launched()) return e;
     if (fused) continue;

@@ -790,6 +790,78 @@ __global__ __launch_bounds__(1024) void gemv_1x16_packed_multi_kernel(const Pack
   gemv_1x16_packed_body<T_, B, PD, XWIN, EB>(p, (int)blockIdx.x % PK_NST, (int)blockDim.x >> 6);
 }
 
+#if AQLM_PK_G == 8
+// Several INDEPENDENT one-row layers in one launch of 256 workgroups per layer: what capture overlap makes of launches that
+// may share a graph node (capture_overlap.h, "Grouped launches").  Every segment is a complete single-layer launch -- its own
+// x, codebook, stream, cells, y and geometry, exactly the arguments of gemv_1x16_packed_kernel / _vg_kernel -- and all of a
+// launch's segments have the block size and the LDS image of one kernel instance.  Within the launch the dispatcher puts a
+// workgroup of the next layer on a CU the moment one leaves; between graph nodes that costs a launch boundary and the tail of
+// the slowest workgroup.  No prefetch waves, no publish form.
+constexpr int PK_GROUP_MAX = capture_overlap::kMaxMerge;  // the planner never puts more launches into a node
+struct PackedGroupSegment {
+  const uint8_t* codebook;
+  const uint16_t* x;
+  const uint32_t* ent;
+  const uint32_t* rowstart;
+  int in_groups, RG, M;
+  uint32_t geom;  // as the single-layer kernels take it (prefetch waves 0)
+  uint32_t ent_bytes;
+  uint32_t ns[4];  // variable geometry: PackedVgArgs
+  PackedGemvRest rest;
+};
+struct PackedGroupParams {
+  PackedGroupSegment seg[PK_GROUP_MAX];
+};
+
+// The segment is read where the launch put it: the kernel arguments are memory (the kernarg segment, constant address space),
+// `gp` is the only argument and so starts at offset 0, and a segment's fields are a few uniform loads at sidx * sizeof(segment)
+// from there.  (Indexing the by-value `gp` with sidx makes hipcc copy it to scratch first; a select chain over the segments,
+// as in the shared-input kernel, costs ~130 scalar instructions in front of the first load of every workgroup.)
+typedef const PackedGroupSegment __attribute__((address_space(4)))* group_segment_ptr;
+template <class T_, int PD, uint32_t XWIN, int EB, bool VG>
+__global__ __launch_bounds__(1024) void gemv_1x16_packed_group_kernel(const PackedGroupParams gp) {
+  (void)gp;
+  const int sidx = (int)blockIdx.x / PK_NST;
+  const group_segment_ptr s = (group_segment_ptr)__builtin_amdgcn_kernarg_segment_ptr() + sidx;
+  PackedGemvParams p{};  // (no prefetch waves, no next layer, no publish: zero)
+  PackedVgArgs vg{};
+  p.codebook = s->codebook;
+  p.x = s->x;
+  p.ent = s->ent;
+  p.rowstart = s->rowstart;
+  p.in_groups = s->in_groups;
+  p.RG = s->RG;
+  p.M = s->M;
+  const uint32_t geom = s->geom;
+  p.ent_bytes = s->ent_bytes;
+  if constexpr (VG) {
+    vg.ns[0] = s->ns[0];
+    vg.ns[1] = s->ns[1];
+    vg.ns[2] = s->ns[2];
+    vg.ns[3] = s->ns[3];
+  }
+  p.winfo = s->rest.winfo;
+  p.partial = s->rest.partial;
+  p.x_row_stride = s->rest.x_row_stride;
+  p.acc = s->rest.acc;
+  p.cb_absmax = s->rest.cb_absmax;
+  p.scales = s->rest.scales;
+  p.bias = s->rest.bias;
+  p.y = s->rest.y;
+  p.y_row_stride = s->rest.y_row_stride;
+#ifdef AQLM_PACKED_TRACE
+  p.trace = s->rest.trace;
+  p.dbg = s->rest.dbg;
+#endif
+  // geom: waves 0..7 | x copies 8..11 | rotated fill 15 | steps 16..31
+  p.NW = (int)(geom & 0xffu);
+  p.XC = (int)((geom >> 8) & 0xfu);
+  p.fill_rotate = (int)((geom >> 15) & 1u);
+  p.T = (int)(geom >> 16);
+  gemv_1x16_packed_body<T_, 1, PD, XWIN, EB, false, VG>(p, (int)blockIdx.x % PK_NST, (int)blockDim.x >> 6, vg);
+}
+#endif
+
 struct PackedFinalizeParams {
   const float* partial;  // [S][B][M]
   const uint16_t* scales;

@@ -982,8 +982,24 @@ int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2, void* str
  * aqlm_hip_capture_overlap_stats: out[0..5] = calls seen on a capturing stream, relaxed (no edge to any call of the run), kept
  * for a conflict, kept for the window, runs started or broken, capture-call failures; process-wide, since the last reset.
  * NULL resets the counters.  Returns 0.
+ *
+ * Grouped launches (tuning key `packed_capture_merge`, 1..8, default 6; 1 = off).  Every node of a replayed graph pays a launch
+ * boundary and waits for the last workgroup of the node before it; within one launch the hardware puts the next workgroup
+ * on a CU the moment one leaves.  With the key at n > 1, a one-row call of aqlm_hip_gemv_1x16_packed / _cells / _chain whose
+ * layer runs on the compact-window kernels (<= 4096 input features, 4-byte entries, codebook range in the descriptor) and
+ * that would have waited for the oldest call of a full window JOINS the node of an earlier such call of the same kernel
+ * instance, block size and LDS image instead (same shape, in practice), up to n calls per node: the node is rewritten
+ * (hipGraphKernelNodeSetParams) to a grouped kernel that runs the layers as segments of one grid, each with its own x,
+ * codebook, cells and y.  A joined call has been checked against the footprint of every call it can run beside, the ones
+ * it shares the node with included; ordering towards everything captured later is as above.  Same bits.  Nothing changes
+ * outside a capture, in runs shorter than `packed_capture_min_run`, or for any other launch.  Should the runtime refuse the
+ * rewrite, the call is captured as a node of its own, as with the key at 1, and the refusal is counted.
+ * aqlm_hip_capture_overlap_stats_ex: the first `count` (0..9) of out[0..5] as above, then out[6] = calls that joined a node
+ * (they are also counted in out[3]), out[7] = rewrites the runtime refused, out[8] = calls that added a node of their own
+ * (out[0] - out[6]).  NULL resets all counters.  Returns 0, or AQLM_HIP_E_INVALID for a count outside 0..9.
  */
 int aqlm_hip_capture_overlap_stats(uint64_t out[6]);
+int aqlm_hip_capture_overlap_stats_ex(uint64_t* out, int count);
 
 /*
  * Tuning / experiment knobs (process-wide, not part of the reference surface; defaults are the shipped
