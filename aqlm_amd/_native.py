@@ -295,7 +295,7 @@ def get_tuning(key: str) -> int:
 
 
 CAPTURE_OVERLAP_FIELDS = ("seen", "relaxed", "kept_conflict", "kept_window", "runs_broken", "api_failures",
-                          "merged", "merge_refused", "nodes_added")
+                          "merged", "merge_refused", "nodes_added", "folded")
 
 
 def capture_overlap_stats(reset: bool = False) -> dict:

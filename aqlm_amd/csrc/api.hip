@@ -80,6 +80,7 @@ static int* tuning_slot(const char* key) {
   if (!strcmp(key, "packed_capture_window")) return &t.packed_capture_window;
   if (!strcmp(key, "packed_capture_min_run")) return &t.packed_capture_min_run;
   if (!strcmp(key, "packed_capture_merge")) return &t.packed_capture_merge;
+  if (!strcmp(key, "packed_group_fold")) return &t.packed_group_fold;
   if (!strcmp(key, "packed_pipe")) return &t.packed_pipe;
   if (!strcmp(key, "packed_prefetch_waves")) return &t.packed_prefetch_waves;
   if (!strcmp(key, "packed_dequant_by_xcd")) return &t.packed_dequant_by_xcd;
@@ -96,8 +97,9 @@ struct CaptureOverlapState {
   std::mutex mu;
   capture_overlap::Planner planner;
   // seen, relaxed, kept for a conflict, kept for the window, runs broken, API failures; then: launches that joined a node
-  // (also counted as kept for the window), rewrites of a node the runtime refused, launches that added a node of their own
-  uint64_t stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // (also counted as kept for the window), rewrites of a node the runtime refused, launches that added a node of their own,
+  // nodes that went over to the folded grouped kernel (group_fold.h)
+  uint64_t stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool off = false;                        // a capture call failed once: every launch as issued from then on
 };
 CaptureOverlapState& capture_state() {
@@ -193,7 +195,7 @@ int CaptureRelax::begin(uint64_t key, const void* member, size_t member_bytes) {
   return 0;
 }
 
-bool CaptureRelax::join(const hipKernelNodeParams* node) {
+bool CaptureRelax::join(const hipKernelNodeParams* node, int folded_delta) {
   if (!active_ || !begun_ || done_ || !plan_.merge) return false;
   CaptureOverlapState& s = capture_state();
   std::lock_guard<std::mutex> lock(s.mu);
@@ -208,6 +210,7 @@ bool CaptureRelax::join(const hipKernelNodeParams* node) {
     ++s.stats[3];
     ++s.stats[6];
     --s.stats[8];
+    s.stats[9] += (uint64_t)(int64_t)folded_delta;
     done_ = true;
     return true;
   }
@@ -309,7 +312,7 @@ extern "C" int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2
 static int capture_overlap_stats(uint64_t* out, int n) {
   aqlm::CaptureOverlapState& s = aqlm::capture_state();
   std::lock_guard<std::mutex> lock(s.mu);
-  for (int i = 0; i < 9; ++i) {
+  for (int i = 0; i < 10; ++i) {
     if (!out) s.stats[i] = 0;
     else if (i < n) out[i] = s.stats[i];
   }
@@ -319,8 +322,8 @@ static int capture_overlap_stats(uint64_t* out, int n) {
 extern "C" int aqlm_hip_capture_overlap_stats(uint64_t out[6]) { return capture_overlap_stats(out, 6); }
 
 extern "C" int aqlm_hip_capture_overlap_stats_ex(uint64_t* out, int count) {
-  if (out && (count < 0 || count > 9)) {
-    aqlm::set_last_error("aqlm_hip_capture_overlap_stats_ex: count must be 0..9 (got %d)", count);
+  if (out && (count < 0 || count > 10)) {
+    aqlm::set_last_error("aqlm_hip_capture_overlap_stats_ex: count must be 0..10 (got %d)", count);
     return AQLM_HIP_E_INVALID;
   }
   return capture_overlap_stats(out, count);

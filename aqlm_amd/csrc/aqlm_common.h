@@ -7,6 +7,7 @@
 
 #include "../../include/aqlm_hip.h"
 #include "capture_overlap.h"
+#include "group_fold.h"
 
 namespace aqlm {
 
@@ -180,6 +181,7 @@ struct Tuning {
   int packed_capture_window = capture_overlap::kDefaultWindow;  // packed 1x16 matvecs captured into a graph: consecutive launches that share no memory and may run side by side (1..8; capture_overlap.h); 1 = every launch after the previous one
   int packed_capture_min_run = capture_overlap::kDefaultMinRun;  // ... launches an uninterrupted run of them must hold before any is relaxed (a graph with branches costs host time per node: capture_overlap.h); 1 = from the second launch on
   int packed_capture_merge = capture_overlap::kDefaultMerge;  // ... launches of one kernel instance that may share a graph node, run by the grouped kernel (1..8; capture_overlap.h, "Grouped launches"); 1 = every launch a node of its own
+  int packed_group_fold = 0;     // ... workgroups of such a node that keep their codebook slice and x in LDS and walk F row groups of their (layer, slice) in turn (group_fold.h): 0 = default (4), 1 = off, 2, 4; a node of fewer than F launches is not folded
   int packed_dequant_by_xcd = 1; // aqlm_hip_dequant_1x16_packed, grid order: 1 = by the measured rule (16-B vectors: the streams that run together on an XCD are the slices of one row group, so their partial-line stores meet in one L2; 32-B vectors: stream-major like the unpack kernel), 0 = always stream-major, 2 = always by XCD (A/B runs)
 };
 Tuning& tuning();
@@ -205,7 +207,9 @@ class CaptureRelax {
   // refused the rewrite (counted, not an error); the stream is set up for an ordinary launch and the caller makes one.
   int begin(uint64_t key = 0, const void* member = nullptr, size_t member_bytes = 0);
   const std::vector<unsigned char>& group() const { return plan_.payload; }
-  bool join(const hipKernelNodeParams* node);  // (null: the caller cannot build the node)
+  // (null: the caller cannot build the node; `folded_delta`: +1 when this rewrite turns the node into its folded form
+  // (group_fold.h), -1 when it turns it back -- added to the count of folded nodes when the rewrite holds)
+  bool join(const hipKernelNodeParams* node, int folded_delta = 0);
   // After the launch (later launches of the call: no effect; nor after a join()).  0, or the error when the stream could not
   // be made to wait for the launches that ran beside this one: the capture would be wrong, so the call fails.
   int launched();

@@ -65,7 +65,9 @@ constexpr int kMaxMerge = 8;  // launches that may share one node (the grouped k
 // Measured on the 64-layer decode step at a window of 2 (profiles/capture_merge.json): 1 launch per node 357-359 us, 2: 377,
 // 3: 361, 4: 345, 5: 336, 6: 334, 8: 338.  Small groups lose: two workgroups of the SAME launch may share a CU where before a
 // workgroup of the other chain sat, and the longer chain waits for its place; from 4 on the saved boundaries and tails win.
-constexpr int kDefaultMerge = 6;
+// With folded nodes (group_fold.h) the best group size moved: four launches per node at four passes per workgroup, 292 us against
+// 329 / 306 for six / eight (fold 2: 327 / 310 / 307; unfolded as above).
+constexpr int kDefaultMerge = 4;
 constexpr size_t kMaxRanges = 256;  // of one tail entry's footprint (a packed matvec brings 6 to 9)
 
 struct Range {

@@ -84,6 +84,12 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
                         : (dtype == AQLM_HIP_F16 ? (const void*)gemv_1x16_packed_group_kernel<F16, 3, PK_XWIN_COMPACT, 4, false>
                                                  : (const void*)gemv_1x16_packed_group_kernel<BF16, 3, PK_XWIN_COMPACT, 4, false>);
     if (int e = ensure_dynamic_lds(gk, lds)) return e;  // on eager launches too: the attribute is in place before a capture needs it
+    // the folded form of the node (group_fold.h; ordinary geometry only): same image, same block size, 256 / F workgroups per member
+    const void* fk = vg ? nullptr
+                        : (dtype == AQLM_HIP_F16 ? (const void*)gemv_1x16_packed_group_fold_kernel<F16, 3, PK_XWIN_COMPACT, 4>
+                                                 : (const void*)gemv_1x16_packed_group_fold_kernel<BF16, 3, PK_XWIN_COMPACT, 4>);
+    if (fk)
+      if (int e = ensure_dynamic_lds(fk, lds)) return e;
     if (!relax) return 0;
     uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(gk) * 0x9E3779B97F4A7C15ull ^ ((uint64_t)threads << 32) ^ (uint64_t)lds;
     if (key == 0) key = 1;
@@ -97,15 +103,24 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     PackedGroupParams gp{};
     memcpy(gp.seg, members.data(), members.size());
     gp.seg[n] = me;
-    void* args[1] = {&gp};
+    // The node is rewritten on every join, so the choice follows the member count: folded from F members on (the grid never
+    // drops under 256 workgroups), the unfolded kernel below that.  The planner's key is the unfolded instance's either way.
+    // The folded kernel finalizes one row per thread (a second row's loads would stand in front of the next pass's ring): a
+    // layer with more rows in a group than the block has threads keeps its node unfolded.
+    const int key_fold = tuning().packed_group_fold;
+    bool one_row_before = fk != nullptr;
+    for (int i = 0; i < n; ++i) one_row_before = one_row_before && gp.seg[i].RG <= (int)threads;
+    const bool was_folded = one_row_before && group_fold::choose(key_fold, n) > 1;
+    int fold = one_row_before && me.RG <= (int)threads ? group_fold::choose(key_fold, n + 1) : 1;
+    void* args[2] = {&gp, &fold};  // (the unfolded kernel takes the first only)
     hipKernelNodeParams node{};
-    node.func = const_cast<void*>(gk);
-    node.gridDim = dim3((unsigned)(n + 1) * PK_NST);
+    node.func = const_cast<void*>(fold > 1 ? fk : gk);
+    node.gridDim = dim3(group_fold::grid(n + 1, fold));
     node.blockDim = dim3(threads);
     node.sharedMemBytes = (unsigned)lds;
     node.kernelParams = args;
     node.extra = nullptr;
-    joined = relax->join(&node);
+    joined = relax->join(&node, (fold > 1 ? 1 : 0) - (was_folded ? 1 : 0));
     return 0;
   };
 #endif

@@ -1,6 +1,6 @@
 // Part of gemv_packed.hip (inside namespace aqlm::PK_NS): the matvec -- parameter structs, LDS helpers and maps (PackedLds), the body
-// (gemv_1x16_packed_body), its kernel wrappers (single layer, variable geometry, shared input) and the finalize kernels.
-// Needs packed_format.h.
+// (gemv_1x16_packed_body), its kernel wrappers (single layer, variable geometry, shared input, grouped and folded grouped) and
+// the finalize kernels.  Needs packed_format.h (and group_fold.h, which aqlm_common.h brings).
 
 struct PackedGemvParams {
   const uint32_t* ent;
@@ -135,9 +135,18 @@ struct PackedVgArgs {
 
 // NOPF: the launch has no prefetch waves (p.NPW == 0 by construction: the expert-routed launch) -- their branches go away at
 // compile time.  (A run-time p.NPW == 0 leaves them in, and with them a path on which hipcc sees the LDS-DMA still in flight.)
-template <class T_, int B, int PD, uint32_t XWIN, int EB, bool PUB = false, bool VG = false, bool NOPF = false>
+// FOLD: the folded grouped launch (gemv_1x16_packed_group_fold_kernel).  The workgroup fills slice, x and the null slots ONCE and
+// then walks `npass` streams of its slice in turn -- `block` is the stream of pass 0, pass j runs row group
+// block / 16 + j * group_step -- each pass with its own entry ring, loop, row tables, scale / bias prefetch and epilogue (same
+// cell protocol, same summation order, same bits in y as a workgroup of its own).  rowval / colend are reused from pass to pass
+// behind a barrier; no LDS-DMA is issued after the first fill barrier (hipcc would guard every LDS read it sees with vmcnt(0)
+// and drain the ring: packed_pipe_kernel.h), so the row starts of a pass come by ordinary loads like scale and bias, and the
+// row-start area of the image stays unused.  Every FOLD branch is `if constexpr`: the other instances compile to what they were.
+template <class T_, int B, int PD, uint32_t XWIN, int EB, bool PUB = false, bool VG = false, bool NOPF = false, bool FOLD = false>
 __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p, const int block, const int NWB,
-                                                      const PackedVgArgs& vg = PackedVgArgs{}) {
+                                                      const PackedVgArgs& vg = PackedVgArgs{}, const int npass = 1,
+                                                      const int group_step = 0) {
+  static_assert(!FOLD || (B == 1 && EB == 4 && !PUB && !VG && NOPF), "folded launch: one row, 4-byte entries, ordinary geometry");
   using LDS = PackedLds<B, XWIN>;
   using ring_t = typename std::conditional<EB == 3, u32x3, u32x4>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -197,7 +206,7 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   __amdgpu_buffer_rsrc_t rs_ent = __builtin_amdgcn_make_buffer_rsrc((void*)p.ent, 0, p.ent_bytes, 0x00020000);
   const int wv = wave < p.NW ? wave : p.NW - 1;  // waves beyond the stream's wave count (shared-input launches) idle
   const uint32_t wbase = (uint32_t)(((size_t)stream_ix * p.NW + wv) * p.T) * (EB == 3 ? (uint32_t)PK_WREG3 : 1024u);
-  const int Tm1 = p.T - 1;
+  int Tm1 = p.T - 1;  // (FOLD: -1 while the ring of a pass that does not exist is requested)
   // (0) 3-byte entries: the row-end flag words of this wave range, word t in lane t -- the OLDEST load of the queue, so
   // it has landed whenever the wait of (5) returns
   u32x2 flagw = {0u, 0u};
@@ -245,16 +254,19 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
     }
     // the stream's row starts (needed by the epilogue only; as an LDS-DMA they are older than the ring loads, see (5)).
     // Rows of the table are only 4-B aligned -> dword DMA, 256 B per wave-instruction.
-    const uint32_t* rs_src = p.rowstart + (size_t)stream_ix * RG1;
-    for (int i = wave; i * 64 < RG1; i += NWD) {
-      const int idx = i * 64 + lane;
-      if (idx < RG1)
-        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(rs_src + idx), (lds_void_ptr)(size_t)(rowstart_off + (uint32_t)i * 256u), 4, 0, 0);
+    // (FOLD: every pass fetches the two row starts of its thread's row into registers, below)
+    if constexpr (!FOLD) {
+      const uint32_t* rs_src = p.rowstart + (size_t)stream_ix * RG1;
+      for (int i = wave; i * 64 < RG1; i += NWD) {
+        const int idx = i * 64 + lane;
+        if (idx < RG1)
+          __builtin_amdgcn_global_load_lds((gbl_void_ptr)(rs_src + idx), (lds_void_ptr)(size_t)(rowstart_off + (uint32_t)i * 256u), 4, 0, 0);
+      }
     }
   }
   // (2) the entry stream of this wave: fixed addresses, PD steps ahead in a register ring with compile-time slots
   const uint32_t voff = (uint32_t)lane * (EB == 3 ? 12u : 16u);
-  const uint32_t ebase = EB == 3 ? wbase + (uint32_t)p.T * 8u : wbase;
+  uint32_t ebase = EB == 3 ? wbase + (uint32_t)p.T * 8u : wbase;  // (FOLD: of the pass whose ring is requested)
   auto fetch = [&](int t) -> ring_t {  // unconditional (a load under a branch derails hipcc's wait counts); steps past the
     // end of the range get an out-of-range offset: the buffer unit answers them with zeros and touches no memory
 #ifdef AQLM_PACKED_TRACE
@@ -296,15 +308,37 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   // last-arrival test they sat at the very end of the kernel's critical path).  Unconditional, always-valid addresses
   // (a branch around a load ends in a vmcnt(0) at the join); younger than the ring, so the wait below lets them fly too.
   uint16_t scale_h, bias_h;
-  {
+  [[maybe_unused]] uint32_t q0_h = 0u, q1_h = 0u;  // FOLD: the row starts of this thread's first row (rs[r], rs[r + 1])
+  // FOLD: what a pass requests for its thread's first row -- scale, bias and the two row starts of row `tid` of row group `g`,
+  // clamped to addresses that exist when the group is short or empty (the table of a stream has RG + 1 words)
+  [[maybe_unused]] auto pass_loads = [&](int g, uint16_t& sc, uint16_t& bi, uint32_t& q0, uint32_t& q1) {
+    const int rb = g * p.RG;
+    int n = p.M - rb;
+    n = n < 0 ? 0 : (n < p.RG ? n : p.RG);
+    const int r = tid < n ? tid : (n > 0 ? n - 1 : 0);
+    const int row = rb + r < p.M ? rb + r : p.M - 1;
+    const uint16_t* bp = p.bias ? p.bias : p.scales;
+    const uint32_t* rs_g = p.rowstart + (size_t)(g * PK_S + slice) * RG1;
+    sc = p.scales[row];
+    bi = bp[row];
+    // rs[r] and rs[r + 1] as ONE 8-byte load of 4-byte alignment (hipcc fuses two dword loads into it anyway): the fill wait
+    // below counts loads, so their number is fixed here and not left to the optimiser
+    typedef uint32_t rs_pair __attribute__((ext_vector_type(2), aligned(4)));
+    const rs_pair q = *reinterpret_cast<const rs_pair*>(rs_g + r);
+    q0 = q.x;
+    q1 = q.y;
+  };
+  if constexpr (FOLD) {
+    pass_loads(group, scale_h, bias_h, q0_h, q1_h);
+  } else {
     const int r = tid < nrows ? tid : (nrows > 0 ? nrows - 1 : 0);
     const uint16_t* sp = p.scales ? p.scales : reinterpret_cast<const uint16_t*>(p.rowstart);  // partials mode: unused
     const uint16_t* bp = p.bias ? p.bias : sp;
     scale_h = sp[row_begin + r];
     bias_h = bp[row_begin + r];
   }
-  constexpr int PDW = PD + 2;
-  if (!pfw) __builtin_amdgcn_s_waitcnt((PDW & 15) | (7 << 4) | (0 << 8) | ((PDW >> 4) << 14));  // vmcnt(PD + 2) lgkmcnt(0)
+  constexpr int PDW = PD + (FOLD ? 3 : 2);  // behind the last LDS-DMA: the ring, scale, bias (FOLD: and the row-start pair)
+  if (!pfw) __builtin_amdgcn_s_waitcnt((PDW & 15) | (7 << 4) | (0 << 8) | ((PDW >> 4) << 14));  // vmcnt(PD + 2) lgkmcnt(0) (FOLD: PD + 3)
   else __builtin_amdgcn_s_waitcnt(63 | (7 << 4) | (0 << 8) | (3 << 14));                          // prefetch waves: lgkmcnt(0) only
   __builtin_amdgcn_s_barrier();
   AQLM_TRACE(2);
@@ -428,6 +462,11 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
     }
   };
 
+  // FOLD: pass j of the workgroup starts here -- ring, scale_h / bias_h / q0_h / q1_h and the row range are those of its stream,
+  // acc and row_addr are zero, and every wave has left epilogue j - 1 (its reads of rowval / colend).  A backward goto and not a
+  // loop around 180 lines: the body of the other instances stays the text (and the instructions) it was.
+  [[maybe_unused]] int pass = 0;
+next_pass:
   if (steps > 0) {
     if constexpr (EB == 4) {  // the column's starting row rides in the spare bits of its first lane-step
       const uint32_t f = pk_get_start_row(ring[0].x, ring[0].y, ring[0].z, ring[0].w);
@@ -473,7 +512,8 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   // sees the same x, so all of them derive the same fixed-point scale from it in the epilogue.  Done AFTER the loop: the
   // waves finish it at different times (the SIMDs favour their older waves), so for most of them this is idle time, and
   // right behind the fill barrier it would stand between every wave and its first lane-step (measured: 0.35 us).
-  if (p.acc != nullptr) {
+  // (FOLD: x stays, so once, behind the loop of pass 0)
+  if (p.acc != nullptr && (!FOLD || pass == 0)) {
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int b = 0; b < B; ++b) {
@@ -499,6 +539,21 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
   asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");  // the asm LDS stores above are invisible to the compiler's counters
   __syncthreads();
   AQLM_TRACE(5);
+  // FOLD: what pass j + 1 needs first is requested HERE, in front of epilogue j, so the epilogue's atomic round trip runs under
+  // it: scale, bias and row starts of the thread's row, then the first PD ring steps (the ring's registers are dead: the loop is
+  // over).  Unconditional; behind the last pass the small loads repeat this pass's addresses and the ring steps are out of
+  // range (zeros, no memory traffic).  Nothing here is an LDS-DMA, so hipcc puts no vmcnt(0) in front of the epilogue's LDS reads.
+  [[maybe_unused]] uint16_t scale_n = 0, bias_n = 0;
+  [[maybe_unused]] uint32_t q0_n = 0u, q1_n = 0u;
+  if constexpr (FOLD) {
+    const bool more = pass + 1 < npass;
+    const int g = more ? group + group_step : group;
+    pass_loads(g, scale_n, bias_n, q0_n, q1_n);
+    ebase = (uint32_t)(((size_t)(g * PK_S + slice) * p.NW + wv) * p.T) * 1024u;
+    Tm1 = more ? p.T - 1 : -1;
+#pragma unroll
+    for (int k = 0; k < PD; ++k) ring[k] = fetch(k);
+  }
   // ---- epilogue: row r = rowval[r] + the column remainders of the columns it crosses, in column order -------------
   float* pub_half = nullptr;
   uint32_t pub_e = 0u;
@@ -512,7 +567,14 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
     const float* colend = reinterpret_cast<const float*>(smem_raw + colend_off);
     const uint32_t T = (uint32_t)p.T;
     for (int r = tid; r < nrows; r += NT) {
-      const uint32_t q0 = rs[r], q1 = rs[r + 1];
+      uint32_t q0, q1;
+      if constexpr (FOLD) {  // requested a loop ago.  The launch code folds only layers with RG <= the block size, so r == tid:
+        q0 = q0_h;           // a load for a further row here would be waited for with vmcnt(0), the next pass's ring in front
+        q1 = q1_h;           // of it, before this row's atomic could go out
+      } else {
+        q0 = rs[r];
+        q1 = rs[r + 1];
+      }
       const uint32_t c0 = q0 / T, c1 = (q1 - 1u) / T;  // first / last column the row touches (column = wave * 64 + lane)
       float v[B];
 #pragma unroll
@@ -559,7 +621,7 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
           mine[b] = ((unsigned long long)q << PK_VAL_SHIFT) + (finite ? 1ull : 1ull + (1ull << PK_CNT_BITS));
           old[b] = __hip_atomic_fetch_add(p.acc + (size_t)b * p.M + row, mine[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        const bool first = r == tid;  // this thread's first (usually only) row: scale and bias were requested in the prologue
+        const bool first = FOLD || r == tid;  // this thread's first (usually only) row: scale and bias were requested in the prologue
         const float scale = pub_half ? 1.f : T_::to_float(first ? scale_h : p.scales[row]);
         const float bias = (pub_half || !p.bias) ? 0.f : T_::to_float(first ? bias_h : p.bias[row]);
 #pragma unroll
@@ -599,6 +661,30 @@ __device__ __forceinline__ void gemv_1x16_packed_body(const PackedGemvParams& p,
           __hip_atomic_store(p.pub_flag + (pub_e & 1u), pub_e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       }
+    }
+  }
+  if constexpr (FOLD) {
+    if (++pass < npass) {  // the next row group of this slice: what was requested in front of the epilogue is its own now
+      group += group_step;
+      stream_ix = group * PK_S + slice;
+      row_begin = group * p.RG;
+      nrows = p.M - row_begin;
+      nrows = nrows < 0 ? 0 : (nrows < p.RG ? nrows : p.RG);
+      scale_h = scale_n;
+      bias_h = bias_n;
+      q0_h = q0_n;
+      q1_h = q1_n;
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+#pragma unroll
+        for (int a = 0; a < NA; ++a) acc[b][a] = 0.f;
+      row_addr = 0;
+      // every row of this pass has a writer and every column of the stream's waves stores its remainder, so nothing of pass j
+      // is read in pass j + 1 -- but loop j + 1 must not write rowval / colend while a wave still reads them in epilogue j.
+      // The bare barrier, not __syncthreads(): its vmcnt(0) would wait for the ring that was just requested.
+      asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
+      __builtin_amdgcn_s_barrier();
+      goto next_pass;
     }
   }
 #ifdef AQLM_PACKED_TRACE
@@ -859,6 +945,49 @@ __global__ __launch_bounds__(1024) void gemv_1x16_packed_group_kernel(const Pack
   p.fill_rotate = (int)((geom >> 15) & 1u);
   p.T = (int)(geom >> 16);
   gemv_1x16_packed_body<T_, 1, PD, XWIN, EB, false, VG>(p, (int)blockIdx.x % PK_NST, (int)blockDim.x >> 6, vg);
+}
+
+// The folded form of the grouped launch (ordinary geometry only: the row groups of a variable-geometry slice differ).  A node
+// of at least F members (F = 2 or 4, the second argument; one instance serves both) runs as members * 256 / F workgroups: in the
+// unfolded grid the 16 row-group workgroups of a (layer, slice) each pull the same 64 KiB slice and 8 KiB of x through their
+// CU's L1 into LDS before they touch a code, and a node of several members holds more workgroups than the chip has LDS slots
+// anyway.  Here one workgroup keeps slice and x and walks F of those row groups in turn (gemv_1x16_packed_body, FOLD); where it
+// sits is group_fold::place (group_fold.h), shared with the host.  Same LDS image, same block size, same bits in y.
+template <class T_, int PD, uint32_t XWIN, int EB>
+__global__ __launch_bounds__(1024) void gemv_1x16_packed_group_fold_kernel(const PackedGroupParams gp, const int fold) {
+  (void)gp;
+  static_assert(PK_S == group_fold::kSlices && PK_NST == group_fold::kStreams, "group_fold.h: 16 slices x 16 row groups");
+  const group_fold::Place at = group_fold::place(blockIdx.x, fold);
+  const group_segment_ptr s = (group_segment_ptr)__builtin_amdgcn_kernarg_segment_ptr() + at.segment;
+  PackedGemvParams p{};
+  p.codebook = s->codebook;
+  p.x = s->x;
+  p.ent = s->ent;
+  p.rowstart = s->rowstart;
+  p.in_groups = s->in_groups;
+  p.RG = s->RG;
+  p.M = s->M;
+  const uint32_t geom = s->geom;
+  p.ent_bytes = s->ent_bytes;
+  p.winfo = s->rest.winfo;
+  p.partial = s->rest.partial;
+  p.x_row_stride = s->rest.x_row_stride;
+  p.acc = s->rest.acc;
+  p.cb_absmax = s->rest.cb_absmax;
+  p.scales = s->rest.scales;
+  p.bias = s->rest.bias;
+  p.y = s->rest.y;
+  p.y_row_stride = s->rest.y_row_stride;
+#ifdef AQLM_PACKED_TRACE
+  p.trace = s->rest.trace;
+  p.dbg = s->rest.dbg;
+#endif
+  p.NW = (int)(geom & 0xffu);
+  p.XC = (int)((geom >> 8) & 0xfu);
+  p.fill_rotate = (int)((geom >> 15) & 1u);
+  p.T = (int)(geom >> 16);
+  gemv_1x16_packed_body<T_, 1, PD, XWIN, EB, false, false, true, true>(p, group_fold::stream(at, 0), (int)blockDim.x >> 6, PackedVgArgs{},
+                                                                       fold, at.group_step);
 }
 #endif
 

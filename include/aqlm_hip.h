@@ -983,7 +983,7 @@ int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2, void* str
  * for a conflict, kept for the window, runs started or broken, capture-call failures; process-wide, since the last reset.
  * NULL resets the counters.  Returns 0.
  *
- * Grouped launches (tuning key `packed_capture_merge`, 1..8, default 6; 1 = off).  Every node of a replayed graph pays a launch
+ * Grouped launches (tuning key `packed_capture_merge`, 1..8, default 4; 1 = off).  Every node of a replayed graph pays a launch
  * boundary and waits for the last workgroup of the node before it; within one launch the hardware puts the next workgroup
  * on a CU the moment one leaves.  With the key at n > 1, a one-row call of aqlm_hip_gemv_1x16_packed / _cells / _chain whose
  * layer runs on the compact-window kernels (<= 4096 input features, 4-byte entries, codebook range in the descriptor) and
@@ -994,9 +994,15 @@ int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2, void* str
  * it shares the node with included; ordering towards everything captured later is as above.  Same bits.  Nothing changes
  * outside a capture, in runs shorter than `packed_capture_min_run`, or for any other launch.  Should the runtime refuse the
  * rewrite, the call is captured as a node of its own, as with the key at 1, and the refusal is counted.
- * aqlm_hip_capture_overlap_stats_ex: the first `count` (0..9) of out[0..5] as above, then out[6] = calls that joined a node
+ * Folded nodes (tuning key `packed_group_fold`: 0 = default, which is 4; 1 = off; 2; 4).  A node of n >= F calls of ordinary
+ * geometry whose layers have at most one row of a row group per thread of the block runs as n * 256 / F workgroups instead of
+ * n * 256: a workgroup fills its 64 KiB codebook slice and x once and walks F row groups of its (layer, slice) in turn, where
+ * the unfolded grid fills them once per row group.  Chosen again at every join, so a node below F calls, a variable-geometry
+ * node and every launch outside a grouped node run the kernels they ran before.  Same LDS image, same block size, same bits.
+ * aqlm_hip_capture_overlap_stats_ex: the first `count` (0..10) of out[0..5] as above, then out[6] = calls that joined a node
  * (they are also counted in out[3]), out[7] = rewrites the runtime refused, out[8] = calls that added a node of their own
- * (out[0] - out[6]).  NULL resets all counters.  Returns 0, or AQLM_HIP_E_INVALID for a count outside 0..9.
+ * (out[0] - out[6]), out[9] = nodes that run the folded kernel.  NULL resets all counters.  Returns 0, or AQLM_HIP_E_INVALID
+ * for a count outside 0..10.  (A caller that asks for 9 gets the nine it got before.)
  */
 int aqlm_hip_capture_overlap_stats(uint64_t out[6]);
 int aqlm_hip_capture_overlap_stats_ex(uint64_t* out, int count);
