@@ -200,6 +200,7 @@ SIGNATURES = {
                                               ctypes.POINTER(_ci)]),
     "aqlm_hip_gemv_1x16_packed_cells": (_ci, [_descp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _cl, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_chain": (_ci, [_descp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _cl, _cl, _ci, _vp, _sz, _descp, _vp, _vp, _vp]),
+    "aqlm_hip_gemv_1x16_packed_chain_plan": (_ci, [_descp, _ci, _ci, _descp, ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_sz)]),
     "aqlm_hip_gemv_1x16_packed_partials": (_ci, [_descp, _vp, _vp, _vp, _ci, _cl, _ci, _vp, _sz, _vp]),
     "aqlm_hip_gemv_1x16_packed_publish": (_ci, [_descp, _vp, _vp, _vp, _ci, _cl, _ci, _xgp, _vp, _vp, _vp]),
     "aqlm_hip_xgmi_state_bytes": (_sz, [_ci]),
@@ -324,3 +325,13 @@ def packed_image_blocks_per_cu(desc: "PackedDesc", rows: int = 1, dtype: int = F
     check(lib.aqlm_hip_gemv_1x16_packed_image(ctypes.byref(desc), int(rows), int(dtype), int(probe_lds_bytes), None, None, ctypes.byref(n)),
           "packed_image")
     return n.value
+
+
+def packed_chain_plan(desc: "PackedDesc", next_desc=None, rows: int = 1, dtype: int = F16):
+    """-> (hint kept, prefetch waves, dynamic LDS bytes) of what aqlm_hip_gemv_1x16_packed_chain would launch for `rows` input rows
+    of the layer `desc` describes when `next_desc` names the next layer, under the current tuning
+    (aqlm_hip_gemv_1x16_packed_chain_plan).  No device needed."""
+    kept, waves, lds = _ci(0), _ci(0), _sz(0)
+    check(lib.aqlm_hip_gemv_1x16_packed_chain_plan(ctypes.byref(desc), int(rows), int(dtype), None if next_desc is None else ctypes.byref(next_desc),
+                                                   ctypes.byref(kept), ctypes.byref(waves), ctypes.byref(lds)), "packed_chain_plan")
+    return bool(kept.value), int(waves.value), int(lds.value)

@@ -55,6 +55,7 @@
 #include <vector>
 
 #include "aqlm_common.h"
+#include "chain_hint.h"  // when aqlm_hip_gemv_1x16_packed_chain passes the next layer on to its prefetch waves (host only)
 
 // The file is compiled twice: as it is for 8-element codebook vectors (16 B; 16 slices of 4096 entries x 16 row groups), and
 // through gemv_packed_g16.hip for 16-element vectors (AQLM_PK_G 16, AQLM_PK_S_LOG 5, AQLM_PK_NG_LOG 3: 32 B per entry, 32 slices
@@ -85,7 +86,7 @@
   X(gemv_1x16_packed_cells) X(gemv_1x16_packed) X(gemv_1x16_packed_chain) X(gemv_1x16_packed_partials)                         \
   X(gemv_1x16_packed_publish) X(gemv_1x16_packed_multi) X(gemv_1x16_packed_multi_cells) X(gemv_1x16_routed_packed_lds_bytes)   \
   X(routed_packed_entry_fill) X(gemv_1x16_routed_packed_geometry) X(gemv_1x16_routed_packed_supported)                         \
-  X(gemv_1x16_routed_packed) X(gemv_1x16_packed_image)
+  X(gemv_1x16_routed_packed) X(gemv_1x16_packed_image) X(gemv_1x16_packed_chain_plan)
 #define PK_TWIN_DECLARE(name) extern "C" __attribute__((visibility("hidden"))) decltype(aqlm_hip_##name) aqlm_hip_g16_##name;
 PK_TWIN_ENTRIES(PK_TWIN_DECLARE)
 #undef PK_TWIN_DECLARE

@@ -30,6 +30,20 @@ struct PackedNext {
   uint32_t block_bytes = 0;
 };
 
+// Chain prefetch, the rules the chain entry and its report (aqlm_hip_gemv_1x16_packed_chain_plan) share.
+// What the prefetch waves are told about the next layer (chain_hint.h): nothing for a variable-geometry buffer (the hint assumes
+// workgroup b of both layers sits on one XCD with the same slice), and nothing where their whole-KiB requests would run past the
+// buffer's last byte (3-byte entries that end the buffer).
+static chain_hint::Hint packed_chain_hint(const PackedLayout& LN) {
+  return chain_hint::decide(LN.off_ent, LN.ent_bytes, (int)LN.nst, LN.used, LN.G.vg != 0);
+}
+// prefetch waves a launch of L asks for when a next layer is named: the tuning key's count (0 = 2, negative = none), at most 7 and
+// at most what 16 waves leave beside the stream's own (the launch drops them all if the image with their dump zones does not fit)
+static int packed_chain_waves(const PackedLayout& L) {
+  const int want = tuning().packed_prefetch_waves < 0 ? 0 : (tuning().packed_prefetch_waves == 0 ? 2 : tuning().packed_prefetch_waves);
+  return std::min(std::min(want, 7), PK_MAX_NW - L.NW);
+}
+
 static int packed_launch_main(const PackedLayout& L, const void* packed, const void* codebook, const uint16_t* x, int nb,
                               long x_row_stride, int dtype, void* workspace, size_t workspace_bytes, hipStream_t stream,
                               const char* who, const PackedFused& fused = PackedFused{}, const PackedNext& next = PackedNext{},
@@ -63,10 +77,7 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
 #endif
   // chain prefetch: up to `packed_prefetch_waves` extra waves per workgroup (default 2) when a next layer is named
   int npw = 0;
-  if (next.ent && next.codebook && next.block_bytes) {
-    const int want = tuning().packed_prefetch_waves < 0 ? 0 : (tuning().packed_prefetch_waves == 0 ? 2 : tuning().packed_prefetch_waves);
-    npw = std::min(std::min(want, 7), PK_MAX_NW - L.NW);
-  }
+  if (next.ent && next.codebook && next.block_bytes) npw = packed_chain_waves(L);
   const uint32_t rotate = tuning().packed_fill_rotate ? 1u : 0u;
 #if AQLM_PK_G == 8
   // Capture overlap, grouped launches (capture_overlap.h): a one-row launch of a compact-window instance that finalizes into y
@@ -339,13 +350,61 @@ extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_chain)(const aqlm_hip_packed_des
       set_last_error("aqlm_hip_gemv_1x16_packed_chain: invalid descriptor / misaligned buffer of the next layer");
       return AQLM_HIP_E_INVALID;
     }
-    next.ent = (const uint8_t*)next_packed + LN.off_ent;
-    next.codebook = LN.relabel ? (const uint8_t*)next_packed + LN.off_cb : (const uint8_t*)next_codebook;
-    next.block_bytes = (uint32_t)(LN.ent_bytes / LN.nst);
-    if (LN.G.vg) next = PackedNext{};  // the hint assumes workgroup b of both layers sits on one XCD with the same slice: uniform geometry only
+    const chain_hint::Hint h = packed_chain_hint(LN);  // without a hint the call is the plain entry
+    if (h.kept) {
+      next.ent = (const uint8_t*)next_packed + h.ent_offset;
+      next.codebook = LN.relabel ? (const uint8_t*)next_packed + LN.off_cb : (const uint8_t*)next_codebook;
+      next.block_bytes = h.block_bytes;
+    }
   }
   return gemv_1x16_packed_impl(desc, packed, codebook, scales, bias, x, y, batch, x_row_stride, y_row_stride, dtype, workspace,
                                workspace_bytes, stream_, next);
+}
+
+// What the chain entry does with its hint, read off the rules it runs (packed_chain_hint, packed_chain_waves, packed_fused) and the
+// LDS map of the kernel instance its dispatch picks.
+extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_chain_plan)(const aqlm_hip_packed_desc* desc, int rows, int dtype,
+                                                     const aqlm_hip_packed_desc* next_desc, int* hint_kept, int* prefetch_waves,
+                                                     size_t* lds_bytes) {
+  PK_G16_FORWARD(desc, gemv_1x16_packed_chain_plan, desc, rows, dtype, next_desc, hint_kept, prefetch_waves, lds_bytes);
+  PackedLayout L, LN;
+  if (!desc_layout(desc, L) || rows < 1 || rows > AQLM_HIP_MAX_GEMV_BATCH || (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16)) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_chain_plan: invalid packed descriptor, rows outside 1..%d or a dtype other than float16 / "
+                   "bfloat16", AQLM_HIP_MAX_GEMV_BATCH);
+    return AQLM_HIP_E_INVALID;
+  }
+  if (next_desc && !desc_layout(next_desc, LN)) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_chain_plan: invalid descriptor of the next layer");
+    return AQLM_HIP_E_INVALID;
+  }
+  const int max_b = packed_max_batch(L.in_groups, L.RG);
+  if (max_b == 0) {
+    set_last_error("aqlm_hip_gemv_1x16_packed_chain_plan: layer does not fit the LDS image (in_features %d)", desc->in_features);
+    return AQLM_HIP_E_UNSUPPORTED;
+  }
+  const int nb = rows - (rows - 1) / max_b * max_b;  // the last launch of the call carries the hint (gemv_1x16_packed_impl)
+  // the two-kernel finalize never passes the hint on, and the variable-geometry kernels have no prefetch waves
+  const bool kept = next_desc && packed_fused(desc) && !L.G.vg && packed_chain_hint(LN).kept;
+  int npw = kept ? packed_chain_waves(L) : 0;
+  auto visit = [&](auto kern, auto lds_map) -> int {
+    using Map = decltype(lds_map);
+    (void)kern;
+    if (Map::total(L.in_groups, L.RG, npw, L.NW) > 160 * 1024) npw = 0;  // as the launch decides (packed_launch_main)
+    if (lds_bytes) *lds_bytes = Map::total(L.in_groups, L.RG, npw, L.NW);
+    return 0;
+  };
+  const bool sf = nb == 1 && packed_b1_slice_first(L.in_groups, L.RG);
+  const bool compact = nb == 1 && packed_b1_compact(L, packed_b1_pd(L));
+  int e;
+#if AQLM_PK_G == 8
+  if (L.G.vg) e = dispatch_packed_vg(dtype, nb, sf, compact, visit);
+  else
+#endif
+    e = dispatch_packed<SingleKernels>(dtype, nb, pick_pd(L), L.EB, sf, compact, visit);
+  if (e) return e;
+  if (hint_kept) *hint_kept = kept ? 1 : 0;
+  if (prefetch_waves) *prefetch_waves = npw;
+  return 0;
 }
 
 extern "C" PK_API int PK_ENTRY(gemv_1x16_packed_partials)(const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,

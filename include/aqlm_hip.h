@@ -434,13 +434,30 @@ int aqlm_hip_gemv_1x16_packed_cells(const aqlm_hip_packed_desc* desc, const void
  * workgroup request the next layer's entry stream and codebook so that they sit in the GPU's L2 / Infinity Cache when the
  * next launch starts (a batch-1 matvec is bound by the latency of its cold start, not by HBM bandwidth, and HBM idles
  * most of the kernel).  A hint: results are identical to aqlm_hip_gemv_1x16_packed; next_* may be NULL (then it IS that
- * call).  The next layer's buffers are only read.
+ * call).  The next layer's buffers are only read, and only inside [next_packed, next_packed + next_desc->used_bytes) and the
+ * 65536 vectors of next_codebook.  The prefetch waves read the next layer's entry stream in whole KiB per workgroup; where that
+ * would run past used_bytes -- a buffer of 3-byte entries that is not relabelled, whose stream of waves x steps x 776 bytes per
+ * workgroup is no whole number of KiB and ends the buffer -- the hint is dropped and the call is the plain one.  So it is for a
+ * variable-geometry next layer (aqlm_amd/csrc/chain_hint.h has the rule).  An invalid next_desc or a next_packed /
+ * next_codebook that is not 16-byte aligned: AQLM_HIP_E_INVALID, nothing is launched.
  */
 int aqlm_hip_gemv_1x16_packed_chain(const aqlm_hip_packed_desc* desc, void* packed, const void* codebook,
                                     const void* scales, const void* bias, const void* x, void* y, int batch,
                                     long x_row_stride, long y_row_stride, int dtype, void* workspace,
                                     size_t workspace_bytes, const aqlm_hip_packed_desc* next_desc,
                                     const void* next_packed, const void* next_codebook, void* stream);
+
+/*
+ * What aqlm_hip_gemv_1x16_packed_chain would do with its hint for `rows` input rows of this layer and this next layer under the
+ * current tuning (no launch, no device needed; the entry and this report read one and the same rule): *hint_kept = 1 when the
+ * next layer's entry stream is handed to the prefetch waves (0: dropped -- variable geometry, requests that would leave the
+ * buffer, or the two-kernel finalize, which never prefetches), *prefetch_waves = the extra waves of every workgroup of the launch
+ * that carries the hint (the last one when the rows go out in several; tuning key packed_prefetch_waves, at most 16 - desc->waves,
+ * 0 when the LDS image with their landing zones would not fit the CU), *lds_bytes = the dynamic LDS of that launch.  Every output
+ * pointer may be NULL.  0, or AQLM_HIP_E_INVALID / _UNSUPPORTED as the chain entry would answer for these descriptors.
+ */
+int aqlm_hip_gemv_1x16_packed_chain_plan(const aqlm_hip_packed_desc* desc, int rows, int dtype, const aqlm_hip_packed_desc* next_desc,
+                                         int* hint_kept, int* prefetch_waves, size_t* lds_bytes);
 
 /*
  * aqlm_hip_gemv_1x16_packed for up to AQLM_HIP_MAX_SEGMENTS prepacked layers that share x, in one launch (+ one
