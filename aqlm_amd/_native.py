@@ -296,7 +296,7 @@ def get_tuning(key: str) -> int:
 
 
 CAPTURE_OVERLAP_FIELDS = ("seen", "relaxed", "kept_conflict", "kept_window", "runs_broken", "api_failures",
-                          "merged", "merge_refused", "nodes_added", "folded")
+                          "merged", "merge_refused", "nodes_added", "folded", "head_regrouped", "head_moved", "head_refused")
 
 
 def capture_overlap_stats(reset: bool = False) -> dict:

@@ -80,6 +80,7 @@ static int* tuning_slot(const char* key) {
   if (!strcmp(key, "packed_capture_window")) return &t.packed_capture_window;
   if (!strcmp(key, "packed_capture_min_run")) return &t.packed_capture_min_run;
   if (!strcmp(key, "packed_capture_merge")) return &t.packed_capture_merge;
+  if (!strcmp(key, "packed_capture_head")) return &t.packed_capture_head;
   if (!strcmp(key, "packed_group_fold")) return &t.packed_group_fold;
   if (!strcmp(key, "packed_pipe")) return &t.packed_pipe;
   if (!strcmp(key, "packed_prefetch_waves")) return &t.packed_prefetch_waves;
@@ -98,9 +99,12 @@ struct CaptureOverlapState {
   capture_overlap::Planner planner;
   // seen, relaxed, kept for a conflict, kept for the window, runs broken, API failures; then: launches that joined a node
   // (also counted as kept for the window), rewrites of a node the runtime refused, launches that added a node of their own,
-  // nodes that went over to the folded grouped kernel (group_fold.h)
-  uint64_t stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // nodes that went over to the folded grouped kernel (group_fold.h); then: runs whose head was regrouped, head launches that
+  // gave up a node of their own, head scripts that stopped early (capture_overlap.h, "Regrouping the head")
+  static constexpr int kStats = 13;
+  uint64_t stats[kStats] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool off = false;                        // a capture call failed once: every launch as issued from then on
+  bool head_off = false;                   // a head script stopped early once: no head is regrouped from then on
 };
 CaptureOverlapState& capture_state() {
   static CaptureOverlapState s;
@@ -130,6 +134,48 @@ bool read_capture(hipStream_t stream, bool& capturing, unsigned long long& id, s
   return true;
 }
 }  // namespace
+
+bool capture_build_node(const unsigned char* members, int n, CaptureNode& out) {
+  if (!members || n < 1 || n > capture_overlap::kMaxMerge) return false;
+  CaptureMember m0;
+  memcpy(&m0, members, sizeof m0);
+  out.params = hipKernelNodeParams{};
+  out.params.blockDim = dim3(m0.threads);
+  out.params.sharedMemBytes = m0.lds;
+  out.params.kernelParams = out.args;
+  out.params.extra = nullptr;
+  out.fold = 1;
+  if (n == 1) {  // the launch as its call made it
+    if (!m0.func || m0.nargs == 0 || m0.nargs > CaptureMember::kMaxArgs) return false;
+    out.store.assign(m0.args, m0.args + CaptureMember::kArgBytes);
+    for (unsigned i = 0; i < m0.nargs; ++i) {
+      if (m0.arg_off[i] >= CaptureMember::kArgBytes) return false;
+      out.args[i] = out.store.data() + m0.arg_off[i];
+    }
+    out.params.func = const_cast<void*>(m0.func);
+    out.params.gridDim = dim3(m0.grid);
+    return true;
+  }
+  if (!m0.group_func || m0.seg_bytes == 0 || m0.seg_bytes > CaptureMember::kSegBytes || m0.seg_bytes % 8 != 0) return false;
+  const size_t segs = (size_t)capture_overlap::kMaxMerge * m0.seg_bytes;  // the grouped kernels' first argument, whole
+  out.store.assign(segs + sizeof(int), 0);
+  bool one_row = m0.fold_func != nullptr;  // the folded kernel finalizes one row per thread
+  for (int i = 0; i < n; ++i) {
+    CaptureMember m;
+    memcpy(&m, members + (size_t)i * sizeof m, sizeof m);
+    if (m.group_func != m0.group_func || m.fold_func != m0.fold_func || m.threads != m0.threads || m.lds != m0.lds || m.seg_bytes != m0.seg_bytes)
+      return false;
+    memcpy(out.store.data() + (size_t)i * m0.seg_bytes, m.seg, m0.seg_bytes);
+    one_row = one_row && m.rows_per_group <= (int)m0.threads;
+  }
+  out.fold = one_row ? group_fold::choose(tuning().packed_group_fold, n) : 1;
+  memcpy(out.store.data() + segs, &out.fold, sizeof(int));
+  out.args[0] = out.store.data();
+  out.args[1] = out.store.data() + segs;  // (the unfolded kernel takes the first only)
+  out.params.func = const_cast<void*>(out.fold > 1 ? m0.fold_func : m0.group_func);
+  out.params.gridDim = dim3(group_fold::grid(n, out.fold));
+  return true;
+}
 
 void CaptureRelax::fail(const char* what, hipError_t e) {
   (void)hipGetLastError();  // the launch that follows checks the sticky error: this one is ours
@@ -182,10 +228,8 @@ int CaptureRelax::begin(uint64_t key, const void* member, size_t member_bytes) {
   if (!active_ || begun_) return 0;
   begun_ = true;
   const int merge = std::min(std::max(tuning().packed_capture_merge, 1), capture_overlap::kMaxMerge);
-  if (merge > 1 && key != 0 && member) {
-    key_ = key;
-    member_.assign(static_cast<const unsigned char*>(member), static_cast<const unsigned char*>(member) + member_bytes);
-  }
+  if (member) member_.assign(static_cast<const unsigned char*>(member), static_cast<const unsigned char*>(member) + member_bytes);
+  if (merge > 1 && key != 0 && member) key_ = key;
   CaptureOverlapState& s = capture_state();
   std::lock_guard<std::mutex> lock(s.mu);
   plan_ = s.planner.run(id_).plan(before_.data(), before_.size(), fp, tuning().packed_capture_window, tuning().packed_capture_min_run,
@@ -222,6 +266,78 @@ bool CaptureRelax::join(const hipKernelNodeParams* node, int folded_delta) {
   return false;
 }
 
+bool CaptureRelax::join_members() {
+  const size_t n = plan_.merge ? (size_t)plan_.member : 0;
+  if (n == 0 || n >= (size_t)capture_overlap::kMaxMerge || plan_.payload.size() != n * sizeof(CaptureMember) || member_.size() != sizeof(CaptureMember))
+    return join(nullptr);
+  std::vector<unsigned char> all(plan_.payload);
+  all.insert(all.end(), member_.begin(), member_.end());
+  // The node is rewritten on every join, so the choice of its form follows the member count: folded from F members on (the grid
+  // never drops under 256 workgroups), the unfolded kernel below that.  The planner's key is the unfolded instance's either way.
+  CaptureNode before, after;
+  if (!capture_build_node(all.data(), (int)n + 1, after)) return join(nullptr);
+  const bool was_folded = capture_build_node(plan_.payload.data(), (int)n, before) && before.fold > 1;
+  return join(&after.params, (after.fold > 1 ? 1 : 0) - (was_folded ? 1 : 0));
+}
+
+// "Regrouping the head" (capture_overlap.h): the run has just reached packed_capture_min_run launches.  Every node is built
+// before the graph is touched; then the script step by step, and the planner is told how far it got.  `now`: the stream's
+// dependency set, kept current.
+void CaptureRelax::regroup_head(capture_overlap::Run& run, std::vector<capture_overlap::NodeId>& now) {
+  CaptureOverlapState& s = capture_state();
+  if (s.head_off || tuning().packed_capture_head == 0) return;
+  const int merge = std::min(std::max(tuning().packed_capture_merge, 1), capture_overlap::kMaxMerge);
+  const capture_overlap::HeadScript script = run.regroup_head(tuning().packed_capture_min_run, merge);
+  if (script.empty()) return;
+  using capture_overlap::HeadStep;
+  std::vector<CaptureNode> nodes(script.steps.size());
+  uint64_t folded = 0;
+  for (size_t k = 0; k < script.steps.size(); ++k) {
+    const HeadStep& st = script.steps[k];
+    if (st.op != HeadStep::kRewrite) continue;
+    if (st.payload.size() != st.members.size() * sizeof(CaptureMember) ||
+        !capture_build_node(st.payload.data(), (int)st.members.size(), nodes[k])) {
+      run.head_applied(0);  // a group that cannot be built: the graph stays as issued
+      ++s.stats[12];
+      return;
+    }
+    folded += nodes[k].fold > 1;
+  }
+  size_t done = 0;
+  hipError_t e = hipSuccess;
+  const char* what = "";
+  for (; done < script.steps.size(); ++done) {
+    const HeadStep& st = script.steps[done];
+    const hipGraphNode_t node = reinterpret_cast<hipGraphNode_t>(static_cast<uintptr_t>(st.node));
+    if (st.op == HeadStep::kRewrite) {
+      what = "hipGraphKernelNodeSetParams";
+      e = hipGraphKernelNodeSetParams(node, &nodes[done].params);
+    } else if (st.op == HeadStep::kSetStreamDeps) {
+      what = "hipStreamUpdateCaptureDependencies";
+      e = set_capture_deps(stream_, {st.node});
+      if (e == hipSuccess) now.assign(1, st.node);
+    } else {
+      what = "hipGraphDestroyNode";
+      e = hipGraphDestroyNode(node);
+    }
+    if (e != hipSuccess) break;
+    head_touched_ = true;
+  }
+  run.head_applied(done);
+  if (done == script.steps.size()) {
+    ++s.stats[10];
+    s.stats[11] += script.moved;
+    s.stats[9] += folded;
+    return;
+  }
+  // every prefix of the script is a correct graph: the capture goes on from what is left, and no head is regrouped again
+  (void)hipGetLastError();
+  ++s.stats[12];
+  s.head_off = true;
+  set_last_error("capture overlap: regrouping of run heads switched off for this process: %s: %s (%d) at step %zu of %zu", what,
+                 hipGetErrorString(e), (int)e, done, script.steps.size());
+}
+
 int CaptureRelax::launched() {
   if (!active_ || !begun_ || done_) return 0;
   done_ = true;
@@ -235,6 +351,7 @@ int CaptureRelax::launched() {
   const bool read = read_capture(stream_, capturing, id, now, err);
   std::vector<capture_overlap::NodeId> want;
   if (read && capturing && id == id_ && now.size() == 1 && run.commit(plan_, now[0], std::move(fp), member_.data(), member_.size())) {
+    if (plan_.head) regroup_head(run, now);
     want = run.tail();
   } else {
     // the new node is not known: everything the call found, and whatever the stream names now
@@ -253,7 +370,7 @@ int CaptureRelax::launched() {
   const hipError_t e = set_capture_deps(stream_, want);
   if (e == hipSuccess) return 0;
   run.reset();
-  const bool moved = changed_ || want.size() > 1;
+  const bool moved = changed_ || head_touched_ || want.size() > 1;
   fail("hipStreamUpdateCaptureDependencies", e);
   return moved ? (int)e : 0;
 }
@@ -312,7 +429,7 @@ extern "C" int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2
 static int capture_overlap_stats(uint64_t* out, int n) {
   aqlm::CaptureOverlapState& s = aqlm::capture_state();
   std::lock_guard<std::mutex> lock(s.mu);
-  for (int i = 0; i < 10; ++i) {
+  for (int i = 0; i < aqlm::CaptureOverlapState::kStats; ++i) {
     if (!out) s.stats[i] = 0;
     else if (i < n) out[i] = s.stats[i];
   }
@@ -322,8 +439,8 @@ static int capture_overlap_stats(uint64_t* out, int n) {
 extern "C" int aqlm_hip_capture_overlap_stats(uint64_t out[6]) { return capture_overlap_stats(out, 6); }
 
 extern "C" int aqlm_hip_capture_overlap_stats_ex(uint64_t* out, int count) {
-  if (out && (count < 0 || count > 10)) {
-    aqlm::set_last_error("aqlm_hip_capture_overlap_stats_ex: count must be 0..10 (got %d)", count);
+  if (out && (count < 0 || count > aqlm::CaptureOverlapState::kStats)) {
+    aqlm::set_last_error("aqlm_hip_capture_overlap_stats_ex: count must be 0..13 (got %d)", count);
     return AQLM_HIP_E_INVALID;
   }
   return capture_overlap_stats(out, count);

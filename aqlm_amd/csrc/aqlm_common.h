@@ -5,6 +5,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+#include <vector>
+
 #include "../../include/aqlm_hip.h"
 #include "capture_overlap.h"
 #include "group_fold.h"
@@ -181,10 +184,64 @@ struct Tuning {
   int packed_capture_window = capture_overlap::kDefaultWindow;  // packed 1x16 matvecs captured into a graph: consecutive launches that share no memory and may run side by side (1..8; capture_overlap.h); 1 = every launch after the previous one
   int packed_capture_min_run = capture_overlap::kDefaultMinRun;  // ... launches an uninterrupted run of them must hold before any is relaxed (a graph with branches costs host time per node: capture_overlap.h); 1 = from the second launch on
   int packed_capture_merge = capture_overlap::kDefaultMerge;  // ... launches of one kernel instance that may share a graph node, run by the grouped kernel (1..8; capture_overlap.h, "Grouped launches"); 1 = every launch a node of its own
+  int packed_capture_head = 1;   // ... once a run holds packed_capture_min_run launches, its first launches -- a chain of single launches until then -- are regrouped in place into grouped / folded nodes (capture_overlap.h, "Regrouping the head"): 1 = on, 0 = they stay single launches
   int packed_group_fold = 0;     // ... workgroups of such a node that keep their codebook slice and x in LDS and walk F row groups of their (layer, slice) in turn (group_fold.h): 0 = default (4), 1 = off, 2, 4; a node of fewer than F launches is not folded
   int packed_dequant_by_xcd = 1; // aqlm_hip_dequant_1x16_packed, grid order: 1 = by the measured rule (16-B vectors: the streams that run together on an XCD are the slices of one row group, so their partial-line stores meet in one L2; 32-B vectors: stream-major like the unpack kernel), 0 = always stream-major, 2 = always by XCD (A/B runs)
 };
 Tuning& tuning();
+
+// What a captured packed matvec leaves with the planner (the payload of capture_overlap.h): enough to build the graph node of
+// any group it is a member of, also inside a call of another kernel instance -- the call that regroups a run's head may have
+// the other shape.  A node of one member launches `func` as the member's own call did; a node of several launches the grouped
+// form of their kernel instance (`group_func`; its only argument is their segments, kMaxMerge of `seg_bytes` each) or, by
+// group_fold::choose and while no member has more rows per group than the block has threads, the folded form (`fold_func`,
+// null: none; second argument the fold factor).
+struct CaptureMember {
+  static constexpr unsigned kMaxArgs = 12, kArgBytes = 320, kSegBytes = 256;
+  const void* func;  // the launch as issued: kernel, geometry, arguments
+  unsigned grid, threads, lds, nargs;
+  uint16_t arg_off[kMaxArgs];  // into args
+  const void* group_func;  // null: the launch shares no node
+  const void* fold_func;
+  unsigned seg_bytes;
+  int rows_per_group;
+  alignas(8) unsigned char args[kArgBytes];
+  alignas(8) unsigned char seg[kSegBytes];
+};
+// the launch half: parameter types from the kernel's own signature, values converted as a launch converts them
+template <class... P, class... A>
+inline bool capture_member_launch(CaptureMember& m, void (*kern)(P...), unsigned grid, unsigned threads, size_t lds, const A&... a) {
+  static_assert(sizeof...(P) == sizeof...(A) && sizeof...(P) <= CaptureMember::kMaxArgs, "one value per kernel parameter");
+  m.func = reinterpret_cast<const void*>(kern);
+  m.grid = grid;
+  m.threads = threads;
+  m.lds = (unsigned)lds;
+  m.nargs = 0;
+  size_t at = 0;
+  bool fits = true;
+  auto put = [&](const auto& v) {
+    static_assert(alignof(decltype(v)) <= 8, "arguments are packed at 8-byte boundaries");
+    at = (at + 7) & ~(size_t)7;
+    if (at + sizeof v > CaptureMember::kArgBytes) {
+      fits = false;
+      return;
+    }
+    memcpy(m.args + at, &v, sizeof v);
+    m.arg_off[m.nargs++] = (uint16_t)at;
+    at += sizeof v;
+  };
+  (put(static_cast<std::remove_cv_t<P>>(a)), ...);
+  return fits;
+}
+// The node of the `n` members at `members` (n x sizeof(CaptureMember) bytes, 1 <= n <= kMaxMerge) under the tuning value
+// packed_group_fold: try_join and the head regrouping build every node through this.  False: the members cannot share a node.
+struct CaptureNode {
+  hipKernelNodeParams params;
+  int fold = 1;  // > 1: the folded form
+  void* args[CaptureMember::kMaxArgs];
+  std::vector<unsigned char> store;  // what args point into (the runtime copies it when the node is set)
+};
+bool capture_build_node(const unsigned char* members, int n, CaptureNode& out);
 
 // The first kernel of a packed matvec call on a stream that is being captured: ordered by the memory the call touches, not
 // by the order of issue (capture_overlap.h has the rule, api.hip the state shared by both builds of the packed entries).
@@ -201,15 +258,18 @@ class CaptureRelax {
   bool capturing() const { return active_; }
   capture_overlap::Footprint fp;
   // `key` != 0: the launch is one grid of a kernel whose grouped form can run several such launches as one (capture_overlap.h,
-  // "Grouped launches"); the key names the kernel instance, block size and LDS bytes, `member` is what the grouped launch needs
-  // to know of this one.  When begin() returns n > 0 the launch may join a node that holds n launches already: group() is
-  // their members in order, and the caller builds the node for n + 1 and hands it to join().  join() false: the runtime
-  // refused the rewrite (counted, not an error); the stream is set up for an ordinary launch and the caller makes one.
+  // "Grouped launches"); the key names the kernel instance, block size and LDS bytes, `member` is the launch's CaptureMember
+  // (kept with the planner also at key 0: the head of a run may be regrouped later).  When begin() returns n > 0 the launch
+  // may join a node that holds n launches already: group() is their members in order, and join_members() builds the node
+  // for n + 1 and hands it to join().  join() false: the runtime refused the rewrite (counted, not an error); the stream is
+  // set up for an ordinary launch and the caller makes one.
   int begin(uint64_t key = 0, const void* member = nullptr, size_t member_bytes = 0);
   const std::vector<unsigned char>& group() const { return plan_.payload; }
   // (null: the caller cannot build the node; `folded_delta`: +1 when this rewrite turns the node into its folded form
   // (group_fold.h), -1 when it turns it back -- added to the count of folded nodes when the rewrite holds)
   bool join(const hipKernelNodeParams* node, int folded_delta = 0);
+  // (the same from the members: builds the node of group() plus this launch's member through capture_build_node)
+  bool join_members();
   // After the launch (later launches of the call: no effect; nor after a join()).  0, or the error when the stream could not
   // be made to wait for the launches that ran beside this one: the capture would be wrong, so the call fails.
   int launched();
@@ -217,8 +277,9 @@ class CaptureRelax {
  private:
   void fail(const char* what, hipError_t e);
   void apply_plan();
+  void regroup_head(capture_overlap::Run& run, std::vector<capture_overlap::NodeId>& now);  // after the commit of launched(); caller holds the mutex
   hipStream_t stream_;
-  bool active_ = false, begun_ = false, done_ = false, changed_ = false;
+  bool active_ = false, begun_ = false, done_ = false, changed_ = false, head_touched_ = false;
   uint64_t key_ = 0;
   std::vector<unsigned char> member_;
   unsigned long long id_ = 0;

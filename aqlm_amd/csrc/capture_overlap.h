@@ -33,6 +33,25 @@
 // key finds its own partner first.  The caller rewrites the node (Plan::target, Plan::member); the members' launch parameters
 // travel with the entry as an opaque payload.  A full group, another key, a footprint that would outgrow kMaxRanges: the
 // answers of step 2 as they were.  The stream's dependency set after a joined launch is the tail, the same nodes as before.
+//
+// Regrouping the head.  A run relaxes and joins nothing until it holds `min_run` launches (kDefaultMinRun has the reason), so
+// the first `min_run` launches of a long run -- its HEAD -- are a chain of single launches, each waiting for the one before:
+// only at the last of them does the planner learn that the run is long.  Until then it keeps, per head launch, the node, the
+// launch's own footprint, key and payload, and whether any of them was planned kConflict or restarted the run (kMaxRanges).
+// If none was, the head launches are pairwise free of hazards (each was checked against the union of those before it), and
+// after the commit that brings the run to `min_run` launches Run::regroup_head() regroups them in place: walking the head in
+// issue order, a launch of key k joins the earliest group of key k with room (merge_max), else it opens one; keyless launches
+// are groups of one; groups are ordered by their first member; group i takes the i-th node of the chain, whatever that node
+// launched before, and the nodes left over -- a suffix of the chain -- go.  The head stays ONE chain in stream order and the
+// run's base, length and later planning are untouched: launch min_run + 1 is still the first relaxed one.  What comes back is
+// an edit script for the caller to apply in order,
+//   Rewrite(node_i, members of group i)          for every group whose node launches something else now,
+//   SetStreamDeps({predecessor}), Destroy(node)  for every surplus node, last to first,
+// every prefix of which leaves a correct graph: after the rewrites alone a launch may run twice, each copy in a node of its
+// own of the one chain (a repeated launch writes the same bits); every destroy removes a node nothing depends on.  The caller
+// reports how far it got (head_applied): after the whole script the tail is the last group's node with that group's key,
+// member count and payload, so that later launches may join it; after a script that stopped, the newest node that is left,
+// with key 0.  Either way the entry keeps the footprint of the whole head.  Runs shorter than `min_run` see none of this.
 #ifndef AQLM_CAPTURE_OVERLAP_H_
 #define AQLM_CAPTURE_OVERLAP_H_
 
@@ -111,6 +130,23 @@ struct Plan {
   NodeId target = 0;                   // its node
   int member = 0;                      // the launch's index among the node's launches (>= 1)
   std::vector<unsigned char> payload;  // what the entry's launches left with commit(), in order
+  bool head = false;                   // the launch is among the run's first `min_run` ("Regrouping the head")
+};
+
+// One step of the edit script that regroups a run's head.
+struct HeadStep {
+  enum Op { kRewrite = 0, kSetStreamDeps = 1, kDestroy = 2 };
+  Op op = kRewrite;
+  NodeId node = 0;                     // kRewrite: the node to rewrite; kSetStreamDeps: the node the stream is to wait for; kDestroy: the node
+  uint64_t key = 0;                    // kRewrite: of the group
+  std::vector<size_t> members;         // kRewrite: the group's launches, as positions in the head
+  std::vector<unsigned char> payload;  // kRewrite: their payloads, in order
+};
+struct HeadScript {
+  std::vector<HeadStep> steps;
+  size_t groups = 0;  // nodes the head keeps
+  size_t moved = 0;   // launches that gave up a node of their own (= nodes destroyed by the whole script)
+  bool empty() const { return steps.empty(); }
 };
 
 class Run {
@@ -127,12 +163,14 @@ class Run {
     Plan p;
     p.key = key;
     p.generation = ++generation_;
+    p.head = true;  // (a launch that starts a run is its first)
     if (!is_tail(deps, num_deps)) {
       p.kind = kBroken;
       p.restart = true;
       p.deps.assign(deps, deps + num_deps);
       return p;
     }
+    p.head = length_ < (size_t)std::max(min_run, 1);
     for (size_t i = 0; i < tail_.size(); ++i)
       if (hazard(tail_[i].fp, fp)) p.leave.push_back(i);
     if (!p.leave.empty()) {
@@ -146,6 +184,7 @@ class Run {
         if (tail_[i].key != key || tail_[i].members >= merge_max) continue;
         if (fp.ranges.size() + tail_[i].fp.ranges.size() > kMaxRanges) {  // too much for one entry: wait for the whole tail
           p.restart = true;
+          p.head = true;
           p.deps.assign(deps, deps + num_deps);
           return p;
         }
@@ -166,6 +205,7 @@ class Run {
     for (size_t i : p.leave) ranges += tail_[i].fp.ranges.size();
     if (ranges > kMaxRanges) {  // too much to answer for: wait for the whole tail (= D) and start over from there
       p.restart = true;
+      p.head = true;
       p.leave.clear();
       p.deps.assign(deps, deps + num_deps);
       return p;
@@ -190,12 +230,17 @@ class Run {
       ++generation_;
       ++length_;
       tail_.push_back(std::move(e));  // the youngest now
+      head_.clear();
       return true;
     }
+    Footprint own;
+    if (p.head && head_.size() == (p.restart ? 0 : length_)) own = fp;
     if (p.restart) {
       base_ = p.deps;
       tail_.clear();
       length_ = 0;
+      head_.clear();
+      head_ok_ = p.kind == kBroken;  // (a restart inside a run, kMaxRanges: its launches are not regrouped)
     } else {
       for (size_t k = p.leave.size(); k-- > 0;) {
         const Footprint& gone = tail_[p.leave[k]].fp;
@@ -203,10 +248,99 @@ class Run {
         tail_.erase(tail_.begin() + (ptrdiff_t)p.leave[k]);
       }
     }
+    // the head: every launch since the run began, while none is relaxed or joined
+    if (p.head && head_.size() == length_) {
+      if (p.kind == kConflict) head_ok_ = false;
+      head_.push_back(HeadLaunch{node, own, p.key, std::vector<unsigned char>(pb, pb + (pb ? payload_bytes : 0))});
+    } else {
+      head_.clear();
+    }
     ++generation_;
     ++length_;
     tail_.push_back(Entry{node, std::move(fp), p.key, 1, std::vector<unsigned char>(pb, pb + (pb ? payload_bytes : 0))});
     return true;
+  }
+
+  // "Regrouping the head": to be called after the commit that brought the run to `min_run` launches (any other time: an empty
+  // script).  An empty script also when a head launch was planned kConflict or restarted the run, when no two head launches
+  // share a non-zero key (or merge_max <= 1), and when a launch that would have to change nodes left no payload to build it
+  // from.  A script that is not empty must be answered by head_applied() before the run plans again.
+  HeadScript regroup_head(int min_run, int merge_max) {
+    HeadScript s;
+    merge_max = std::min(merge_max, kMaxMerge);
+    const size_t n = head_.size();
+    if (length_ < (size_t)std::max(min_run, 1)) return s;  // not yet
+    if (!head_ok_ || merge_max <= 1 || n < 2 || n != length_ || n != (size_t)std::max(min_run, 1) || tail_.size() != 1 ||
+        tail_[0].node != head_[n - 1].node) {
+      head_.clear();
+      return s;
+    }
+    std::vector<std::vector<size_t>> groups;
+    for (size_t i = 0; i < n; ++i) {
+      size_t g = groups.size();
+      for (size_t k = 0; head_[i].key != 0 && k < groups.size() && g == groups.size(); ++k)
+        if (head_[groups[k][0]].key == head_[i].key && groups[k].size() < (size_t)merge_max) g = k;
+      if (g == groups.size()) groups.emplace_back();
+      groups[g].push_back(i);
+    }
+    bool possible = groups.size() < n;
+    for (size_t g = 0; g < groups.size(); ++g)
+      for (size_t i : groups[g])
+        if (i != g && head_[i].payload.empty()) possible = false;  // cannot be built in another node
+    if (!possible) {
+      head_.clear();
+      return s;
+    }
+    for (size_t g = 0; g < groups.size(); ++g) {
+      if (groups[g].size() == 1 && groups[g][0] == g) continue;  // the node launches exactly that already
+      HeadStep st;
+      st.op = HeadStep::kRewrite;
+      st.node = head_[g].node;
+      st.key = head_[groups[g][0]].key;
+      st.members = groups[g];
+      for (size_t i : groups[g]) st.payload.insert(st.payload.end(), head_[i].payload.begin(), head_[i].payload.end());
+      s.steps.push_back(std::move(st));
+    }
+    for (size_t j = n; j-- > groups.size();) {
+      HeadStep dep, gone;
+      dep.op = HeadStep::kSetStreamDeps;
+      dep.node = head_[j - 1].node;
+      gone.op = HeadStep::kDestroy;
+      gone.node = head_[j].node;
+      s.steps.push_back(std::move(dep));
+      s.steps.push_back(std::move(gone));
+    }
+    s.groups = groups.size();
+    s.moved = n - groups.size();
+    pending_ = s;
+    pending_last_ = std::move(groups.back());
+    ++generation_;  // nothing planned before the script holds afterwards
+    return s;
+  }
+
+  // The caller applied the first `steps_done` steps of the script regroup_head() returned (all of them: the head is
+  // regrouped; fewer: the script stopped there and the run keeps what is still true).  tail() is what the stream is to wait for.
+  void head_applied(size_t steps_done) {
+    if (pending_.empty() || tail_.size() != 1 || head_.empty()) return;
+    ++generation_;
+    Entry& e = tail_[0];
+    if (steps_done >= pending_.steps.size()) {
+      e.node = head_[pending_.groups - 1].node;
+      e.key = head_[pending_last_[0]].key;
+      e.members = (int)pending_last_.size();
+      e.payload.clear();
+      for (size_t i : pending_last_) e.payload.insert(e.payload.end(), head_[i].payload.begin(), head_[i].payload.end());
+    } else {
+      size_t destroyed = 0;
+      for (size_t k = 0; k < steps_done; ++k) destroyed += pending_.steps[k].op == HeadStep::kDestroy;
+      e.node = head_[head_.size() - 1 - destroyed].node;  // the newest node that is left; what it launches now is not tracked
+      e.key = 0;
+      e.members = 1;
+      e.payload.clear();
+    }
+    pending_ = HeadScript{};
+    pending_last_.clear();
+    head_.clear();
   }
 
   bool latest(const Plan& p) const { return p.generation == generation_; }
@@ -217,6 +351,10 @@ class Run {
     base_.clear();
     tail_.clear();
     length_ = 0;
+    head_.clear();
+    head_ok_ = false;
+    pending_ = HeadScript{};
+    pending_last_.clear();
   }
 
   std::vector<NodeId> tail() const {
@@ -245,8 +383,18 @@ class Run {
     }
     return true;
   }
+  struct HeadLaunch {
+    NodeId node;
+    Footprint fp;  // its own
+    uint64_t key;
+    std::vector<unsigned char> payload;
+  };
   std::vector<NodeId> base_;
   std::vector<Entry> tail_;  // oldest first
+  std::vector<HeadLaunch> head_;  // the run's launches so far, while there are at most `min_run` of them
+  bool head_ok_ = false;          // none of them was planned kConflict or restarted the run after its first launch
+  HeadScript pending_;            // the script regroup_head() handed out, until head_applied()
+  std::vector<size_t> pending_last_;  // its last group
   size_t length_ = 0;        // launches of the run so far
   uint64_t generation_ = 0;
 };

@@ -84,10 +84,15 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
   // is one grid of 256 workgroups, and gemv_1x16_packed_group_kernel runs up to PK_GROUP_MAX such grids of one instance, block
   // size and LDS image as one.  When the planner lets this launch join a node, the node is rewritten to the grouped kernel
   // with this layer as one more segment and nothing is launched.  `joined` false: launch as usual (begin() has been called).
-  auto try_join = [&](bool vg, const PackedGroupSegment& me, unsigned threads, size_t lds, bool& joined) -> int {
+  // `member` holds the launch as it would be made (capture_member_launch); the grouped forms are added here, and the whole
+  // travels with the planner, which may also regroup the launch later ("Regrouping the head").
+  static_assert(sizeof(PackedGroupSegment) <= CaptureMember::kSegBytes && sizeof(PackedGroupSegment) % 8 == 0 &&
+                    sizeof(PackedGroupParams) == (size_t)capture_overlap::kMaxMerge * sizeof(PackedGroupSegment),
+                "capture_build_node lays the segments out as PackedGroupParams");
+  auto try_join = [&](bool vg, const PackedGroupSegment& me, unsigned threads, size_t lds, CaptureMember& member, bool& joined) -> int {
     joined = false;
     if (tuning().packed_capture_merge <= 1) {
-      if (relax) relax->begin();
+      if (relax) relax->begin(0, member.func ? &member : nullptr, sizeof member);
       return 0;
     }
     const void* gk = vg ? (dtype == AQLM_HIP_F16 ? (const void*)gemv_1x16_packed_group_kernel<F16, 3, PK_XWIN_COMPACT, 4, true>
@@ -104,34 +109,14 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
     if (!relax) return 0;
     uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(gk) * 0x9E3779B97F4A7C15ull ^ ((uint64_t)threads << 32) ^ (uint64_t)lds;
     if (key == 0) key = 1;
-    const int n = relax->begin(key, &me, sizeof me);
-    if (n <= 0) return 0;
-    const std::vector<unsigned char>& members = relax->group();
-    if (n >= PK_GROUP_MAX || members.size() != (size_t)n * sizeof(PackedGroupSegment)) {
-      relax->join(nullptr);
-      return 0;
-    }
-    PackedGroupParams gp{};
-    memcpy(gp.seg, members.data(), members.size());
-    gp.seg[n] = me;
-    // The node is rewritten on every join, so the choice follows the member count: folded from F members on (the grid never
-    // drops under 256 workgroups), the unfolded kernel below that.  The planner's key is the unfolded instance's either way.
     // The folded kernel finalizes one row per thread (a second row's loads would stand in front of the next pass's ring): a
-    // layer with more rows in a group than the block has threads keeps its node unfolded.
-    const int key_fold = tuning().packed_group_fold;
-    bool one_row_before = fk != nullptr;
-    for (int i = 0; i < n; ++i) one_row_before = one_row_before && gp.seg[i].RG <= (int)threads;
-    const bool was_folded = one_row_before && group_fold::choose(key_fold, n) > 1;
-    int fold = one_row_before && me.RG <= (int)threads ? group_fold::choose(key_fold, n + 1) : 1;
-    void* args[2] = {&gp, &fold};  // (the unfolded kernel takes the first only)
-    hipKernelNodeParams node{};
-    node.func = const_cast<void*>(fold > 1 ? fk : gk);
-    node.gridDim = dim3(group_fold::grid(n + 1, fold));
-    node.blockDim = dim3(threads);
-    node.sharedMemBytes = (unsigned)lds;
-    node.kernelParams = args;
-    node.extra = nullptr;
-    joined = relax->join(&node, (fold > 1 ? 1 : 0) - (was_folded ? 1 : 0));
+    // layer with more rows in a group than the block has threads keeps its node unfolded (capture_build_node).
+    member.group_func = gk;
+    member.fold_func = fk;
+    member.seg_bytes = (unsigned)sizeof me;
+    member.rows_per_group = me.RG;
+    memcpy(member.seg, &me, sizeof me);
+    if (relax->begin(key, &member, sizeof member) > 0) joined = relax->join_members();
     return 0;
   };
 #endif
@@ -151,6 +136,12 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
       r.next_block_bytes = next.block_bytes;
     }
     bool joined = false;
+    const uint32_t geom = (uint32_t)L.NW | ((uint32_t)L.XC << 8) | ((uint32_t)npw << 12) | (rotate << 15) | ((uint32_t)L.T << 16);
+    // the launch below, for the planner (a launch whose arguments do not fit travels without: it is never moved)
+    CaptureMember member{};
+    const bool described = relax && relax->capturing() &&
+                           capture_member_launch(member, kern, (unsigned)PK_NST, (unsigned)(L.NW + npw) * 64u, lds_final, cb, x, ent, rowstart,
+                                                 L.in_groups, geom, L.RG, (uint32_t)L.ent_bytes, L.M, r);
 #if AQLM_PK_G == 8
     if (decltype(lds_map)::TIGHT && nb == 1 && npw == 0 && fused.y && !fused.pub) {
       PackedGroupSegment me{};
@@ -164,13 +155,12 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
       me.geom = (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16);
       me.ent_bytes = (uint32_t)L.ent_bytes;
       me.rest = r;
-      if (int e = try_join(false, me, (unsigned)L.NW * 64u, lds_final, joined)) return e;
+      if (int e = try_join(false, me, (unsigned)L.NW * 64u, lds_final, member, joined)) return e;
     } else
 #endif
-    if (relax) relax->begin();
+    if (relax) relax->begin(0, described ? &member : nullptr, sizeof member);
     if (joined) return 0;
-    hipLaunchKernelGGL(kern, dim3(PK_NST), dim3((L.NW + npw) * 64), lds_final, stream, cb, x, ent, rowstart, L.in_groups,
-                       (uint32_t)L.NW | ((uint32_t)L.XC << 8) | ((uint32_t)npw << 12) | (rotate << 15) | ((uint32_t)L.T << 16), L.RG,
+    hipLaunchKernelGGL(kern, dim3(PK_NST), dim3((L.NW + npw) * 64), lds_final, stream, cb, x, ent, rowstart, L.in_groups, geom, L.RG,
                        (uint32_t)L.ent_bytes, L.M, r);
     return check_hip(hipGetLastError(), "gemv_1x16_packed launch");
   };
@@ -189,6 +179,12 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
       const size_t lds = decltype(lds_map)::total(L.in_groups, L.RG, 0, L.NW);
       if (int e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
       bool joined = false;
+      const uint32_t geom = (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16);
+      CaptureMember member{};
+      const bool described = relax && relax->capturing() &&
+                             capture_member_launch(member, kern, (unsigned)PK_NST, (unsigned)L.NW * 64u, lds, cb, x, ent,
+                                                   (uint32_t)(L.off_ent - L.off_rowstart), (uint32_t)L.in_groups | ((uint32_t)L.RG << 12), geom, L.M,
+                                                   ns[0], ns[1], ns[2], ns[3], rest);
       if (decltype(lds_map)::TIGHT && nb == 1 && fused.y) {
         PackedGroupSegment me{};
         me.codebook = cb;
@@ -202,14 +198,13 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
         me.ent_bytes = (uint32_t)PK_NST * (uint32_t)L.NW * (uint32_t)L.T * 1024u;  // as the variable-geometry kernel derives it
         for (int i = 0; i < 4; ++i) me.ns[i] = ns[i];
         me.rest = rest;
-        if (int e = try_join(true, me, (unsigned)L.NW * 64u, lds, joined)) return e;
+        if (int e = try_join(true, me, (unsigned)L.NW * 64u, lds, member, joined)) return e;
       } else if (relax) {
-        relax->begin();
+        relax->begin(0, described ? &member : nullptr, sizeof member);
       }
       if (joined) return 0;
       hipLaunchKernelGGL(kern, dim3(PK_NST), dim3(L.NW * 64), lds, stream, cb, x, ent, (uint32_t)(L.off_ent - L.off_rowstart),
-                         (uint32_t)L.in_groups | ((uint32_t)L.RG << 12), (uint32_t)L.NW | ((uint32_t)L.XC << 8) | (rotate << 15) | ((uint32_t)L.T << 16),
-                         L.M, ns[0], ns[1], ns[2], ns[3], rest);
+                         (uint32_t)L.in_groups | ((uint32_t)L.RG << 12), geom, L.M, ns[0], ns[1], ns[2], ns[3], rest);
       return check_hip(hipGetLastError(), "gemv_1x16_packed (variable geometry) launch");
     };
     return dispatch_packed_vg(dtype, nb, sf, compact, launch_vg);

@@ -1016,10 +1016,22 @@ int aqlm_hip_checksum(const void* data, size_t bytes, void* out_u64x2, void* str
  * n * 256: a workgroup fills its 64 KiB codebook slice and x once and walks F row groups of its (layer, slice) in turn, where
  * the unfolded grid fills them once per row group.  Chosen again at every join, so a node below F calls, a variable-geometry
  * node and every launch outside a grouped node run the kernels they ran before.  Same LDS image, same block size, same bits.
- * aqlm_hip_capture_overlap_stats_ex: the first `count` (0..10) of out[0..5] as above, then out[6] = calls that joined a node
+ * The head of a run (tuning key `packed_capture_head`: 1 = on, the default; 0 = off).  The first `packed_capture_min_run` calls
+ * of a run are captured as a chain of single launches, because only the last of them shows that the run is long.  At that call
+ * they are regrouped in place: calls of one kernel instance, block size and LDS image share grouped / folded nodes of up to
+ * `packed_capture_merge` calls, exactly the nodes later calls get; the head stays one chain in stream order, its first nodes are
+ * rewritten (hipGraphKernelNodeSetParams) and the nodes left over are destroyed from the end of the chain
+ * (hipStreamUpdateCaptureDependencies, hipGraphDestroyNode), each a node nothing depends on.  Only a head whose calls are
+ * pairwise free of hazards is regrouped; a call of a kernel with no grouped form keeps a node to itself.  Same bits; out[0..8]
+ * count what they counted before, at the time each call was planned.  Runs shorter than `packed_capture_min_run` are not touched.
+ * Should the runtime refuse a step, the graph is correct as it stands (a call may then run twice, one copy after the other, writing
+ * the same bits), the capture goes on, the refusal is counted and no head is regrouped again in this process.
+ * aqlm_hip_capture_overlap_stats_ex: the first `count` (0..13) of out[0..5] as above, then out[6] = calls that joined a node
  * (they are also counted in out[3]), out[7] = rewrites the runtime refused, out[8] = calls that added a node of their own
- * (out[0] - out[6]), out[9] = nodes that run the folded kernel.  NULL resets all counters.  Returns 0, or AQLM_HIP_E_INVALID
- * for a count outside 0..10.  (A caller that asks for 9 gets the nine it got before.)
+ * (out[0] - out[6]), out[9] = nodes that run the folded kernel (the head's included), out[10] = runs whose head was regrouped,
+ * out[11] = head calls that gave up a node of their own (the nodes destroyed), out[12] = head regroupings that stopped early.
+ * NULL resets all counters.  Returns 0, or AQLM_HIP_E_INVALID for a count outside 0..13.  (A caller that asks for 9 or 10 gets
+ * what it got before.)
  */
 int aqlm_hip_capture_overlap_stats(uint64_t out[6]);
 int aqlm_hip_capture_overlap_stats_ex(uint64_t* out, int count);
