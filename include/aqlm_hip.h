@@ -24,6 +24,15 @@
  *     scale_bias_unflatten_output, cuda_kernel.cpp:95-111); accumulation is fp32;
  *   - dtype: AQLM_HIP_F16 or AQLM_HIP_BF16 for x / y / codebooks / scales / bias alike
  *     (check_use_bfloat16, cuda_kernel.cpp:9-25);
+ *   - output of the dense forward entries (aqlm_hip_gemv_1x16 / _kx8 / _generic and their _multi forms, the aqlm_hip_gemv_1x16_packed*
+ *     and aqlm_hip_gemv_8x8_lut* matvecs, aqlm_hip_gemm_1x16_mfma, aqlm_hip_gemm_1x16_scan, aqlm_hip_gemm_kx8_mfma[_ws],
+ *     aqlm_hip_gemm_8x8_mfma): x / y row strides in elements; y 2-byte aligned with y_row_stride >= out_features (columns past
+ *     out_features are not touched): exactly the batch x out_features windows [b * y_row_stride, b * y_row_stride + out_features) are
+ *     written, whatever y's alignment and the stride's residue -- no other alignment of y is required and the layout of y selects no
+ *     kernel, so a row's bits do not depend on it.  The segments of a _multi entry carry their own y and y_row_stride and may lie
+ *     side by side in one buffer (q / k / v).  A workspace is used only up to the advertised size (aqlm_hip_workspace_bytes,
+ *     aqlm_hip_gemm_1x16_scan_workspace_bytes) and accumulator cells only up to batch x out_features x 8 bytes; nothing behind them is
+ *     written (tests/test_y_layout_gpu.py);
  *   - return 0 on success; a positive value is a hipError_t from the launch; negative values are
  *     AQLM_HIP_E_*.  aqlm_hip_last_error() returns a thread-local human-readable message.
  */
