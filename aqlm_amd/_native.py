@@ -183,6 +183,11 @@ SIGNATURES = {
     "aqlm_hip_codebook_grad_1x16": (_ci, [_vp, _cl, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _ci, _vp, _sz, _vp]),
     "aqlm_hip_scales_grad_1x16_supported": (_ci, [_ci, _ci, _ci]),
     "aqlm_hip_scales_grad_1x16": (_ci, [_vp, _cl, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
+    "aqlm_hip_codebook_grad_kx8_supported": (_ci, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_codebook_grad_kx8_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_codebook_grad_kx8": (_ci, [_vp, _cl, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_scales_grad_kx8_supported": (_ci, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_scales_grad_kx8": (_ci, [_vp, _cl, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

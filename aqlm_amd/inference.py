@@ -319,6 +319,24 @@ class QuantizedLinear(nn.Module):
         return tuning.takes_codebook_grad_kernel(self.num_codebooks, self.nbits_per_codebook, self.out_group_size, self.in_group_size,
                                                  on_gpu, dtypes_ok, supported, torch.compiler.is_compiling())
 
+    def _takes_codebook_grad_kernel_kx8(self, input: Optional[torch.Tensor]) -> bool:
+        """`tuning.takes_codebook_grad_kernel_kx8` for this layer and this input (None: any input in the parameters' dtype)."""
+        from . import tuning
+
+        cb, dt = self.codebooks, self.codebooks.dtype
+        scheme = (1 <= self.num_codebooks <= 8 and self.nbits_per_codebook == 8 and self.out_group_size == 1
+                  and self.in_group_size in (8, 16, 32))
+        on_gpu = cb.is_cuda and self.scales.is_cuda and (input is None or input.is_cuda)
+        dtypes_ok = (dt in (torch.float16, torch.bfloat16) and self.scales.dtype == dt
+                     and (self.bias is None or self.bias.dtype == dt) and (input is None or input.dtype == dt))
+        supported = False
+        if scheme and on_gpu and tuning.CODEBOOK_GRAD_KERNEL:
+            from .inference_kernels import hip_kernel
+
+            supported = hip_kernel.codebook_grad_kx8_supported(self.out_features, self.in_features, self.num_codebooks, self.in_group_size)
+        return tuning.takes_codebook_grad_kernel_kx8(self.num_codebooks, self.nbits_per_codebook, self.out_group_size,
+                                                     self.in_group_size, on_gpu, dtypes_ok, supported, torch.compiler.is_compiling())
+
     def codebook_grad_index(self):
         """The inverted index of this layer's codes (hip_kernel.CodebookGradIndex) that the codebook gradient is summed through:
         derived state like the packed codes -- keyed on ``codes_fingerprint(self.codes)``, forgotten by ``_reset_derived()`` /
@@ -349,6 +367,10 @@ class QuantizedLinear(nn.Module):
         if self._takes_codebook_grad_kernel(input):
             index = self.codebook_grad_index()  # (first: inside a capture a missing index raises before any launch)
             return _TrainableMatmul1x16.apply(input, self.codebooks, self.scales, self.bias, self._codes_for_ops(), index)
+        if self._takes_codebook_grad_kernel_kx8(input):
+            # no index: the canonical codes are all the route reads (dropped planar 8x8 codes follow the rules of
+            # `codebook_grad_index`'s docstring: restored for good after a non-strict drop, unpacked per call after a strict one)
+            return _TrainableMatmulKx8.apply(input, self.codebooks, self.scales, self.bias, self._codes_for_ops())
         from .utils import _dequantize_weight
 
         # the reference's definition under autograd; the arithmetic on the codes outside inference mode (`unpack_int_data` runs
@@ -652,6 +674,50 @@ class _TrainableMatmul1x16(torch.autograd.Function):
             if need_scales:
                 grad_scales = hip_kernel.scales_grad_1x16(dw, codes, codebooks, out_dtype=scales.dtype).reshape(scales.shape)
         return grad_input, grad_codebooks, grad_scales, grad_bias, None, None
+
+
+class _TrainableMatmulKx8(torch.autograd.Function):
+    """A K x 8 layer (1 to 8 codebooks of 256 entries, g 8 / 16 / 32) on the GPU with trainable codebooks / scales / bias.  Forward:
+    the kernel the frozen layer runs for that row count on the canonical codes and the live parameters.  Backward, in the order of
+    `_TrainableMatmul1x16`: grad_input by the frozen layer's backward kernel (only if needed), dbias, ``dW = grad_y^T @ x`` by the
+    library GEMM (fp32 with ``tuning.CODEBOOK_GRAD_FP32_DW``), then aqlm_hip_codebook_grad_kx8 (fixed-point sums in LDS, no index)
+    and aqlm_hip_scales_grad_kx8.  Gradients in each parameter's dtype."""
+
+    @staticmethod
+    def forward(ctx, input, codebooks, scales, bias, codes):
+        from .inference_kernels import get_forward_pass_kernel
+
+        ctx.save_for_backward(input, codes, codebooks, scales)
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return get_forward_pass_kernel(codebooks, math.prod(input.shape[:-1]) > GEMV_MAX_ROWS)(input, codes, codebooks, scales, bias)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import tuning
+        from .inference_kernels import get_backward_pass_kernel, hip_kernel
+
+        input, codes, codebooks, scales = ctx.saved_tensors
+        grad_output = grad_output.contiguous()
+        need_input, need_codebooks, need_scales, need_bias = ctx.needs_input_grad[:4]
+        grad_input = grad_codebooks = grad_scales = grad_bias = None
+        if need_input:
+            rows = math.prod(grad_output.shape[:-1])
+            grad_input = get_backward_pass_kernel(codebooks, rows > GEMV_MAX_ROWS)(grad_output, codes, codebooks, scales, None)
+        gy = grad_output.reshape(-1, grad_output.shape[-1])
+        if need_bias and ctx.bias_dtype is not None:
+            grad_bias = gy.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+        if need_codebooks or need_scales:
+            x = input.reshape(-1, input.shape[-1])
+            if tuning.CODEBOOK_GRAD_FP32_DW:
+                dw = torch.mm(gy.t(), x, out_dtype=torch.float32)
+            else:
+                dw = torch.mm(gy.t(), x)
+            if need_codebooks:
+                grad_codebooks = hip_kernel.codebook_grad_kx8(dw, scales, codes, int(codebooks.shape[3]),
+                                                              out_dtype=codebooks.dtype).reshape(codebooks.shape)
+            if need_scales:
+                grad_scales = hip_kernel.scales_grad_kx8(dw, codes, codebooks, out_dtype=scales.dtype).reshape(scales.shape)
+        return grad_input, grad_codebooks, grad_scales, grad_bias, None
 
 
 class _MatmulFromPacked(torch.autograd.Function):

@@ -1133,6 +1133,82 @@ def scales_grad_1x16(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = No
 
 
 # ------------------------------------------------------------------------------------------------------
+# the same gradients for the K x 8 schemes (aqlm_hip_codebook_grad_kx8, aqlm_hip_scales_grad_kx8): no index
+# ------------------------------------------------------------------------------------------------------
+def codebook_grad_kx8_supported(out_features: int, in_features: int, num_codebooks: int, in_group_size: int) -> bool:
+    args = (int(out_features), int(in_features), int(num_codebooks), int(in_group_size))
+    return bool(_lib.aqlm_hip_codebook_grad_kx8_supported(*args) and _lib.aqlm_hip_scales_grad_kx8_supported(*args))
+
+
+def _check_kx8_codes(codes, dw, out_features, in_features, K, g, what):
+    if (codes.dtype != torch.int8 or codes.numel() != out_features * (in_features // max(g, 1)) * K or not codes.is_contiguous()
+            or codes.device != dw.device):
+        raise ValueError(f"{what}: codes must be contiguous int8 [{out_features}, {in_features // max(g, 1)}, {K}] on {dw.device}")
+
+
+def _codebook_grad_kx8_op(dw, scales, codes, geometry):
+    out_features, in_features, K, g, out_dt = (int(x) for x in geometry)
+    _check_dw(dw, out_features, in_features, "codebook_grad_kx8")
+    _check_kx8_codes(codes, dw, out_features, in_features, K, g, "codebook_grad_kx8")
+    dt = _native.F16
+    if scales is not None:
+        if scales.numel() != out_features or scales.device != dw.device:
+            raise ValueError(f"codebook_grad_kx8: scales must hold {out_features} elements on {dw.device}")
+        dt = _dtype_id(scales)
+        scales = _c(scales)
+    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
+    out = torch.empty((K, 256, g), dtype=out_dtype, device=dw.device)
+    ws_bytes = int(_lib.aqlm_hip_codebook_grad_kx8_workspace_bytes(out_features, in_features, K, g))
+    ws = _workspace(dw.device, max(ws_bytes, 16))
+    with _device_guard(dw.device):
+        rc = _lib.aqlm_hip_codebook_grad_kx8(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], _ptr(scales), dt, codes.data_ptr(),
+                                             out_features, in_features, K, g, out.data_ptr(), out_dt, ws.data_ptr(), ws.numel() * 4,
+                                             _stream_ptr(dw.device))
+    if rc:
+        _native.check(rc, "aqlm codebook grad kx8")
+    return out
+
+
+def codebook_grad_kx8(dw, scales, codes, in_group_size: int, out_dtype: Optional[torch.dtype] = None):
+    """dC [K, 256, g] (``out_dtype``, default dW's dtype) of a K x 8 layer from ``dw`` [out, in], ``scales`` ([out] elements or None =
+    1) and the canonical ``codes`` [out, in / g, K] int8: per entry the sum of ``scales[o] * dW[o, j*g : j*g + g]`` over the positions
+    that use it, taken as fixed-point integers (include/aqlm_hip.h has the arithmetic) -- exact in the quantised terms and the same
+    bits under any schedule.  Every element is written (+0 for unused entries; NaN everywhere when dW or the scales hold a
+    non-finite value).  Three launches on the current stream, the int64 partials in the cached per-stream workspace (a fresh one
+    inside a hipGraph capture)."""
+    g = int(in_group_size)
+    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
+    return _codebook_grad_kx8_op(dw, scales, codes, [int(codes.shape[0]), int(codes.shape[1]) * g, int(codes.shape[2]), g, out_dt])
+
+
+def _scales_grad_kx8_op(dw, codes, codebooks, geometry):
+    out_features, in_features, K, g, out_dt = (int(x) for x in geometry)
+    _check_dw(dw, out_features, in_features, "scales_grad_kx8")
+    _check_kx8_codes(codes, dw, out_features, in_features, K, g, "scales_grad_kx8")
+    if tuple(codebooks.shape) != (K, 256, 1, g) or codebooks.device != dw.device:
+        raise ValueError(f"scales_grad_kx8: codebooks must be [{K}, 256, 1, {g}] on {dw.device}, got {tuple(codebooks.shape)}")
+    dt = _dtype_id(codebooks)
+    codebooks = _c(codebooks)
+    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
+    out = torch.empty((out_features,), dtype=out_dtype, device=dw.device)
+    with _device_guard(dw.device):
+        rc = _lib.aqlm_hip_scales_grad_kx8(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], codes.data_ptr(), codebooks.data_ptr(), dt,
+                                           out_features, in_features, K, g, out.data_ptr(), out_dt, _stream_ptr(dw.device))
+    if rc:
+        _native.check(rc, "aqlm scales grad kx8")
+    return out
+
+
+def scales_grad_kx8(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = None):
+    """ds [out] (``out_dtype``, default dW's dtype): ``sum over j, t of dW[o, j*g + t] * sum over c of codebooks[c, code(o, j, c), 0,
+    t]`` -- the unscaled codebooks [K, 256, 1, g], the canonical codes [out, in / g, K] int8; fp32 in a fixed order, one rounding
+    (include/aqlm_hip.h)."""
+    K, g = int(codebooks.shape[0]), int(codebooks.shape[3])
+    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
+    return _scales_grad_kx8_op(dw, codes, codebooks, [int(codes.shape[0]), int(codes.shape[1]) * g, K, g, out_dt])
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
@@ -2350,6 +2426,15 @@ _LIB.define("scales_grad_1x16(Tensor dw, Tensor codes, Tensor codebooks, int[] g
 _LIB.impl("scales_grad_1x16", _scales_grad_op, "CUDA")
 torch.library.register_fake("aqlm::scales_grad_1x16")(
     lambda dw, codes, codebooks, geometry: dw.new_empty((int(geometry[0]),), dtype=_GRAD_FAKE_DT[int(geometry[3])]))
+# ... of a K x 8 layer; geometry = [out_features, in_features, K, g, output dtype id]
+_LIB.define("codebook_grad_kx8(Tensor dw, Tensor? scales, Tensor codes, int[] geometry) -> Tensor")
+_LIB.impl("codebook_grad_kx8", _codebook_grad_kx8_op, "CUDA")
+torch.library.register_fake("aqlm::codebook_grad_kx8")(
+    lambda dw, scales, codes, geometry: dw.new_empty((int(geometry[2]), 256, int(geometry[3])), dtype=_GRAD_FAKE_DT[int(geometry[4])]))
+_LIB.define("scales_grad_kx8(Tensor dw, Tensor codes, Tensor codebooks, int[] geometry) -> Tensor")
+_LIB.impl("scales_grad_kx8", _scales_grad_kx8_op, "CUDA")
+torch.library.register_fake("aqlm::scales_grad_kx8")(
+    lambda dw, codes, codebooks, geometry: dw.new_empty((int(geometry[0]),), dtype=_GRAD_FAKE_DT[int(geometry[4])]))
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

@@ -12,12 +12,18 @@ lane, packed matvec, planar look-up tables, dense W, shared-input launches) and 
     ``grad_input`` (the frozen layer's kernel), ``dbias``, one library GEMM ``dW = grad_y^T @ x`` and two launches that reduce dW
     to the codebook and scale gradients through an inverted index of the codes (``aqlm_hip_codebook_grad_1x16``,
     ``aqlm_hip_scales_grad_1x16``; DESIGN.md section 4.8l): no atomics, bit-reproducible;
-  * everything else (host tensors, other schemes, ``out_group_size > 1``, fp32 master parameters, ``CODEBOOK_GRAD_KERNEL =
-    False``): the reference's definition under autograd, ``F.linear(x, _dequantize_weight(codes % 2**nbits, codebooks, scales),
-    bias)`` -- slow, correct, never silent.
+  * K x 8 layers (1 to 8 codebooks of 256 entries, g 8 / 16 / 32: 2x8 g8, 1x8 g8, 8x8 g32, 4x8 g16 ...) under the same
+    conditions: the same forward and backward, with dW reduced by ``aqlm_hip_codebook_grad_kx8`` -- no index: the K * 256 * g sums
+    live in LDS while dW streams past once per pass of 64 / g codebooks, taken as fixed-point integers, so that LDS atomics
+    cannot change a bit and the sum of the quantised terms is exact -- and ``aqlm_hip_scales_grad_kx8`` (codebooks staged in
+    LDS).  A non-finite element of dW or the scales makes the WHOLE codebook gradient NaN (a gradient scaler skips the step);
+  * everything else (host tensors, other schemes such as codebooks of other sizes or g 4, ``out_group_size > 1``, fp32 master
+    parameters, ``CODEBOOK_GRAD_KERNEL = False``): the reference's definition under autograd, ``F.linear(x,
+    _dequantize_weight(codes % 2**nbits, codebooks, scales), bias)`` -- slow, correct, never silent.
 
-Memory: the index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
-state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.
+Memory: the 1x16 index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
+state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.  The
+K x 8 route keeps no derived state: its transient is the per-stream workspace (at most 33.6 MB).
 
 Precision: fp16 / bf16 parameters stepped by a plain optimizer lose every update smaller than half a unit in the last place of
 the parameter (Adam's small steps on a codebook entry of magnitude 1 vanish below 5e-4 in fp16).  This module does not ship an
@@ -48,6 +54,14 @@ def takes_codebook_grad_kernel(num_codebooks: int, nbits_per_codebook: int, out_
     bf16), ``supported`` (the library's ``_supported`` queries for the shape), not ``compiling`` and the switch."""
     return bool(CODEBOOK_GRAD_KERNEL and num_codebooks == 1 and nbits_per_codebook == 16 and out_group_size == 1
                 and in_group_size in (8, 16) and on_gpu and dtypes_ok and supported and not compiling)
+
+
+def takes_codebook_grad_kernel_kx8(num_codebooks: int, nbits_per_codebook: int, out_group_size: int, in_group_size: int, on_gpu: bool,
+                                   dtypes_ok: bool, supported: bool, compiling: bool) -> bool:
+    """The same for the K x 8 route: 1 to 8 codebooks of 8 bits, ``out_group_size`` 1, g 8, 16 or 32; the other arguments and the
+    switch as in ``takes_codebook_grad_kernel``.  The two predicates are never true together."""
+    return bool(CODEBOOK_GRAD_KERNEL and 1 <= num_codebooks <= 8 and nbits_per_codebook == 8 and out_group_size == 1
+                and in_group_size in (8, 16, 32) and on_gpu and dtypes_ok and supported and not compiling)
 
 
 def param_grad_needed(layer) -> bool:
@@ -88,7 +102,7 @@ def make_trainable(model: nn.Module, codebooks: bool = True, scales: bool = True
 def prepare(model: nn.Module) -> int:
     """Build the inverted index of every ``QuantizedLinear`` with a trainable parameter that would take the HIP route, now: a
     hipGraph capture needs it to exist, and the memory (4 bytes per code) is then allocated at a known time.  Call it after
-    ``make_trainable``.  Returns the bytes the indices hold."""
+    ``make_trainable``.  Returns the bytes the indices hold.  K x 8 layers need nothing built: their route has no index."""
     from .inference import QuantizedLinear
 
     total = 0

@@ -793,6 +793,57 @@ int aqlm_hip_scales_grad_1x16(const void* dw, long dw_row_stride, int dw_dtype, 
                               int out_features, int in_features, int in_group_size, void* out, int out_dtype, void* stream);
 
 /*
+ * The same two gradients for the K x 8 schemes: K = num_codebooks in 1..8 codebooks of 256 entries, out_group_size 1, g in
+ * {8, 16, 32}; canonical codes [out][in / g][K] int8 (the entry is the byte & 0xff), dW as above.  No index: the K * 256 * g sums
+ * of the codebook gradient live in LDS while a workgroup streams its rows of dW once.
+ * aqlm_hip_codebook_grad_kx8:  out [K][256][g] in out_dtype, 16-byte aligned.  The sums are taken as FIXED-POINT INTEGERS, so the
+ * result is a function of the arguments alone -- integer adds commute, no schedule changes a bit -- and the sum of the quantised
+ * terms is exact:
+ *     P      = out_features * (in_features / g)      positions; every accumulator receives at most P terms
+ *     shift  = 62 - bit_length(P)                    a function of the shape alone; |sum| <= P * 2^shift < 2^62
+ *     bound  = (double)max|s| * (double)max|dW|      maxima over the layer; s = 1 when scales is NULL
+ *     (m, E) = frexp(bound)                          bound = m * 2^E, m in [0.5, 1): every |s * dW| < 2^E
+ *     q(o, col) = llrint((double)s[o] * (double)dW[o, col] * 2^(shift - E))
+ *                 the product is exact in double, the scaling exact, round to nearest even
+ *     S[c][v][t] = sum of q(o, j * g + t) over the positions (o, j) with (codes[o][j][c] & 0xff) == v        (int64, exact)
+ *     out[c][v][t] = round_to_out_dtype(ldexpf((float)S, E - shift))
+ *                 (float)S is the round-to-nearest-even int64 -> fp32 conversion, then the fp32 -> out_dtype rounding of the
+ *                 1x16 entries
+ * so |out - exact| <= n * u / 2 + (2^-24 + u_out) * (|exact| + n * u / 2) for an entry of n positions, u = 2^(E - shift), plus the
+ * output's subnormal spacing.  bound == 0: every output is +0.  ANY non-finite element of dW or scales (told by the exponent
+ * bits): EVERY output element is NaN -- a gradient scaler skips such a step.  Every one of the K * 256 * g outputs is written by
+ * every call (+0 for an unused entry): no memset, no dependence on what out or workspace held.  Three launches: the maxima per
+ * row block; the accumulation, one workgroup per (row block, pass of 64 / g codebooks) with an int64 image of at most 128 KiB in
+ * LDS (64-bit integer LDS atomics; no float atomics, no global atomics); the finish, which adds the row blocks' int64 partials.
+ * Row blocks:  B = min(out_features, max(1, 256 / passes)), passes = ceil(K / (64 / g)); block b owns the rows
+ * [b * out / B, (b + 1) * out / B).  The result does not depend on B.  `workspace` (16-byte aligned; nothing is kept in it):
+ * aqlm_hip_codebook_grad_kx8_workspace_bytes = B * K * 256 * g * 8 bytes of partials + 8192 bytes of maxima (<= 33.6 MB; the maxima
+ * launch has up to 1024 row blocks of its own, two words each).
+ * aqlm_hip_scales_grad_kx8:  out[o] = sum over j, t of dW[o, j * g + t] * w_j[t], w_j[t] = ((C_0[v_0][t] + C_1[v_1][t]) + ...) in
+ * fp32 in codebook order, the UNSCALED codebooks [K][256][g] in `dtype` (staged in LDS); one wave per row -- lane l adds the
+ * products of the groups l, l + 64, ... in order (fp32, fused multiply-add over t ascending), a fixed tree adds the lanes --, one
+ * rounding to out_dtype.  Ordinary IEEE propagation: a NaN poisons its own row only.
+ * Both: stream-ordered, no allocation, no synchronisation (hipGraph-capturable), no scratch.  Checks, in order: a null pointer
+ * (scales may be NULL), misalignment (dw / out of the codebook gradient / workspace / codebooks 16 bytes, the output of the scales
+ * gradient 4, scales 2), non-positive sizes or in_features % g != 0, a row stride below in_features or a workspace that is too
+ * small (AQLM_HIP_E_INVALID); then dw_dtype / out_dtype outside fp16 / bf16 / fp32, dtype outside fp16 / bf16, K outside 1..8, g
+ * outside {8, 16, 32}, 2^30 or more positions or dW rows not 16-byte aligned (AQLM_HIP_E_UNSUPPORTED).  Nothing is launched on bad
+ * arguments.  The ..._supported queries answer for the four sizes.
+ */
+#define AQLM_HIP_CODEBOOK_GRAD_KX8_MAX_CODEBOOKS 8
+#define AQLM_HIP_CODEBOOK_GRAD_KX8_MAX_ROW_BLOCKS 256
+#define AQLM_HIP_CODEBOOK_GRAD_KX8_MAXIMA_BLOCKS 1024
+int aqlm_hip_codebook_grad_kx8_supported(int out_features, int in_features, int num_codebooks, int in_group_size);
+size_t aqlm_hip_codebook_grad_kx8_workspace_bytes(int out_features, int in_features, int num_codebooks, int in_group_size);
+int aqlm_hip_codebook_grad_kx8(const void* dw, long dw_row_stride, int dw_dtype, const void* scales, int dtype, const void* codes,
+                               int out_features, int in_features, int num_codebooks, int in_group_size, void* out, int out_dtype,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int aqlm_hip_scales_grad_kx8_supported(int out_features, int in_features, int num_codebooks, int in_group_size);
+int aqlm_hip_scales_grad_kx8(const void* dw, long dw_row_stride, int dw_dtype, const void* codes, const void* codebooks, int dtype,
+                             int out_features, int in_features, int num_codebooks, int in_group_size, void* out, int out_dtype,
+                             void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the

@@ -1,8 +1,11 @@
 #!/usr/bin/env python
-"""Training codebooks and scales of 1x16 g8 layers on the MI355X: the indexed gradient kernels (aqlm_hip_codebook_grad_1x16,
-aqlm_hip_scales_grad_1x16; aqlm_amd/tuning.py) against the reference's definition under autograd, with the frozen layer as the floor.
+"""Training codebooks and scales on the MI355X: the gradient kernels (aqlm_amd/tuning.py) against the reference's definition under
+autograd, with the frozen layer as the floor.  ``--scheme 1x16g8`` (default): the indexed kernels aqlm_hip_codebook_grad_1x16 /
+aqlm_hip_scales_grad_1x16 at 4096 x 4096, 4096 -> 14336, 14336 -> 4096.  ``--scheme 2x8g8`` (4096 x 4096, 4096 -> 11008, 11008 ->
+4096) and ``--scheme 8x8g32`` (4096 x 4096): the fixed-point LDS kernels aqlm_hip_codebook_grad_kx8 / aqlm_hip_scales_grad_kx8; their
+rows go to profiles/codebook_grad_kx8.json (one file for the K x 8 schemes: a run replaces the rows of its own scheme).
 
-Per shape (4096 x 4096, 4096 -> 14336, 14336 -> 4096; fp16, uniform random codes) and row count (512, 2048, 8192), one training
+Per shape (fp16, uniform random codes) and row count (512, 2048, 8192), one training
 step = forward + backward with a gradient for the input, the codebook and the scales:
   hip      the HIP route (forward kernel of the frozen layer; grad_input, dW GEMM, the two gradient launches);
   torch    the torch route (``tuning.CODEBOOK_GRAD_KERNEL = False``): F.linear(x, _dequantize_weight(...)) under autograd;
@@ -13,8 +16,11 @@ events around every step.  ``*_peak_mb``: the peak of the allocator during one e
 ``dw_gemm_us``, ``codebook_grad_us``, ``scales_grad_us``: the three pieces of the HIP route's backward on their own, alternating
 (dW then still sits in the Infinity Cache, as it does in a step: it was just written).  ``index_build_us`` / ``index_mb``: the
 one-off inverted index of the layer (torch ops) and what it holds.  ``ratio`` = hip / torch of the eager step.
+K x 8 rows have no index; they add ``maxima_us`` / ``accumulate_us`` / ``finish_us``, the three launches of the codebook gradient
+on their own (device time per kernel from torch.profiler over --iters calls; ``kernel_times_error`` when the profiler is not
+usable), and ``lds_add_per_ns`` = positions * g * K 64-bit LDS adds / the accumulate launch's time.
 
-    python tools/codebook_grad_benchmark.py [--iters 10] [--repeats 3] [--out profiles/codebook_grad.json]
+    python tools/codebook_grad_benchmark.py [--scheme 1x16g8|2x8g8|8x8g32] [--iters 10] [--repeats 3] [--out FILE]
 """
 import argparse
 import json
@@ -26,6 +32,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = [(4096, 4096), (4096, 14336), (14336, 4096)]  # (in, out)
+# scheme -> (num_codebooks, nbits, g, shapes, default output)
+SCHEMES = {"1x16g8": (1, 16, 8, SHAPES, "codebook_grad.json"),
+           "2x8g8": (2, 8, 8, [(4096, 4096), (4096, 11008), (11008, 4096)], "codebook_grad_kx8.json"),
+           "8x8g32": (8, 8, 32, [(4096, 4096)], "codebook_grad_kx8.json")}
 ROWS = [512, 2048, 8192]
 
 
@@ -69,30 +79,60 @@ def captured(fn):
     return g
 
 
+def kernel_times(fn, iters, names):
+    """Mean device time in microseconds of the kernels whose name holds one of ``names``, over ``iters`` calls of fn."""
+    from torch.profiler import ProfilerActivity, profile
+
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+    total, count = {n: 0.0 for n in names}, {n: 0 for n in names}
+    for ev in prof.events():
+        for n in names:
+            if n in ev.name:
+                total[n] += float(getattr(ev, "device_time", 0.0) or getattr(ev, "cuda_time", 0.0))
+                count[n] += 1
+    missing = [n for n in names if count[n] == 0]
+    if missing:
+        raise RuntimeError(f"no kernel events for {missing}")
+    return {n: round(total[n] / count[n], 1) for n in names}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scheme", choices=sorted(SCHEMES), default="1x16g8")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join("profiles", "codebook_grad.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    K, nbits, G, shapes, out_name = SCHEMES[args.scheme]
+    kx8 = nbits == 8
+    if args.out is None:
+        args.out = os.path.join("profiles", out_name)
     assert torch.cuda.is_available(), "this benchmark needs the MI355X"
     dev = torch.device("cuda:0")
 
     import aqlm
     import aqlm.tuning as tuning
-    from aqlm_amd.inference import _TrainableMatmul1x16
+    from aqlm_amd.inference import _TrainableMatmul1x16, _TrainableMatmulKx8
     from aqlm_amd.inference_kernels import hip_kernel as hk
 
     results = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "repeats": args.repeats, "chunk": hk.CODEBOOK_GRAD_CHUNK,
                "rows": []}
-    for fin, fout in SHAPES:
+    if kx8:
+        del results["chunk"]
+    for fin, fout in shapes:
         gen = torch.Generator(device=dev).manual_seed(fin + fout)
 
         def layer(trainable):
-            m = aqlm.QuantizedLinear(fin, fout, 8, 1, 1, 16, bias=False, device=dev, dtype=torch.float16)
+            m = aqlm.QuantizedLinear(fin, fout, G, 1, K, nbits, bias=False, device=dev, dtype=torch.float16)
             g2 = torch.Generator(device=dev).manual_seed(fin * 3 + fout)
+            lo = -(2 ** (nbits - 1))
             with torch.no_grad():
-                m.codes.copy_(torch.randint(-32768, 32768, m.codes.shape, generator=g2, device=dev, dtype=torch.int32).to(torch.int16))
+                m.codes.copy_(torch.randint(lo, -lo, m.codes.shape, generator=g2, device=dev, dtype=torch.int32).to(m.codes.dtype))
                 m.codebooks.copy_(torch.randn(m.codebooks.shape, generator=g2, device=dev) * 0.05)
                 m.scales.copy_(torch.rand(m.scales.shape, generator=g2, device=dev) * 0.2 + 0.05)
             if trainable:
@@ -100,14 +140,16 @@ def main():
             return m
 
         train, frozen = layer(True), layer(False)
-        hk.build_codebook_grad_index(train.codes, 8)  # warm-up of the sort
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        index = hk.build_codebook_grad_index(train.codes, 8)
-        b.record()
-        b.synchronize()
-        index_us, index_mb = a.elapsed_time(b) * 1e3, index.nbytes() / 2 ** 20
+        index = None
+        if not kx8:
+            hk.build_codebook_grad_index(train.codes, 8)  # warm-up of the sort
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            index = hk.build_codebook_grad_index(train.codes, 8)
+            b.record()
+            b.synchronize()
+            index_us, index_mb = a.elapsed_time(b) * 1e3, index.nbytes() / 2 ** 20
         tuning.prepare(torch.nn.ModuleDict({"l": train}))
         for rows in ROWS:
             x = (torch.randn((rows, fin), generator=gen, device=dev) * 0.5).half().requires_grad_(True)
@@ -122,9 +164,12 @@ def main():
                 return run
 
             fns = {"hip": step(train, True), "torch": step(train, False), "frozen": step(frozen, True)}
-            row = {"in": fin, "out": fout, "rows": rows, "index_build_us": round(index_us, 1), "index_mb": round(index_mb, 2)}
+            if kx8:
+                row = {"scheme": args.scheme, "in": fin, "out": fout, "rows": rows}
+            else:
+                row = {"in": fin, "out": fout, "rows": rows, "index_build_us": round(index_us, 1), "index_mb": round(index_mb, 2)}
             tuning.CODEBOOK_GRAD_KERNEL = True
-            assert type(train(x).grad_fn).__name__ == _TrainableMatmul1x16.__name__ + "Backward"
+            assert type(train(x).grad_fn).__name__ == (_TrainableMatmulKx8 if kx8 else _TrainableMatmul1x16).__name__ + "Backward"
             # the two routes agree (fp16 storage: the torch route rounds dW, the scaled dW and its scatter-add to fp16)
             fns["hip"]()
             g_hip = train.codebooks.grad.float().clone()
@@ -157,8 +202,18 @@ def main():
             tuning.CODEBOOK_GRAD_KERNEL = True
             gy2, x2 = gy.reshape(-1, fout), x.detach().reshape(-1, fin)
             dw = torch.mm(gy2.t(), x2)
-            parts = [lambda: torch.mm(gy2.t(), x2), lambda: hk.codebook_grad_1x16(dw, train.scales, index, out_dtype=torch.float16),
-                     lambda: hk.scales_grad_1x16(dw, train.codes, train.codebooks, out_dtype=torch.float16)]
+            if kx8:
+                parts = [lambda: torch.mm(gy2.t(), x2), lambda: hk.codebook_grad_kx8(dw, train.scales, train.codes, G, out_dtype=torch.float16),
+                         lambda: hk.scales_grad_kx8(dw, train.codes, train.codebooks, out_dtype=torch.float16)]
+                try:
+                    for name, t in kernel_times(parts[1], args.iters, ("maxima", "accumulate", "finish")).items():
+                        row[f"{name}_us"] = t
+                    row["lds_add_per_ns"] = round(fout * fin * K / (row["accumulate_us"] * 1e3), 2)
+                except Exception as e:  # reported, not hidden
+                    row["kernel_times_error"] = f"{type(e).__name__}: {e}"[:200]
+            else:
+                parts = [lambda: torch.mm(gy2.t(), x2), lambda: hk.codebook_grad_1x16(dw, train.scales, index, out_dtype=torch.float16),
+                         lambda: hk.scales_grad_1x16(dw, train.codes, train.codebooks, out_dtype=torch.float16)]
             for name, (t, spread) in zip(("dw_gemm", "codebook_grad", "scales_grad"), rounds_alternating(parts, args.iters, args.repeats)):
                 row[f"{name}_us"], row[f"{name}_spread_us"] = t, spread
             row["ratio"] = round(row["hip_eager_us"] / row["torch_eager_us"], 3)
@@ -168,6 +223,10 @@ def main():
         del train, frozen, index
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if kx8 and os.path.exists(args.out):  # one file for the K x 8 schemes: the other schemes' rows stay
+        with open(args.out) as f:
+            kept = [r for r in json.load(f).get("rows", []) if r.get("scheme") != args.scheme]
+        results["rows"] = kept + results["rows"]
     with open(args.out, "w") as f:
         json.dump(results, f, indent=1)
         f.write("\n")
