@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("AQLM_AMD_HIP_LIB") or os.path.join(_HERE, "libaqlm_hi
 ABI_VERSION = 9
 
 F16, BF16 = 0, 1
-F32 = 2   # dW and the outputs of the gradient entries only (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16)
+F32 = 2   # dW and the outputs of the gradient entries, and the reference of aqlm_hip_code_search_1x16, only
+CODE_SEARCH_EPS = 2.0 ** -17   # AQLM_HIP_CODE_SEARCH_EPS
 E_INVALID, E_UNSUPPORTED = -1, -2
 MAX_GEMV_BATCH = 8
 OP_GEMM_1X16_MFMA = 1
@@ -188,6 +189,9 @@ SIGNATURES = {
     "aqlm_hip_codebook_grad_kx8": (_ci, [_vp, _cl, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _sz, _vp]),
     "aqlm_hip_scales_grad_kx8_supported": (_ci, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_scales_grad_kx8": (_ci, [_vp, _cl, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
+    "aqlm_hip_code_search_1x16_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_code_search_1x16_workspace_bytes": (_sz, [_cl, _ci]),
+    "aqlm_hip_code_search_1x16": (_ci, [_vp, _ci, _cl, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _cl, _vp, _vp, _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

@@ -1209,6 +1209,74 @@ def scales_grad_kx8(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = Non
 
 
 # ------------------------------------------------------------------------------------------------------
+# nearest-codeword search of the 1x16 schemes (the V step of PV-tuning; aqlm_hip_code_search_1x16)
+# ------------------------------------------------------------------------------------------------------
+CODE_SEARCH_EPS = _native.CODE_SEARCH_EPS  # the accuracy contract of include/aqlm_hip.h: computed scores within eps * (|r|^2 + max|C|^2)
+
+
+def code_search_1x16_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
+    return bool(_lib.aqlm_hip_code_search_1x16_supported(int(out_features), int(in_features), int(in_group_size)))
+
+
+def _code_search_1x16_impl(reference, scales, codebook, group_ids, codes_out, geometry):
+    out_features, in_features, g = (int(x) for x in geometry)
+    if (reference.dim() != 2 or tuple(reference.shape) != (out_features, in_features) or reference.dtype not in _GRAD_DT
+            or not reference.is_cuda):
+        raise ValueError(f"code_search_1x16: reference must be fp16 / bf16 / fp32 [{out_features}, {in_features}] on the GPU, got "
+                         f"{reference.dtype} {tuple(reference.shape)}")
+    if reference.stride(1) != 1 or reference.stride(0) < in_features:  # a transposed or expanded view: the kernel walks rows
+        reference = reference.contiguous()
+    if codebook.numel() != CODEBOOK_GRAD_ENTRIES * g or codebook.device != reference.device:
+        raise ValueError(f"code_search_1x16: the codebook must hold 65536 x {g} elements on {reference.device}")
+    dt = _dtype_id(codebook)
+    codebook = _c(codebook)
+    if scales is not None:
+        if scales.numel() != out_features or scales.device != reference.device or scales.dtype != codebook.dtype:
+            raise ValueError(f"code_search_1x16: scales must hold {out_features} elements of {codebook.dtype} on {reference.device}")
+        scales = _c(scales)
+    total = out_features * (in_features // max(g, 1))
+    if group_ids is not None:
+        if group_ids.dtype not in (torch.int32, torch.int64) or group_ids.dim() != 1 or group_ids.device != reference.device:
+            raise ValueError("code_search_1x16: group_ids must be a 1-d int32 / int64 tensor on the reference's device")
+        group_ids = _c(group_ids)
+        n = int(group_ids.numel())
+    else:
+        n = total
+    if codes_out is None:
+        codes_out = torch.empty((n,), dtype=torch.int16, device=reference.device)
+    elif codes_out.dtype != torch.int16 or codes_out.numel() != n or not codes_out.is_contiguous() or codes_out.device != reference.device:
+        raise ValueError(f"code_search_1x16: codes_out must be contiguous int16 [{n}] on {reference.device}")
+    if n == 0:
+        return codes_out
+    ws_bytes = int(_lib.aqlm_hip_code_search_1x16_workspace_bytes(n, g))
+    ws = _workspace(reference.device, max(ws_bytes, 16))
+    with _device_guard(reference.device):
+        rc = _lib.aqlm_hip_code_search_1x16(reference.data_ptr(), _GRAD_DT[reference.dtype], reference.stride(0), _ptr(scales),
+                                            codebook.data_ptr(), dt, out_features, in_features, g, _ptr(group_ids),
+                                            int(group_ids is not None and group_ids.dtype == torch.int64), n, codes_out.data_ptr(),
+                                            ws.data_ptr(), ws.numel() * 4, _stream_ptr(reference.device))
+    if rc:
+        _native.check(rc, "aqlm code search")
+    return codes_out
+
+
+def _code_search_1x16_op(reference, scales, codebook, group_ids, geometry):
+    return _code_search_1x16_impl(reference, scales, codebook, group_ids, None, geometry)
+
+
+def code_search_1x16(reference, scales, codebook, in_group_size: int, group_ids=None, codes_out=None):
+    """int16 codes: for every group of ``in_group_size`` weights of ``reference`` [out, in] (fp32 / fp16 / bf16, any row stride; a view
+    with another column stride is copied first) --
+    or for the flat groups ``group_ids`` (int32 / int64, ``o * (in / g) + j``), in their order -- the codeword of ``codebook`` (65536
+    x g elements, fp16 / bf16) that minimises ``|C_c|^2 - 2 <reference_group / scales[o], C_c>``; ``scales`` ([out] elements in the
+    codebook dtype) None = 1.  Equal computed scores give the smallest index; the accuracy contract is in include/aqlm_hip.h
+    (``CODE_SEARCH_EPS``).  ``codes_out`` (int16, one entry per group searched): written in place when given -- an id outside the
+    layer leaves its entry as it was.  Two launches on the current stream, |C|^2 in the cached per-stream workspace."""
+    g = int(in_group_size)
+    return _code_search_1x16_impl(reference, scales, codebook, group_ids, codes_out, [int(reference.shape[0]), int(reference.shape[1]), g])
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
@@ -2435,6 +2503,13 @@ _LIB.define("scales_grad_kx8(Tensor dw, Tensor codes, Tensor codebooks, int[] ge
 _LIB.impl("scales_grad_kx8", _scales_grad_kx8_op, "CUDA")
 torch.library.register_fake("aqlm::scales_grad_kx8")(
     lambda dw, codes, codebooks, geometry: dw.new_empty((int(geometry[0]),), dtype=_GRAD_FAKE_DT[int(geometry[4])]))
+
+# nearest-codeword search of a 1x16 layer; geometry = [out_features, in_features, g]
+_LIB.define("code_search_1x16(Tensor reference, Tensor? scales, Tensor codebook, Tensor? group_ids, int[] geometry) -> Tensor")
+_LIB.impl("code_search_1x16", _code_search_1x16_op, "CUDA")
+torch.library.register_fake("aqlm::code_search_1x16")(
+    lambda reference, scales, codebook, group_ids, geometry: reference.new_empty(
+        (int(group_ids.numel()) if group_ids is not None else int(geometry[0]) * (int(geometry[1]) // int(geometry[2])),), dtype=torch.int16))
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

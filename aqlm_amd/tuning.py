@@ -1,10 +1,13 @@
-"""Fine-tuning the continuous parameters of AQLM layers: codebooks, scales and biases train, the codes stay fixed -- what the
-reference's ``finetune.py`` does after quantising.
+"""PV-tuning of AQLM layers: the continuous parameters train (codebooks, scales and biases -- what the reference's ``finetune.py``
+does after quantising: the P step), and the codes of a layer are re-chosen against a dense target (the reference's
+``beam_search_optimal_codes``: the V step).
 
     import aqlm
     params = aqlm.tuning.make_trainable(model)          # codebooks and scales of every QuantizedLinear
     aqlm.tuning.prepare(model)                          # optional: build the inverted indices now (needed before a hipGraph capture)
     opt = torch.optim.SGD(params, lr=1e-4)
+    ...
+    changed = aqlm.tuning.update_codes_(layer, reference_weight, max_update_fraction=0.01)   # every n steps
 
 A ``QuantizedLinear`` with a trainable parameter leaves every inference route that reads a derived copy of its weights (fast
 lane, packed matvec, planar look-up tables, dense W, shared-input launches) and runs under autograd:
@@ -21,6 +24,23 @@ lane, packed matvec, planar look-up tables, dense W, shared-input launches) and 
     parameters, ``CODEBOOK_GRAD_KERNEL = False``): the reference's definition under autograd, ``F.linear(x,
     _dequantize_weight(codes % 2**nbits, codebooks, scales), bias)`` -- slow, correct, never silent.
 
+Updating the codes (``find_optimal_codes``, ``update_codes_``): for every group of weights the codes that minimise ``||reference -
+dequantised||^2`` with the codebooks and scales held fixed, optionally only for the ``max_update_fraction`` of the groups that are
+furthest from the target, and only while the change stays within ``trust_ratio``:
+  * 1x16 layers (g 8 / 16, ``out_group_size`` 1) with every tensor on the MI355X, codebooks and scales in one of fp16 / bf16 and
+    the target in fp32 / fp16 / bf16: ``aqlm_hip_code_search_1x16`` -- the 65536 scores of a group are
+    accumulators of the matrix unit and never reach memory; equal scores give the smallest index, the result is a function of
+    the inputs alone.  Selection and trust ratio are torch operations around the kernel (they synchronise: the V step is not
+    meant to be captured into a hipGraph);
+  * everything else (several codebooks with beam search, 8-bit codebooks, ``out_group_size > 1``, host tensors, fp32 parameters,
+    ``CODE_SEARCH_KERNEL = False``): a torch route written from the reference's definition -- chunked scores, the best
+    ``beam_size`` hypotheses per step, ``dim_order`` -- slow, correct, never silent.
+A group whose unscaled target has a non-finite element keeps its previous code (the reference's result there is whatever
+``argmin`` makes of NaNs); so does, on the kernel route, a group with an element of magnitude 2^100 or more (the kernel's stated
+range).  The new codes are written in place, so the version counter of ``codes`` moves and every derived copy
+(packed and planar codes, dense W, the fast lane, the inverted index) is rebuilt at the next call by the fingerprint rule that
+already covers ``load_state_dict``.  Not offered: ``stochastic_rounding_tau`` and ``force_update`` (``NotImplementedError``).
+
 Memory: the 1x16 index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
 state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.  The
 K x 8 route keeps no derived state: its transient is the per-stream workspace (at most 33.6 MB).
@@ -30,11 +50,13 @@ the parameter (Adam's small steps on a codebook entry of magnitude 1 vanish belo
 fp32-master-weight optimizer wrapper; keep the parameters in fp32 (``model.float()``: the torch route above) when that matters.
 
 Out of scope: the experts of a ``QuantizedMixtralExperts`` block (their routed launches carry gradients to the hidden states
-only) and ``ShardedQuantizedLinear`` -- ``make_trainable`` leaves both frozen and names them in ``.skipped`` of its result.
+only) and ``ShardedQuantizedLinear`` -- ``make_trainable`` leaves both frozen and names them in ``.skipped`` of its result, and
+``update_codes_`` raises ``TypeError`` for them; a search kernel for the K x 8 schemes (they take the torch route).
 """
 from __future__ import annotations
 
-from typing import List
+import math
+from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -45,6 +67,10 @@ CODEBOOK_GRAD_KERNEL = True
 # instead of the storage dtype the reference's autograd produces it in: one rounding less in front of the two reductions, twice
 # the bytes of the transient.
 CODEBOOK_GRAD_FP32_DW = False
+# The switch of the code search kernel: False sends every ``find_optimal_codes`` call through the torch route.
+CODE_SEARCH_KERNEL = True
+# Scores the torch route materialises at a time (fp32 values: 512 MiB).
+CODE_SEARCH_CHUNK_VALUES = 1 << 27
 
 
 def takes_codebook_grad_kernel(num_codebooks: int, nbits_per_codebook: int, out_group_size: int, in_group_size: int, on_gpu: bool,
@@ -78,7 +104,7 @@ class TrainableParameters(list):
 
 def make_trainable(model: nn.Module, codebooks: bool = True, scales: bool = True, bias: bool = False) -> TrainableParameters:
     """Set ``requires_grad`` on the chosen parameters of every ``QuantizedLinear`` of ``model`` and return them (a list, for an
-    optimizer).  The codes never train.  ``QuantizedMixtralExperts`` blocks (and the expert layers inside them) and
+    optimizer).  The codes are not parameters of an optimizer (``update_codes_`` re-chooses them).  ``QuantizedMixtralExperts`` blocks (and the expert layers inside them) and
     ``ShardedQuantizedLinear`` modules are left frozen: their names are in ``.skipped`` of the result."""
     from .inference import QuantizedLinear
     from .moe import QuantizedMixtralExperts
@@ -113,3 +139,221 @@ def prepare(model: nn.Module) -> int:
         if trains and m._takes_codebook_grad_kernel(None):
             total += m.codebook_grad_index().nbytes()
     return total
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the V step: new codes against a dense target
+# ---------------------------------------------------------------------------------------------------------------------------
+def takes_code_search_kernel(num_codebooks: int, nbits_per_codebook: int, out_group_size: int, in_group_size: int, on_gpu: bool,
+                             dtypes_ok: bool, supported: bool) -> bool:
+    """Whether a ``find_optimal_codes`` call runs ``aqlm_hip_code_search_1x16`` -- a pure function of: the scheme (1x16,
+    ``out_group_size`` 1, g 8 or 16), ``on_gpu`` (every tensor on the GPU), ``dtypes_ok`` (codebooks and scales in ONE of fp16 / bf16,
+    the target in fp32 / fp16 / bf16), ``supported`` (the library's ``_supported`` query for the shape) and the switch."""
+    return bool(CODE_SEARCH_KERNEL and num_codebooks == 1 and nbits_per_codebook == 16 and out_group_size == 1
+                and in_group_size in (8, 16) and on_gpu and dtypes_ok and supported)
+
+
+def _greedy_codes_torch(reference: torch.Tensor, codebook: torch.Tensor, chunk_values: int) -> torch.Tensor:
+    """[N] int64: per row of ``reference`` [N, d] the first index that minimises ``|C_c|^2 - 2 <r, C_c>`` over ``codebook`` [S, d]."""
+    norms = codebook.square().sum(-1)[None]
+    transposed = codebook.T.contiguous()
+    rows = max(1, chunk_values // codebook.shape[0])
+    out = torch.empty((reference.shape[0],), dtype=torch.int64, device=reference.device)
+    for a in range(0, reference.shape[0], rows):
+        out[a:a + rows] = torch.addmm(norms, reference[a:a + rows], transposed, alpha=-2).argmin(-1)
+    return out
+
+
+def _beam_codes_torch(reference: torch.Tensor, codebooks: torch.Tensor, codes: torch.Tensor, beam_size: int, dim_order: Sequence[int],
+                      chunk_values: int) -> torch.Tensor:
+    """[N, K] int64: ``codes`` [N, K] improved one codebook at a time in ``dim_order``.  A step frees its codebook's term of every
+    hypothesis, scores all ``beams x S`` continuations by the squared error they leave and keeps the best ``beam_size`` (the last
+    step: the best one).  Like the reference, a step subtracts the chosen entries from the residues POSITION BY POSITION: the
+    residue at beam position b stays there when the hypothesis that now occupies b descends from another position."""
+    num_codebooks, size, _ = codebooks.shape
+    norms = codebooks.square().sum(-1)  # [K, S]
+    beams = codes[:, None, :].clone()  # [N, beams, K]
+    kept = codebooks[0][codes[:, 0]]
+    for c in range(1, num_codebooks):
+        kept = kept + codebooks[c][codes[:, c]]
+    residue = (reference - kept)[:, None, :]  # [N, beams, d]
+    for step, c in enumerate(dim_order):
+        last = step == len(dim_order) - 1
+        residue = residue + codebooks[c][beams[..., c]]
+        width, keep = residue.shape[1], (1 if last else beam_size)
+        picked = torch.empty((reference.shape[0], keep), dtype=torch.int64, device=reference.device)
+        rows = max(1, chunk_values // (size * width))
+        for a in range(0, reference.shape[0], rows):
+            part = residue[a:a + rows]
+            scores = torch.matmul(part, codebooks[c].T)  # [n, beams, S]
+            if beam_size > 1:
+                scores = part.square().sum(-1, keepdim=True) - 2 * scores + norms[c]
+            else:
+                scores = -2 * scores + norms[c]  # one hypothesis: its residue's norm is the same for every candidate
+            picked[a:a + rows] = torch.topk(scores.flatten(1), keep, dim=-1, largest=False, sorted=True).indices
+        source, chosen = picked // size, picked % size
+        beams = torch.gather(beams, 1, source[:, :, None].expand(-1, -1, num_codebooks)).clone()
+        beams[..., c] = chosen
+        if not last:
+            residue = residue - codebooks[c][chosen]
+    return beams[:, 0, :]
+
+
+def _group_sq_norms(delta: torch.Tensor, out_group_size: int, in_group_size: int) -> torch.Tensor:
+    """[out_groups, in_groups]: the squared sum of every (out_group_size, in_group_size) tile of ``delta`` [out, in]."""
+    return delta.reshape(delta.shape[0] // out_group_size, out_group_size, delta.shape[1] // in_group_size,
+                         in_group_size).square().sum(dim=(1, 3))
+
+
+@torch.no_grad()
+def find_optimal_codes(reference_weight: torch.Tensor, codebooks: torch.Tensor, prev_codes: torch.Tensor,
+                       scales: Optional[torch.Tensor], *, beam_size: int = 1, max_update_fraction: float = 1.0,
+                       trust_ratio: Optional[float] = None, code_selection_temperature: float = 0.0,
+                       dim_order: Optional[Sequence[int]] = None, generator: Optional[torch.Generator] = None, **unsupported) -> torch.Tensor:
+    """New codes (shape and dtype of ``prev_codes``) that minimise ``||reference_weight - dequantised||^2`` with ``codebooks`` [K, S,
+    out_group_size, in_group_size] and ``scales`` ([out_groups, 1, 1, 1] or None) held fixed -- the reference's
+    ``beam_search_optimal_codes`` on this package's tensors: ``prev_codes`` [out_groups, in_groups, K] in the stored int8 / int16
+    wrap-around form.
+
+    ``beam_size``: hypotheses kept per step of the search over several codebooks (with one codebook it does not change the
+    answer).  ``dim_order``: the order in which the codebooks are revisited (default 0 .. K - 1).  ``max_update_fraction`` < 1:
+    only the ceil(fraction * groups) groups with the largest ``||reference - dequant(prev)||^2`` are searched (the others keep
+    their codes) -- chosen by top-k, or with ``code_selection_temperature`` T > 0 sampled without replacement in proportion to
+    norm^(1 / T) from ``generator``.  ``trust_ratio``: the changes are admitted in that order while the cumulative ``||dW||`` stays
+    within ``trust_ratio * ||W_prev||``; one change is always admitted.  A group whose unscaled target has a non-finite element
+    keeps its previous codes.  Routes: module docstring.  ``stochastic_rounding_tau`` and ``force_update`` raise
+    ``NotImplementedError``."""
+    for name in ("stochastic_rounding_tau", "force_update"):
+        if name in unsupported:
+            raise NotImplementedError(f"find_optimal_codes: {name} is not offered (the reference's defaults do not use it)")
+    if unsupported:
+        raise TypeError(f"find_optimal_codes: unexpected arguments {sorted(unsupported)}")
+    if not 0 < max_update_fraction <= 1 or (trust_ratio is not None and not trust_ratio > 0) or beam_size < 1:
+        raise ValueError("find_optimal_codes: 0 < max_update_fraction <= 1, trust_ratio > 0, beam_size >= 1")
+    out_groups, in_groups, num_codebooks = prev_codes.shape
+    K, size, out_group_size, in_group_size = codebooks.shape
+    if K != num_codebooks or tuple(reference_weight.shape) != (out_groups * out_group_size, in_groups * in_group_size):
+        raise ValueError(f"find_optimal_codes: codes {tuple(prev_codes.shape)}, codebooks {tuple(codebooks.shape)} and a target of "
+                         f"{tuple(reference_weight.shape)} do not describe one layer")
+    order = list(range(K)) if dim_order is None else [int(c) for c in dim_order]
+    if sorted(order) != list(range(K)):
+        raise ValueError(f"find_optimal_codes: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    nbits = int(math.log2(size))
+    num_groups = out_groups * in_groups
+
+    tensors = [reference_weight, codebooks, prev_codes] + ([] if scales is None else [scales])
+    on_gpu = all(t.is_cuda for t in tensors)
+    dtypes_ok = (codebooks.dtype in (torch.float16, torch.bfloat16) and (scales is None or scales.dtype == codebooks.dtype)
+                 and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16) and prev_codes.dtype == torch.int16)
+    supported = False
+    if CODE_SEARCH_KERNEL and on_gpu and K == 1 and nbits == 16 and out_group_size == 1 and in_group_size in (8, 16):
+        from .inference_kernels import hip_kernel
+
+        supported = hip_kernel.code_search_1x16_supported(reference_weight.shape[0], reference_weight.shape[1], in_group_size)
+    kernel = takes_code_search_kernel(K, nbits, out_group_size, in_group_size, on_gpu, dtypes_ok, supported)
+
+    from .utils import _dequantize_weight
+
+    device = reference_weight.device
+    compute = torch.float64 if reference_weight.dtype == torch.float64 else torch.float32
+    books = codebooks.detach().to(compute)
+    factors = None if scales is None else scales.detach().to(compute)
+    unsigned_prev = prev_codes.to(torch.int64) % size
+    flat_prev = unsigned_prev.reshape(num_groups, K)
+
+    # the groups that may change, most important first
+    selected = prev_weight = None
+    if max_update_fraction < 1 or trust_ratio is not None:
+        prev_weight = _dequantize_weight(unsigned_prev, books, factors)
+        count = int(math.ceil(max_update_fraction * num_groups))
+        distance = _group_sq_norms(reference_weight.to(compute) - prev_weight, out_group_size, in_group_size).flatten()
+        if code_selection_temperature > 0:
+            selected = torch.pow(distance, 0.5 / code_selection_temperature).multinomial(count, replacement=False, generator=generator)
+        else:
+            selected = torch.topk(distance, k=count, largest=True, sorted=True).indices
+    searched = selected if max_update_fraction < 1 else None
+
+    def unscaled(ids):
+        """[n, out_group_size * in_group_size]: the targets of the groups ``ids`` (None: all) divided by their scales."""
+        tiles = reference_weight.reshape(out_groups, out_group_size, in_groups, in_group_size).permute(0, 2, 1, 3).reshape(
+            num_groups, out_group_size, in_group_size)
+        tiles = (tiles if ids is None else tiles[ids]).to(compute)
+        if factors is not None:
+            per_group = factors.reshape(out_groups, 1).expand(out_groups, in_groups).reshape(num_groups)
+            tiles = tiles / (per_group if ids is None else per_group[ids])[:, None, None]
+        return tiles.flatten(1)
+
+    if kernel:
+        from .inference_kernels import hip_kernel
+
+        found = hip_kernel.code_search_1x16(reference_weight.detach(), None if scales is None else scales.detach().reshape(-1),
+                                            codebooks.detach(), in_group_size, group_ids=searched)
+        found = (found.to(torch.int64) % size)[:, None]
+        targets = None
+    else:
+        targets = unscaled(searched)
+        before = flat_prev if searched is None else flat_prev[searched]
+        flat_books = books.flatten(-2, -1)
+        if K == 1:
+            found = _greedy_codes_torch(targets, flat_books[0], CODE_SEARCH_CHUNK_VALUES)[:, None]
+        else:
+            found = _beam_codes_torch(targets, flat_books, before, beam_size, order, CODE_SEARCH_CHUNK_VALUES)
+    # a group with a non-finite target keeps what it had
+    before = flat_prev if searched is None else flat_prev[searched]
+    if targets is None:  # (the kernel route: out_group_size 1, a group is a run of a row)
+        quotient = reference_weight.to(compute)
+        if factors is not None:
+            quotient = quotient / factors.reshape(out_groups, 1)
+        # (... and one beyond the kernel's stated range, max|r| >= 2^100, where its fp32 scores can overflow and tie)
+        finite = (quotient.abs() < 2.0 ** 100).reshape(out_groups, in_groups, in_group_size).all(-1).flatten()
+        if searched is not None:
+            finite = finite[searched]
+    else:
+        finite = torch.isfinite(targets).all(-1)
+    found = torch.where(finite[:, None], found, before)
+    flat_new = found if searched is None else flat_prev.index_put((searched[:, None], torch.arange(K, device=device)[None, :]), found)
+
+    if trust_ratio is not None:
+        new_weight = _dequantize_weight(flat_new.reshape(out_groups, in_groups, K), books, factors)
+        change = _group_sq_norms(new_weight - prev_weight, out_group_size, in_group_size).flatten()[selected]
+        cumulative = change.cumsum(0).sqrt()
+        admitted = 1 + int(torch.searchsorted(cumulative, trust_ratio * prev_weight.norm(), side="left"))
+        kept = selected[:admitted]
+        flat_new = flat_prev.index_put((kept[:, None], torch.arange(K, device=device)[None, :]), flat_new[kept])
+
+    wrapped = torch.where(flat_new >= size // 2, flat_new - size, flat_new) if prev_codes.dtype in (torch.int8, torch.int16) and nbits in (8, 16) \
+        else flat_new
+    return wrapped.to(prev_codes.dtype).reshape(prev_codes.shape)
+
+
+@torch.no_grad()
+def update_codes_(layer, reference_weight: torch.Tensor, **options) -> torch.Tensor:
+    """Re-choose the codes of ``layer`` (a ``QuantizedLinear``) against the dense target ``reference_weight`` [out, in] with
+    ``find_optimal_codes`` (same options) and write them IN PLACE: the parameter object stays, its version counter moves, and every
+    derived copy of the codes (packed / planar codes, dense W, fast lane, inverted index) is rebuilt at the layer's next call.  A
+    layer whose canonical codes were dropped gets them back first; codes that are an inference tensor raise ``RuntimeError``.  Returns the number of groups whose codes changed (a 0-dim
+    tensor on the layer's device).  The experts of a ``QuantizedMixtralExperts`` block and ``ShardedQuantizedLinear`` raise
+    ``TypeError``."""
+    from .inference import QuantizedLinear
+    from .moe import QuantizedMixtralExperts
+    from .sharded import ShardedQuantizedLinear
+
+    if isinstance(layer, (QuantizedMixtralExperts, ShardedQuantizedLinear)) or getattr(layer, "_moe_expert", False):
+        raise TypeError(f"update_codes_: {type(layer).__name__}{' (an expert of a QuantizedMixtralExperts block)' if getattr(layer, '_moe_expert', False) else ''}"
+                        " is outside the scope of the code update (as it is of make_trainable)")
+    if not isinstance(layer, QuantizedLinear):
+        raise TypeError(f"update_codes_: expected a QuantizedLinear, got {type(layer).__name__}")
+    for name in ("stochastic_rounding_tau", "force_update"):
+        if name in options:
+            raise NotImplementedError(f"update_codes_: {name} is not offered (the reference's defaults do not use it)")
+    layer.restore_canonical_codes()
+    codes = layer.codes
+    if codes.is_inference():
+        # an inference tensor carries no version counter and cannot be written outside inference mode: the in-place write that the
+        # derived state is keyed on does not exist for it
+        raise RuntimeError("update_codes_: the codes of this layer are an inference tensor (the model was built or loaded under "
+                           "torch.inference_mode()); they cannot be written in place -- build the model outside inference mode")
+    new = find_optimal_codes(reference_weight, layer.codebooks.detach(), codes.detach(), layer.scales.detach(), **options)
+    changed = (new != codes).any(-1).sum()
+    codes.copy_(new)
+    return changed

@@ -50,7 +50,8 @@ extern "C" {
 
 #define AQLM_HIP_F16 0
 #define AQLM_HIP_BF16 1
-#define AQLM_HIP_F32 2 /* dW and the outputs of the gradient entries (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16) only */
+#define AQLM_HIP_F32 2 /* dW and the outputs of the gradient entries (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16) and the
+                          reference of aqlm_hip_code_search_1x16 only */
 
 #define AQLM_HIP_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, misaligned buffer) */
 #define AQLM_HIP_E_UNSUPPORTED (-2) /* shape / scheme outside what the entry point implements */
@@ -842,6 +843,45 @@ int aqlm_hip_scales_grad_kx8_supported(int out_features, int in_features, int nu
 int aqlm_hip_scales_grad_kx8(const void* dw, long dw_row_stride, int dw_dtype, const void* codes, const void* codebooks, int dtype,
                              int out_features, int in_features, int num_codebooks, int in_group_size, void* out, int out_dtype,
                              void* stream);
+
+/*
+ * The V step of PV-tuning for the 1x16 schemes (one codebook of 65536 entries, out_group_size 1, g = 8 / 16): the nearest codeword
+ * of every group of g weights -- the reference's `_greedy_find_best_codes` (src/beam_search_l2.py) without its 65536 x groups score
+ * matrix.  For group n = o * (in_features / g) + j:
+ *     r_n     = reference[o, j * g : (j + 1) * g] / scales[o]     widened to fp32 first, IEEE division; scales NULL: r_n = reference
+ *     S(n, c) = |C_c|^2 - 2 <r_n, C_c>
+ *     codes_out = the code with the smallest S THE KERNEL COMPUTED; equal computed scores resolve to the smallest index.  Stored as
+ *     the checkpoint stores it: the 16 bits in an int16 (32768 ... 65535 are negative).
+ * Accuracy: the computed score is within E(n) = eps * (|r_n|^2 + max_c |C_c|^2) of the exact one, eps =
+ * AQLM_HIP_CODE_SEARCH_EPS = 2^-17, so the chosen code's exact score is at most min + 2 E(n), and the chosen code EQUALS the exact
+ * argmin whenever the exact margin between the best and the second best exceeds 2 E(n).  eps follows from the arithmetic (DESIGN.md
+ * 4.8m), it is not fitted: r is scaled by an exact power of two to max|r| in [2^10, 2^11) and split into two operands of the
+ * codebook dtype, hi = round(r'), lo = round(r' - hi) (relative error of the pair <= 2^-21 fp16 incl. a flushed tail, 2^-18 bf16);
+ * products of two 16-bit operands are exact in fp32; the matrix unit adds 2 g <= 32 of them in fp32 (<= 2^-19 of |r||C| summed);
+ * |C_c|^2 is g fp32 fused multiply-adds (<= 2^-20); one fused multiply-add forms S (2^-23).  Valid while 2^-100 <= max|r_n| < 2^100
+ * or r_n = 0 (above it 2 |r||C| can leave fp32: scores become infinite and tie; below it the factor of the scaling is clamped).  A
+ * group with an Inf or NaN element of r_n, or beyond that range, still yields SOME value in 0 ... 65535 (non-finite: the search
+ * runs with r = 0); aqlm.tuning keeps the previous code of a group that is non-finite or has max|r_n| >= 2^100.
+ * group_ids NULL: every group, num_groups == out * in / g, entry i of codes_out is group i.  Else flat ids (int32, or int64 when
+ * group_ids_int64) in any order, repeats allowed: entry i is the code of group group_ids[i]; an id outside [0, out * in / g) writes
+ * NOTHING to its slot and forms no address.  `workspace` (16-byte aligned, nothing is kept in it):
+ * aqlm_hip_code_search_1x16_workspace_bytes = 65536 * 4 bytes (|C_c|^2 in fp32, filled by a first launch of every call) for
+ * 1 <= num_groups <= AQLM_HIP_CODE_SEARCH_MAX_GROUPS and g 8 / 16, else 0.  Two launches, stream-ordered, no allocation, no
+ * synchronisation, no atomics, no scratch: the output is a function of the arguments alone.
+ * Checks, in order: a null pointer (scales and group_ids may be NULL); misalignment (codebook / workspace 16 bytes, the others
+ * their element); non-positive sizes or in_features % g != 0, a row stride below in_features, num_groups < 1 or != out * in / g
+ * without group_ids (AQLM_HIP_E_INVALID); reference_dtype outside fp16 / bf16 / fp32, dtype outside fp16 / bf16, g outside {8, 16},
+ * more than AQLM_HIP_CODE_SEARCH_MAX_GROUPS groups in the layer or the call (AQLM_HIP_E_UNSUPPORTED); a workspace that is too small
+ * (AQLM_HIP_E_INVALID).  Nothing is launched on bad arguments.
+ */
+#define AQLM_HIP_CODE_SEARCH_MAX_GROUPS 2147483647L
+#define AQLM_HIP_CODE_SEARCH_EPS 7.62939453125e-06 /* 2^-17 */
+int aqlm_hip_code_search_1x16_supported(int out_features, int in_features, int in_group_size);
+size_t aqlm_hip_code_search_1x16_workspace_bytes(long num_groups, int in_group_size);
+int aqlm_hip_code_search_1x16(const void* reference, int reference_dtype, long reference_row_stride, const void* scales,
+                              const void* codebook, int dtype, int out_features, int in_features, int in_group_size,
+                              const void* group_ids, int group_ids_int64, long num_groups, void* codes_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
