@@ -1277,6 +1277,89 @@ def code_search_1x16(reference, scales, codebook, in_group_size: int, group_ids=
 
 
 # ------------------------------------------------------------------------------------------------------
+# beam search over the codebooks of the K x 8 schemes (the V step of PV-tuning; aqlm_hip_code_search_kx8)
+# ------------------------------------------------------------------------------------------------------
+CODE_SEARCH_KX8_MAX_BEAM = 16  # AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM
+
+
+def code_search_kx8_supported(out_features: int, in_features: int, num_codebooks: int, in_group_size: int, beam_size: int) -> bool:
+    return bool(_lib.aqlm_hip_code_search_kx8_supported(int(out_features), int(in_features), int(num_codebooks), int(in_group_size),
+                                                        int(beam_size)))
+
+
+def _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out, geometry, want_scores):
+    out_features, in_features, K, g, beam_size = (int(x) for x in geometry[:5])
+    order = [int(c) for c in geometry[5:]]
+    if (reference.dim() != 2 or tuple(reference.shape) != (out_features, in_features) or reference.dtype not in _GRAD_DT
+            or not reference.is_cuda):
+        raise ValueError(f"code_search_kx8: reference must be fp16 / bf16 / fp32 [{out_features}, {in_features}] on the GPU, got "
+                         f"{reference.dtype} {tuple(reference.shape)}")
+    if reference.stride(1) != 1 or reference.stride(0) < in_features:  # a transposed or expanded view: the kernel walks rows
+        reference = reference.contiguous()
+    if codebooks.numel() != K * 256 * g or codebooks.device != reference.device:
+        raise ValueError(f"code_search_kx8: the codebooks must hold {K} x 256 x {g} elements on {reference.device}")
+    dt = _dtype_id(codebooks)
+    codebooks = _c(codebooks)
+    if scales is not None:
+        if scales.numel() != out_features or scales.device != reference.device or scales.dtype != codebooks.dtype:
+            raise ValueError(f"code_search_kx8: scales must hold {out_features} elements of {codebooks.dtype} on {reference.device}")
+        scales = _c(scales)
+    total = out_features * (in_features // max(g, 1))
+    if prev_codes.dtype != torch.int8 or prev_codes.numel() != total * K or prev_codes.device != reference.device:
+        raise ValueError(f"code_search_kx8: prev_codes must hold {total} x {K} int8 codes (the whole layer) on {reference.device}")
+    prev_codes = _c(prev_codes)
+    if order and sorted(order) != list(range(K)):
+        raise ValueError(f"code_search_kx8: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    if group_ids is not None:
+        if group_ids.dtype not in (torch.int32, torch.int64) or group_ids.dim() != 1 or group_ids.device != reference.device:
+            raise ValueError("code_search_kx8: group_ids must be a 1-d int32 / int64 tensor on the reference's device")
+        group_ids = _c(group_ids)
+        n = int(group_ids.numel())
+    else:
+        n = total
+    if codes_out is None:
+        codes_out = torch.empty((n, K), dtype=torch.int8, device=reference.device)
+    elif codes_out.dtype != torch.int8 or codes_out.numel() != n * K or not codes_out.is_contiguous() or codes_out.device != reference.device:
+        raise ValueError(f"code_search_kx8: codes_out must be contiguous int8 [{n}, {K}] on {reference.device}")
+    scores = torch.empty((n,), dtype=torch.float32, device=reference.device) if want_scores else None
+    if n == 0:
+        return codes_out, scores
+    dim_order = (ctypes.c_int * K)(*order) if order else None
+    with _device_guard(reference.device):
+        rc = _lib.aqlm_hip_code_search_kx8(reference.data_ptr(), _GRAD_DT[reference.dtype], reference.stride(0), _ptr(scales),
+                                           codebooks.data_ptr(), dt, prev_codes.data_ptr(), out_features, in_features, K, g, beam_size,
+                                           dim_order, _ptr(group_ids), int(group_ids is not None and group_ids.dtype == torch.int64), n,
+                                           codes_out.data_ptr(), _ptr(scores), None, 0, _stream_ptr(reference.device))
+    if rc:
+        _native.check(rc, "aqlm code search kx8")
+    return codes_out, scores
+
+
+def _code_search_kx8_op(reference, scales, codebooks, prev_codes, group_ids, geometry):
+    return _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, None, geometry, True)
+
+
+def code_search_kx8(reference, scales, codebooks, prev_codes, in_group_size: int, beam_size: int, dim_order=None, group_ids=None,
+                    codes_out=None, return_scores: bool = False):
+    """int8 codes [n, K]: for every group of ``in_group_size`` weights of ``reference`` [out, in] (fp32 / fp16 / bf16, any row stride; a
+    view with another column stride is copied first) -- or for the flat groups ``group_ids`` (int32 / int64, ``o * (in / g) + j``), in
+    their order -- the codes the reference's beam search over the ``K`` codebooks (``codebooks``: K x 256 x g elements, fp16 / bf16)
+    reaches from ``prev_codes`` (int8, the WHOLE layer's [out * in / g, K], read at the group's id) with ``beam_size`` hypotheses,
+    revisiting the codebooks in ``dim_order`` (default 0 .. K - 1); ``scales`` ([out] elements in the codebook dtype) None = 1.  The
+    arithmetic is fixed operation for operation in include/aqlm_hip.h (tests/kx8_search_model.py is its numpy restatement): equal
+    scores go to the smaller flat index ``position * 256 + code``.  ``codes_out`` (int8, K entries per group searched): written in
+    place when given -- an id outside the layer leaves its entries as they were.  ``return_scores``: also the fp32 score of the
+    returned hypothesis on the last step, [n].  One launch on the current stream, no workspace."""
+    g, K = int(in_group_size), int(codebooks.shape[0])
+    order = [] if dim_order is None else [int(c) for c in dim_order]
+    if dim_order is not None and sorted(order) != list(range(K)):
+        raise ValueError(f"code_search_kx8: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    codes, scores = _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out,
+                                          [int(reference.shape[0]), int(reference.shape[1]), K, g, int(beam_size)] + order, return_scores)
+    return (codes, scores) if return_scores else codes
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
@@ -2510,6 +2593,19 @@ _LIB.impl("code_search_1x16", _code_search_1x16_op, "CUDA")
 torch.library.register_fake("aqlm::code_search_1x16")(
     lambda reference, scales, codebook, group_ids, geometry: reference.new_empty(
         (int(group_ids.numel()) if group_ids is not None else int(geometry[0]) * (int(geometry[1]) // int(geometry[2])),), dtype=torch.int16))
+# beam search over the codebooks of a K x 8 layer; geometry = [out_features, in_features, K, g, beam_size] + dim_order (or nothing);
+# returns the codes [n, K] int8 and the fp32 score of every returned hypothesis [n]
+_LIB.define("code_search_kx8(Tensor reference, Tensor? scales, Tensor codebooks, Tensor prev_codes, Tensor? group_ids, int[] geometry)"
+            " -> (Tensor, Tensor)")
+_LIB.impl("code_search_kx8", _code_search_kx8_op, "CUDA")
+
+
+def _fake_code_search_kx8(reference, scales, codebooks, prev_codes, group_ids, geometry):
+    n = int(group_ids.numel()) if group_ids is not None else int(geometry[0]) * (int(geometry[1]) // int(geometry[3]))
+    return reference.new_empty((n, int(geometry[2])), dtype=torch.int8), reference.new_empty((n,), dtype=torch.float32)
+
+
+torch.library.register_fake("aqlm::code_search_kx8")(_fake_code_search_kx8)
 
 
 # expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)

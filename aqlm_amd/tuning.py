@@ -32,12 +32,17 @@ furthest from the target, and only while the change stays within ``trust_ratio``
     accumulators of the matrix unit and never reach memory; equal scores give the smallest index, the result is a function of
     the inputs alone.  Selection and trust ratio are torch operations around the kernel (they synchronise: the V step is not
     meant to be captured into a hipGraph);
-  * everything else (several codebooks with beam search, 8-bit codebooks, ``out_group_size > 1``, host tensors, fp32 parameters,
+  * K x 8 layers (1 to 8 codebooks of 256 entries, g 8 / 16 / 32, ``out_group_size`` 1, ``beam_size`` up to 16) under the same
+    conditions, codes int8: ``aqlm_hip_code_search_kx8`` -- the reference's beam search over the codebooks
+    in ``dim_order``, one wave per group, the ``beams x 256`` scores of a step in registers.  It is held to its own arithmetic bit
+    for bit (every product and sum one fp32 operation in a stated order, equal scores to the smaller ``position * 256 + code``):
+    tests/kx8_search_model.py restates it;
+  * everything else (``beam_size > 16``, codebooks of other sizes, ``out_group_size > 1``, host tensors, fp32 parameters,
     ``CODE_SEARCH_KERNEL = False``): a torch route written from the reference's definition -- chunked scores, the best
     ``beam_size`` hypotheses per step, ``dim_order`` -- slow, correct, never silent.
 A group whose unscaled target has a non-finite element keeps its previous code (the reference's result there is whatever
-``argmin`` makes of NaNs); so does, on the kernel route, a group with an element of magnitude 2^100 or more (the kernel's stated
-range).  The new codes are written in place, so the version counter of ``codes`` moves and every derived copy
+``argmin`` makes of NaNs); so does, on a kernel route, a group with an element of magnitude 2^100 (K x 8: 2^60) or more (the
+kernels' stated ranges).  The new codes are written in place, so the version counter of ``codes`` moves and every derived copy
 (packed and planar codes, dense W, the fast lane, the inverted index) is rebuilt at the next call by the fingerprint rule that
 already covers ``load_state_dict``.  Not offered: ``stochastic_rounding_tau`` and ``force_update`` (``NotImplementedError``).
 
@@ -51,7 +56,7 @@ fp32-master-weight optimizer wrapper; keep the parameters in fp32 (``model.float
 
 Out of scope: the experts of a ``QuantizedMixtralExperts`` block (their routed launches carry gradients to the hidden states
 only) and ``ShardedQuantizedLinear`` -- ``make_trainable`` leaves both frozen and names them in ``.skipped`` of its result, and
-``update_codes_`` raises ``TypeError`` for them; a search kernel for the K x 8 schemes (they take the torch route).
+``update_codes_`` raises ``TypeError`` for them.
 """
 from __future__ import annotations
 
@@ -153,6 +158,15 @@ def takes_code_search_kernel(num_codebooks: int, nbits_per_codebook: int, out_gr
                 and in_group_size in (8, 16) and on_gpu and dtypes_ok and supported)
 
 
+def takes_code_search_kernel_kx8(num_codebooks: int, nbits_per_codebook: int, out_group_size: int, in_group_size: int, beam_size: int,
+                                 on_gpu: bool, dtypes_ok: bool, supported: bool) -> bool:
+    """The same for ``aqlm_hip_code_search_kx8``: 1 to 8 codebooks of 8 bits, ``out_group_size`` 1, g 8, 16 or 32, ``beam_size`` 1 to 16;
+    ``dtypes_ok``: codebooks and scales in ONE of fp16 / bf16, the target in fp32 / fp16 / bf16, codes int8; the other arguments and the
+    switch as in ``takes_code_search_kernel``.  The two predicates are never true together."""
+    return bool(CODE_SEARCH_KERNEL and 1 <= num_codebooks <= 8 and nbits_per_codebook == 8 and out_group_size == 1
+                and in_group_size in (8, 16, 32) and 1 <= beam_size <= 16 and on_gpu and dtypes_ok and supported)
+
+
 def _greedy_codes_torch(reference: torch.Tensor, codebook: torch.Tensor, chunk_values: int) -> torch.Tensor:
     """[N] int64: per row of ``reference`` [N, d] the first index that minimises ``|C_c|^2 - 2 <r, C_c>`` over ``codebook`` [S, d]."""
     norms = codebook.square().sum(-1)[None]
@@ -243,14 +257,23 @@ def find_optimal_codes(reference_weight: torch.Tensor, codebooks: torch.Tensor, 
 
     tensors = [reference_weight, codebooks, prev_codes] + ([] if scales is None else [scales])
     on_gpu = all(t.is_cuda for t in tensors)
-    dtypes_ok = (codebooks.dtype in (torch.float16, torch.bfloat16) and (scales is None or scales.dtype == codebooks.dtype)
-                 and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16) and prev_codes.dtype == torch.int16)
+    floats_ok = (codebooks.dtype in (torch.float16, torch.bfloat16) and (scales is None or scales.dtype == codebooks.dtype)
+                 and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16))
+    dtypes_ok = floats_ok and prev_codes.dtype == torch.int16
     supported = False
     if CODE_SEARCH_KERNEL and on_gpu and K == 1 and nbits == 16 and out_group_size == 1 and in_group_size in (8, 16):
         from .inference_kernels import hip_kernel
 
         supported = hip_kernel.code_search_1x16_supported(reference_weight.shape[0], reference_weight.shape[1], in_group_size)
     kernel = takes_code_search_kernel(K, nbits, out_group_size, in_group_size, on_gpu, dtypes_ok, supported)
+    supported_kx8 = False
+    if (CODE_SEARCH_KERNEL and on_gpu and 1 <= K <= 8 and nbits == 8 and out_group_size == 1 and in_group_size in (8, 16, 32)
+            and 1 <= beam_size <= 16):
+        from .inference_kernels import hip_kernel
+
+        supported_kx8 = hip_kernel.code_search_kx8_supported(reference_weight.shape[0], reference_weight.shape[1], K, in_group_size, beam_size)
+    kernel_kx8 = takes_code_search_kernel_kx8(K, nbits, out_group_size, in_group_size, beam_size, on_gpu,
+                                              floats_ok and prev_codes.dtype == torch.int8, supported_kx8)
 
     from .utils import _dequantize_weight
 
@@ -290,6 +313,14 @@ def find_optimal_codes(reference_weight: torch.Tensor, codebooks: torch.Tensor, 
                                             codebooks.detach(), in_group_size, group_ids=searched)
         found = (found.to(torch.int64) % size)[:, None]
         targets = None
+    elif kernel_kx8:
+        from .inference_kernels import hip_kernel
+
+        found = hip_kernel.code_search_kx8(reference_weight.detach(), None if scales is None else scales.detach().reshape(-1),
+                                           codebooks.detach(), prev_codes.detach().reshape(num_groups, K), in_group_size, beam_size,
+                                           dim_order=order, group_ids=searched)
+        found = found.to(torch.int64) % size
+        targets = None
     else:
         targets = unscaled(searched)
         before = flat_prev if searched is None else flat_prev[searched]
@@ -300,14 +331,10 @@ def find_optimal_codes(reference_weight: torch.Tensor, codebooks: torch.Tensor, 
             found = _beam_codes_torch(targets, flat_books, before, beam_size, order, CODE_SEARCH_CHUNK_VALUES)
     # a group with a non-finite target keeps what it had
     before = flat_prev if searched is None else flat_prev[searched]
-    if targets is None:  # (the kernel route: out_group_size 1, a group is a run of a row)
-        quotient = reference_weight.to(compute)
-        if factors is not None:
-            quotient = quotient / factors.reshape(out_groups, 1)
-        # (... and one beyond the kernel's stated range, max|r| >= 2^100, where its fp32 scores can overflow and tie)
-        finite = (quotient.abs() < 2.0 ** 100).reshape(out_groups, in_groups, in_group_size).all(-1).flatten()
-        if searched is not None:
-            finite = finite[searched]
+    if targets is None:  # (the kernel routes)
+        # (... and one beyond the kernel's stated range, max|r| >= 2^100 for 1x16 and 2^60 for K x 8, where fp32 scores can overflow
+        # and tie)
+        finite = (unscaled(searched).abs() < 2.0 ** (60 if kernel_kx8 else 100)).all(-1)
     else:
         finite = torch.isfinite(targets).all(-1)
     found = torch.where(finite[:, None], found, before)

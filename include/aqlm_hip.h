@@ -884,6 +884,59 @@ int aqlm_hip_code_search_1x16(const void* reference, int reference_dtype, long r
                               size_t workspace_bytes, void* stream);
 
 /*
+ * The V step of PV-tuning for the K x 8 schemes (1 <= K <= 8 codebooks of 256 entries, out_group_size 1, g = 8 / 16 / 32: 2x8 g8,
+ * 1x8 g8, 4x8 g16, 8x8 g32 ...): the reference's `_beam_search_update_codes_groupwise` (src/beam_search_l2.py) for every group of
+ * one layer, without its [groups, beams, 256] score tensor.  The entry is held to ITS OWN ARITHMETIC bit for bit, not to an error
+ * bound (a beam step must get the whole order of its best beam_size + 1 scores right, and at depth a share of the groups has two
+ * of them closer than any bound a kernel could promise: DESIGN.md 4.8n); tests/kx8_search_model.py restates it in numpy.  Every
+ * operation below is ONE IEEE fp32 operation, rounded to nearest; there are no fused multiply-adds.  For group
+ * n = o * (in_features / g) + j, with the codebooks C_c [256][d = g] widened exactly from fp16 / bf16 to fp32:
+ *     r        = float(reference[o, j * g : (j + 1) * g]) / float(scales[o])        a true division; scales NULL: r = reference
+ *     dot(a,b) : acc = a_0 * b_0, then acc = acc + a_j * b_j for j = 1 .. d - 1     (the product is rounded, then the sum)
+ *     cn[c][s] = dot(C_c[s], C_c[s])
+ *     kept     = C_0[p_0], then kept = kept + C_c[p_c] for c = 1 .. K - 1           p: prev_codes of the group, the int8 mod 256
+ *     res[0]   = r - kept                                                           one position, whose beam is p
+ *     for each step c of dim_order (a permutation of 0 .. K - 1; NULL: 0, 1 .. K - 1):
+ *         res[b]  = res[b] + C_c[beam[b][c]]                                        for each position b
+ *         rn[b]   = dot(res[b], res[b])
+ *         S(b, s) = (rn[b] - 2 * dot(res[b], C_c[s])) + cn[c][s]                    (the doubling is exact; the same formula at
+ *                                                                                    beam_size 1, where the reference drops rn)
+ *         keep the best 1 hypothesis on the last step, else min(beam_size, positions * 256), ordered by (S, b * 256 + s)
+ *         ascending: equal scores compare as floats (-0 equals +0) and go to the smaller flat index; rank i takes the codes of
+ *         its source position b with code c replaced by s;
+ *         not the last step: res[i] = res_old[i] - C_c[chosen_i], POSITION BY POSITION as the reference does it -- the residue of
+ *         old position i stays at position i even when the hypothesis now at i came from another position; after the first step
+ *         every new position starts from old position 0
+ *     codes_out = the codes of rank 0 (int8 [num_groups, K], the 8 bits as the checkpoint stores them: 128 .. 255 are negative);
+ *     scores_out (fp32 [num_groups], may be NULL) = its S on the last step.
+ * The contract holds while every element of r and of the codebooks is finite and below 2^60 in magnitude.  Outside that range the
+ * kernel still writes SOME code in 0 .. 255 per codebook: no address and no source position is derived from a score, so NaNs can
+ * neither index out of range nor stall a loop; aqlm.tuning keeps the previous codes of such a group.
+ * reference: fp32 / fp16 / bf16, any row stride >= in_features (elements).  codebooks [K, 256, g] fp16 / bf16, 16-byte aligned;
+ * scales [out] in the same dtype, or NULL.  prev_codes int8 [out * in / g, K] for the WHOLE layer, read at the group's id.
+ * group_ids as in aqlm_hip_code_search_1x16: NULL = every group (num_groups == out * in / g, entry i is group i), else flat ids
+ * (int32, or int64 when group_ids_int64) in any order, repeats allowed; an id outside [0, out * in / g) writes NOTHING to its slot
+ * of codes_out / scores_out and forms no address.  aqlm_hip_code_search_kx8_workspace_bytes is 0: `workspace` may be NULL (|C|^2 is
+ * formed from the registers that hold the candidates).  One launch, stream-ordered, no allocation, no synchronisation, no global
+ * atomics, no scratch: the output is a function of the arguments alone.
+ * Supported (aqlm_hip_code_search_kx8_supported): 1 <= K <= 8, g in {8, 16, 32}, 1 <= beam_size <=
+ * AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM, in_features % g == 0, at most AQLM_HIP_CODE_SEARCH_MAX_GROUPS groups.
+ * Checks, in the order of aqlm_hip_code_search_1x16: a null pointer (scales, dim_order, group_ids, scores_out and workspace may be
+ * NULL); misalignment (codebooks 16 bytes, the others their element); non-positive out / in / g or in_features % g != 0, a row
+ * stride below in_features, num_groups < 1 or != out * in / g without group_ids (AQLM_HIP_E_INVALID); reference_dtype outside fp16 /
+ * bf16 / fp32, dtype outside fp16 / bf16, K, g or beam_size outside the supported set, too many groups (AQLM_HIP_E_UNSUPPORTED); a
+ * dim_order (host memory) that is no permutation (AQLM_HIP_E_INVALID).  Nothing is launched on bad arguments.
+ */
+#define AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM 16
+int aqlm_hip_code_search_kx8_supported(int out_features, int in_features, int num_codebooks, int in_group_size, int beam_size);
+size_t aqlm_hip_code_search_kx8_workspace_bytes(long num_groups, int num_codebooks, int in_group_size, int beam_size); /* may be 0 */
+int aqlm_hip_code_search_kx8(const void* reference, int reference_dtype, long reference_row_stride, const void* scales,
+                             const void* codebooks, int dtype, const void* prev_codes, int out_features, int in_features,
+                             int num_codebooks, int in_group_size, int beam_size, const int* dim_order /* host, NULL = natural */,
+                             const void* group_ids, int group_ids_int64, long num_groups, void* codes_out, void* scores_out /* NULL ok */,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the
