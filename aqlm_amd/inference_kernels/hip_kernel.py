@@ -18,7 +18,7 @@ import contextlib
 import ctypes
 import os
 from types import SimpleNamespace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -1357,6 +1357,72 @@ def code_search_kx8(reference, scales, codebooks, prev_codes, in_group_size: int
     codes, scores = _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out,
                                           [int(reference.shape[0]), int(reference.shape[1]), K, g, int(beam_size)] + order, return_scores)
     return (codes, scores) if return_scores else codes
+
+
+# ------------------------------------------------------------------------------------------------------
+# the calibrated beam search of the K x 8 schemes, one input group per launch (aqlm_hip_code_search_kx8_xtx)
+# ------------------------------------------------------------------------------------------------------
+def code_search_kx8_xtx_supported(out_features: int, num_codebooks: int, in_group_size: int, beam_size: int, positions_in: int = 1) -> bool:
+    return bool(_lib.aqlm_hip_code_search_kx8_xtx_supported(int(out_features), int(num_codebooks), int(in_group_size), int(beam_size),
+                                                            int(positions_in)))
+
+
+class XtxStep(NamedTuple):
+    """What one launch of aqlm_hip_code_search_kx8_xtx returns, every tensor [beam_size, out, ...] with rank 0 the best."""
+
+    loss: torch.Tensor     # fp32 [beam, out]
+    codes: torch.Tensor    # int8 [beam, out, K]
+    source: torch.Tensor   # uint8 [beam, out]: the position at entry
+    delta: torch.Tensor    # fp32 [beam, out, g]
+    t: Optional[torch.Tensor]  # fp32 [beam, out, g] when asked for
+
+
+def code_search_kx8_xtx_step(t, loss, codes_in, H, q, codebooks, scales, beam_size: int, dim_order=None, return_t: bool = False) -> XtxStep:
+    """One launch of aqlm_hip_code_search_kx8_xtx: all K codebook steps of the calibrated beam search for ONE input group and every
+    output row (include/aqlm_hip.h has the definition and the arithmetic, tests/kx8_xtx_model.py its numpy restatement).  ``t`` fp32
+    [positions, out, g] -- the group's slice of ``T = (W_ref - W_position) XTX``, any position / row stride with g contiguous (a view
+    into a wider buffer is read in place) --, ``loss`` fp32 [positions, out], ``codes_in`` int8 [positions, out, K], ``H`` fp32 [g, g] =
+    ``XTX[group, group]``, ``q`` fp32 [K, 256] = ``C H C^T`` unscaled, ``codebooks`` K x 256 x g elements fp16 / bf16, ``scales`` [out]
+    elements in the same dtype or None.  One launch on the current stream; no workspace, no synchronisation."""
+    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError(f"code_search_kx8_xtx_step: t must be fp32 [positions, out, g] on the GPU, got {t.dtype} {tuple(t.shape)}")
+    positions, out_features, g = (int(x) for x in t.shape)
+    K, beam_size = int(codebooks.shape[0]), int(beam_size)
+    dev = t.device
+    if t.stride(2) != 1 or t.stride(1) < g or (positions > 1 and t.stride(0) < g):
+        t = t.contiguous()
+    if codebooks.numel() != K * 256 * g or codebooks.device != dev:
+        raise ValueError(f"code_search_kx8_xtx_step: the codebooks must hold {K} x 256 x {g} elements on {dev}")
+    dt = _dtype_id(codebooks)
+    codebooks = _c(codebooks)
+    for name, x, shape, dtype in (("loss", loss, (positions, out_features), torch.float32), ("codes_in", codes_in, (positions, out_features, K), torch.int8),
+                                  ("H", H, (g, g), torch.float32), ("q", q, (K, 256), torch.float32)):
+        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
+            raise ValueError(f"code_search_kx8_xtx_step: {name} must be {dtype} {list(shape)} on {dev}, got {x.dtype} {tuple(x.shape)}")
+    loss, codes_in, H, q = _c(loss), _c(codes_in), _c(H), _c(q)
+    if scales is not None:
+        if scales.numel() != out_features or scales.device != dev or scales.dtype != codebooks.dtype:
+            raise ValueError(f"code_search_kx8_xtx_step: scales must hold {out_features} elements of {codebooks.dtype} on {dev}")
+        scales = _c(scales)
+    order = None if dim_order is None else [int(c) for c in dim_order]
+    if order is not None and sorted(order) != list(range(K)):
+        raise ValueError(f"code_search_kx8_xtx_step: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    if not code_search_kx8_xtx_supported(out_features, K, g, beam_size, positions):
+        raise NotImplementedError(f"code_search_kx8_xtx_step: K={K} g={g} beam_size={beam_size} positions={positions} is outside the kernel")
+    out = XtxStep(torch.empty((beam_size, out_features), dtype=torch.float32, device=dev),
+                  torch.empty((beam_size, out_features, K), dtype=torch.int8, device=dev),
+                  torch.empty((beam_size, out_features), dtype=torch.uint8, device=dev),
+                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev),
+                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev) if return_t else None)
+    with _device_guard(dev):
+        rc = _lib.aqlm_hip_code_search_kx8_xtx(t.data_ptr(), t.stride(0), t.stride(1), loss.data_ptr(), codes_in.data_ptr(), H.data_ptr(),
+                                               q.data_ptr(), codebooks.data_ptr(), dt, _ptr(scales), out_features, K, g, beam_size, positions,
+                                               None if order is None else (ctypes.c_int * K)(*order), out.loss.data_ptr(),
+                                               out.codes.data_ptr(), out.source.data_ptr(), out.delta.data_ptr(), _ptr(out.t), None, 0,
+                                               _stream_ptr(dev))
+    if rc:
+        _native.check(rc, "aqlm code search kx8 xtx")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -46,6 +46,12 @@ kernels' stated ranges).  The new codes are written in place, so the version cou
 (packed and planar codes, dense W, the fast lane, the inverted index) is rebuilt at the next call by the fingerprint rule that
 already covers ``load_state_dict``.  Not offered: ``stochastic_rounding_tau`` and ``force_update`` (``NotImplementedError``).
 
+The calibrated update (``find_optimal_codes_calibrated``, ``update_codes_calibrated_``, ``calibrated_error``): the codes that lower
+``||X W_ref^T - X W_q^T||^2`` given ``XTX = X^T X`` of calibration activations -- the reference's src/beam_search_xtx.py, the search
+that produces an AQLM layer.  K x 8 layers on the MI355X (fp16 / bf16 codebooks and scales, int8 codes, fp32 ``XTX``, ``beam_size`` up
+to 16) run ``aqlm_hip_code_search_kx8_xtx`` once per input group (tests/kx8_xtx_model.py restates its
+arithmetic); everything else runs a torch route of the same incremental form.
+
 Memory: the 1x16 index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
 state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.  The
 K x 8 route keeps no derived state: its transient is the per-stream workspace (at most 33.6 MB).
@@ -381,6 +387,278 @@ def update_codes_(layer, reference_weight: torch.Tensor, **options) -> torch.Ten
         raise RuntimeError("update_codes_: the codes of this layer are an inference tensor (the model was built or loaded under "
                            "torch.inference_mode()); they cannot be written in place -- build the model outside inference mode")
     new = find_optimal_codes(reference_weight, layer.codebooks.detach(), codes.detach(), layer.scales.detach(), **options)
+    changed = (new != codes).any(-1).sum()
+    codes.copy_(new)
+    return changed
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the calibrated V step: new codes against the layer's OUTPUT on calibration data (XTX = X^T X)
+# ---------------------------------------------------------------------------------------------------------------------------
+def takes_code_search_kernel_kx8_xtx(num_codebooks: int, nbits_per_codebook: int, out_group_size: int, in_group_size: int, beam_size: int,
+                                     on_gpu: bool, dtypes_ok: bool, supported: bool) -> bool:
+    """Whether a ``find_optimal_codes_calibrated`` call runs ``aqlm_hip_code_search_kx8_xtx`` -- a pure function of: the scheme (1 to 8
+    codebooks of 8 bits, ``out_group_size`` 1, g 8, 16 or 32), ``beam_size`` 1 to 16, ``on_gpu`` (every tensor on the GPU), ``dtypes_ok``
+    (codebooks and scales in ONE of fp16 / bf16, codes int8, ``XTX`` fp32, the target fp32 / fp16 / bf16 -- a float64 target asks for
+    float64 arithmetic and takes the torch route), ``supported`` (the library's ``_supported`` query) and the ``CODE_SEARCH_KERNEL``
+    switch.  No region is declined on timing grounds: the kernel route took 0.06 to 0.27 of the torch route's time in every cell
+    measured (profiles/code_update_xtx.json)."""
+    return bool(CODE_SEARCH_KERNEL and 1 <= num_codebooks <= 8 and nbits_per_codebook == 8 and out_group_size == 1
+                and in_group_size in (8, 16, 32) and 1 <= beam_size <= 16 and on_gpu and dtypes_ok and supported)
+
+
+def _channel_errors(weight: torch.Tensor, reference: torch.Tensor, XTX: torch.Tensor) -> torch.Tensor:
+    """[out]: ``(W - W_ref)[o] XTX (W - W_ref)[o]^T``"""
+    error = weight - reference
+    return ((error @ XTX) * error).sum(-1)
+
+
+@torch.no_grad()
+def calibrated_error(weight_or_layer, reference_weight: torch.Tensor, XTX: torch.Tensor) -> torch.Tensor:
+    """``sum_o (W - W_ref)[o] XTX (W - W_ref)[o]^T`` -- ``||X W^T - X W_ref^T||^2`` for ``XTX = X^T X``, the objective of the calibrated code
+    search (the reference's ``_channelwise_squared_error``, summed) -- for a dense ``W`` [out, in] or a ``QuantizedLinear`` (its
+    dequantised weight).  Computed in the dtype of ``reference_weight`` (fp16 / bf16: in fp32); a 0-dim tensor."""
+    compute = reference_weight.dtype if reference_weight.dtype in (torch.float32, torch.float64) else torch.float32
+    if isinstance(weight_or_layer, torch.Tensor):
+        weight = weight_or_layer
+    else:
+        from .utils import _dequantize_weight, unpack_int_data
+
+        layer = weight_or_layer
+        layer.restore_canonical_codes()
+        nbits = int(math.log2(layer.codebooks.shape[1]))
+        weight = _dequantize_weight(unpack_int_data(layer.codes.detach(), nbits), layer.codebooks.detach().to(compute),
+                                    layer.scales.detach().to(compute))
+    return _channel_errors(weight.to(compute), reference_weight.to(compute), XTX.to(compute)).sum()
+
+
+def _calibrated_codes_torch(XTX: torch.Tensor, reference: torch.Tensor, books: torch.Tensor, codes: torch.Tensor,
+                            factors: Optional[torch.Tensor], beam_size: int, group_order: Sequence[int],
+                            dim_orders: Sequence[Sequence[int]], chunk_values: int) -> torch.Tensor:
+    """[out_groups, in_groups, K] int64: the reference's ``beam_search_optimal_codes`` of src/beam_search_xtx.py in its incremental
+    form.  With ``T_b = (W_ref - W_b) XTX`` per beam position, the K steps of an input group read and write only ``T_b[group]``, the
+    block ``H = XTX[group, group]`` and ``q_c[s] = C_c[s] H C_c[s]^T``; the other columns of ``T`` take the group's weight change once,
+    when the group is done.  ``books`` [K, S, out_group_size, g], ``codes`` unsigned, ``factors`` [out_groups] or None, all tensors in
+    the compute dtype.  Transient memory: two copies of ``T`` [beam_size, out, in] and one chunk of scores."""
+    K, size, ogs, g = books.shape
+    og, ng, _ = codes.shape
+    from .utils import _dequantize_weight
+
+    s = torch.ones((og,), dtype=books.dtype, device=books.device) if factors is None else factors.reshape(og)
+    error = reference - _dequantize_weight(codes, books, s.reshape(og, 1, 1, 1))
+    T = (error @ XTX).reshape(1, og, ogs, ng * g)
+    loss = (T[0] * error.reshape(og, ogs, ng * g)).sum(dim=(-1, -2))[None]  # [P, og]
+    beams = codes[None]  # [P, og, ng, K]
+    flat_books = books.flatten(2)  # [K, S, ogs * g]
+    rows = torch.arange(og, device=books.device)[None, :]
+    s4 = s[None, :, None, None]
+    for j, order in zip(group_order, dim_orders):
+        cols = slice(j * g, (j + 1) * g)
+        H = XTX[cols, cols]
+        q = torch.einsum("ksrf,fh,ksrh->ks", books, H, books)
+        tl = T[..., cols].clone()  # [P, og, ogs, g]
+        local = beams[:, :, j, :].clone()  # [P, og, K]
+        ancestor = torch.arange(tl.shape[0], device=books.device)[:, None].expand(-1, og)
+        delta = torch.zeros_like(tl)
+        for c in order:
+            P = tl.shape[0]
+            code = local[..., c]
+            prev_entry = books[c][code]  # [P, og, ogs, g]
+            u = (tl + (s4 * prev_entry) @ H).flatten(2)
+            base = loss + 2 * s * (prev_entry.flatten(2) * u).sum(-1) - s * s * q[c][code]
+            keep = min(beam_size, P * size)
+            values = torch.empty((og, keep), dtype=books.dtype, device=books.device)
+            picked = torch.empty((og, keep), dtype=torch.int64, device=books.device)
+            n = max(1, chunk_values // (P * size))
+            for a in range(0, og, n):
+                sa = s[a:a + n, None]
+                scores = base[:, a:a + n, None] - (2 * sa) * (u[:, a:a + n] @ flat_books[c].T) + (sa * sa) * q[c][None, :]
+                top = torch.topk(scores.permute(1, 0, 2).flatten(1), keep, dim=-1, largest=False, sorted=True)
+                values[a:a + n], picked[a:a + n] = top.values, top.indices
+            source, chosen = (picked // size).T, (picked % size).T  # [keep, og]
+            dw = s4 * (books[c][chosen] - books[c][code[source, rows]])
+            tl = tl[source, rows] - dw @ H
+            delta = delta[source, rows] + dw
+            local = local[source, rows].clone()
+            local[..., c] = chosen
+            ancestor = ancestor[source, rows]
+            loss = values.T
+        T = T[ancestor, rows] - delta @ XTX[cols, :]
+        beams = beams[ancestor, rows].clone()
+        beams[:, :, j, :] = local
+    return beams[0]
+
+
+# Input groups per block of the kernel route: within a block every group's weight change reaches the block's own columns of T at once
+# (a gather and a small GEMM); the other columns take the whole block's change in one GEMM at the block's end.
+CALIBRATED_BLOCK_GROUPS = 16
+
+
+def _calibrated_codes_kernel(XTX: torch.Tensor, reference: torch.Tensor, codebooks: torch.Tensor, prev_codes: torch.Tensor,
+                             scales: Optional[torch.Tensor], beam_size: int, group_order: Sequence[int],
+                             dim_orders: Sequence[Sequence[int]], block_groups: int) -> torch.Tensor:
+    """[out, in_groups, K] int8: the same search with one ``aqlm_hip_code_search_kx8_xtx`` launch per input group.  A host loop, no
+    ``.item()`` and no host synchronisation; hypotheses are carried by back-pointers (``source`` of every launch) resolved at the end.
+    The initial ``T`` and losses are formed in float64 and rounded once.  Transient memory: ``T`` [beam_size, out, in] fp32 and, at a
+    block's end, its gathered copy; float64 copies of ``XTX`` and the target while ``T`` is formed."""
+    from .inference_kernels import hip_kernel
+    from .utils import _dequantize_weight
+
+    K, size, _, g = codebooks.shape
+    out, ng, _ = prev_codes.shape
+    fin, dev = ng * g, reference.device
+    flat_books = codebooks.detach().reshape(K, size, g).contiguous()
+    flat_scales = None if scales is None else scales.detach().reshape(-1).contiguous()
+    wide = torch.float64
+    error = reference.to(wide) - _dequantize_weight(prev_codes.to(torch.int64) % size, codebooks.detach().to(wide),
+                                                    None if scales is None else scales.detach().to(wide))
+    T = error @ XTX.to(wide)
+    loss = (T * error).sum(-1).to(torch.float32)[None].contiguous()
+    T = T.to(torch.float32)[None]  # [P, out, in]
+    del error
+    blocks = XTX.reshape(ng, g, ng, g).diagonal(dim1=0, dim2=2).permute(2, 0, 1).contiguous()  # [ng, g, g]
+    books32 = flat_books.to(torch.float32)
+    q_all = torch.einsum("ksf,jfh,ksh->jks", books32, blocks, books32).contiguous()  # [ng, K, 256]
+    columns = (torch.tensor(list(group_order), dtype=torch.int64)[:, None] * g + torch.arange(g)[None, :]).flatten().to(dev)
+    history = []
+    block_groups = max(1, int(block_groups))
+    for start in range(0, ng, block_groups):
+        members = list(group_order[start:start + block_groups])
+        cols = columns[start * g:(start + len(members)) * g]
+        width = cols.numel()
+        x_rows = XTX.index_select(0, cols)  # [width, in]
+        x_block = x_rows.index_select(1, cols)  # [width, width]
+        t_block = T.index_select(2, cols)  # [P, out, width]
+        d_block = ancestor = None
+        for i, j in enumerate(members):
+            P = t_block.shape[0]
+            step = hip_kernel.code_search_kx8_xtx_step(t_block[:, :, i * g:(i + 1) * g], loss, prev_codes[None, :, j, :].expand(P, out, K).contiguous(),
+                                                       blocks[j], q_all[j], flat_books, flat_scales, beam_size, dim_order=dim_orders[start + i])
+            loss = step.loss
+            history.append((j, step.codes, step.source))
+            source = step.source.to(torch.int64)
+            wide_source = source[:, :, None].expand(-1, -1, width)
+            t_block = torch.gather(t_block, 0, wide_source)
+            t_block.view(-1, width).addmm_(step.delta.view(-1, g), x_block[i * g:(i + 1) * g], alpha=-1)
+            d_block = torch.zeros_like(t_block) if d_block is None else torch.gather(d_block, 0, wide_source)
+            d_block[:, :, i * g:(i + 1) * g] = step.delta
+            ancestor = source if ancestor is None else torch.gather(ancestor, 0, source)
+        if start + len(members) < ng:  # the columns outside the block: one gather and one GEMM for the whole block
+            T = torch.gather(T, 0, ancestor[:, :, None].expand(-1, -1, fin))
+            T.view(-1, fin).addmm_(d_block.view(-1, width), x_rows, alpha=-1)
+    new = prev_codes.clone()
+    position = torch.zeros((1, out), dtype=torch.int64, device=dev)
+    for j, codes, source in reversed(history):
+        new[:, j, :] = torch.gather(codes, 0, position[:, :, None].expand(-1, -1, K))[0]
+        position = torch.gather(source.to(torch.int64), 0, position)
+    return new
+
+
+def _permutation(values, n: int, what: str) -> List[int]:
+    got = [int(v) for v in values]
+    if sorted(got) != list(range(n)):
+        raise ValueError(f"find_optimal_codes_calibrated: {what} must be a permutation of 0 .. {n - 1}, got {got}")
+    return got
+
+
+@torch.no_grad()
+def find_optimal_codes_calibrated(XTX: torch.Tensor, reference_weight: torch.Tensor, codebooks: torch.Tensor, prev_codes: torch.Tensor,
+                                  scales: Optional[torch.Tensor], *, beam_size: int = 1, group_order: Optional[Sequence[int]] = None,
+                                  dim_order=None, **unsupported) -> torch.Tensor:
+    """New codes (shape, dtype and wrap-around form of ``prev_codes``) that lower ``||X W_ref^T - X W_q^T||^2`` for ``XTX = X^T X`` [in, in]
+    with ``codebooks`` [K, S, out_group_size, in_group_size] and ``scales`` ([out_groups, 1, 1, 1] or None) held fixed -- the reference's
+    ``beam_search_optimal_codes`` of src/beam_search_xtx.py, the search that PRODUCES an AQLM layer: the input groups are visited once
+    each in ``group_order`` (default 0 .. in_groups - 1), the codebooks of a group in ``dim_order`` (one permutation of 0 .. K - 1, or
+    one per visited group: the reference draws a fresh one per group), ``beam_size`` hypotheses per output group survive every step
+    and the best one is returned.  "No change" is always a candidate, so the objective (``calibrated_error``) never rises.
+
+    Routes: K x 8 layers (1 to 8 codebooks of 256 entries, g 8 / 16 / 32, ``out_group_size`` 1, ``beam_size`` up to 16) with every tensor
+    on the MI355X, codebooks and scales in one of fp16 / bf16, codes int8, ``XTX`` fp32 and a target in fp32 / fp16 / bf16 run
+    ``aqlm_hip_code_search_kx8_xtx`` once per input group (transient: ``T`` [beam_size, out, in] fp32, twice at the
+    end of every ``CALIBRATED_BLOCK_GROUPS`` groups); everything else -- 1x16, host tensors, fp32 / fp64 parameters, a float64
+    target (on the GPU too), ``out_group_size > 1``, ``beam_size > 16``, ``CODE_SEARCH_KERNEL = False`` -- runs a torch route written
+    from the reference's definition (float64 when the target is float64;
+    scores in chunks of ``CODE_SEARCH_CHUNK_VALUES``; the same transient in the compute dtype).  ``sparsity_regularizer`` raises
+    ``NotImplementedError``."""
+    if unsupported.pop("sparsity_regularizer", 0):
+        raise NotImplementedError("find_optimal_codes_calibrated: sparsity_regularizer is not offered")
+    if unsupported:
+        raise TypeError(f"find_optimal_codes_calibrated: unexpected arguments {sorted(unsupported)}")
+    if beam_size < 1:
+        raise ValueError("find_optimal_codes_calibrated: beam_size >= 1")
+    if prev_codes.dim() != 3 or codebooks.dim() != 4:
+        raise ValueError("find_optimal_codes_calibrated: codes are [out_groups, in_groups, K], codebooks [K, S, out_group_size, in_group_size]")
+    out_groups, in_groups, num_codebooks = prev_codes.shape
+    K, size, out_group_size, in_group_size = codebooks.shape
+    out_features, in_features = out_groups * out_group_size, in_groups * in_group_size
+    if K != num_codebooks or tuple(reference_weight.shape) != (out_features, in_features):
+        raise ValueError(f"find_optimal_codes_calibrated: codes {tuple(prev_codes.shape)}, codebooks {tuple(codebooks.shape)} and a target of "
+                         f"{tuple(reference_weight.shape)} do not describe one layer")
+    if tuple(XTX.shape) != (in_features, in_features):
+        raise ValueError(f"find_optimal_codes_calibrated: XTX must be [{in_features}, {in_features}], got {tuple(XTX.shape)}")
+    if scales is not None and scales.numel() != out_groups:
+        raise ValueError(f"find_optimal_codes_calibrated: scales must hold one factor per output group ({out_groups}), got {tuple(scales.shape)}")
+    groups = list(range(in_groups)) if group_order is None else _permutation(group_order, in_groups, "group_order")
+    if dim_order is None:
+        orders = [list(range(K))] * in_groups
+    else:
+        given = list(dim_order)
+        if given and (isinstance(given[0], (list, tuple)) or getattr(given[0], "ndim", 0) >= 1):
+            if len(given) != in_groups:
+                raise ValueError(f"find_optimal_codes_calibrated: dim_order holds {len(given)} permutations for {in_groups} input groups")
+            orders = [_permutation(one, K, "every dim_order") for one in given]
+        else:
+            orders = [_permutation(given, K, "dim_order")] * in_groups
+    nbits = int(math.log2(size))
+
+    tensors = [XTX, reference_weight, codebooks, prev_codes] + ([] if scales is None else [scales])
+    on_gpu = all(t.is_cuda for t in tensors)
+    dtypes_ok = (codebooks.dtype in (torch.float16, torch.bfloat16) and (scales is None or scales.dtype == codebooks.dtype)
+                 and prev_codes.dtype == torch.int8 and XTX.dtype == torch.float32
+                 and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16))
+    supported = False
+    if (CODE_SEARCH_KERNEL and on_gpu and 1 <= K <= 8 and nbits == 8 and out_group_size == 1 and in_group_size in (8, 16, 32)
+            and 1 <= beam_size <= 16):
+        from .inference_kernels import hip_kernel
+
+        supported = hip_kernel.code_search_kx8_xtx_supported(out_features, K, in_group_size, beam_size, beam_size)
+    if takes_code_search_kernel_kx8_xtx(K, nbits, out_group_size, in_group_size, beam_size, on_gpu, dtypes_ok, supported):
+        return _calibrated_codes_kernel(XTX, reference_weight, codebooks, prev_codes, scales, beam_size, groups, orders,
+                                        CALIBRATED_BLOCK_GROUPS).reshape(prev_codes.shape)
+
+    compute = torch.float64 if reference_weight.dtype == torch.float64 else torch.float32
+    found = _calibrated_codes_torch(XTX.to(compute), reference_weight.to(compute), codebooks.detach().to(compute),
+                                    prev_codes.to(torch.int64) % size, None if scales is None else scales.detach().to(compute),
+                                    beam_size, groups, orders, CODE_SEARCH_CHUNK_VALUES)
+    wrapped = torch.where(found >= size // 2, found - size, found) if prev_codes.dtype in (torch.int8, torch.int16) and nbits in (8, 16) \
+        else found
+    return wrapped.to(prev_codes.dtype).reshape(prev_codes.shape)
+
+
+@torch.no_grad()
+def update_codes_calibrated_(layer, reference_weight: torch.Tensor, XTX: torch.Tensor, **options) -> torch.Tensor:
+    """Re-choose the codes of ``layer`` (a ``QuantizedLinear``) against the dense target ``reference_weight`` [out, in] under the
+    calibration statistics ``XTX`` with ``find_optimal_codes_calibrated`` (same options) and write them IN PLACE, by the rules of
+    ``update_codes_``: dropped canonical codes come back first, inference tensors raise ``RuntimeError``, the version counter of
+    ``codes`` moves so that every derived copy is rebuilt at the layer's next call, and the experts of a ``QuantizedMixtralExperts``
+    block and ``ShardedQuantizedLinear`` raise ``TypeError``.  Returns the number of groups whose codes changed (a 0-dim tensor)."""
+    from .inference import QuantizedLinear
+    from .moe import QuantizedMixtralExperts
+    from .sharded import ShardedQuantizedLinear
+
+    if isinstance(layer, (QuantizedMixtralExperts, ShardedQuantizedLinear)) or getattr(layer, "_moe_expert", False):
+        raise TypeError(f"update_codes_calibrated_: {type(layer).__name__}{' (an expert of a QuantizedMixtralExperts block)' if getattr(layer, '_moe_expert', False) else ''}"
+                        " is outside the scope of the code update (as it is of make_trainable)")
+    if not isinstance(layer, QuantizedLinear):
+        raise TypeError(f"update_codes_calibrated_: expected a QuantizedLinear, got {type(layer).__name__}")
+    if options.get("sparsity_regularizer", 0):
+        raise NotImplementedError("update_codes_calibrated_: sparsity_regularizer is not offered")
+    layer.restore_canonical_codes()
+    codes = layer.codes
+    if codes.is_inference():
+        raise RuntimeError("update_codes_calibrated_: the codes of this layer are an inference tensor (the model was built or loaded under "
+                           "torch.inference_mode()); they cannot be written in place -- build the model outside inference mode")
+    new = find_optimal_codes_calibrated(XTX, reference_weight, layer.codebooks.detach(), codes.detach(), layer.scales.detach(), **options)
     changed = (new != codes).any(-1).sum()
     codes.copy_(new)
     return changed

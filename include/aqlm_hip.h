@@ -937,6 +937,55 @@ int aqlm_hip_code_search_kx8(const void* reference, int reference_dtype, long re
                              void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The CALIBRATED code search of the K x 8 schemes: one input group of the reference's src/beam_search_xtx.py, the beam search that
+ * minimises ||X W_ref^T - X W_q^T||^2 through XTX = X^T X, for every output row o of one layer; all K codebook steps of the group run
+ * in the launch.  With E_b = W_ref[o] - W_b[o] the error of beam position b and T_b = E_b XTX, the group's steps
+ * need only the slice t[b] = T_b[group] (g numbers), H = XTX[group, group] and q[c][s] = C_c[s] H C_c[s]^T (unscaled; the caller
+ * forms it).  Like aqlm_hip_code_search_kx8 the entry is held to ITS OWN ARITHMETIC bit for bit (tests/kx8_xtx_model.py restates it
+ * in numpy): every operation below is ONE IEEE fp32 operation rounded to nearest, no fused multiply-adds, sums over f ascending
+ * (acc = a_0 * b_0, then acc = acc + a_f * b_f).  For row o with scale s = float(scales[o]) (scales NULL: s = 1), 2s = 2 * s (exact),
+ * ss = s * s, the codebooks widened exactly to fp32, and P positions (positions_in at entry), position b holding loss L[b], slice
+ * t[b], the group's codes beam[b] (codes_in, the int8 mod 256), entry position src[b] = b and weight change d[b] = 0:
+ *     for each step c of dim_order (a permutation of 0 .. K - 1; NULL: 0, 1 .. K - 1), p = beam[b][c]:
+ *         w[b][f]  = s * C_c[p][f]
+ *         u[b][f'] = t[b][f'] + sum_f w[b][f] * H[f][f']
+ *         base[b]  = (L[b] + 2s * sum_f C_c[p][f] * u[b][f]) - ss * q[c][p]
+ *         S(b, s') = (base[b] - 2s * sum_f C_c[s'][f] * u[b][f]) + ss * q[c][s']          a result of -0 is replaced by +0
+ *         keep the best min(beam_size, P * 256) = beam_size hypotheses -- on EVERY step, the last one too: the reference returns
+ *         position 0 only at the end of its call -- ordered by (S, b * 256 + s') ascending: equal scores go to the smaller flat
+ *         index.  Rank i, from source position b with code s':
+ *             beam[i] = beam[b] with code c replaced by s';  src[i] = src[b];  L[i] = S(b, s')
+ *             dw[f]    = s * C_c[s'][f] - s * C_c[p][f]
+ *             d[i][f]  = d[b][f] + dw[f]
+ *             t[i][f'] = t[b][f'] - sum_f dw[f] * H[f][f']
+ *         (state follows the hypothesis: the reference re-dequantises every survivor)
+ *     loss_out [beam_size][out] fp32 = L;  codes_out [beam_size][out][K] int8 (128 .. 255 negative);  source [beam_size][out] uint8 = src,
+ *     the position AT ENTRY a hypothesis descends from;  delta [beam_size][out][g] fp32 = d, the group's new weights minus those of the
+ *     source position at entry, scaled (the caller owes T_b[other columns] -= delta XTX[group, other columns]);  t_out
+ *     [beam_size][out][g] fp32 (may be NULL) = t.  Rank 0 is the best.
+ * t: fp32 [positions_in][out][g] with element strides per position and per row (a view into a wider buffer works), g contiguous;
+ * loss fp32 [positions_in][out]; codes_in int8 [positions_in][out][K]; H fp32 [g][g] (not assumed symmetric); q fp32 [K][256];
+ * codebooks [K][256][g] fp16 / bf16, 16-byte aligned; scales [out] in the same dtype or NULL; dim_order in host memory or NULL.
+ * No address, LDS slot or source position is formed from a score: NaN / Inf in t, loss, H or q still give codes in 0 .. 255 and
+ * sources below positions_in, and cannot stall a loop.  One launch, stream-ordered, no allocation, no synchronisation, no global
+ * atomics, no scratch; aqlm_hip_code_search_kx8_xtx_workspace_bytes is 0 and `workspace` may be NULL: the output is a function of
+ * the arguments alone.
+ * Supported (aqlm_hip_code_search_kx8_xtx_supported): out >= 1, 1 <= K <= 8, g in {8, 16, 32}, 1 <= beam_size, positions_in <=
+ * AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM.
+ * Checks, in the order of aqlm_hip_code_search_kx8: a null pointer (scales, dim_order, t_out and workspace may be NULL); misalignment
+ * (codebooks 16 bytes, the others their element); out or g below 1, a row stride of t below g, or a position stride below g with
+ * several positions (AQLM_HIP_E_INVALID); dtype outside fp16 / bf16, K, g, beam_size or positions_in outside the supported set
+ * (AQLM_HIP_E_UNSUPPORTED); a dim_order that is no permutation (AQLM_HIP_E_INVALID).  Nothing is launched on bad arguments.
+ */
+int aqlm_hip_code_search_kx8_xtx_supported(int out_features, int num_codebooks, int in_group_size, int beam_size, int positions_in);
+size_t aqlm_hip_code_search_kx8_xtx_workspace_bytes(int out_features, int num_codebooks, int in_group_size, int beam_size); /* 0 */
+int aqlm_hip_code_search_kx8_xtx(const void* t, long t_position_stride, long t_row_stride, const void* loss, const void* codes_in,
+                                 const void* h, const void* q, const void* codebooks, int dtype, const void* scales, int out_features,
+                                 int num_codebooks, int in_group_size, int beam_size, int positions_in,
+                                 const int* dim_order /* host, NULL = natural */, void* loss_out, void* codes_out, void* source_out,
+                                 void* delta_out, void* t_out /* NULL ok */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the
