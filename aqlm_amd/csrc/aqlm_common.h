@@ -340,6 +340,18 @@ inline int check_group_size(const char* who, int in_group_size) {
   set_last_error("%s: only codebooks with 8 or 16 features are supported, got %d", who, in_group_size);
   return AQLM_HIP_E_UNSUPPORTED;
 }
+// x_row_stride of the dense forward entries (include/aqlm_hip.h, "input of the dense forward entries"), the one place that looks at its
+// sign.  One row has no stride: the argument is not read there and becomes in_features, so that it passes every later check and
+// selects no kernel.  At 2+ rows a negative stride is refused for every entry alike; 0 and overlapping rows are legal.
+inline int check_x_row_stride(const char* who, int batch, int in_features, long& x_row_stride) {
+  if (batch <= 1) {
+    x_row_stride = in_features;
+    return 0;
+  }
+  if (x_row_stride >= 0) return 0;
+  set_last_error("%s: negative x_row_stride %ld (rows of x)", who, x_row_stride);
+  return AQLM_HIP_E_INVALID;
+}
 
 template <int V>
 struct GroupSize {

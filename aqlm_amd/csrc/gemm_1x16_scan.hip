@@ -441,6 +441,7 @@ extern "C" int aqlm_hip_gemm_1x16_scan(const void* codes, const void* codebook, 
     set_last_error("aqlm_hip_gemm_1x16_scan: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemm_1x16_scan", batch, in_features, xs)) return e;
   if (in_features % 256 != 0 || !aligned16(codes) || !aligned16(codebook) || !aligned16(X) || xs % 8 != 0) {
     set_last_error("aqlm_hip_gemm_1x16_scan: needs in_features %% 256 == 0 (codebook vectors of 8) and 16-B aligned codes / codebook / X rows");
     return AQLM_HIP_E_UNSUPPORTED;

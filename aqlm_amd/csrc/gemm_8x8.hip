@@ -255,6 +255,7 @@ extern "C" int aqlm_hip_gemm_8x8_mfma(const void* codes, const void* codebooks, 
     set_last_error("aqlm_hip_gemm_8x8_mfma: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemm_8x8_mfma", batch, in_features, xs)) return e;
   if (in_features % 256 != 0 || in_features < 256 * E8_NW || !aligned16(codebooks) || !aligned16(X) || !aligned16(codes) || xs % 8 != 0) {
     set_last_error("aqlm_hip_gemm_8x8_mfma: needs in_features %% 256 == 0, >= %d, and 16-B aligned codes / codebooks / X rows", 256 * E8_NW);
     return AQLM_HIP_E_UNSUPPORTED;

@@ -1512,6 +1512,7 @@ extern "C" int aqlm_hip_gemm_kx8_mfma_ws(const void* codes, const void* codebook
     set_last_error("aqlm_hip_gemm_kx8_mfma: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemm_kx8_mfma", batch, in_features, xs)) return e;
   KxPlan probe{};
   if (!plan_kx8(std::min(batch, 128), out_features, in_features, probe) || !aligned16(codebooks) || !aligned16(X) || xs % 8 != 0) {
     set_last_error("aqlm_hip_gemm_kx8_mfma: needs in_features %% 128 == 0, >= 384, and 16-B aligned codebooks / X rows");
@@ -1651,6 +1652,7 @@ extern "C" int aqlm_hip_gemm_1x16_mfma(const void* codes, const void* codebook, 
     set_last_error("aqlm_hip_gemm_1x16_mfma: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemm_1x16_mfma", batch, in_features, xs)) return e;
   if (in_features % BK != 0 || !aligned16(codes) || !aligned16(codebook) || !aligned16(X) || xs % 8 != 0) {
     set_last_error("aqlm_hip_gemm_1x16_mfma: needs in_features %% 64 == 0 and 16-B aligned codes/codebook/X rows");
     return AQLM_HIP_E_UNSUPPORTED;
@@ -1744,42 +1746,52 @@ extern "C" int aqlm_hip_gemm_1x16_mfma(const void* codes, const void* codebook, 
       }
       continue;
     }
-    const GemmPlan g = plan_gemm(nb, out_features, in_features);
-    GemmParams p{};
-    p.codes = (const uint8_t*)codes;
-    p.codebook = (const uint8_t*)codebook;
-    p.X = (const uint16_t*)X + (long)b0 * xs;
-    p.partial = (float*)workspace;
-    p.M = out_features;
-    p.K = in_features;
-    p.B = nb;
-    p.Bpad = g.Bpad;
-    p.in_groups = in_features / in_group_size;
-    p.kslice = g.kslice;
-    p.ksplit = g.ksplit;
-    p.xs = xs;
-    p.cb_bytes = 65536 * in_group_size * 2;
-    p.x_bytes = (uint32_t)std::min<long>(((long)(nb - 1) * xs + in_features) * 2, 0xffffffffL);
-    int e;
-    if (dtype == AQLM_HIP_F16)
-      e = in_group_size == 8 ? launch_gemm<F16, 8>(p, g.nbt, stream) : launch_gemm<F16, 16>(p, g.nbt, stream);
-    else
-      e = in_group_size == 8 ? launch_gemm<BF16, 8>(p, g.nbt, stream) : launch_gemm<BF16, 16>(p, g.nbt, stream);
-    if (e) return e;
-    FinalizeParams f{};
-    f.partial = (const float*)workspace;
-    f.scales = (const uint16_t*)scales;
-    f.bias = (const uint16_t*)bias;
-    f.Y = (uint16_t*)Y + (long)b0 * ys;
-    f.M = out_features;
-    f.B = nb;
-    f.Bpad = g.Bpad;
-    f.ksplit = g.ksplit;
-    f.ys = ys;
-    dim3 grid((out_features + 31) / 32, g.nbt);
-    if (dtype == AQLM_HIP_F16) hipLaunchKernelGGL(gemm_finalize_kernel<F16>, grid, dim3(256), 0, stream, f);
-    else hipLaunchKernelGGL(gemm_finalize_kernel<BF16>, grid, dim3(256), 0, stream, f);
-    if (int e2 = check_hip(hipGetLastError(), "gemm_finalize launch")) return e2;
+    // The register-staged kernel forms a row's X offset in 32 bits behind a bounds-checked descriptor of x_bytes.  A slab whose extent
+    // ((rows - 1) * xs + in_features) * 2 passes 2^32 (xs above ~2^24 at 128 rows) is cut into sub-slabs whose extent fits, down to
+    // single rows, X and Y rebased per sub-slab.  The extent stays <= 0xfffffff0: the kernel reads zeros for k past its slice at
+    // offset 0xfffffff0, which the descriptor range-checks dword by dword, so a larger extent would let those loads see memory.
+    // The K split is the plan's whatever the rows (plan_gemm takes it from M and K), so a row's bits do not depend on the cut; at
+    // ordinary strides there is one sub-slab and the launch is what it always was.
+    const long sub_max = xs > 0 ? std::max<long>(1, ((0xfffffff0L / 2 - in_features) / xs) + 1) : nb;
+    for (int s0 = 0; s0 < nb; s0 += (int)std::min<long>(sub_max, nb)) {
+      const int ns = (int)std::min<long>(sub_max, nb - s0);
+      const GemmPlan g = plan_gemm(ns, out_features, in_features);
+      GemmParams p{};
+      p.codes = (const uint8_t*)codes;
+      p.codebook = (const uint8_t*)codebook;
+      p.X = (const uint16_t*)X + (long)(b0 + s0) * xs;
+      p.partial = (float*)workspace;
+      p.M = out_features;
+      p.K = in_features;
+      p.B = ns;
+      p.Bpad = g.Bpad;
+      p.in_groups = in_features / in_group_size;
+      p.kslice = g.kslice;
+      p.ksplit = g.ksplit;
+      p.xs = xs;
+      p.cb_bytes = 65536 * in_group_size * 2;
+      p.x_bytes = (uint32_t)std::min<long>(((long)(ns - 1) * xs + in_features) * 2, 0xffffffffL);
+      int e;
+      if (dtype == AQLM_HIP_F16)
+        e = in_group_size == 8 ? launch_gemm<F16, 8>(p, g.nbt, stream) : launch_gemm<F16, 16>(p, g.nbt, stream);
+      else
+        e = in_group_size == 8 ? launch_gemm<BF16, 8>(p, g.nbt, stream) : launch_gemm<BF16, 16>(p, g.nbt, stream);
+      if (e) return e;
+      FinalizeParams f{};
+      f.partial = (const float*)workspace;
+      f.scales = (const uint16_t*)scales;
+      f.bias = (const uint16_t*)bias;
+      f.Y = (uint16_t*)Y + (long)(b0 + s0) * ys;
+      f.M = out_features;
+      f.B = ns;
+      f.Bpad = g.Bpad;
+      f.ksplit = g.ksplit;
+      f.ys = ys;
+      dim3 grid((out_features + 31) / 32, g.nbt);
+      if (dtype == AQLM_HIP_F16) hipLaunchKernelGGL(gemm_finalize_kernel<F16>, grid, dim3(256), 0, stream, f);
+      else hipLaunchKernelGGL(gemm_finalize_kernel<BF16>, grid, dim3(256), 0, stream, f);
+      if (int e2 = check_hip(hipGetLastError(), "gemm_finalize launch")) return e2;
+    }
   }
   return 0;
 }

@@ -315,6 +315,7 @@ extern "C" int aqlm_hip_gemv_1x16(const void* codes, const void* codebook, const
   if (int e = validate_common(codes, codebook, scales, x, y, out_features, in_features, in_group_size, batch, dtype,
                               "aqlm_hip_gemv_1x16"))
     return e;
+  if (int e = check_x_row_stride("aqlm_hip_gemv_1x16", batch, in_features, xs)) return e;
   if (in_group_size != 8 && in_group_size != 16) {
     // mirrors cuda_kernel.cpp:136-145
     set_last_error("aqlm_hip_gemv_1x16: only codebooks with 8 or 16 features are supported, got %d", in_group_size);
@@ -373,6 +374,7 @@ extern "C" int aqlm_hip_gemv_1x16_multi(const aqlm_hip_segment* segments, int nu
     total_rows += sg.out_features;
     fast = fast && aligned16(sg.codes) && aligned16(sg.codebook);
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemv_1x16_multi", batch, in_features, xs)) return e;
   if (in_group_size != 8 && in_group_size != 16) {
     set_last_error("aqlm_hip_gemv_1x16_multi: only codebooks with 8 or 16 features are supported, got %d", in_group_size);
     return AQLM_HIP_E_UNSUPPORTED;
@@ -475,6 +477,7 @@ extern "C" int aqlm_hip_gemv_kx8(const void* codes, const void* codebooks, const
   if (int e = validate_common(codes, codebooks, scales, x, y, out_features, in_features, in_group_size, batch, dtype,
                               "aqlm_hip_gemv_kx8"))
     return e;
+  if (int e = check_x_row_stride("aqlm_hip_gemv_kx8", batch, in_features, xs)) return e;
   if (num_codebooks < 1 || num_codebooks > 16) {
     set_last_error("aqlm_hip_gemv_kx8: num_codebooks %d outside 1..16", num_codebooks);
     return AQLM_HIP_E_UNSUPPORTED;
@@ -551,6 +554,7 @@ extern "C" int aqlm_hip_gemv_generic(const void* codes, const void* codebooks, c
   if (int e = validate_common(codes, codebooks, scales, x, y, out_features, in_features, in_group_size, batch, dtype,
                               "aqlm_hip_gemv_generic"))
     return e;
+  if (int e = check_x_row_stride("aqlm_hip_gemv_generic", batch, in_features, xs)) return e;
   if (nbits < 1 || nbits > 16 || num_codebooks < 1) {
     set_last_error("aqlm_hip_gemv_generic: nbits %d / num_codebooks %d unsupported", nbits, num_codebooks);
     return AQLM_HIP_E_UNSUPPORTED;
@@ -577,6 +581,7 @@ extern "C" int aqlm_hip_gemv_kx8_multi(const aqlm_hip_segment* segments, int num
     total_rows += sg.out_features;
     aligned = aligned && aligned16(sg.codes) && aligned16(sg.codebook);
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemv_kx8_multi", batch, in_features, xs)) return e;
   if (num_codebooks < 1 || num_codebooks > 16) {
     set_last_error("aqlm_hip_gemv_kx8_multi: num_codebooks %d outside 1..16", num_codebooks);
     return AQLM_HIP_E_UNSUPPORTED;

@@ -830,8 +830,9 @@ static int lut_entry(const char* name, const void* codes, const void* codebooks,
     set_last_error("%s: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", name, dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  if (int e = check_x_row_stride(name, batch, in_features, x_row_stride)) return e;
   if (!aligned16(codebooks) || !aligned16(x) || (reinterpret_cast<uintptr_t>(codes) & 7u)) {
-    set_last_error("%s: misaligned buffer", name);
+    set_last_error("%s: misaligned buffer (codebooks and x 16-B, codes 8-B aligned)", name);
     return AQLM_HIP_E_UNSUPPORTED;
   }
   const int e = gemv_8x8_lut(codes, codebooks, scales, bias, x, y, out_features, in_features, in_group_size, dtype,
@@ -839,7 +840,7 @@ static int lut_entry(const char* name, const void* codes, const void* codebooks,
   if (e == AQLM_HIP_E_UNSUPPORTED) set_last_error("%s: in_group_size %d not in {8,16,32}", name, in_group_size);
   if (e == AQLM_HIP_E_INVALID)
     set_last_error("%s: workspace / cells too small (batch x out_features x 8 bytes), null or misaligned, a planar fused call without a "
-                   "positive codebook_absmax, or batch outside 1..%d / x rows not 16-B aligned", name, AQLM_HIP_MAX_GEMV_BATCH);
+                   "positive codebook_absmax, or batch outside 1..%d / x rows not 16-B aligned / x_row_stride >= 2^31", name, AQLM_HIP_MAX_GEMV_BATCH);
   return e;
 }
 

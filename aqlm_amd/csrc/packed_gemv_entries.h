@@ -215,7 +215,7 @@ static int packed_launch_main(const PackedLayout& L, const void* packed, const v
 }
 
 static int packed_check_args(const char* who, const aqlm_hip_packed_desc* desc, const void* packed, const void* codebook,
-                             const void* x, int batch, long x_row_stride, int dtype, PackedLayout& L, int& max_b) {
+                             const void* x, int batch, long& x_row_stride, int dtype, PackedLayout& L, int& max_b) {
   if (!packed || !codebook || !x || !desc) {
     set_last_error("%s: null pointer argument", who);
     return AQLM_HIP_E_INVALID;
@@ -228,6 +228,7 @@ static int packed_check_args(const char* who, const aqlm_hip_packed_desc* desc, 
     set_last_error("%s: invalid packed descriptor", who);
     return AQLM_HIP_E_INVALID;
   }
+  if (int e = check_x_row_stride(who, batch, desc->in_features, x_row_stride)) return e;
   if (batch < 1 || batch > AQLM_HIP_MAX_GEMV_BATCH || !aligned16(packed) || !aligned16(codebook) || !aligned16(x) ||
       (batch > 1 && x_row_stride % 8 != 0)) {
     set_last_error("%s: batch must be 1..%d and packed / codebook / x rows 16-B aligned (batch %d)", who,
@@ -494,6 +495,7 @@ static int gemv_1x16_packed_multi_impl(const aqlm_hip_segment* segments, const a
                    dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  if (int e = check_x_row_stride("aqlm_hip_gemv_1x16_packed_multi", batch, in_features, x_row_stride)) return e;
   if (batch < 1 || batch > AQLM_HIP_MAX_GEMV_BATCH || !aligned16(x) || (batch > 1 && x_row_stride % 8 != 0)) {
     set_last_error("aqlm_hip_gemv_1x16_packed_multi: batch must be 1..%d with 16-B aligned rows (batch %d)",
                    AQLM_HIP_MAX_GEMV_BATCH, batch);

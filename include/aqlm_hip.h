@@ -33,6 +33,23 @@
  *     side by side in one buffer (q / k / v).  A workspace is used only up to the advertised size (aqlm_hip_workspace_bytes,
  *     aqlm_hip_gemm_1x16_scan_workspace_bytes) and accumulator cells only up to batch x out_features x 8 bytes; nothing behind them is
  *     written (tests/test_y_layout_gpu.py);
+ *   - input of the same dense forward entries: exactly the batch windows [b * x_row_stride, b * x_row_stride + in_features) of x are
+ *     read and nothing else of it.  Any x_row_stride >= in_features is legal, and so are 0 (every row is row 0) and
+ *     0 < x_row_stride < in_features (overlapping rows), as long as the alignment rule below holds.  A negative x_row_stride at
+ *     batch > 1 is AQLM_HIP_E_INVALID on every entry, refused by one shared check before anything is launched.  At batch == 1
+ *     x_row_stride is not read and selects no kernel: any value gives the result of x_row_stride == in_features.
+ *     Alignment: aqlm_hip_gemv_1x16 / _kx8 / _generic and aqlm_hip_gemv_1x16_multi / _kx8_multi accept any 2-byte aligned x and any
+ *     stride; an x that is not 16-byte aligned, or at batch > 1 a stride that is no multiple of 8, takes the generic kernel (the
+ *     bits of the same call under the tuning key force_generic).  Every other entry needs a 16-byte aligned x and, at batch > 1,
+ *     x_row_stride % 8 == 0; otherwise it writes nothing to y, names x in the message and returns AQLM_HIP_E_UNSUPPORTED
+ *     (aqlm_hip_gemm_1x16_mfma, aqlm_hip_gemm_1x16_scan, aqlm_hip_gemm_kx8_mfma[_ws], aqlm_hip_gemm_8x8_mfma, and the
+ *     aqlm_hip_gemv_8x8_lut* matvecs for the pointer) or AQLM_HIP_E_INVALID (the aqlm_hip_gemv_1x16_packed* matvecs; the stride of
+ *     aqlm_hip_gemv_8x8_lut_batch, which must also be below 2^31).
+ *     Routing: a row's value does not depend on x_row_stride; its bits may, because the route does.  The K x 8 entries
+ *     (aqlm_hip_gemm_kx8_mfma[_ws], and through them aqlm_hip_gemv_kx8 from kx8_mfma_min_rows rows and aqlm_hip_gemv_kx8_multi) take the X-resident
+ *     kernel only for 0 < x_row_stride < 2^22 and the phased kernel only for 0 < x_row_stride < 2^21; at 0 and from those limits on
+ *     the streaming kernel runs (the bits of the same call under kx8_xres 0).  Every other entry gives the same bits at every legal
+ *     stride, up to rows that lie more than 4 GiB behind x (tests/test_x_layout_gpu.py);
  *   - return 0 on success; a positive value is a hipError_t from the launch; negative values are
  *     AQLM_HIP_E_*.  aqlm_hip_last_error() returns a thread-local human-readable message.
  */
