@@ -296,8 +296,24 @@ int run(const void* codes, const void* codebook, const void* scales, const void*
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool aligned2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0; }
 // an id array (int64 or int32) is aligned to its element
 inline bool ids_aligned(const void* ids, int ids_int64) { return (reinterpret_cast<uintptr_t>(ids) & (ids_int64 ? 7u : 3u)) == 0; }
+// the reference of the code searches (fp16, bf16 or fp32) is aligned to its element; element `idx` of it as fp32
+inline bool ref_aligned(const void* p, int dtype) { return dtype == AQLM_HIP_F32 ? aligned4(p) : aligned2(p); }
+__device__ __forceinline__ float load_ref(const void* p, size_t idx, int dtype) {
+  if (dtype == AQLM_HIP_F32) return reinterpret_cast<const float*>(p)[idx];
+  const uint16_t u = reinterpret_cast<const uint16_t*>(p)[idx];
+  return dtype == AQLM_HIP_BF16 ? BF16::to_float(u) : F16::to_float(u);
+}
+// dW and the outputs of the gradient kernels: fp16, bf16 or fp32
+inline bool dw_dtype_ok(int dtype) { return dtype == AQLM_HIP_F16 || dtype == AQLM_HIP_BF16 || dtype == AQLM_HIP_F32; }
+inline size_t dtype_bytes(int dtype) { return dtype == AQLM_HIP_F32 ? 4 : 2; }
+// the 16 bits of an fp16 / bf16 scale as fp32, for kernels that are not instantiated per scale dtype
+__device__ __forceinline__ float half_bits_to_float(uint32_t u16, int is_bf16) {
+  return is_bf16 ? __uint_as_float(u16 << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)u16);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that the indexed entry points share (routed, routed packed, bucket, grouped, transposed, LoRA).  Each sets the

@@ -44,12 +44,6 @@ static __device__ __forceinline__ cs_f32x16 cs_mfma(const u32x4& a, const u32x4&
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cs_bf16x8, a), __builtin_bit_cast(cs_bf16x8, b), c, 0, 0, 0);
 }
 
-static __device__ __forceinline__ float cs_load_ref(const void* p, size_t idx, int dtype) {
-  if (dtype == AQLM_HIP_F32) return reinterpret_cast<const float*>(p)[idx];
-  const uint16_t u = reinterpret_cast<const uint16_t*>(p)[idx];
-  return dtype == AQLM_HIP_BF16 ? BF16::to_float(u) : F16::to_float(u);
-}
-
 // |C_c|^2 in fp32: fused multiply-adds over t ascending from 0
 template <class T, int G>
 __global__ __launch_bounds__(kCsThreads) void code_search_norms_kernel(const uint16_t* __restrict__ codebook, float* __restrict__ norms) {
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(kCsThreads) void code_search_1x16_kernel(CodeSearch
       const size_t base = (size_t)o * (size_t)a.ref_stride + (size_t)j * G;
 #pragma unroll
       for (int e = 0; e < G; ++e) {
-        const float x = cs_load_ref(a.reference, base + e, a.ref_dtype);
+        const float x = load_ref(a.reference, base + e, a.ref_dtype);
         r[e] = a.scales ? x / s : x;  // IEEE division (correctly rounded: the compiler's default for HIP), as the definition divides
         const float ax = __builtin_fabsf(r[e]);
         bad = bad || !(ax < __builtin_inff());  // Inf or NaN
@@ -248,7 +242,6 @@ static bool cs_shape_ok(int out_features, int in_features, int g) {
   if (out_features < 1 || in_features < 1 || (g != 8 && g != 16) || in_features % g != 0) return false;
   return (long)out_features * (long)(in_features / g) <= AQLM_HIP_CODE_SEARCH_MAX_GROUPS;
 }
-static bool cs_ref_aligned(const void* p, int dt) { return (reinterpret_cast<uintptr_t>(p) & (dt == AQLM_HIP_F32 ? 3u : 1u)) == 0; }
 
 }  // namespace aqlm
 
@@ -271,7 +264,7 @@ extern "C" int aqlm_hip_code_search_1x16(const void* reference, int reference_dt
   if (int e = check_not_null(who, reference && codebook && codes_out && workspace)) return e;
   const bool ids_ok = !group_ids || ids_aligned(group_ids, group_ids_int64);
   if (int e = check_aligned(who, "reference / scales / codebook / group_ids / codes_out / workspace",
-                            cs_ref_aligned(reference, reference_dtype) && (reinterpret_cast<uintptr_t>(scales) & 1u) == 0 && aligned16(codebook) &&
+                            ref_aligned(reference, reference_dtype) && (reinterpret_cast<uintptr_t>(scales) & 1u) == 0 && aligned16(codebook) &&
                                 ids_ok && (reinterpret_cast<uintptr_t>(codes_out) & 1u) == 0 && aligned16(workspace)))
     return e;
   if (int e = check_sizes(who, out_features, in_features, in_group_size)) return e;

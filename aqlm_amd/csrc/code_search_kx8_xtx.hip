@@ -6,7 +6,7 @@
 // H = XTX[group, group] and q_c[s] = C_c[s] H C_c[s]^T; what the group's change does to the other columns of T_b is the caller's
 // (`delta`).  The entry is held to ITS OWN ARITHMETIC bit for bit (tests/kx8_xtx_model.py restates it in numpy): every product and
 // every sum below is one IEEE fp32 operation, so this translation unit switches contraction off and passes every product through
-// kxx_mul.
+// kxb_mul (kx8_beam.h, which holds everything this kernel shares with code_search_kx8.hip).
 //
 //   work       one wave (a workgroup of 64 threads) per output row, grid-stride over the rows; lane l owns the candidates
 //              s = 4 l .. 4 l + 3 of the step's codebook, widened into registers once per step.
@@ -15,28 +15,15 @@
 //              (the reference re-dequantises every hypothesis: state follows the hypothesis, not the position).
 //   scores     S(b, s) = (base[b] - 2 scale dot(C_c[s], u[b])) + scale^2 q_c[s]: 4 * positions values per lane, kept in registers as
 //              order-preserving unsigned integers (a score of -0 is stored as +0 first).
-//   selection  by the 64-bit key (score bits, b * 256 + s), as in code_search_kx8.hip (the helpers are copies: that file is
-//              untouched).  The index half of a key is built from lane and loop counters alone, LDS slots from lane counts, and a
-//              source position is clamped to the positions that exist: no address is ever formed from a score.
+//   selection  kx8_select_body.h: the best `keep` 64-bit keys (score bits, b * 256 + s) in order, with their scores; its comment has
+//              the two ways and why no address is ever formed from a score.  A source position is clamped to the positions that
+//              exist.
 // No global atomics, no scratch, no workspace; the output is a function of the arguments alone.
-#include "aqlm_common.h"
+#include "kx8_beam.h"
 
 #pragma clang fp contract(off)
 
 namespace aqlm {
-
-// A product that the sum after it cannot absorb (see kxs_mul of code_search_kx8.hip: the library's -ffp-contract=fast fuses in the
-// code generator whatever the pragma says; a product that went through an empty asm operand is no product to it).
-static __device__ __forceinline__ float kxx_mul(float a, float b) {
-  float p = a * b;
-  asm("" : "+v"(p));
-  return p;
-}
-
-constexpr int kKxxEntries = 256;
-constexpr int kKxxMaxBooks = 8;
-constexpr int kKxxPerLane = kKxxEntries / WAVE;  // candidates per lane: 4
-constexpr unsigned kKxxMaxBlocks = 256 * 32;     // grid-stride above this
 
 struct Kx8XtxArgs {
   const float* t;             // [positions_in][out][g], strided
@@ -56,47 +43,13 @@ struct Kx8XtxArgs {
   int num_codebooks;
   int beam;
   int positions_in;
-  signed char order[kKxxMaxBooks];
+  signed char order[kKxbMaxBooks];
 };
 
-// fp32 bits <-> unsigned integers in the order of the floats; -0 becomes +0 first, so that equal floats have equal keys
-static __device__ __forceinline__ uint32_t kxx_ordered(float s) {
-  uint32_t b = __float_as_uint(s);
-  b = b == 0x80000000u ? 0u : b;
-  return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
-}
-static __device__ __forceinline__ float kxx_unordered(uint32_t u) {
-  return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-}
-
-template <int CTRL>
-static __device__ __forceinline__ uint64_t kxx_dpp_min(uint64_t v) {
-  const uint64_t o = ((uint64_t)dpp_u32<CTRL>((uint32_t)(v >> 32)) << 32) | dpp_u32<CTRL>((uint32_t)v);
-  return o < v ? o : v;
-}
-static __device__ __forceinline__ uint64_t kxx_wave_min(uint64_t v) {
-  v = kxx_dpp_min<0xB1>(v);
-  v = kxx_dpp_min<0x4E>(v);
-  v = kxx_dpp_min<0x141>(v);
-  v = kxx_dpp_min<0x140>(v);
-  uint64_t r[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    r[i] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 16 * i) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 16 * i);
-  const uint64_t x = r[0] < r[1] ? r[0] : r[1], y = r[2] < r[3] ? r[2] : r[3];
-  return x < y ? x : y;
-}
-static __device__ __forceinline__ uint32_t kxx_wave_min_u32(uint32_t v) {
-  uint32_t o;
-  o = dpp_u32<0xB1>(v);  v = o < v ? o : v;
-  o = dpp_u32<0x4E>(v);  v = o < v ? o : v;
-  o = dpp_u32<0x141>(v); v = o < v ? o : v;
-  o = dpp_u32<0x140>(v); v = o < v ? o : v;
-  const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-  const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-  const uint32_t a = r0 < r1 ? r0 : r1, b = r2 < r3 ? r2 : r3;
-  return a < b ? a : b;
+// equal floats must have equal keys: a score of -0 enters kxb_ordered as +0 (a test of the bit pattern, as the scores are integers next)
+static __device__ __forceinline__ float kxx_plus_zero(float s) {
+  const uint32_t b = __float_as_uint(s);
+  return __uint_as_float(b == 0x80000000u ? 0u : b);
 }
 
 // T: the codebook dtype, G: the group size, PMAX: the beam positions the registers and LDS are laid out for
@@ -111,7 +64,7 @@ __global__ __launch_bounds__(WAVE) void code_search_kx8_xtx_kernel(Kx8XtxArgs a)
   __shared__ float base[PMAX];
   __shared__ uint32_t win[PMAX];   // the flat index b * 256 + s of rank i
   __shared__ uint32_t wins[PMAX];  // its score, as an ordered integer
-  __shared__ uint8_t beams[2][PMAX][kKxxMaxBooks];
+  __shared__ uint8_t beams[2][PMAX][kKxbMaxBooks];
   __shared__ uint8_t src[2][PMAX];
   __shared__ uint64_t cand[WAVE];
   const int lane = threadIdx.x;
@@ -120,13 +73,13 @@ __global__ __launch_bounds__(WAVE) void code_search_kx8_xtx_kernel(Kx8XtxArgs a)
   const int e_own = lane & (G - 1);  // the element this lane serves in every element-wise pass (G divides 64)
   if (keep > PMAX || a.positions_in > PMAX) return;  // (the launcher picks PMAX >= both; a guard for the LDS arrays, wave-uniform)
 
-  auto entry = [&](int c, int code, int e) { return T::to_float(a.codebooks[((size_t)c * kKxxEntries + (size_t)code) * G + e]); };
+  auto entry = [&](int c, int code, int e) { return T::to_float(a.codebooks[((size_t)c * kKxbEntries + (size_t)code) * G + e]); };
 
   for (int idx = lane; idx < G * G; idx += WAVE) hm[idx / G][idx % G] = a.h[idx];
 
   for (long o = blockIdx.x; o < a.out; o += gridDim.x) {
     const float s = a.scales ? T::to_float(a.scales[o]) : 1.0f;
-    const float two_s = kxx_mul(2.0f, s), ss = kxx_mul(s, s);
+    const float two_s = kxb_mul(2.0f, s), ss = kxb_mul(s, s);
     int P = a.positions_in, cur = 0;
     for (int idx = lane; idx < P * G; idx += WAVE) {
       const int b = idx / G;
@@ -150,141 +103,52 @@ __global__ __launch_bounds__(WAVE) void code_search_kx8_xtx_kernel(Kx8XtxArgs a)
       // ---- w[b] = scale * C_c[beam[b][c]] ----
       for (int idx = lane; idx < P * G; idx += WAVE) {
         const int b = idx / G;
-        wb[b][e_own] = kxx_mul(s, entry(c, beams[cur][b][c], e_own));
+        wb[b][e_own] = kxb_mul(s, entry(c, beams[cur][b][c], e_own));
       }
       // ---- the lane's four candidates, widened, and their scaled q ----
-      float cw[kKxxPerLane][G];
-      {
-        const u32x4* from = reinterpret_cast<const u32x4*>(a.codebooks + ((size_t)c * kKxxEntries + (size_t)kKxxPerLane * lane) * G);
+      float cw[kKxbPerLane][G];
+      kxb_load_candidates<T, G>(a.codebooks, c, lane, cw);
+      float sq[kKxbPerLane];
 #pragma unroll
-        for (int q = 0; q < kKxxPerLane; ++q)
-#pragma unroll
-          for (int p = 0; p < G / 8; ++p) {
-            const u32x4 w = from[q * (G / 8) + p];
-            cw[q][8 * p + 0] = T::lo(w.x); cw[q][8 * p + 1] = T::hi(w.x);
-            cw[q][8 * p + 2] = T::lo(w.y); cw[q][8 * p + 3] = T::hi(w.y);
-            cw[q][8 * p + 4] = T::lo(w.z); cw[q][8 * p + 5] = T::hi(w.z);
-            cw[q][8 * p + 6] = T::lo(w.w); cw[q][8 * p + 7] = T::hi(w.w);
-          }
-      }
-      float sq[kKxxPerLane];
-#pragma unroll
-      for (int q = 0; q < kKxxPerLane; ++q) sq[q] = kxx_mul(ss, a.q[(size_t)c * kKxxEntries + kKxxPerLane * lane + q]);
+      for (int q = 0; q < kKxbPerLane; ++q) sq[q] = kxb_mul(ss, a.q[(size_t)c * kKxbEntries + kKxbPerLane * lane + q]);
       __syncthreads();
       // ---- u[b][f'] = t[b][f'] + sum_f w[b][f] H[f][f'] ----
       for (int idx = lane; idx < P * G; idx += WAVE) {
         const int b = idx / G;
-        float acc = kxx_mul(wb[b][0], hm[0][e_own]);
-        for (int f = 1; f < G; ++f) acc = acc + kxx_mul(wb[b][f], hm[f][e_own]);
+        float acc = kxb_mul(wb[b][0], hm[0][e_own]);
+        for (int f = 1; f < G; ++f) acc = acc + kxb_mul(wb[b][f], hm[f][e_own]);
         uu[b][e_own] = tt[cur][b][e_own] + acc;
       }
       __syncthreads();
       // ---- base[b] = (L[b] + 2 scale <P, u[b]>) - scale^2 q_c[p] ----
       if (lane < P) {
         const int p = beams[cur][lane][c];
-        float acc = kxx_mul(entry(c, p, 0), uu[lane][0]);
-        for (int f = 1; f < G; ++f) acc = acc + kxx_mul(entry(c, p, f), uu[lane][f]);
-        base[lane] = (ls[cur][lane] + kxx_mul(two_s, acc)) - kxx_mul(ss, a.q[(size_t)c * kKxxEntries + p]);
+        float acc = kxb_mul(entry(c, p, 0), uu[lane][0]);
+        for (int f = 1; f < G; ++f) acc = acc + kxb_mul(entry(c, p, f), uu[lane][f]);
+        base[lane] = (ls[cur][lane] + kxb_mul(two_s, acc)) - kxb_mul(ss, a.q[(size_t)c * kKxbEntries + p]);
       }
       __syncthreads();
 
       // ---- scores: 4 per position, as ordered integers ----
-      uint32_t u[PMAX * kKxxPerLane];
+      uint32_t u[PMAX * kKxbPerLane];
 #pragma unroll
-      for (int k = 0; k < PMAX * kKxxPerLane; ++k) u[k] = 0xffffffffu;
+      for (int k = 0; k < PMAX * kKxbPerLane; ++k) u[k] = 0xffffffffu;
 #pragma unroll
       for (int b = 0; b < PMAX; ++b) {
         if (b < P) {  // wave-uniform
-          const float4* up = reinterpret_cast<const float4*>(uu[b]);
-          float acc[kKxxPerLane];
-#pragma unroll
-          for (int p = 0; p < G / 4; ++p) {
-            const float4 uv = up[p];
-            const float ue[4] = {uv.x, uv.y, uv.z, uv.w};
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-              for (int q = 0; q < kKxxPerLane; ++q) {
-                const float prod = kxx_mul(cw[q][4 * p + t], ue[t]);
-                acc[q] = (p == 0 && t == 0) ? prod : acc[q] + prod;
-              }
-          }
+          float acc[kKxbPerLane];
+          kxb_dot4<G>(uu[b], cw, acc);
           const float bb = base[b];
 #pragma unroll
-          for (int q = 0; q < kKxxPerLane; ++q) u[b * kKxxPerLane + q] = kxx_ordered((bb - kxx_mul(two_s, acc[q])) + sq[q]);
+          for (int q = 0; q < kKxbPerLane; ++q) u[b * kKxbPerLane + q] = kxb_ordered(kxx_plus_zero((bb - kxb_mul(two_s, acc[q])) + sq[q]));
         }
       }
 
-      // ---- the best `keep` keys, in order (code_search_kx8.hip explains the two ways) ----
+      // ---- the best `keep` keys, in order, and their scores ----
       bool rounds = keep == 1;
-      if (!rounds) {
-        uint32_t mine = 0xffffffffu;
-#pragma unroll
-        for (int b = 0; b < PMAX; ++b) {
-          if (b < P) {
-#pragma unroll
-            for (int q = 0; q < kKxxPerLane; ++q) mine = u[b * kKxxPerLane + q] < mine ? u[b * kKxxPerLane + q] : mine;
-          }
-        }
-        uint32_t bound = 0;
-        for (int r = 0; r < keep; ++r) {
-          bound = kxx_wave_min_u32(mine);
-          const unsigned long long at = __builtin_amdgcn_ballot_w64(mine == bound);
-          if (lane == (int)__builtin_ctzll(at | (1ull << 63))) mine = 0xffffffffu;
-        }
-        int n = 0;  // wave-uniform
-#pragma unroll
-        for (int b = 0; b < PMAX; ++b) {
-          if (b < P) {
-#pragma unroll
-            for (int q = 0; q < kKxxPerLane; ++q) {
-              const bool in = u[b * kKxxPerLane + q] <= bound;
-              const unsigned long long set = __builtin_amdgcn_ballot_w64(in);
-              if (set != 0) {  // wave-uniform
-                const int at = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(set >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)set, 0u));
-                if (in && at < WAVE)
-                  cand[at] = ((uint64_t)u[b * kKxxPerLane + q] << 32) | (uint32_t)(b * kKxxEntries + kKxxPerLane * lane + q);
-                n += (int)__builtin_popcountll(set);
-              }
-            }
-          }
-        }
-        if (n > WAVE || n < keep) {  // (n < keep cannot happen: `keep` lanes hold a key within the bound)
-          rounds = true;
-        } else {
-          __syncthreads();
-          const uint64_t key = lane < n ? cand[lane] : ~0ull;
-          int rank = 0;
-          for (int i = 0; i < n; ++i) rank += cand[i] < key ? 1 : 0;  // keys are distinct (their index halves are): so are the ranks
-          if (lane < n && rank < keep) {
-            win[rank] = (uint32_t)key;
-            wins[rank] = (uint32_t)(key >> 32);
-          }
-        }
-      }
-      if (rounds) {
-        uint64_t taken = 0;
-        for (int r = 0; r < keep; ++r) {
-          uint64_t best = ~0ull;
-#pragma unroll
-          for (int b = 0; b < PMAX; ++b) {
-            if (b < P) {
-#pragma unroll
-              for (int q = 0; q < kKxxPerLane; ++q) {
-                const uint64_t key = ((uint64_t)u[b * kKxxPerLane + q] << 32) | (uint32_t)(b * kKxxEntries + kKxxPerLane * lane + q);
-                const bool ok = (r == 0 || key > taken) && key < best;
-                best = ok ? key : best;
-              }
-            }
-          }
-          best = kxx_wave_min(best);
-          taken = best;
-          if (lane == 0) {
-            win[r] = (uint32_t)best;
-            wins[r] = (uint32_t)(best >> 32);
-          }
-        }
-      }
+#define KXB_SELECT_SCORES 1
+#include "kx8_select_body.h"
+#undef KXB_SELECT_SCORES
       __syncthreads();
 
       // ---- rank i descends from its source position: codes, entry position, loss, weight change ----
@@ -299,14 +163,14 @@ __global__ __launch_bounds__(WAVE) void code_search_kx8_xtx_kernel(Kx8XtxArgs a)
         uint32_t from = win[lane] >> 8;
         from = from < (uint32_t)P ? from : 0u;
         src[nxt][lane] = src[cur][from];
-        ls[nxt][lane] = kxx_unordered(wins[lane]);
+        ls[nxt][lane] = kxb_unordered(wins[lane]);
       }
       for (int idx = lane; idx < keep * G; idx += WAVE) {
         const int i = idx / G;
         const uint32_t flat = win[i];
         uint32_t from = flat >> 8;
         from = from < (uint32_t)P ? from : 0u;
-        const float dw = kxx_mul(s, entry(c, (int)(flat & 255u), e_own)) - kxx_mul(s, entry(c, beams[cur][from][c], e_own));
+        const float dw = kxb_mul(s, entry(c, (int)(flat & 255u), e_own)) - kxb_mul(s, entry(c, beams[cur][from][c], e_own));
         wb[i][e_own] = dw;
         dl[nxt][i][e_own] = dl[cur][from][e_own] + dw;
       }
@@ -316,8 +180,8 @@ __global__ __launch_bounds__(WAVE) void code_search_kx8_xtx_kernel(Kx8XtxArgs a)
         const int i = idx / G;
         uint32_t from = win[i] >> 8;
         from = from < (uint32_t)P ? from : 0u;
-        float acc = kxx_mul(wb[i][0], hm[0][e_own]);
-        for (int f = 1; f < G; ++f) acc = acc + kxx_mul(wb[i][f], hm[f][e_own]);
+        float acc = kxb_mul(wb[i][0], hm[0][e_own]);
+        for (int f = 1; f < G; ++f) acc = acc + kxb_mul(wb[i][f], hm[f][e_own]);
         tt[nxt][i][e_own] = tt[cur][from][e_own] - acc;
       }
       __syncthreads();
@@ -343,20 +207,7 @@ __global__ __launch_bounds__(WAVE) void code_search_kx8_xtx_kernel(Kx8XtxArgs a)
 }
 
 static bool kxx_scheme_ok(int num_codebooks, int g, int beam_size, int positions_in) {
-  return num_codebooks >= 1 && num_codebooks <= kKxxMaxBooks && (g == 8 || g == 16 || g == 32) && beam_size >= 1 &&
-         beam_size <= AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM && positions_in >= 1 && positions_in <= AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM;
-}
-
-template <class T, int G>
-static int kxx_launch(const Kx8XtxArgs& a, unsigned blocks, hipStream_t stream) {
-  // the positions the LDS and registers must hold: those at entry, and the beam_size survivors that EVERY step keeps (the only
-  // step of a single codebook too)
-  const int width = a.positions_in > a.beam ? a.positions_in : a.beam;
-  if (width == 1) hipLaunchKernelGGL((code_search_kx8_xtx_kernel<T, G, 1>), dim3(blocks), dim3(WAVE), 0, stream, a);
-  else if (width <= 4) hipLaunchKernelGGL((code_search_kx8_xtx_kernel<T, G, 4>), dim3(blocks), dim3(WAVE), 0, stream, a);
-  else if (width <= 8) hipLaunchKernelGGL((code_search_kx8_xtx_kernel<T, G, 8>), dim3(blocks), dim3(WAVE), 0, stream, a);
-  else hipLaunchKernelGGL((code_search_kx8_xtx_kernel<T, G, 16>), dim3(blocks), dim3(WAVE), 0, stream, a);
-  return check_hip(hipGetLastError(), "code_search_kx8_xtx launch");
+  return kxb_search_scheme_ok(num_codebooks, g, beam_size) && positions_in >= 1 && positions_in <= AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM;
 }
 
 }  // namespace aqlm
@@ -380,10 +231,9 @@ extern "C" int aqlm_hip_code_search_kx8_xtx(const void* t, long t_position_strid
   static const char* who = "aqlm_hip_code_search_kx8_xtx";
   (void)workspace; (void)workspace_bytes;
   if (int e = check_not_null(who, t && loss && codes_in && h && q && codebooks && loss_out && codes_out && source_out && delta_out)) return e;
-  auto a4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
   if (int e = check_aligned(who, "t / loss / H / q / scales / codebooks / loss_out / delta / t_out",
-                            a4(t) && a4(loss) && a4(h) && a4(q) && (reinterpret_cast<uintptr_t>(scales) & 1u) == 0 && aligned16(codebooks) &&
-                                a4(loss_out) && a4(delta_out) && a4(t_out)))
+                            aligned4(t) && aligned4(loss) && aligned4(h) && aligned4(q) && aligned2(scales) && aligned16(codebooks) &&
+                                aligned4(loss_out) && aligned4(delta_out) && aligned4(t_out)))
     return e;
   if (out_features < 1 || in_group_size < 1) {
     set_last_error("%s: bad sizes (out=%d g=%d)", who, out_features, in_group_size);
@@ -401,16 +251,7 @@ extern "C" int aqlm_hip_code_search_kx8_xtx(const void* t, long t_position_strid
     return AQLM_HIP_E_UNSUPPORTED;
   }
   Kx8XtxArgs a{};
-  unsigned seen = 0;
-  for (int i = 0; i < num_codebooks; ++i) {
-    const int c = dim_order ? dim_order[i] : i;
-    if (c < 0 || c >= num_codebooks || (seen >> c & 1u)) {
-      set_last_error("%s: dim_order must be a permutation of 0 .. %d (entry %d is %d)", who, num_codebooks - 1, i, c);
-      return AQLM_HIP_E_INVALID;
-    }
-    seen |= 1u << c;
-    a.order[i] = (signed char)c;
-  }
+  if (int e = kxb_parse_dim_order(who, dim_order, num_codebooks, a.order)) return e;
   a.t = (const float*)t;
   a.loss = (const float*)loss;
   a.codes_in = (const int8_t*)codes_in;
@@ -430,13 +271,12 @@ extern "C" int aqlm_hip_code_search_kx8_xtx(const void* t, long t_position_strid
   a.beam = beam_size;
   a.positions_in = positions_in;
   hipStream_t stream = (hipStream_t)stream_;
-  const unsigned blocks = (unsigned)out_features < kKxxMaxBlocks ? (unsigned)out_features : kKxxMaxBlocks;
-  if (dtype == AQLM_HIP_F16) {
-    if (in_group_size == 8) return kxx_launch<F16, 8>(a, blocks, stream);
-    if (in_group_size == 16) return kxx_launch<F16, 16>(a, blocks, stream);
-    return kxx_launch<F16, 32>(a, blocks, stream);
-  }
-  if (in_group_size == 8) return kxx_launch<BF16, 8>(a, blocks, stream);
-  if (in_group_size == 16) return kxx_launch<BF16, 16>(a, blocks, stream);
-  return kxx_launch<BF16, 32>(a, blocks, stream);
+  const unsigned blocks = (unsigned)out_features < kKxbMaxBlocks ? (unsigned)out_features : kKxbMaxBlocks;
+  // the positions the LDS and registers must hold: those at entry, and the beam_size survivors that EVERY step keeps (the only
+  // step of a single codebook too)
+  const int width = positions_in > beam_size ? positions_in : beam_size;
+  return kxb_dispatch(dtype, in_group_size, width, [&](auto ty, auto gs, auto pmax) {
+    hipLaunchKernelGGL((code_search_kx8_xtx_kernel<decltype(ty), decltype(gs)::value, decltype(pmax)::value>), dim3(blocks), dim3(WAVE), 0, stream, a);
+    return check_hip(hipGetLastError(), "code_search_kx8_xtx launch");
+  });
 }

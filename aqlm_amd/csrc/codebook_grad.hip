@@ -26,10 +26,6 @@ struct F32 {
   static constexpr int id = AQLM_HIP_F32;
 };
 
-static __device__ __forceinline__ float half_bits_to_float(uint32_t u16, int is_bf16) {
-  return is_bf16 ? __uint_as_float(u16 << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)u16);
-}
-
 // G consecutive elements at `p` (16-byte aligned) as fp32, loaded in 16-byte pieces
 template <class DW, int G>
 static __device__ __forceinline__ void load_group(const void* p, float (&v)[G]) {
@@ -225,11 +221,6 @@ static long cg_max_chunks(int out_features, int in_features, int g) {
   const long n = (long)out_features * (long)(in_features / g);
   return std::min<long>(n, kCgEntries) + n / kCgChunk;
 }
-
-static bool dw_dtype_ok(int dt) { return dt == AQLM_HIP_F16 || dt == AQLM_HIP_BF16 || dt == AQLM_HIP_F32; }
-static size_t dtype_bytes(int dt) { return dt == AQLM_HIP_F32 ? 4 : 2; }
-static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static bool aligned2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0; }
 
 // f(DW{}, GroupSize<g>{}) for the three dW types
 template <class F>

@@ -35,10 +35,6 @@ struct F32 {
   static constexpr int id = AQLM_HIP_F32;
 };
 
-static __device__ __forceinline__ float kx8_half_bits_to_float(uint32_t u16, int is_bf16) {
-  return is_bf16 ? __uint_as_float(u16 << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)u16);
-}
-
 template <class DW>
 static __device__ __host__ __forceinline__ constexpr size_t kx8_elem_bytes() {
   return DW::id == AQLM_HIP_F32 ? 4 : 2;
@@ -159,7 +155,7 @@ __global__ __launch_bounds__(kKx8Threads) void codebook_grad_kx8_maxima_kernel(K
   }
   if (a.scales) {
     for (int r = r0 + (int)threadIdx.x; r < r1; r += kKx8Threads) {
-      const uint32_t u = __float_as_uint(kx8_half_bits_to_float(a.scales[r], a.scales_bf16)) & 0x7fffffffu;
+      const uint32_t u = __float_as_uint(half_bits_to_float(a.scales[r], a.scales_bf16)) & 0x7fffffffu;
       ms = u > ms ? u : ms;
     }
   } else {
@@ -206,7 +202,7 @@ __global__ __launch_bounds__(kKx8Threads) void codebook_grad_kx8_accumulate_kern
       const uint8_t* cp = a.codes + ((size_t)o * nj + j) * (size_t)a.K + c0;
 #pragma unroll
       for (int ci = 0; ci < KS; ++ci) base[u][ci] = ci < nc ? (uint32_t)(ci * kKx8Entries + cp[ci]) * ES : 0u;
-      s[u] = a.scales ? (double)kx8_half_bits_to_float(a.scales[o], a.scales_bf16) : 1.0;
+      s[u] = a.scales ? (double)half_bits_to_float(a.scales[o], a.scales_bf16) : 1.0;
       grp[u] = dw + ((size_t)o * (size_t)a.dws + (size_t)j * G) * kx8_elem_bytes<DW>();
     }
 #pragma unroll
@@ -356,11 +352,6 @@ static int kx8_bit_length(long v) {
   return n;
 }
 
-static bool kx8_dw_dtype_ok(int dt) { return dt == AQLM_HIP_F16 || dt == AQLM_HIP_BF16 || dt == AQLM_HIP_F32; }
-static size_t kx8_dtype_bytes(int dt) { return dt == AQLM_HIP_F32 ? 4 : 2; }
-static bool kx8_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static bool kx8_aligned2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0; }
-
 // f(DW{}, GroupSize<g>{}) for the three dW types and the three group sizes
 template <class F>
 static int kx8_dispatch(int dw_dtype, int g, F&& f) {
@@ -385,7 +376,7 @@ static int kx8_check_shape(const char* who, long dw_row_stride, int dw_dtype, in
                    dw_row_stride, in_features, workspace_bytes, need);
     return AQLM_HIP_E_INVALID;
   }
-  if (!kx8_dw_dtype_ok(dw_dtype) || !kx8_dw_dtype_ok(out_dtype)) {
+  if (!dw_dtype_ok(dw_dtype) || !dw_dtype_ok(out_dtype)) {
     set_last_error("%s: dW and the output are float16, bfloat16 or float32 (dtype ids %d, %d)", who, dw_dtype, out_dtype);
     return AQLM_HIP_E_UNSUPPORTED;
   }
@@ -398,7 +389,7 @@ static int kx8_check_shape(const char* who, long dw_row_stride, int dw_dtype, in
     set_last_error("%s: only codebooks with 8, 16 or 32 features are supported, got %d", who, g);
     return AQLM_HIP_E_UNSUPPORTED;
   }
-  if (!shape_ok || ((size_t)dw_row_stride * kx8_dtype_bytes(dw_dtype)) % 16 != 0) {
+  if (!shape_ok || ((size_t)dw_row_stride * dtype_bytes(dw_dtype)) % 16 != 0) {
     set_last_error("%s: shape outside the kernel (fewer than 2^30 positions, dW rows 16-byte aligned; got out=%d in=%d g=%d, row stride %ld)",
                    who, out_features, in_features, g, dw_row_stride);
     return AQLM_HIP_E_UNSUPPORTED;
@@ -424,7 +415,7 @@ extern "C" int aqlm_hip_codebook_grad_kx8(const void* dw, long dw_row_stride, in
                                           void* out, int out_dtype, void* workspace, size_t workspace_bytes, void* stream_) {
   static const char* who = "aqlm_hip_codebook_grad_kx8";
   if (int e = check_not_null(who, dw && codes && out && workspace)) return e;
-  if (int e = check_aligned(who, "dw / scales / out / workspace", aligned16(dw) && kx8_aligned2(scales) && aligned16(out) && aligned16(workspace)))
+  if (int e = check_aligned(who, "dw / scales / out / workspace", aligned16(dw) && aligned2(scales) && aligned16(out) && aligned16(workspace)))
     return e;
   if (int e = kx8_check_shape(who, dw_row_stride, dw_dtype, dtype, out_features, in_features, num_codebooks, in_group_size, out_dtype, true,
                               workspace_bytes))
@@ -473,7 +464,7 @@ extern "C" int aqlm_hip_scales_grad_kx8(const void* dw, long dw_row_stride, int 
                                         int out_dtype, void* stream_) {
   static const char* who = "aqlm_hip_scales_grad_kx8";
   if (int e = check_not_null(who, dw && codes && codebooks && out)) return e;
-  if (int e = check_aligned(who, "dw / codebooks / out", aligned16(dw) && aligned16(codebooks) && kx8_aligned4(out))) return e;
+  if (int e = check_aligned(who, "dw / codebooks / out", aligned16(dw) && aligned16(codebooks) && aligned4(out))) return e;
   if (int e = kx8_check_shape(who, dw_row_stride, dw_dtype, dtype, out_features, in_features, num_codebooks, in_group_size, out_dtype, false,
                               0))
     return e;

@@ -1287,9 +1287,18 @@ def code_search_kx8_supported(out_features: int, in_features: int, num_codebooks
                                                         int(beam_size)))
 
 
+def _dim_order(who: str, dim_order, K: int):
+    """``dim_order`` as a list of ints (None stays None); anything but a permutation of 0 .. K - 1 is a ValueError in ``who``'s name."""
+    if dim_order is None:
+        return None
+    order = [int(c) for c in dim_order]
+    if sorted(order) != list(range(K)):
+        raise ValueError(f"{who}: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    return order
+
+
 def _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out, geometry, want_scores):
     out_features, in_features, K, g, beam_size = (int(x) for x in geometry[:5])
-    order = [int(c) for c in geometry[5:]]
     if (reference.dim() != 2 or tuple(reference.shape) != (out_features, in_features) or reference.dtype not in _GRAD_DT
             or not reference.is_cuda):
         raise ValueError(f"code_search_kx8: reference must be fp16 / bf16 / fp32 [{out_features}, {in_features}] on the GPU, got "
@@ -1308,8 +1317,7 @@ def _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, c
     if prev_codes.dtype != torch.int8 or prev_codes.numel() != total * K or prev_codes.device != reference.device:
         raise ValueError(f"code_search_kx8: prev_codes must hold {total} x {K} int8 codes (the whole layer) on {reference.device}")
     prev_codes = _c(prev_codes)
-    if order and sorted(order) != list(range(K)):
-        raise ValueError(f"code_search_kx8: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    order = _dim_order("code_search_kx8", geometry[5:] or None, K)  # (the geometry ends after beam_size: no dim_order)
     if group_ids is not None:
         if group_ids.dtype not in (torch.int32, torch.int64) or group_ids.dim() != 1 or group_ids.device != reference.device:
             raise ValueError("code_search_kx8: group_ids must be a 1-d int32 / int64 tensor on the reference's device")
@@ -1351,9 +1359,7 @@ def code_search_kx8(reference, scales, codebooks, prev_codes, in_group_size: int
     place when given -- an id outside the layer leaves its entries as they were.  ``return_scores``: also the fp32 score of the
     returned hypothesis on the last step, [n].  One launch on the current stream, no workspace."""
     g, K = int(in_group_size), int(codebooks.shape[0])
-    order = [] if dim_order is None else [int(c) for c in dim_order]
-    if dim_order is not None and sorted(order) != list(range(K)):
-        raise ValueError(f"code_search_kx8: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    order = _dim_order("code_search_kx8", dim_order, K) or []
     codes, scores = _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out,
                                           [int(reference.shape[0]), int(reference.shape[1]), K, g, int(beam_size)] + order, return_scores)
     return (codes, scores) if return_scores else codes
@@ -1404,9 +1410,7 @@ def code_search_kx8_xtx_step(t, loss, codes_in, H, q, codebooks, scales, beam_si
         if scales.numel() != out_features or scales.device != dev or scales.dtype != codebooks.dtype:
             raise ValueError(f"code_search_kx8_xtx_step: scales must hold {out_features} elements of {codebooks.dtype} on {dev}")
         scales = _c(scales)
-    order = None if dim_order is None else [int(c) for c in dim_order]
-    if order is not None and sorted(order) != list(range(K)):
-        raise ValueError(f"code_search_kx8_xtx_step: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
+    order = _dim_order("code_search_kx8_xtx_step", dim_order, K)
     if not code_search_kx8_xtx_supported(out_features, K, g, beam_size, positions):
         raise NotImplementedError(f"code_search_kx8_xtx_step: K={K} g={g} beam_size={beam_size} positions={positions} is outside the kernel")
     out = XtxStep(torch.empty((beam_size, out_features), dtype=torch.float32, device=dev),

@@ -61,31 +61,38 @@ def layer(K, g, dtype, fin=64, out=OUT, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-def step_case(K, g, beam, dtype, positions):
+def step_case(K, g, beam, dtype, positions, out=OUT, rows=None):
     """The inputs of one launch for group 1 of ``layer``: position b holds the previous codes with the codes of group 0 shifted by b (so
-    the positions differ), its T slice and its loss, all float32 values formed in float64."""
-    c = layer(K, g, dtype)
+    the positions differ), its T slice and its loss, all float32 values formed in float64.  ``rows``: "equal" makes the 256 rows of every
+    codebook one row (the shift then changes no weight: the positions are equal too), "pairs" makes row 2i + 1 a copy of row 2i."""
+    c = dict(layer(K, g, dtype, out=out))
+    if rows is not None:
+        c["books"] = c["books"].clone()
+        if rows == "equal":
+            c["books"][:] = c["books"][:, :1]
+        else:
+            c["books"][:, 1::2] = c["books"][:, 0::2]
     books, s = c["books"].double(), c["scales"].double()
     XTX = c["XTX"].double()
     t, loss = [], []
     for b in range(positions):
         codes = c["prev"].clone()
         codes[:, 0, :] = (codes[:, 0, :] + 7 * b) % 256
-        weight = sum(books[k][codes[..., k]] for k in range(K)).reshape(OUT, -1) * s[:, None]
+        weight = sum(books[k][codes[..., k]] for k in range(K)).reshape(out, -1) * s[:, None]
         error = c["reference"].double() - weight
         T = error @ XTX
         t.append(T[:, g:2 * g])
         loss.append((T * error).sum(-1))
     H = c["XTX"][g:2 * g, g:2 * g].contiguous()
     q = torch.from_numpy(model.group_q(c["books"].float().numpy(), H.numpy(), np.float64)).float()
-    codes_in = c["prev"][None, :, 1, :].expand(positions, OUT, K).contiguous()
+    codes_in = c["prev"][None, :, 1, :].expand(positions, out, K).contiguous()
     return {"t": torch.stack(t).float().contiguous(), "loss": torch.stack(loss).float().contiguous(), "codes_in": codes_in, "H": H, "q": q,
             "books": c["books"], "scales": c["scales"]}
 
 
 @functools.lru_cache(maxsize=None)
-def expected(K, g, beam, dtype, positions, scaled=True, order=None):
-    c = step_case(K, g, beam, dtype, positions)
+def expected(K, g, beam, dtype, positions, scaled=True, order=None, out=OUT, rows=None):
+    c = step_case(K, g, beam, dtype, positions, out, rows)
     return model.step(c["t"].numpy(), c["loss"].numpy(), c["codes_in"].numpy(), c["H"].numpy(), c["q"].numpy(), c["books"].float().numpy(),
                       c["scales"].float().numpy() if scaled else None, beam, None if order is None else list(order))
 
@@ -173,6 +180,39 @@ def test_non_finite_H_or_q_still_gives_codes_and_sources_in_range(hk, where, poi
     assert int(got.source.max()) < beam
     again = launch(hk, c, beam)
     assert torch.equal(got.codes, again.codes) and torch.equal(got.source, again.source), "still a function of the arguments"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# exact ties: both ways of the selection (kx8_select_body.h) with equal keys, and the scores they pass on
+# ---------------------------------------------------------------------------------------------------------------------------
+TIES = ([(K, 8, beam, positions, torch.float16) for K in (2, 3) for beam in (4, 16) for positions in (1, 4)]
+        + [(2, 32, 16, 4, torch.float16), (3, 8, 4, 4, torch.bfloat16)])
+TIE_IDS = [f"{K}x8-g{g}-beam{beam}-p{positions}-{'bf16' if dtype == torch.bfloat16 else 'fp16'}" for K, g, beam, positions, dtype in TIES]
+
+
+@pytest.mark.parametrize("K,g,beam,positions,dtype", TIES, ids=TIE_IDS)
+def test_codebooks_of_equal_rows_tie_every_candidate(hk, K, g, beam, positions, dtype):
+    """Every key of a step has the same score (the 256 candidates of a position, and the positions among themselves): far more than 64
+    reach the bound, so every step goes the general way, and rank i is flat index i -- position 0, code i."""
+    c, want = step_case(K, g, beam, dtype, positions, 8, "equal"), expected(K, g, beam, dtype, positions, out=8, rows="equal")
+    assert bool((c["q"] == c["q"][:, :1]).all()) and bool((c["t"] == c["t"][:1]).all()) and bool((c["loss"] == c["loss"][:1]).all())
+    ranks = np.broadcast_to(np.arange(beam)[:, None], (beam, 8))
+    assert (want["codes"][:, :, :K - 1] == 0).all() and (want["codes"][:, :, K - 1] == ranks).all() and (want["source"] == 0).all(), \
+        "the inputs tie: the model's stable sort keeps flat indices 0 .. beam_size - 1 on every step"
+    assert (bits(want["loss"]) == bits(want["loss"])[:1]).all()
+    hold_to_model(launch(hk, c, beam), want, f"{K}x8 g{g} beam {beam} {dtype}, {positions} positions, equal rows")
+
+
+@pytest.mark.parametrize("K,g,beam,positions,dtype", TIES, ids=TIE_IDS)
+def test_rows_equal_in_pairs_tie_inside_the_counting_way(hk, K, g, beam, positions, dtype):
+    """Candidates 2i and 2i + 1 of every position have the same score: the few keys within the bound hold exact ties, which the
+    count on the full key gives to the smaller flat index."""
+    c, want = step_case(K, g, beam, dtype, positions, 8, "pairs"), expected(K, g, beam, dtype, positions, out=8, rows="pairs")
+    assert bool((c["q"][:, 1::2] == c["q"][:, 0::2]).all()) and bool((c["books"][:, 1::2] == c["books"][:, 0::2]).all())
+    pairs = bits(want["loss"]).numpy().reshape(beam // 2, 2, 8)
+    print(f"{int((pairs[:, 0] == pairs[:, 1]).sum())} of {pairs[:, 0].size} adjacent survivors of the last step have equal scores")
+    assert (pairs[:, 0] == pairs[:, 1]).any(), "the inputs must tie among the survivors"
+    hold_to_model(launch(hk, c, beam), want, f"{K}x8 g{g} beam {beam} {dtype}, {positions} positions, rows equal in pairs")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
