@@ -287,7 +287,7 @@ class CaptureRelax {
   capture_overlap::Plan plan_;
 };
 
-// slice-scan MFMA kernel of the 1x16 g8 scheme at 2+ rows (gemm_1x16_scan.hip); the large-batch op of gemm_mfma.hip routes to it
+// slice-scan MFMA kernel of the 1x16 g8 scheme at 2+ rows (gemm_1x16_scan.hip); aqlm_hip_gemm_1x16_mfma (gemm_mfma_entries.h) routes to it
 namespace scan {
 size_t workspace_bytes(int B, int M, int K);  // 0: no plan (in_features % 256 != 0)
 int run(const void* codes, const void* codebook, const void* scales, const void* bias, const void* X, void* Y, int batch, int out_features,
@@ -316,9 +316,9 @@ __device__ __forceinline__ float half_bits_to_float(uint32_t u16, int is_bf16) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Argument checks that the indexed entry points share (routed, routed packed, bucket, grouped, transposed, LoRA).  Each sets the
-// message and returns the code when its condition is violated, else 0; an entry point calls them in the order in which it
-// reports: `if (int e = check_...(who, ...)) return e;`
+// Argument checks that the indexed entry points (routed, routed packed, bucket, grouped, transposed, LoRA) and the dense MFMA GEMM
+// entries share.  Each sets the message and returns the code when its condition is violated, else 0; an entry point calls them in
+// the order in which it reports: `if (int e = check_...(who, ...)) return e;`
 // ---------------------------------------------------------------------------------------------
 inline int check_not_null(const char* who, bool all_set) {
   if (all_set) return 0;
@@ -344,6 +344,12 @@ inline int check_pairs(const char* who, int num_pairs, int top_k, int max_pairs)
 inline int check_sizes(const char* who, int out_features, int in_features, int in_group_size) {
   if (out_features > 0 && in_features > 0 && in_group_size > 0 && in_features % in_group_size == 0) return 0;
   set_last_error("%s: bad sizes (out=%d in=%d g=%d)", who, out_features, in_features, in_group_size);
+  return AQLM_HIP_E_INVALID;
+}
+// the three sizes of a dense forward entry
+inline int check_positive(const char* who, int batch, int out_features, int in_features) {
+  if (batch > 0 && out_features > 0 && in_features > 0) return 0;
+  set_last_error("%s: sizes must be positive", who);
   return AQLM_HIP_E_INVALID;
 }
 inline int check_dtype(const char* who, int dtype) {
@@ -378,6 +384,16 @@ template <class F>
 inline int dispatch_dtype_group(int dtype, int in_group_size, F&& f) {
   if (dtype == AQLM_HIP_F16) return in_group_size == 8 ? f(F16{}, GroupSize<8>{}) : f(F16{}, GroupSize<16>{});
   return in_group_size == 8 ? f(BF16{}, GroupSize<8>{}) : f(BF16{}, GroupSize<16>{});
+}
+template <int V>
+struct Codebooks {
+  static constexpr int value = V;
+};
+// its sibling for the 1x8 / 2x8 entries (num_codebooks checked to be 1 or 2): f(F16{} or BF16{}, Codebooks<1>{} or Codebooks<2>{})
+template <class F>
+inline int dispatch_dtype_k(int dtype, int num_codebooks, F&& f) {
+  if (dtype == AQLM_HIP_F16) return num_codebooks == 2 ? f(F16{}, Codebooks<2>{}) : f(F16{}, Codebooks<1>{});
+  return num_codebooks == 2 ? f(BF16{}, Codebooks<2>{}) : f(BF16{}, Codebooks<1>{});
 }
 
 }  // namespace aqlm

@@ -429,19 +429,11 @@ extern "C" int aqlm_hip_gemm_1x16_scan(const void* codes, const void* codebook, 
                                        int batch, int out_features, int in_features, long xs, long ys, int dtype, void* workspace,
                                        size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!codes || !codebook || !scales || !X || !Y) {
-    set_last_error("aqlm_hip_gemm_1x16_scan: null pointer argument");
-    return AQLM_HIP_E_INVALID;
-  }
-  if (batch <= 0 || out_features <= 0 || in_features <= 0) {
-    set_last_error("aqlm_hip_gemm_1x16_scan: sizes must be positive");
-    return AQLM_HIP_E_INVALID;
-  }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("aqlm_hip_gemm_1x16_scan: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (int e = check_x_row_stride("aqlm_hip_gemm_1x16_scan", batch, in_features, xs)) return e;
+  const char* who = "aqlm_hip_gemm_1x16_scan";
+  if (int e = check_not_null(who, codes && codebook && scales && X && Y)) return e;
+  if (int e = check_positive(who, batch, out_features, in_features)) return e;
+  if (int e = check_dtype(who, dtype)) return e;
+  if (int e = check_x_row_stride(who, batch, in_features, xs)) return e;
   if (in_features % 256 != 0 || !aligned16(codes) || !aligned16(codebook) || !aligned16(X) || xs % 8 != 0) {
     set_last_error("aqlm_hip_gemm_1x16_scan: needs in_features %% 256 == 0 (codebook vectors of 8) and 16-B aligned codes / codebook / X rows");
     return AQLM_HIP_E_UNSUPPORTED;

@@ -229,6 +229,11 @@ int launch_e8(const E8Params& p, hipStream_t stream) {
   return check_hip(hipGetLastError(), "gemm_8x8g32_rows16 launch");
 }
 
+template <class T>  // the slab's batch tiles pick the instance
+int launch_e8_slab(const E8Params& p, hipStream_t stream) {
+  return p.B <= 16 ? launch_e8<T, 1>(p, stream) : (p.B <= 32 ? launch_e8<T, 2>(p, stream) : launch_e8<T, 4>(p, stream));
+}
+
 }  // namespace
 
 }  // namespace aqlm
@@ -239,48 +244,35 @@ extern "C" int aqlm_hip_gemm_8x8_mfma(const void* codes, const void* codebooks, 
                                       void* Y, int batch, int out_features, int in_features, int in_group_size, long xs, long ys,
                                       int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!codes || !codebooks || !scales || !X || !Y) {
-    set_last_error("aqlm_hip_gemm_8x8_mfma: null pointer argument");
-    return AQLM_HIP_E_INVALID;
-  }
-  if (batch <= 0 || out_features <= 0 || in_features <= 0) {
-    set_last_error("aqlm_hip_gemm_8x8_mfma: sizes must be positive");
-    return AQLM_HIP_E_INVALID;
-  }
+  const char* who = "aqlm_hip_gemm_8x8_mfma";
+  if (int e = check_not_null(who, codes && codebooks && scales && X && Y)) return e;
+  if (int e = check_positive(who, batch, out_features, in_features)) return e;
   if (in_group_size != 32) {
     set_last_error("aqlm_hip_gemm_8x8_mfma: 8 codebooks of 256 x 32 only, got group %d", in_group_size);
     return AQLM_HIP_E_UNSUPPORTED;
   }
-  if (dtype != AQLM_HIP_F16 && dtype != AQLM_HIP_BF16) {
-    set_last_error("aqlm_hip_gemm_8x8_mfma: AQLM HIP kernels only support float16 and bfloat16 (dtype id %d)", dtype);
-    return AQLM_HIP_E_UNSUPPORTED;
-  }
-  if (int e = check_x_row_stride("aqlm_hip_gemm_8x8_mfma", batch, in_features, xs)) return e;
+  if (int e = check_dtype(who, dtype)) return e;
+  if (int e = check_x_row_stride(who, batch, in_features, xs)) return e;
   if (in_features % 256 != 0 || in_features < 256 * E8_NW || !aligned16(codebooks) || !aligned16(X) || !aligned16(codes) || xs % 8 != 0) {
     set_last_error("aqlm_hip_gemm_8x8_mfma: needs in_features %% 256 == 0, >= %d, and 16-B aligned codes / codebooks / X rows", 256 * E8_NW);
     return AQLM_HIP_E_UNSUPPORTED;
   }
+  E8Params p{};
+  p.codes = (const uint8_t*)codes;
+  p.codebooks = (const uint8_t*)codebooks;
+  p.scales = (const uint16_t*)scales;
+  p.bias = (const uint16_t*)bias;
+  p.xs = xs;
+  p.ys = ys;
+  p.M = out_features;
+  p.in_groups = in_features / 32;
+  p.ntiles = (out_features + 15) / 16;
+  p.nchunks = p.in_groups / 8;
   for (int b0 = 0; b0 < batch; b0 += 64) {  // slabs of 64 rows (the codes are re-read per slab: they are 2 bits per weight)
-    const int nb = std::min(64, batch - b0);
-    E8Params p{};
-    p.codes = (const uint8_t*)codes;
-    p.codebooks = (const uint8_t*)codebooks;
     p.X = (const uint16_t*)X + (long)b0 * xs;
-    p.scales = (const uint16_t*)scales;
-    p.bias = (const uint16_t*)bias;
     p.Y = (uint16_t*)Y + (long)b0 * ys;
-    p.xs = xs;
-    p.ys = ys;
-    p.M = out_features;
-    p.B = nb;
-    p.in_groups = in_features / 32;
-    p.ntiles = (out_features + 15) / 16;
-    p.nchunks = p.in_groups / 8;
-    const int nbt = nb <= 16 ? 1 : (nb <= 32 ? 2 : 4);
-    int e;
-    if (dtype == AQLM_HIP_F16) e = nbt == 1 ? launch_e8<F16, 1>(p, stream) : (nbt == 2 ? launch_e8<F16, 2>(p, stream) : launch_e8<F16, 4>(p, stream));
-    else e = nbt == 1 ? launch_e8<BF16, 1>(p, stream) : (nbt == 2 ? launch_e8<BF16, 2>(p, stream) : launch_e8<BF16, 4>(p, stream));
-    if (e) return e;
+    p.B = std::min(64, batch - b0);
+    if (int e = dtype == AQLM_HIP_F16 ? launch_e8_slab<F16>(p, stream) : launch_e8_slab<BF16>(p, stream)) return e;
   }
   return 0;
 }

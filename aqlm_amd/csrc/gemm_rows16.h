@@ -1,6 +1,6 @@
-// Types, LDS map and plan of the 16-row fused 1x16 MFMA GEMM (a block owns 16 output rows over all of K; gemm_mfma.hip describes
-// the design), shared by gemm_1x16_rows16_kernel (gemm_mfma.hip) and the expert-grouped kernel of moe_grouped.hip.  The kernel
-// body itself is gemm_rows16_body.h.
+// Types, LDS map and plan of the 16-row fused 1x16 MFMA GEMM (a block owns 16 output rows over all of K; gemm_1x16_rows16.h, a part
+// of gemm_mfma.hip, describes the design), shared by gemm_1x16_rows16_kernel (there) and the expert-grouped kernel of
+// moe_grouped.hip.  The kernel body itself is gemm_rows16_body.h.
 #pragma once
 #include <algorithm>
 

@@ -1,5 +1,5 @@
-// Body of the 16-row fused 1x16 MFMA GEMM (gemm_mfma.hip describes the design), shared TEXTUALLY by two kernels: it is
-// #included inside the braces of gemm_1x16_rows16_kernel (gemm_mfma.hip) and gemm_1x16_grouped_kernel (moe_grouped.hip).  A
+// Body of the 16-row fused 1x16 MFMA GEMM (gemm_1x16_rows16.h, a part of gemm_mfma.hip, describes the design), shared TEXTUALLY
+// by two kernels: it is #included inside the braces of gemm_1x16_rows16_kernel (there) and gemm_1x16_grouped_kernel (moe_grouped.hip).  A
 // function, even a force-inlined one, is simplified on its own before it is inlined and the kernels' instruction streams moved
 // (operand order, scheduling); the fragment keeps gemm_1x16_rows16_kernel's code exactly what it was when the body lived in it.
 //

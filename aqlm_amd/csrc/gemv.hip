@@ -455,14 +455,14 @@ static int dispatch_kx8_nb(int nb, const GemvParams& p, hipStream_t s) {
 }  // namespace aqlm
 
 // 2..8 rows of a 1x8 / 2x8 g8 layer: the matvec kernels pay one more x read + 4 dot products per code and row (2x8 g8 4096^2:
-// 7.0 / 11.7 / 16.5 / 19.0 us at 2 / 3 / 6 / 8 rows), the fused dequant -> MFMA op with X resident in LDS (round 5, gemm_mfma.hip)
+// 7.0 / 11.7 / 16.5 / 19.0 us at 2 / 3 / 6 / 8 rows), the fused dequant -> MFMA op with X resident in LDS (round 5, gemm_kx8_xres.h)
 // costs 5.0 / 5.1 / 5.4 / 5.7 us (4096 -> 11008 at 6 rows: 34.5 vs 9.5 us; profiles/r05_gemm_kx8_xres.log).  From `kx8_mfma_min_rows`
 // rows on (tuning key, default 2, 0 = never) the matvec entries hand the call to aqlm_hip_gemm_kx8_mfma: exact products, fp32 sums
 // like the matvec kernels, and a row's bits there depend neither on the other rows nor on their number (2..16 rows) -- only the
 // single-row kernels (replicated-LDS matvec, another summation order) differ from it in the last fp32 bit before the rounding.
 namespace aqlm {
 int gemm_kx8_xres_multi(const aqlm_hip_segment* segments, int num_segments, const void* X, int in_features, int K, int batch, long xs,
-                        int dtype, hipStream_t stream);  // gemm_mfma.hip
+                        int dtype, hipStream_t stream);  // gemm_mfma_entries.h
 }
 
 static bool kx8_rows_take_mfma(int batch, int K, int G) {

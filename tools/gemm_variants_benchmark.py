@@ -1,6 +1,6 @@
 """Large-batch 1x16 op: the K-split LDS-DMA pipeline (gemm_variant 3) against the 16-row no-split kernel (2) and a dense fp16
 GEMM, over layer shapes, group sizes and batch rows (hipGraph replay over 24 distinct layers, HIP events).  The selection rule of
-aqlm_hip_gemm_1x16_mfma (gemm_mfma.hip: R16_ROWS_ANY / R16_ROWS_SMALL / R16_SMALL_LAYER) was read off this table.
+aqlm_hip_gemm_1x16_mfma (gemm_1x16_rows16.h: R16_ROWS_ANY / R16_ROWS_SMALL / R16_SMALL_LAYER) was read off this table.
 
     python tools/gemm_variants_benchmark.py [--out profiles/r04_gemm_rows16_shapes.json]
 """
