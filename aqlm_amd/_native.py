@@ -200,6 +200,10 @@ SIGNATURES = {
     "aqlm_hip_code_search_kx8_xtx_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_code_search_kx8_xtx": (_ci, [_vp, _cl, _cl, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(_ci),
                                      _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aqlm_hip_code_search_1x16_xtx_supported": (_ci, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_code_search_1x16_xtx_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_code_search_1x16_xtx": (_ci, [_vp, _cl, _cl, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _sz, _vp]),
     "aqlm_hip_gemv_kx8_multi": (_ci, [_segp, _ci, _vp, _ci, _ci, _ci, _ci, _cl, _ci, _vp]),
     "aqlm_hip_gemv_kx8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_prepack_1x16_bytes": (_sz, [_ci, _ci, _ci]),

@@ -1430,6 +1430,65 @@ def code_search_kx8_xtx_step(t, loss, codes_in, H, q, codebooks, scales, beam_si
 
 
 # ------------------------------------------------------------------------------------------------------
+# the calibrated search of the 1x16 schemes, one input group per call (aqlm_hip_code_search_1x16_xtx)
+# ------------------------------------------------------------------------------------------------------
+CODE_SEARCH_1X16_XTX_MAX_BEAM = 8  # AQLM_HIP_CODE_SEARCH_1X16_XTX_MAX_BEAM
+
+
+def code_search_1x16_xtx_supported(out_features: int, in_group_size: int, beam_size: int, positions_in: int = 1) -> bool:
+    return bool(_lib.aqlm_hip_code_search_1x16_xtx_supported(int(out_features), int(in_group_size), int(beam_size), int(positions_in)))
+
+
+def code_search_1x16_xtx_step(t, loss, codes_in, H, q, codebook, scales, beam_size: int, return_t: bool = False) -> XtxStep:
+    """One call of aqlm_hip_code_search_1x16_xtx: the calibrated search of ONE input group of a 1x16 layer for every output row
+    (include/aqlm_hip.h has the definition and the arithmetic, tests/x16_xtx_model.py its numpy restatement).  ``t`` fp32 [positions, out,
+    g] -- any position / row stride with g contiguous (a view into a wider buffer is read in place) --, ``loss`` fp32 [positions, out],
+    ``codes_in`` int16 [positions, out, 1], ``H`` fp32 [g, g] = ``XTX[group, group]``, ``q`` fp32 [65536] (or [1, 65536]) = ``C H C^T``
+    unscaled, ``codebook`` 65536 x g elements fp16 / bf16, ``scales`` [out] elements in the same dtype or None.  Returns an ``XtxStep``
+    with int16 codes [beam_size, out, 1].  Three launches on the current stream through a workspace allocated on the current device;
+    no synchronisation."""
+    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError(f"code_search_1x16_xtx_step: t must be fp32 [positions, out, g] on the GPU, got {t.dtype} {tuple(t.shape)}")
+    positions, out_features, g = (int(x) for x in t.shape)
+    beam_size = int(beam_size)
+    dev = t.device
+    if t.stride(2) != 1 or t.stride(1) < g or (positions > 1 and t.stride(0) < g):
+        t = t.contiguous()
+    if codebook.numel() != 65536 * g or codebook.device != dev:
+        raise ValueError(f"code_search_1x16_xtx_step: the codebook must hold 65536 x {g} elements on {dev}")
+    dt = _dtype_id(codebook)
+    codebook = _c(codebook)
+    if q.dim() == 2 and q.shape[0] == 1:
+        q = q[0]
+    for name, x, shape, dtype in (("loss", loss, (positions, out_features), torch.float32), ("codes_in", codes_in, (positions, out_features, 1), torch.int16),
+                                  ("H", H, (g, g), torch.float32), ("q", q, (65536,), torch.float32)):
+        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
+            raise ValueError(f"code_search_1x16_xtx_step: {name} must be {dtype} {list(shape)} on {dev}, got {x.dtype} {tuple(x.shape)}")
+    loss, codes_in, H, q = _c(loss), _c(codes_in), _c(H), _c(q)
+    if scales is not None:
+        if scales.numel() != out_features or scales.device != dev or scales.dtype != codebook.dtype:
+            raise ValueError(f"code_search_1x16_xtx_step: scales must hold {out_features} elements of {codebook.dtype} on {dev}")
+        scales = _c(scales)
+    if not code_search_1x16_xtx_supported(out_features, g, beam_size, positions):
+        raise NotImplementedError(f"code_search_1x16_xtx_step: g={g} beam_size={beam_size} positions={positions} is outside the kernel")
+    out = XtxStep(torch.empty((beam_size, out_features), dtype=torch.float32, device=dev),
+                  torch.empty((beam_size, out_features, 1), dtype=torch.int16, device=dev),
+                  torch.empty((beam_size, out_features), dtype=torch.uint8, device=dev),
+                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev),
+                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev) if return_t else None)
+    need = int(_lib.aqlm_hip_code_search_1x16_xtx_workspace_bytes(out_features, g, beam_size, positions))
+    with _device_guard(dev):
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        rc = _lib.aqlm_hip_code_search_1x16_xtx(t.data_ptr(), t.stride(0), t.stride(1), loss.data_ptr(), codes_in.data_ptr(), H.data_ptr(),
+                                                q.data_ptr(), codebook.data_ptr(), dt, _ptr(scales), out_features, g, beam_size, positions,
+                                                out.loss.data_ptr(), out.codes.data_ptr(), out.source.data_ptr(), out.delta.data_ptr(),
+                                                _ptr(out.t), workspace.data_ptr(), need, _stream_ptr(dev))
+    if rc:
+        _native.check(rc, "aqlm code search 1x16 xtx")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------
 # expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
 # ------------------------------------------------------------------------------------------------------
 ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words

@@ -50,7 +50,8 @@ The calibrated update (``find_optimal_codes_calibrated``, ``update_codes_calibra
 ``||X W_ref^T - X W_q^T||^2`` given ``XTX = X^T X`` of calibration activations -- the reference's src/beam_search_xtx.py, the search
 that produces an AQLM layer.  K x 8 layers on the MI355X (fp16 / bf16 codebooks and scales, int8 codes, fp32 ``XTX``, ``beam_size`` up
 to 16) run ``aqlm_hip_code_search_kx8_xtx`` once per input group (tests/kx8_xtx_model.py restates its
-arithmetic); everything else runs a torch route of the same incremental form.
+arithmetic); 1x16 layers (int16 codes, ``beam_size`` up to 8) run ``aqlm_hip_code_search_1x16_xtx`` the same way (section 4.8q;
+tests/x16_xtx_model.py); everything else runs a torch route of the same incremental form.
 
 Memory: the 1x16 index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
 state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.  The
@@ -407,6 +408,18 @@ def takes_code_search_kernel_kx8_xtx(num_codebooks: int, nbits_per_codebook: int
                 and in_group_size in (8, 16, 32) and 1 <= beam_size <= 16 and on_gpu and dtypes_ok and supported)
 
 
+def takes_code_search_kernel_1x16_xtx(nbits_per_codebook: int, num_codebooks: int, out_group_size: int, in_group_size: int, beam_size: int,
+                                      on_gpu: bool, dtypes_ok: bool, supported: bool) -> bool:
+    """Whether a ``find_optimal_codes_calibrated`` call runs ``aqlm_hip_code_search_1x16_xtx`` -- a pure function of: the scheme (ONE
+    codebook of 16 bits, ``out_group_size`` 1, g 8 or 16), ``beam_size`` 1 to 8, ``on_gpu`` (every tensor on the GPU), ``dtypes_ok``
+    (codebooks and scales in ONE of fp16 / bf16, codes int16, ``XTX`` fp32, the target fp32 / fp16 / bf16 -- a float64 target asks for
+    float64 arithmetic and takes the torch route), ``supported`` (the library's ``_supported`` query) and the ``CODE_SEARCH_KERNEL``
+    switch.  No region is declined on timing grounds: the kernel route took 0.028 to 0.124 of the torch route's time in every cell
+    measured (profiles/code_update_xtx_1x16.json)."""
+    return bool(CODE_SEARCH_KERNEL and num_codebooks == 1 and nbits_per_codebook == 16 and out_group_size == 1
+                and in_group_size in (8, 16) and 1 <= beam_size <= 8 and on_gpu and dtypes_ok and supported)
+
+
 def _channel_errors(weight: torch.Tensor, reference: torch.Tensor, XTX: torch.Tensor) -> torch.Tensor:
     """[out]: ``(W - W_ref)[o] XTX (W - W_ref)[o]^T``"""
     error = weight - reference
@@ -494,14 +507,29 @@ def _calibrated_codes_torch(XTX: torch.Tensor, reference: torch.Tensor, books: t
 CALIBRATED_BLOCK_GROUPS = 16
 
 
+def _xtx_step_kx8(t, loss, codes_in, H, q, books, scales, beam_size, order):
+    from .inference_kernels import hip_kernel
+
+    return hip_kernel.code_search_kx8_xtx_step(t, loss, codes_in, H, q, books, scales, beam_size, dim_order=order)
+
+
+def _xtx_step_1x16(t, loss, codes_in, H, q, books, scales, beam_size, order):
+    from .inference_kernels import hip_kernel
+
+    return hip_kernel.code_search_1x16_xtx_step(t, loss, codes_in, H, q[0], books, scales, beam_size)  # (one codebook: no order)
+
+
 def _calibrated_codes_kernel(XTX: torch.Tensor, reference: torch.Tensor, codebooks: torch.Tensor, prev_codes: torch.Tensor,
                              scales: Optional[torch.Tensor], beam_size: int, group_order: Sequence[int],
-                             dim_orders: Sequence[Sequence[int]], block_groups: int) -> torch.Tensor:
-    """[out, in_groups, K] int8: the same search with one ``aqlm_hip_code_search_kx8_xtx`` launch per input group.  A host loop, no
-    ``.item()`` and no host synchronisation; hypotheses are carried by back-pointers (``source`` of every launch) resolved at the end.
-    The initial ``T`` and losses are formed in float64 and rounded once.  Transient memory: ``T`` [beam_size, out, in] fp32 and, at a
-    block's end, its gathered copy; float64 copies of ``XTX`` and the target while ``T`` is formed."""
-    from .inference_kernels import hip_kernel
+                             dim_orders: Sequence[Sequence[int]], block_groups: int, step_fn=_xtx_step_kx8,
+                             q_per_block: bool = False) -> torch.Tensor:
+    """[out, in_groups, K] in the dtype of ``prev_codes``: the same search with one call of ``step_fn`` per input group
+    (``_xtx_step_kx8``: ``aqlm_hip_code_search_kx8_xtx``, int8 codes, tables of 256; ``_xtx_step_1x16``: ``aqlm_hip_code_search_1x16_xtx``,
+    int16 codes, one table of 65536).  A host loop, no ``.item()`` and no host synchronisation; hypotheses are carried by back-pointers
+    (``source`` of every launch) resolved at the end.  The initial ``T`` and losses are formed in float64 and rounded once.
+    ``q_per_block``: ``q = C H C^T`` is formed for the groups of a block when the block starts (a table of 65536 entries: 256 KB per
+    group), not for the whole layer up front.  Transient memory: ``T`` [beam_size, out, in] fp32 and, at a block's end, its gathered
+    copy; float64 copies of ``XTX`` and the target while ``T`` is formed."""
     from .utils import _dequantize_weight
 
     K, size, _, g = codebooks.shape
@@ -518,7 +546,7 @@ def _calibrated_codes_kernel(XTX: torch.Tensor, reference: torch.Tensor, codeboo
     del error
     blocks = XTX.reshape(ng, g, ng, g).diagonal(dim1=0, dim2=2).permute(2, 0, 1).contiguous()  # [ng, g, g]
     books32 = flat_books.to(torch.float32)
-    q_all = torch.einsum("ksf,jfh,ksh->jks", books32, blocks, books32).contiguous()  # [ng, K, 256]
+    q_all = None if q_per_block else torch.einsum("ksf,jfh,ksh->jks", books32, blocks, books32).contiguous()  # [ng, K, size]
     columns = (torch.tensor(list(group_order), dtype=torch.int64)[:, None] * g + torch.arange(g)[None, :]).flatten().to(dev)
     history = []
     block_groups = max(1, int(block_groups))
@@ -530,10 +558,13 @@ def _calibrated_codes_kernel(XTX: torch.Tensor, reference: torch.Tensor, codeboo
         x_block = x_rows.index_select(1, cols)  # [width, width]
         t_block = T.index_select(2, cols)  # [P, out, width]
         d_block = ancestor = None
+        if q_per_block:  # [members, K, size]: (C_c H_j) . C_c row by row
+            h_block = blocks[torch.tensor(members, dtype=torch.int64, device=dev)]
+            q_block = ((books32[None] @ h_block[:, None]) * books32[None]).sum(-1).contiguous()
         for i, j in enumerate(members):
             P = t_block.shape[0]
-            step = hip_kernel.code_search_kx8_xtx_step(t_block[:, :, i * g:(i + 1) * g], loss, prev_codes[None, :, j, :].expand(P, out, K).contiguous(),
-                                                       blocks[j], q_all[j], flat_books, flat_scales, beam_size, dim_order=dim_orders[start + i])
+            step = step_fn(t_block[:, :, i * g:(i + 1) * g], loss, prev_codes[None, :, j, :].expand(P, out, K).contiguous(), blocks[j],
+                           q_block[i] if q_per_block else q_all[j], flat_books, flat_scales, beam_size, dim_orders[start + i])
             loss = step.loss
             history.append((j, step.codes, step.source))
             source = step.source.to(torch.int64)
@@ -575,8 +606,11 @@ def find_optimal_codes_calibrated(XTX: torch.Tensor, reference_weight: torch.Ten
     Routes: K x 8 layers (1 to 8 codebooks of 256 entries, g 8 / 16 / 32, ``out_group_size`` 1, ``beam_size`` up to 16) with every tensor
     on the MI355X, codebooks and scales in one of fp16 / bf16, codes int8, ``XTX`` fp32 and a target in fp32 / fp16 / bf16 run
     ``aqlm_hip_code_search_kx8_xtx`` once per input group (transient: ``T`` [beam_size, out, in] fp32, twice at the
-    end of every ``CALIBRATED_BLOCK_GROUPS`` groups); everything else -- 1x16, host tensors, fp32 / fp64 parameters, a float64
-    target (on the GPU too), ``out_group_size > 1``, ``beam_size > 16``, ``CODE_SEARCH_KERNEL = False`` -- runs a torch route written
+    end of every ``CALIBRATED_BLOCK_GROUPS`` groups); 1x16 layers (one codebook of 65536 entries, g 8 / 16, ``out_group_size`` 1,
+    ``beam_size`` up to 8, int16 codes, the same dtypes otherwise) run ``aqlm_hip_code_search_1x16_xtx`` through the same host loop
+    (``q`` is formed per block of groups; a ``dim_order`` is accepted and has no effect); everything else -- host
+    tensors, fp32 / fp64 parameters, a float64 target (on the GPU too), ``out_group_size > 1``, ``beam_size > 16`` (1x16: > 8),
+    ``CODE_SEARCH_KERNEL = False`` -- runs a torch route written
     from the reference's definition (float64 when the target is float64;
     scores in chunks of ``CODE_SEARCH_CHUNK_VALUES``; the same transient in the compute dtype).  ``sparsity_regularizer`` raises
     ``NotImplementedError``."""
@@ -625,6 +659,19 @@ def find_optimal_codes_calibrated(XTX: torch.Tensor, reference_weight: torch.Ten
     if takes_code_search_kernel_kx8_xtx(K, nbits, out_group_size, in_group_size, beam_size, on_gpu, dtypes_ok, supported):
         return _calibrated_codes_kernel(XTX, reference_weight, codebooks, prev_codes, scales, beam_size, groups, orders,
                                         CALIBRATED_BLOCK_GROUPS).reshape(prev_codes.shape)
+
+    wide_ok = (codebooks.dtype in (torch.float16, torch.bfloat16) and (scales is None or scales.dtype == codebooks.dtype)
+               and prev_codes.dtype == torch.int16 and XTX.dtype == torch.float32
+               and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16))
+    wide_supported = False
+    if CODE_SEARCH_KERNEL and on_gpu and K == 1 and nbits == 16 and out_group_size == 1 and in_group_size in (8, 16) and 1 <= beam_size <= 8:
+        from .inference_kernels import hip_kernel
+
+        wide_supported = hip_kernel.code_search_1x16_xtx_supported(out_features, in_group_size, beam_size, beam_size)
+    if takes_code_search_kernel_1x16_xtx(nbits, K, out_group_size, in_group_size, beam_size, on_gpu, wide_ok, wide_supported):
+        # (dim_order of a one-codebook layer was checked above and has no effect)
+        return _calibrated_codes_kernel(XTX, reference_weight, codebooks, prev_codes, scales, beam_size, groups, orders,
+                                        CALIBRATED_BLOCK_GROUPS, _xtx_step_1x16, True).reshape(prev_codes.shape)
 
     compute = torch.float64 if reference_weight.dtype == torch.float64 else torch.float32
     found = _calibrated_codes_torch(XTX.to(compute), reference_weight.to(compute), codebooks.detach().to(compute),

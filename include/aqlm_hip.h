@@ -1003,6 +1003,50 @@ int aqlm_hip_code_search_kx8_xtx(const void* t, long t_position_stride, long t_r
                                  void* delta_out, void* t_out /* NULL ok */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The CALIBRATED code search of the 1x16 schemes (one codebook of 65536 entries, out_group_size 1, g = 8 / 16): one input group of
+ * the same search for every output row o of one layer.  It is aqlm_hip_code_search_kx8_xtx with K = 1 and 65536
+ * candidates per position, and it is held to the same arithmetic bit for bit (tests/x16_xtx_model.py restates it in numpy): every
+ * operation below is ONE IEEE fp32 operation rounded to nearest, no fused multiply-adds, sums over f ascending from the first
+ * product.  For row o with scale s = float(scales[o]) (scales NULL: s = 1), 2s = 2 * s, ss = s * s, and position b of positions_in
+ * holding loss L[b], slice t[b] and code p = codes_in[b] (the int16 mod 65536):
+ *     w[f]     = s * C[p][f]
+ *     u[b][f'] = t[b][f'] + sum_f w[f] * H[f][f']
+ *     base[b]  = (L[b] + 2s * sum_f C[p][f] * u[b][f]) - ss * q[p]
+ *     S(b, s') = (base[b] - 2s * sum_f C[s'][f] * u[b][f]) + ss * q[s']                  a result of -0 is replaced by +0
+ *     keep the best beam_size of the positions_in * 65536 hypotheses, ordered by (S, b * 65536 + s') ascending: equal scores go to
+ *     the smaller flat index; NaN scores come last, in the order of their flat indices.  Rank i, from (b, s'):
+ *         codes_out[i] = s';  source[i] = b;  loss_out[i] = S(b, s')
+ *         dw[f] = s * C[s'][f] - s * C[p][f];  delta[i][f] = dw[f];  t_out[i][f'] = t[b][f'] - sum_f dw[f] * H[f][f']
+ * The 65536 scores of a position are never all formed in this arithmetic: the matrix unit scans approximate scores, and a candidate
+ * is re-scored exactly unless its approximate score exceeds the largest of the beam_size best exact scores met so far by more than
+ * a bound E on the approximation's error, derived from the arithmetic.  The result is the definition's whatever
+ * the order of the scan.  A rank that only a NaN score could take gets position 0 and the smallest code not yet among the ranks
+ * before it, with loss NaN (the definition's answer when the scores of position 0 are NaN).
+ * t: fp32 [positions_in][out][g] with element strides per position and per row, g contiguous; loss fp32 [positions_in][out];
+ * codes_in / codes_out int16 [positions][out] (32768 .. 65535 negative); H fp32 [g][g] (not assumed symmetric); q fp32 [65536],
+ * q[s] = C[s] H C[s]^T unscaled, 16-byte aligned; codebook [65536][g] fp16 / bf16, 16-byte aligned; scales [out] in the same dtype or
+ * NULL; loss_out fp32 [beam_size][out]; source uint8 [beam_size][out]; delta and t_out (may be NULL) fp32 [beam_size][out][g].
+ * No address, LDS slot or loop bound is formed from a score: NaN / Inf in t, loss, H or q still give codes in 0 .. 65535 and
+ * sources below positions_in, and cannot stall a loop (a column whose bound is not finite refines every candidate).  Three
+ * stream-ordered launches through `workspace` (aqlm_hip_code_search_1x16_xtx_workspace_bytes, 16-byte aligned): the maxima of |C|
+ * and |q|, the scan over column blocks x codebook splits, the merge of a row's lists.  No allocation, no synchronisation, no global
+ * atomics, no scratch: the output is a function of the arguments alone.
+ * Supported (aqlm_hip_code_search_1x16_xtx_supported): out >= 1, g in {8, 16}, 1 <= beam_size, positions_in <=
+ * AQLM_HIP_CODE_SEARCH_1X16_XTX_MAX_BEAM.
+ * Checks, in the order of aqlm_hip_code_search_kx8_xtx: a null pointer (scales and t_out may be NULL); misalignment; out or g below 1,
+ * a row stride of t below g, or a position stride below g with several positions (AQLM_HIP_E_INVALID); dtype outside fp16 / bf16, g,
+ * beam_size or positions_in outside the supported set (AQLM_HIP_E_UNSUPPORTED); a workspace below the size the query returns
+ * (AQLM_HIP_E_INVALID).  Nothing is launched on bad arguments.
+ */
+#define AQLM_HIP_CODE_SEARCH_1X16_XTX_MAX_BEAM 8
+int aqlm_hip_code_search_1x16_xtx_supported(int out_features, int in_group_size, int beam_size, int positions_in);
+size_t aqlm_hip_code_search_1x16_xtx_workspace_bytes(int out_features, int in_group_size, int beam_size, int positions_in);
+int aqlm_hip_code_search_1x16_xtx(const void* t, long t_position_stride, long t_row_stride, const void* loss, const void* codes_in,
+                                  const void* h, const void* q, const void* codebook, int dtype, const void* scales, int out_features,
+                                  int in_group_size, int beam_size, int positions_in, void* loss_out, void* codes_out, void* source_out,
+                                  void* delta_out, void* t_out /* NULL ok */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Row-parallel ("in"-split) layers over several MI355X: the finalize of the prepacked matvec fused with a ONE-SHOT
  * all-reduce over xGMI (no reference counterpart -- the reference has no tensor parallelism; BASELINE.json north star:
  * the 70B layer 8192 -> 28672 split over 8 GPUs).  Every rank runs aqlm_hip_gemv_1x16_packed_partials on its shard (the
