@@ -17,6 +17,7 @@ ABI_VERSION = 9
 F16, BF16 = 0, 1
 F32 = 2   # dW and the outputs of the gradient entries, and the reference of aqlm_hip_code_search_1x16, only
 CODE_SEARCH_EPS = 2.0 ** -17   # AQLM_HIP_CODE_SEARCH_EPS
+KMEANS_EPS = 2.0 ** -17        # AQLM_HIP_KMEANS_EPS
 E_INVALID, E_UNSUPPORTED = -1, -2
 MAX_GEMV_BATCH = 8
 OP_GEMM_1X16_MFMA = 1
@@ -192,6 +193,10 @@ SIGNATURES = {
     "aqlm_hip_code_search_1x16_supported": (_ci, [_ci, _ci, _ci]),
     "aqlm_hip_code_search_1x16_workspace_bytes": (_sz, [_cl, _ci]),
     "aqlm_hip_code_search_1x16": (_ci, [_vp, _ci, _cl, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _cl, _vp, _vp, _sz, _vp]),
+    "aqlm_hip_kmeans_supported": (_ci, [_cl, _ci, _ci]),
+    "aqlm_hip_kmeans_workspace_bytes": (_sz, [_cl, _ci, _ci]),
+    "aqlm_hip_kmeans_assign": (_ci, [_vp, _cl, _vp, _ci, _ci, ctypes.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aqlm_hip_kmeans_update": (_ci, [_vp, _vp, _cl, _ci, _ci, ctypes.c_float, _vp, _vp]),
     "aqlm_hip_code_search_kx8_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
     "aqlm_hip_code_search_kx8_workspace_bytes": (_sz, [_cl, _ci, _ci, _ci]),
     "aqlm_hip_code_search_kx8": (_ci, [_vp, _ci, _cl, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(_ci), _vp, _ci, _cl, _vp,

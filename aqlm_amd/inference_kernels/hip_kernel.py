@@ -1277,6 +1277,84 @@ def code_search_1x16(reference, scales, codebook, in_group_size: int, group_ids=
 
 
 # ------------------------------------------------------------------------------------------------------
+# k-means initialisation: one Lloyd iteration (aqlm_hip_kmeans_assign, aqlm_hip_kmeans_update)
+# ------------------------------------------------------------------------------------------------------
+KMEANS_EPS = _native.KMEANS_EPS  # the accuracy contract of include/aqlm_hip.h: computed scores within eps * (|x|^2 + max|C|^2)
+
+
+def kmeans_supported(n: int, k: int, d: int) -> bool:
+    return bool(_lib.aqlm_hip_kmeans_supported(int(n), int(k), int(d)))
+
+
+def _kmeans_operands(who, data, centroids):
+    if data.dim() != 2 or data.dtype != torch.float32 or not data.is_cuda:
+        raise ValueError(f"{who}: data must be fp32 [n, d] on the GPU, got {data.dtype} {tuple(data.shape)} on {data.device}")
+    if centroids.dim() != 2 or centroids.dtype != torch.float32 or centroids.device != data.device or centroids.shape[1] != data.shape[1]:
+        raise ValueError(f"{who}: centroids must be fp32 [k, {data.shape[1]}] on {data.device}, got {centroids.dtype} "
+                         f"{tuple(centroids.shape)} on {centroids.device}")
+    n, d, k = int(data.shape[0]), int(data.shape[1]), int(centroids.shape[0])
+    if not kmeans_supported(n, k, d):
+        raise NotImplementedError(f"{who}: n={n} k={k} d={d} is outside the kernel (d 8 or 16, k a multiple of 128 up to 65536, "
+                                  "1 <= n < 2^31)")
+    return n, k, d
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    t = _c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _kmeans_assign_op(data, centroids, data_absmax, with_sums):
+    n, k, d = _kmeans_operands("kmeans_assign", data, centroids)
+    data, centroids = _aligned16(data), _aligned16(centroids)
+    codes = torch.empty((n,), dtype=torch.int32, device=data.device)
+    sums = torch.empty((k, d) if with_sums else (0, d), dtype=torch.int64, device=data.device)
+    counts = torch.empty((k,) if with_sums else (0,), dtype=torch.int32, device=data.device)
+    ws_bytes = int(_lib.aqlm_hip_kmeans_workspace_bytes(n, k, d))
+    ws = _workspace(data.device, ws_bytes)
+    with _device_guard(data.device):
+        rc = _lib.aqlm_hip_kmeans_assign(data.data_ptr(), n, centroids.data_ptr(), k, d, float(data_absmax), codes.data_ptr(),
+                                         sums.data_ptr() if with_sums else None, counts.data_ptr() if with_sums else None,
+                                         ws.data_ptr(), ws.numel() * 4, _stream_ptr(data.device))
+    if rc:
+        _native.check(rc, "aqlm kmeans assign")
+    return codes, sums, counts
+
+
+def kmeans_assign(data, centroids, data_absmax: float, with_sums: bool = True):
+    """-> (codes int32 [n], sums int64 [k, d], counts int32 [k]): per row of ``data`` [n, d] (fp32, d 8 / 16) the index of the row of
+    ``centroids`` [k, d] (fp32, k a multiple of 128 up to 65536) that minimises ``|C_c|^2 - 2 <x_n, C_c>`` -- equal computed scores
+    give the smallest index, the accuracy contract is in include/aqlm_hip.h (``KMEANS_EPS``) -- and the fixed-point sums and counts of
+    every cluster's points in the unit that ``data_absmax`` (>= every |element| of ``data``) and n set (tests/kmeans_model.py restates
+    it); a point with a non-finite element or one above ``data_absmax`` adds nothing.  ``with_sums=False``: the codes alone (the other two
+    tensors are empty).  Memsets and three launches on the current stream, the centroids' split image in the cached workspace."""
+    return _kmeans_assign_op(data, centroids, float(data_absmax), bool(with_sums))
+
+
+def kmeans_update_(centroids, sums, counts, n: int, data_absmax: float) -> None:
+    """``centroids[c] = sums[c] * 2^-s / counts[c]`` in place where ``counts[c] > 0`` (double arithmetic, one rounding to fp32); an empty
+    cluster keeps its centroid bit for bit.  ``n`` and ``data_absmax``: those of the ``kmeans_assign`` call that made the sums."""
+    if centroids.dim() != 2 or centroids.dtype != torch.float32 or not centroids.is_cuda or not centroids.is_contiguous():
+        raise ValueError(f"kmeans_update_: centroids must be contiguous fp32 [k, d] on the GPU, got {centroids.dtype} {tuple(centroids.shape)}")
+    k, d = int(centroids.shape[0]), int(centroids.shape[1])
+    if (sums.dtype != torch.int64 or tuple(sums.shape) != (k, d) or not sums.is_contiguous() or sums.device != centroids.device
+            or counts.dtype != torch.int32 or tuple(counts.shape) != (k,) or not counts.is_contiguous() or counts.device != centroids.device):
+        raise ValueError(f"kmeans_update_: sums must be contiguous int64 [{k}, {d}] and counts int32 [{k}] on {centroids.device}")
+    with _device_guard(centroids.device):
+        rc = _lib.aqlm_hip_kmeans_update(sums.data_ptr(), counts.data_ptr(), int(n), k, d, float(data_absmax), centroids.data_ptr(),
+                                         _stream_ptr(centroids.device))
+    if rc:
+        _native.check(rc, "aqlm kmeans update")
+
+
+def kmeans_update(centroids, sums, counts, n: int, data_absmax: float) -> torch.Tensor:
+    """``kmeans_update_`` on a copy: the new centroids."""
+    out = centroids.detach().clone(memory_format=torch.contiguous_format)
+    kmeans_update_(out, sums, counts, n, data_absmax)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------
 # beam search over the codebooks of the K x 8 schemes (the V step of PV-tuning; aqlm_hip_code_search_kx8)
 # ------------------------------------------------------------------------------------------------------
 CODE_SEARCH_KX8_MAX_BEAM = 16  # AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM
@@ -2722,6 +2800,22 @@ _LIB.impl("code_search_1x16", _code_search_1x16_op, "CUDA")
 torch.library.register_fake("aqlm::code_search_1x16")(
     lambda reference, scales, codebook, group_ids, geometry: reference.new_empty(
         (int(group_ids.numel()) if group_ids is not None else int(geometry[0]) * (int(geometry[1]) // int(geometry[2])),), dtype=torch.int16))
+# one Lloyd iteration of k-means: the assignment with the clusters' fixed-point sums, and the update of the centroids in place
+_LIB.define("kmeans_assign(Tensor data, Tensor centroids, float data_absmax, bool with_sums) -> (Tensor, Tensor, Tensor)")
+_LIB.impl("kmeans_assign", _kmeans_assign_op, "CUDA")
+
+
+def _fake_kmeans_assign(data, centroids, data_absmax, with_sums):
+    k, d = (int(centroids.shape[0]), int(centroids.shape[1])) if with_sums else (0, int(centroids.shape[1]))
+    return (data.new_empty((data.shape[0],), dtype=torch.int32), data.new_empty((k, d), dtype=torch.int64),
+            data.new_empty((k,), dtype=torch.int32))
+
+
+torch.library.register_fake("aqlm::kmeans_assign")(_fake_kmeans_assign)
+_LIB.define("kmeans_update_(Tensor(a!) centroids, Tensor sums, Tensor counts, int n, float data_absmax) -> ()")
+_LIB.impl("kmeans_update_", kmeans_update_, "CUDA")
+torch.library.register_fake("aqlm::kmeans_update_")(lambda centroids, sums, counts, n, data_absmax: None)
+
 # beam search over the codebooks of a K x 8 layer; geometry = [out_features, in_features, K, g, beam_size] + dim_order (or nothing);
 # returns the codes [n, K] int8 and the fp32 score of every returned hypothesis [n]
 _LIB.define("code_search_kx8(Tensor reference, Tensor? scales, Tensor codebooks, Tensor prev_codes, Tensor? group_ids, int[] geometry)"

@@ -53,6 +53,12 @@ to 16) run ``aqlm_hip_code_search_kx8_xtx`` once per input group (DESIGN.md sect
 arithmetic); 1x16 layers (int16 codes, ``beam_size`` up to 8) run ``aqlm_hip_code_search_1x16_xtx`` the same way (section 4.8q;
 tests/x16_xtx_model.py); everything else runs a torch route of the same incremental form.
 
+The first codes and codebooks (``fit_kmeans``, ``find_nearest_cluster``, ``init_aq_kmeans``, ``init_layer_kmeans_``): the reference's
+residual k-means (src/aq.py ``init_aq_kmeans``, src/kmeans.py).  fp32 data on the MI355X with 8 or 16 values per point and 128 to
+65536 centroids (a multiple of 128) runs one Lloyd iteration as ``aqlm_hip_kmeans_assign`` -- the assignment on the matrix unit with
+both operands as split fp16 pairs, the clusters' sums as fixed-point integers in the same launch -- and ``aqlm_hip_kmeans_update``
+(tests/kmeans_model.py restates the integer side); everything else runs the reference's formula in torch.
+
 Memory: the 1x16 index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
 state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.  The
 K x 8 route keeps no derived state: its transient is the per-stream workspace (at most 33.6 MB).
@@ -68,6 +74,7 @@ only) and ``ShardedQuantizedLinear`` -- ``make_trainable`` leaves both frozen an
 from __future__ import annotations
 
 import math
+import warnings
 from typing import List, Optional, Sequence
 
 import torch
@@ -709,3 +716,221 @@ def update_codes_calibrated_(layer, reference_weight: torch.Tensor, XTX: torch.T
     changed = (new != codes).any(-1).sum()
     codes.copy_(new)
     return changed
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# residual k-means: the first codes and codebooks of a layer (the reference's init_aq_kmeans)
+# ---------------------------------------------------------------------------------------------------------------------------
+# The switch of the k-means kernels: False sends every k-means call through the torch route.
+KMEANS_KERNEL = True
+# Scores the torch route of k-means materialises at a time (the reference's ``block_size_vals`` is 2^30).
+KMEANS_CHUNK_VALUES = 1 << 27
+_KMEANS_NOT_OFFERED = ("greedy_init", "use_faiss", "devices")
+
+
+def takes_kmeans_kernel(k: int, dim: int, on_gpu: bool, dtype: torch.dtype, out_group_size: int = 1) -> bool:
+    """Whether a k-means call runs ``aqlm_hip_kmeans_assign`` / ``aqlm_hip_kmeans_update`` -- a pure function of: ``k`` (a multiple of
+    128 from 128 to 65536: both the 256-entry and the 65536-entry codebooks), ``dim`` (8 or 16 values per point), ``on_gpu`` (data and
+    centroids on the GPU), ``dtype`` (fp32), ``out_group_size`` 1 (the points of ``init_aq_kmeans`` are then groups of ``dim`` input
+    features) and the ``KMEANS_KERNEL`` switch.  No region is declined on timing grounds: the kernel route took 0.028 to 0.068 of the
+    torch route's time per iteration and 0.032 to 0.139 for a whole initialisation in every cell measured, k = 256 included
+    (profiles/kmeans.json)."""
+    return bool(KMEANS_KERNEL and on_gpu and dtype == torch.float32 and dim in (8, 16) and out_group_size == 1
+                and 128 <= k <= 65536 and k % 128 == 0)
+
+
+def _kmeans_refuse(who: str, options: dict) -> None:
+    for name in _KMEANS_NOT_OFFERED:
+        if options.pop(name, None):
+            raise NotImplementedError(f"{who}: {name} is not offered")
+    if options:
+        raise TypeError(f"{who}: unexpected arguments {sorted(options)}")
+
+
+def _kmeans_absmax(who: str, data: torch.Tensor) -> float:
+    """max|data| -- the one synchronisation of a fit; a NaN or an Inf anywhere in ``data`` comes out of it and raises."""
+    if data.dim() != 2 or not data.is_floating_point() or data.shape[0] < 1:
+        raise ValueError(f"{who}: data must be a floating-point [n, d] tensor with n >= 1, got {data.dtype} {tuple(data.shape)}")
+    absmax = float(data.abs().max())
+    if not math.isfinite(absmax):
+        raise ValueError(f"{who}: data holds a non-finite value")
+    return absmax
+
+
+def _nearest_torch(data: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """[n] int64, the reference's formula: ``argmax_c <x, C_c> - |C_c|^2 / 2`` in chunks of ``KMEANS_CHUNK_VALUES`` scores."""
+    norms = torch.bmm(centroids[:, None, :], centroids[:, :, None]).flatten()
+    rows = max(1, KMEANS_CHUNK_VALUES // centroids.shape[0])
+    out = torch.empty((data.shape[0],), dtype=torch.int64, device=data.device)
+    for a in range(0, data.shape[0], rows):
+        out[a:a + rows] = torch.addmm(norms, data[a:a + rows], centroids.T, beta=-0.5).argmax(1)
+    return out
+
+
+def _kmeans_nearest(data: torch.Tensor, centroids: torch.Tensor, kernel: bool) -> torch.Tensor:
+    if kernel:
+        from .inference_kernels import hip_kernel
+
+        return hip_kernel.kmeans_assign(data, centroids, 0.0, with_sums=False)[0].to(torch.int64)
+    return _nearest_torch(data, centroids)
+
+
+def _kmeans_step(data: torch.Tensor, centroids: torch.Tensor, absmax: float, kernel: bool) -> torch.Tensor:
+    """The centroids after one Lloyd iteration; a cluster without points keeps its centroid."""
+    if kernel:
+        from .inference_kernels import hip_kernel
+
+        _, sums, counts = hip_kernel.kmeans_assign(data, centroids, absmax)
+        return hip_kernel.kmeans_update(centroids, sums, counts, data.shape[0], absmax)
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", message="index_reduce.. is in beta")
+        return centroids.clone().index_reduce_(0, _nearest_torch(data, centroids), data, "mean", include_self=False)
+
+
+def _randperm(n: int, generator: Optional[torch.Generator], device) -> torch.Tensor:
+    where = generator.device if generator is not None else "cpu"
+    return torch.randperm(n, generator=generator, device=where).to(device)
+
+
+@torch.no_grad()
+def _fit_kmeans(data, k, max_iter, check_every, rtol, atol, initial_centroids, generator, out_group_size=1):
+    absmax = _kmeans_absmax("fit_kmeans", data)
+    if k < 1:
+        raise ValueError(f"fit_kmeans: k = {k} centroids")
+    if initial_centroids is None:
+        rows = _randperm(data.shape[0], generator, data.device)[:k]
+        if k > data.shape[0]:  # fewer points than centroids (a 65536-entry codebook on a small layer): the draw repeats
+            rows = rows[torch.arange(k, device=data.device) % data.shape[0]]
+        centroids = data[rows, :]
+    else:
+        if tuple(initial_centroids.shape) != (k, data.shape[1]):
+            raise ValueError(f"fit_kmeans: initial_centroids must be [{k}, {data.shape[1]}], got {tuple(initial_centroids.shape)}")
+        centroids = initial_centroids.to(device=data.device, dtype=data.dtype)
+    data = data.contiguous()
+    centroids = centroids.contiguous()
+    kernel = takes_kmeans_kernel(k, data.shape[1], data.is_cuda, data.dtype, out_group_size)
+    iterations = 0
+    for i in range(max_iter):
+        new_centroids = _kmeans_step(data, centroids, absmax, kernel)
+        iterations = i + 1
+        if i % check_every == 0 and torch.allclose(new_centroids, centroids, rtol=rtol, atol=atol):
+            break
+        centroids = new_centroids
+    indices = _kmeans_nearest(data, centroids, kernel)
+    return centroids, indices, centroids[indices], iterations
+
+
+def fit_kmeans(data: torch.Tensor, k: int, max_iter: int = 1000, check_every: int = 10, rtol: float = 1e-6, atol: float = 1e-8,
+               initial_centroids: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, *,
+               return_iterations: bool = False, **unsupported):
+    """Lloyd's k-means of ``data`` [n, d] into ``k`` centroids -- the reference's ``fit_kmeans`` (src/kmeans.py:24-117) -> ``(centroids
+    [k, d], indices int64 [n], reconstructed [n, d])``, with the number of Lloyd iterations run as a fourth item under
+    ``return_iterations``.  The start is ``initial_centroids`` or ``data[randperm(n, generator)[:k]]`` (with fewer than ``k`` points the
+    draw repeats -- the reference fails there: the repeats tie with their originals, never win and stay where they are, so a
+    65536-entry codebook can be fitted to a small layer).  Every iteration assigns each
+    point to ``argmin_c |C_c|^2 - 2 <x, C_c>`` and moves every centroid that has points to their mean (one without keeps its place);
+    at ``i % check_every == 0`` the loop stops when ``allclose(new, old, rtol, atol)`` and keeps the OLD centroids, as the reference
+    does (this synchronises: k-means is not meant to be captured); a last assignment gives the indices.
+
+    Routes: fp32 data on the MI355X with d 8 / 16 and k a multiple of 128 up to 65536 runs ``aqlm_hip_kmeans_assign`` /
+    ``aqlm_hip_kmeans_update`` (the n x k scores are accumulators of the matrix unit; equal scores give the smallest
+    index; the means are sums of fixed-point integers, so they are bit-reproducible); everything else (host tensors, other d or k,
+    other dtypes, ``KMEANS_KERNEL = False``) runs the reference's formula in torch.  Once per fit ``data`` is checked to be finite
+    (one synchronisation; ``ValueError`` on both routes).  Not offered: ``greedy_init``, ``use_faiss``, ``devices``
+    (``NotImplementedError``)."""
+    _kmeans_refuse("fit_kmeans", unsupported)
+    out = _fit_kmeans(data, int(k), int(max_iter), int(check_every), rtol, atol, initial_centroids, generator)
+    return out if return_iterations else out[:3]
+
+
+@torch.no_grad()
+def find_nearest_cluster(data: torch.Tensor, centroids: torch.Tensor, **unsupported):
+    """``(indices int64 [n], reconstructed [n, d])``: per row of ``data`` the nearest row of ``centroids`` and that row -- the reference's
+    ``find_nearest_cluster`` (src/kmeans.py:162-186); routes and the finite check as in ``fit_kmeans`` (the kernel route is the
+    assignment entry without its sums)."""
+    _kmeans_refuse("find_nearest_cluster", unsupported)
+    _kmeans_absmax("find_nearest_cluster", data)
+    if centroids.dim() != 2 or centroids.shape[1] != data.shape[1]:
+        raise ValueError(f"find_nearest_cluster: centroids must be [k, {data.shape[1]}], got {tuple(centroids.shape)}")
+    centroids = centroids.to(device=data.device, dtype=data.dtype).contiguous()
+    kernel = takes_kmeans_kernel(centroids.shape[0], data.shape[1], data.is_cuda, data.dtype)
+    indices = _kmeans_nearest(data.contiguous(), centroids, kernel)
+    return indices, centroids[indices]
+
+
+@torch.no_grad()
+def init_aq_kmeans(reference_weight: torch.Tensor, *, num_codebooks: int, out_group_size: int, in_group_size: int, codebook_size: int,
+                   max_iter: int = 100, max_points_per_centroid: Optional[int] = None, generator: Optional[torch.Generator] = None,
+                   **options):
+    """Initial ``(codes int64 [out_groups, in_groups, K], codebooks fp32 [K, codebook_size, out_group_size, in_group_size])`` of an AQLM
+    layer by residual k-means -- the reference's ``init_aq_kmeans`` (src/aq.py:288-356): for each codebook in turn the residue of
+    ``reference_weight`` [out, in], cut into groups of ``out_group_size x in_group_size`` weights, is clustered into ``codebook_size``
+    centroids (``fit_kmeans`` with ``max_iter``, default the 100 of the reference's recipes, and the other ``options`` it takes:
+    ``check_every``, ``rtol``, ``atol``) -- on a random subsample of ``max_points_per_centroid * codebook_size`` groups when that is
+    set -- then every group takes its nearest centroid, which is subtracted from the residue.  Routes as in ``fit_kmeans``;
+    ``out_group_size > 1`` runs the torch route.  A float64 weight is clustered in float64, any other in fp32."""
+    _kmeans_refuse("init_aq_kmeans", {name: options.pop(name) for name in _KMEANS_NOT_OFFERED if name in options})
+    fit_options = {name: options.pop(name) for name in ("check_every", "rtol", "atol") if name in options}
+    if options:
+        raise TypeError(f"init_aq_kmeans: unexpected arguments {sorted(options)}")
+    if reference_weight.dim() != 2 or reference_weight.shape[0] % out_group_size or reference_weight.shape[1] % in_group_size:
+        raise ValueError(f"init_aq_kmeans: a weight of {tuple(reference_weight.shape)} does not divide into groups of "
+                         f"{out_group_size} x {in_group_size}")
+    out_features, in_features = reference_weight.shape
+    out_groups, in_groups = out_features // out_group_size, in_features // in_group_size
+    compute = torch.float64 if reference_weight.dtype == torch.float64 else torch.float32
+    residue = (reference_weight.detach().to(compute).reshape(out_groups, out_group_size, in_groups, in_group_size).swapaxes(-3, -2)
+               .reshape(out_groups * in_groups, out_group_size * in_group_size).clone())
+    kernel = takes_kmeans_kernel(codebook_size, residue.shape[1], residue.is_cuda, residue.dtype, out_group_size)
+    codes, codebooks = [], []
+    for _ in range(num_codebooks):
+        sample = residue
+        if max_points_per_centroid is not None:
+            sample = residue[_randperm(residue.shape[0], generator, residue.device)[:max_points_per_centroid * codebook_size], :]
+        book = _fit_kmeans(sample, int(codebook_size), int(max_iter), int(fit_options.get("check_every", 10)), fit_options.get("rtol", 1e-6),
+                           fit_options.get("atol", 1e-8), None, generator, out_group_size)[0]
+        chosen = _kmeans_nearest(residue, book, kernel)
+        residue -= book[chosen]
+        codes.append(chosen.reshape(out_groups, in_groups, 1))
+        codebooks.append(book.reshape(1, codebook_size, out_group_size, in_group_size))
+    return torch.cat(codes, dim=-1), torch.cat(codebooks, dim=0).to(torch.float32)
+
+
+@torch.no_grad()
+def init_layer_kmeans_(layer, reference_weight: torch.Tensor, **options) -> torch.Tensor:
+    """Give ``layer`` (a ``QuantizedLinear``) its first codes, codebooks and scales from the dense ``reference_weight`` [out, in], as the
+    reference's ``QuantizedWeight.__init__`` does with ``scale_nbits = 0`` (src/aq.py:76-115): ``scales`` = the norm of every output
+    group + 1e-9, ``init_aq_kmeans`` (same ``options``) on ``W / scales``.  Everything is written IN PLACE -- the codes in the
+    checkpoint's storage type, codebooks and scales in the layer's dtype -- so the version counters move and every derived copy
+    (packed / planar codes, dense W, fast lane, inverted index) is rebuilt at the layer's next call, by the rule of ``update_codes_``;
+    dropped canonical codes come back first, inference tensors raise ``RuntimeError``, the experts of a ``QuantizedMixtralExperts``
+    block and ``ShardedQuantizedLinear`` raise ``TypeError``.  Returns ``||W - W_q||^2 / ||W||^2`` of the values written (a 0-dim
+    tensor, before their rounding to the layer's dtype)."""
+    from .inference import QuantizedLinear
+    from .moe import QuantizedMixtralExperts
+    from .sharded import ShardedQuantizedLinear
+    from .utils import _dequantize_weight, pack_int_data
+
+    if isinstance(layer, (QuantizedMixtralExperts, ShardedQuantizedLinear)) or getattr(layer, "_moe_expert", False):
+        raise TypeError(f"init_layer_kmeans_: {type(layer).__name__}{' (an expert of a QuantizedMixtralExperts block)' if getattr(layer, '_moe_expert', False) else ''}"
+                        " is outside the scope of the initialisation (as it is of make_trainable)")
+    if not isinstance(layer, QuantizedLinear):
+        raise TypeError(f"init_layer_kmeans_: expected a QuantizedLinear, got {type(layer).__name__}")
+    _kmeans_refuse("init_layer_kmeans_", {name: options[name] for name in _KMEANS_NOT_OFFERED if name in options})
+    if tuple(reference_weight.shape) != (layer.out_features, layer.in_features):
+        raise ValueError(f"init_layer_kmeans_: the layer is {layer.in_features} -> {layer.out_features}, the weight {tuple(reference_weight.shape)}")
+    layer.restore_canonical_codes()
+    if layer.codes.is_inference() or layer.codebooks.is_inference() or layer.scales.is_inference():
+        raise RuntimeError("init_layer_kmeans_: the parameters of this layer are inference tensors (the model was built or loaded under "
+                           "torch.inference_mode()); they cannot be written in place -- build the model outside inference mode")
+    weight = reference_weight.detach().to(device=layer.codes.device, dtype=torch.float32)
+    out_groups = layer.out_features // layer.out_group_size
+    scales = weight.reshape(out_groups, -1).norm(dim=-1) + 1e-9
+    unscaled = (weight.reshape(out_groups, -1) / scales[:, None]).reshape_as(weight)
+    codes, codebooks = init_aq_kmeans(unscaled, num_codebooks=layer.num_codebooks, out_group_size=layer.out_group_size,
+                                      in_group_size=layer.in_group_size, codebook_size=layer.codebook_size, **options)
+    layer.codes.copy_(pack_int_data(codes, layer.nbits_per_codebook))
+    layer.codebooks.copy_(codebooks)
+    layer.scales.copy_(scales.reshape(-1, 1, 1, 1))
+    error = weight - _dequantize_weight(codes, codebooks, scales.reshape(-1, 1, 1, 1))
+    return error.square().sum() / weight.square().sum()

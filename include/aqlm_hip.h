@@ -901,6 +901,49 @@ int aqlm_hip_code_search_1x16(const void* reference, int reference_dtype, long r
                               size_t workspace_bytes, void* stream);
 
 /*
+ * Residual k-means initialisation (the reference's init_aq_kmeans, src/aq.py:288-356): one Lloyd iteration as two entries.
+ *
+ * aqlm_hip_kmeans_assign replaces the chunked `addmm(bmm norms, data, C^T, beta=-0.5).argmax(1)` of fit_kmeans and
+ * find_nearest_cluster (src/kmeans.py:64-72, 105-112, 175-182) and, when sums_out / counts_out are given, the scatter half of
+ * `index_reduce_(..., "mean", include_self=False)` (src/kmeans.py:76-80).  data [n, d] and centroids [k, d] are contiguous fp32:
+ *     S(n, c)      = |C_c|^2 - 2 <x_n, C_c>
+ *     codes_out[n] = the int32 index of the smallest S THE KERNEL COMPUTED; equal computed scores resolve to the smallest index.
+ * Accuracy, in the form of aqlm_hip_code_search_1x16: the computed score is within E(n) = eps * (|x_n|^2 + max_c |C_c|^2) of the
+ * exact one, eps = AQLM_HIP_KMEANS_EPS = 2^-17, so the chosen index EQUALS the exact argmin whenever the exact margin exceeds 2 E(n).
+ * eps follows from the arithmetic: both operands are scaled by an exact power of two (a point by its own, max|x_n|
+ * into [2^10, 2^11); the centroids by one for the table, max_ct |C_ct| into [2^10, 2^11)) and split into fp16 pairs hi = round(v'),
+ * lo = round(v' - hi); the matrix unit sums hi.hi + lo.hi + hi.lo (d = 8: + lo.lo) of exact products in fp32; |C_c|^2 is d fp32
+ * fused multiply-adds over t ascending; one fused multiply-add forms S.  Valid while every max|x_n| and max|C_ct| is 0 or in
+ * [2^-50, 2^50).  A point with an Inf or NaN element searches with x = 0; a centroid with one never wins; every index is in range.
+ * sums_out ([k, d] int64) and counts_out ([k] int32), both or neither: ZEROED by the entry, then point n adds q_t = rint(x_nt * 2^s)
+ * (ties to even) to sums_out[codes_out[n]][t] and 1 to counts_out[codes_out[n]], s = min(40, 62 - ceil_log2(n)) - E with
+ * data_absmax = m * 2^E, 1 <= m < 2 (zero and subnormal data_absmax: E = -126): integer adds, so the result does not depend on
+ * their order and cannot overflow.  A point with a non-finite element or an element above data_absmax adds nothing.
+ * `workspace` (16-byte aligned, nothing is kept in it): aqlm_hip_kmeans_workspace_bytes = 256 + k * 4 + k * d * 4 bytes (a header,
+ * |C_c|^2, the two fp16 images of the centroids) for a supported shape, else 0.  Supported (aqlm_hip_kmeans_supported): d in {8, 16},
+ * k a multiple of 128 in 128 ... AQLM_HIP_KMEANS_MAX_CENTROIDS, 1 <= n <= AQLM_HIP_KMEANS_MAX_POINTS.  Memsets and three launches,
+ * stream-ordered, no allocation, no synchronisation, no scratch.
+ * Checks, in order: a null pointer (sums_out and counts_out may be NULL together); misalignment (data / centroids / workspace 16
+ * bytes, sums_out 8, the others 4); n, k or d below 1, or a data_absmax that is negative or not finite (AQLM_HIP_E_INVALID); a
+ * shape that is not supported (AQLM_HIP_E_UNSUPPORTED); a workspace that is too small (AQLM_HIP_E_INVALID).  Nothing is launched
+ * on bad arguments.
+ *
+ * aqlm_hip_kmeans_update replaces the mean of that index_reduce_ (src/kmeans.py:76-80): with the n and data_absmax the sums were
+ * made with, centroids_inout[c][t] = (float)((double)sums[c][t] * 2^-s / (double)counts[c]) where counts[c] > 0; an empty
+ * cluster keeps its centroid bit for bit (include_self=False on a clone).  One launch.  Checks: null pointer; misalignment; sizes
+ * and data_absmax as above; the shape.
+ */
+#define AQLM_HIP_KMEANS_MAX_POINTS 2147483647L
+#define AQLM_HIP_KMEANS_MAX_CENTROIDS 65536
+#define AQLM_HIP_KMEANS_EPS 7.62939453125e-06 /* 2^-17 */
+int aqlm_hip_kmeans_supported(long n, int k, int d);
+size_t aqlm_hip_kmeans_workspace_bytes(long n, int k, int d);
+int aqlm_hip_kmeans_assign(const void* data, long n, const void* centroids, int k, int d, float data_absmax, void* codes_out,
+                           void* sums_out, void* counts_out, void* workspace, size_t workspace_bytes, void* stream);
+int aqlm_hip_kmeans_update(const void* sums, const void* counts, long n, int k, int d, float data_absmax, void* centroids_inout,
+                           void* stream);
+
+/*
  * The V step of PV-tuning for the K x 8 schemes (1 <= K <= 8 codebooks of 256 entries, out_group_size 1, g = 8 / 16 / 32: 2x8 g8,
  * 1x8 g8, 4x8 g16, 8x8 g32 ...): the reference's `_beam_search_update_codes_groupwise` (src/beam_search_l2.py) for every group of
  * one layer, without its [groups, beams, 256] score tensor.  The entry is held to ITS OWN ARITHMETIC bit for bit, not to an error
