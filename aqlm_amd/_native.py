@@ -193,6 +193,16 @@ SIGNATURES = {
     "aqlm_hip_code_search_1x16_supported": (_ci, [_ci, _ci, _ci]),
     "aqlm_hip_code_search_1x16_workspace_bytes": (_sz, [_cl, _ci]),
     "aqlm_hip_code_search_1x16": (_ci, [_vp, _ci, _cl, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _cl, _vp, _vp, _sz, _vp]),
+    "aqlm_hip_calib_delta_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_calib_delta": (_ci, [_vp, _vp, _vp, _vp, _ci, _cl, _ci, _ci, _ci, _ci, _ci, _vp, _cl, _vp]),
+    "aqlm_hip_calib_rows_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_calib_rows": (_ci, [_vp, _cl, _vp, _cl, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "aqlm_hip_calib_codebook_grad_1x16_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_calib_codebook_grad_1x16_workspace_bytes": (_sz, [_ci, _ci, _ci]),
+    "aqlm_hip_calib_codebook_grad_1x16": (_ci, [_vp, _cl, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _sz, _vp]),
+    "aqlm_hip_calib_codebook_grad_kx8_supported": (_ci, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_calib_codebook_grad_kx8_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
+    "aqlm_hip_calib_codebook_grad_kx8": (_ci, [_vp, _cl, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _sz, _vp]),
     "aqlm_hip_kmeans_supported": (_ci, [_cl, _ci, _ci]),
     "aqlm_hip_kmeans_workspace_bytes": (_sz, [_cl, _ci, _ci]),
     "aqlm_hip_kmeans_assign": (_ci, [_vp, _cl, _vp, _ci, _ci, ctypes.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -307,7 +307,10 @@ __device__ __forceinline__ float load_ref(const void* p, size_t idx, int dtype) 
   const uint16_t u = reinterpret_cast<const uint16_t*>(p)[idx];
   return dtype == AQLM_HIP_BF16 ? BF16::to_float(u) : F16::to_float(u);
 }
-// dW and the outputs of the gradient kernels: fp16, bf16 or fp32
+// dW and the outputs of the gradient kernels: fp16, bf16 or fp32 (the tag of the third beside F16 / BF16)
+struct F32 {
+  static constexpr int id = AQLM_HIP_F32;
+};
 inline bool dw_dtype_ok(int dtype) { return dtype == AQLM_HIP_F16 || dtype == AQLM_HIP_BF16 || dtype == AQLM_HIP_F32; }
 inline size_t dtype_bytes(int dtype) { return dtype == AQLM_HIP_F32 ? 4 : 2; }
 // the 16 bits of an fp16 / bf16 scale as fp32, for kernels that are not instantiated per scale dtype

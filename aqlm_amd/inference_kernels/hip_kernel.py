@@ -1209,6 +1209,119 @@ def scales_grad_kx8(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = Non
 
 
 # ------------------------------------------------------------------------------------------------------
+# one step of the calibrated training of codebooks and scales on fp32 masters (aqlm_hip_calib_*; tuning.calibrated_loss_and_grads)
+# ------------------------------------------------------------------------------------------------------
+def calib_supported(out_features: int, in_features: int, num_codebooks: int, nbits_per_codebook: int, in_group_size: int) -> bool:
+    """All entries of the calibrated step take this layer (out_group_size 1: 1x16 with g 8 / 16, K x 8 with K 1..8 and g 8 / 16 / 32)."""
+    o, i, K, nbits, g = int(out_features), int(in_features), int(num_codebooks), int(nbits_per_codebook), int(in_group_size)
+    if not (_lib.aqlm_hip_calib_delta_supported(o, i, K, nbits, g) and _lib.aqlm_hip_calib_rows_supported(o, i, K, nbits, g)):
+        return False
+    if nbits == 16:
+        return bool(_lib.aqlm_hip_calib_codebook_grad_1x16_supported(o, i, g))
+    return bool(_lib.aqlm_hip_calib_codebook_grad_kx8_supported(o, i, K, g))
+
+
+def _calib_layer(who, codes, codebooks, scales):
+    """(codes, codebooks [K, S, g] fp32, scales [out] fp32 or None, out, in, K, nbits, g) of checked operands on one GPU."""
+    if codebooks.dim() != 4 or codebooks.shape[2] != 1 or codebooks.dtype != torch.float32 or not codebooks.is_cuda:
+        raise ValueError(f"{who}: codebooks must be GPU fp32 [K, S, 1, g], got {codebooks.dtype} {tuple(codebooks.shape)} on {codebooks.device}")
+    K, size, _, g = (int(v) for v in codebooks.shape)
+    nbits = {256: 8, 65536: 16}.get(size, 0)
+    want = torch.int16 if nbits == 16 else torch.int8
+    if codes.dim() != 3 or codes.shape[2] != K or codes.dtype != want or not codes.is_contiguous() or codes.device != codebooks.device:
+        raise ValueError(f"{who}: codes must be contiguous {want} [out, in / g, {K}] on {codebooks.device}, got {codes.dtype} {tuple(codes.shape)}")
+    out_features, in_features = int(codes.shape[0]), int(codes.shape[1]) * g
+    if scales is not None:
+        if scales.numel() != out_features or scales.dtype != torch.float32 or scales.device != codebooks.device:
+            raise ValueError(f"{who}: scales must hold {out_features} fp32 elements on {codebooks.device}")
+        scales = _c(scales.detach()).reshape(-1)
+    return codes, _c(codebooks.detach()), scales, out_features, in_features, K, nbits, g
+
+
+def _check_calib_matrix(who, name, m, out_features, in_features, device, dtypes=(torch.float32,)):
+    if m.dim() != 2 or tuple(m.shape) != (out_features, in_features) or m.stride(1) != 1 or m.dtype not in dtypes or m.device != device:
+        raise ValueError(f"{who}: {name} must be a {' / '.join(str(d) for d in dtypes)} [{out_features}, {in_features}] with a unit inner "
+                         f"stride on {device}, got {m.dtype} {tuple(m.shape)} strides {tuple(m.stride())} on {m.device}")
+
+
+def calib_delta(codes, codebooks, scales, reference_weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """D [out, in] fp32 = ``scales * sum_c codebooks[c][codes[..., c]] - reference_weight``: every operation one fp32 operation, the bits of
+    torch's fp32 ``_dequantize_weight(...) - reference_weight`` (include/aqlm_hip.h, aqlm_hip_calib_delta).  ``reference_weight`` fp32 / fp16
+    / bf16 with any row stride; ``out``: an fp32 [out, in] to write (rows 16-byte aligned), default a new one.  One launch."""
+    codes, books, scales, o, i, K, nbits, g = _calib_layer("calib_delta", codes, codebooks, scales)
+    if scales is None:
+        raise ValueError("calib_delta: scales are required")
+    _check_calib_matrix("calib_delta", "reference_weight", reference_weight, o, i, books.device, tuple(_GRAD_DT))
+    if out is None:
+        out = torch.empty((o, i), dtype=torch.float32, device=books.device)
+    _check_calib_matrix("calib_delta", "out", out, o, i, books.device)
+    with _device_guard(books.device):
+        rc = _lib.aqlm_hip_calib_delta(codes.data_ptr(), books.data_ptr(), scales.data_ptr(), reference_weight.data_ptr(),
+                                       _GRAD_DT[reference_weight.dtype], reference_weight.stride(0), o, i, K, nbits, g, out.data_ptr(),
+                                       out.stride(0), _stream_ptr(books.device))
+    if rc:
+        _native.check(rc, "aqlm calib delta")
+    return out
+
+
+def calib_rows(g_matrix, delta, codes, codebooks):
+    """``(ds_raw [out], rowloss [out])`` fp32 of ``G = D @ XTX`` and the stored ``D``: ``ds_raw[o] = sum G[o] * w[o]`` (w: the UNSCALED
+    dequantised row), ``rowloss[o] = sum G[o] * D[o]``; one wave per row in the fixed order of ``scales_grad_1x16`` (include/aqlm_hip.h,
+    aqlm_hip_calib_rows).  One launch."""
+    codes, books, _, o, i, K, nbits, g = _calib_layer("calib_rows", codes, codebooks, None)
+    _check_calib_matrix("calib_rows", "G", g_matrix, o, i, books.device)
+    _check_calib_matrix("calib_rows", "D", delta, o, i, books.device)
+    out = torch.empty((2, o), dtype=torch.float32, device=books.device)
+    with _device_guard(books.device):
+        rc = _lib.aqlm_hip_calib_rows(g_matrix.data_ptr(), g_matrix.stride(0), delta.data_ptr(), delta.stride(0), codes.data_ptr(),
+                                      books.data_ptr(), o, i, K, nbits, g, out[0].data_ptr(), out[1].data_ptr(), _stream_ptr(books.device))
+    if rc:
+        _native.check(rc, "aqlm calib rows")
+    return out[0], out[1]
+
+
+def calib_codebook_grad_1x16(g_matrix, scales, index: CodebookGradIndex) -> torch.Tensor:
+    """dC [65536, g] fp32: per entry the sum of ``scales[o] * G[o, j*g : j*g + g]`` over the positions of its list -- the launches and the
+    order of ``codebook_grad_1x16`` with fp32 scales (aqlm_hip_calib_codebook_grad_1x16).  Every element is written."""
+    o, i, g = index.geometry()
+    _check_calib_matrix("calib_codebook_grad_1x16", "G", g_matrix, o, i, index.order.device)
+    if scales.numel() != o or scales.dtype != torch.float32 or scales.device != g_matrix.device:
+        raise ValueError(f"calib_codebook_grad_1x16: scales must hold {o} fp32 elements on {g_matrix.device}")
+    scales = _c(scales.detach()).reshape(-1)
+    out = torch.empty((CODEBOOK_GRAD_ENTRIES, g), dtype=torch.float32, device=g_matrix.device)
+    ws_bytes = int(_lib.aqlm_hip_calib_codebook_grad_1x16_workspace_bytes(o, i, g))
+    ws = _workspace(g_matrix.device, max(ws_bytes, 16))
+    with _device_guard(g_matrix.device):
+        rc = _lib.aqlm_hip_calib_codebook_grad_1x16(g_matrix.data_ptr(), g_matrix.stride(0), scales.data_ptr(), index.starts.data_ptr(),
+                                                    index.order.data_ptr(), index.chunks.data_ptr(), index.chunk_starts.data_ptr(), o, i, g,
+                                                    out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(g_matrix.device))
+    if rc:
+        _native.check(rc, "aqlm calib codebook grad")
+    return out
+
+
+def calib_codebook_grad_kx8(g_matrix, scales, codes, in_group_size: int) -> torch.Tensor:
+    """dC [K, 256, g] fp32 of a K x 8 layer: the fixed-point sums of ``codebook_grad_kx8`` with fp32 scales
+    (aqlm_hip_calib_codebook_grad_kx8); NaN everywhere when ``G`` or the scales hold a non-finite value."""
+    g = int(in_group_size)
+    o, i, K = int(codes.shape[0]), int(codes.shape[1]) * g, int(codes.shape[2])
+    _check_calib_matrix("calib_codebook_grad_kx8", "G", g_matrix, o, i, codes.device)
+    _check_kx8_codes(codes, g_matrix, o, i, K, g, "calib_codebook_grad_kx8")
+    if scales.numel() != o or scales.dtype != torch.float32 or scales.device != g_matrix.device:
+        raise ValueError(f"calib_codebook_grad_kx8: scales must hold {o} fp32 elements on {g_matrix.device}")
+    scales = _c(scales.detach()).reshape(-1)
+    out = torch.empty((K, 256, g), dtype=torch.float32, device=g_matrix.device)
+    ws_bytes = int(_lib.aqlm_hip_calib_codebook_grad_kx8_workspace_bytes(o, i, K, g))
+    ws = _workspace(g_matrix.device, max(ws_bytes, 16))
+    with _device_guard(g_matrix.device):
+        rc = _lib.aqlm_hip_calib_codebook_grad_kx8(g_matrix.data_ptr(), g_matrix.stride(0), scales.data_ptr(), codes.data_ptr(), o, i, K, g,
+                                                   out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(g_matrix.device))
+    if rc:
+        _native.check(rc, "aqlm calib codebook grad kx8")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------
 # nearest-codeword search of the 1x16 schemes (the V step of PV-tuning; aqlm_hip_code_search_1x16)
 # ------------------------------------------------------------------------------------------------------
 CODE_SEARCH_EPS = _native.CODE_SEARCH_EPS  # the accuracy contract of include/aqlm_hip.h: computed scores within eps * (|r|^2 + max|C|^2)

@@ -59,13 +59,21 @@ residual k-means (src/aq.py ``init_aq_kmeans``, src/kmeans.py).  fp32 data on th
 both operands as split fp16 pairs, the clusters' sums as fixed-point integers in the same launch -- and ``aqlm_hip_kmeans_update``
 (tests/kmeans_model.py restates the integer side); everything else runs the reference's formula in torch.
 
+Producing a layer (``accumulate_xtx_``, ``calibrated_loss_and_grads``, ``quantize_layer_``): the loop of the reference's
+``AQEngine.quantize`` (aq_engine.py) -- the k-means initialisation, then per epoch Adam steps on fp32 masters of the codebooks and scales
+against ``tr((W_q - W_ref) XTX (W_q - W_ref)^T) / out_features`` and one calibrated search.  A step on the MI355X runs
+``aqlm_hip_calib_delta``, one library GEMM ``G = D XTX``, ``aqlm_hip_calib_rows`` and ``aqlm_hip_calib_codebook_grad_1x16`` / ``_kx8``
+(tests/calib_grad_model.py restates their arithmetic); everything else runs autograd through
+``_dequantize_weight``.
+
 Memory: the 1x16 index costs 4 bytes per code (plus ~0.5 MB of tables) next to the 2 bytes of the codes themselves; it is derived
 state of the layer (rebuilt when the codes change, never saved, copied or pickled).  ``checkpoint.memory_report`` lists it.  The
 K x 8 route keeps no derived state: its transient is the per-stream workspace (at most 33.6 MB).
 
 Precision: fp16 / bf16 parameters stepped by a plain optimizer lose every update smaller than half a unit in the last place of
-the parameter (Adam's small steps on a codebook entry of magnitude 1 vanish below 5e-4 in fp16).  This module does not ship an
+the parameter (Adam's small steps on a codebook entry of magnitude 1 vanish below 5e-4 in fp16).  ``make_trainable`` does not ship an
 fp32-master-weight optimizer wrapper; keep the parameters in fp32 (``model.float()``: the torch route above) when that matters.
+``quantize_layer_`` keeps fp32 masters of its own.
 
 Out of scope: the experts of a ``QuantizedMixtralExperts`` block (their routed launches carry gradients to the hidden states
 only) and ``ShardedQuantizedLinear`` -- ``make_trainable`` leaves both frozen and names them in ``.skipped`` of its result, and
@@ -934,3 +942,251 @@ def init_layer_kmeans_(layer, reference_weight: torch.Tensor, **options) -> torc
     layer.scales.copy_(scales.reshape(-1, 1, 1, 1))
     error = weight - _dequantize_weight(codes, codebooks, scales.reshape(-1, 1, 1, 1))
     return error.square().sum() / weight.square().sum()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# calibrated training of codebooks and scales, and the loop that produces a layer (the reference's AQEngine: aq_engine.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+# The switch of the calibrated gradient kernels: False sends every ``calibrated_loss_and_grads`` call through the torch route.
+CALIBRATED_GRAD_KERNEL = True
+
+
+def takes_calibrated_grad_kernel(num_codebooks: int, nbits_per_codebook: int, out_group_size: int, in_group_size: int, on_gpu: bool,
+                                 dtypes_ok: bool, supported: bool) -> bool:
+    """Whether a ``calibrated_loss_and_grads`` call runs the ``aqlm_hip_calib_*`` entries -- a pure function of: the scheme (one codebook
+    of 16 bits with g 8 / 16, or 1 to 8 codebooks of 8 bits with g 8 / 16 / 32; ``out_group_size`` 1), ``on_gpu`` (every tensor on the GPU),
+    ``dtypes_ok`` (codebooks, scales and ``XTX`` fp32, the target fp32 / fp16 / bf16, codes int16 for 16 bits and int8 for 8), ``supported``
+    (the library's ``_supported`` queries) and the ``CALIBRATED_GRAD_KERNEL`` switch.  No region is declined on timing grounds: the kernel
+    route took 0.10 to 0.37 of the torch route's time per step in every cell measured (profiles/calibrated_train.json)."""
+    wide = num_codebooks == 1 and nbits_per_codebook == 16 and in_group_size in (8, 16)
+    narrow = 1 <= num_codebooks <= 8 and nbits_per_codebook == 8 and in_group_size in (8, 16, 32)
+    return bool(CALIBRATED_GRAD_KERNEL and (wide or narrow) and out_group_size == 1 and on_gpu and dtypes_ok and supported)
+
+
+def _calibrated_grad_route(codes, codebooks, scales, reference_weight, XTX) -> bool:
+    K, size, out_group_size, in_group_size = codebooks.shape
+    nbits = int(math.log2(size))
+    on_gpu = all(t.is_cuda for t in (codes, codebooks, scales, reference_weight, XTX))
+    dtypes_ok = (codebooks.dtype == torch.float32 and scales.dtype == torch.float32 and XTX.dtype == torch.float32
+                 and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                 and codes.dtype == (torch.int16 if nbits == 16 else torch.int8))
+    supported = False
+    if CALIBRATED_GRAD_KERNEL and on_gpu and out_group_size == 1 and nbits in (8, 16):
+        from .inference_kernels import hip_kernel
+
+        supported = hip_kernel.calib_supported(reference_weight.shape[0], reference_weight.shape[1], K, nbits, in_group_size)
+    return takes_calibrated_grad_kernel(K, nbits, out_group_size, in_group_size, on_gpu, dtypes_ok, supported)
+
+
+def calibrated_loss_and_grads(codes: torch.Tensor, codebooks: torch.Tensor, scales: torch.Tensor, reference_weight: torch.Tensor,
+                              XTX: torch.Tensor, *, index=None):
+    """``(loss, d_codebooks, d_scales)`` of the calibrated objective ``loss = tr((W_q - W_ref) XTX (W_q - W_ref)^T) / out_features`` -- the
+    reference's ``AQEngine._compute_mse`` (aq_engine.py:108-131) and its backward -- for ``codes`` [out_groups, in_groups, K] in the stored
+    int8 / int16 wrap-around form, ``codebooks`` [K, S, out_group_size, in_group_size] and ``scales`` [out_groups, 1, 1, 1].  ``loss`` is a
+    0-dim tensor (fp64 on the kernel route, which adds the fp32 shares of the rows in fp64; the compute dtype on the torch route), the
+    gradients have the shapes of their parameters.
+
+    ``XTX`` IS TAKEN TO BE SYMMETRIC (``X^T X`` is; ``quantize_layer_`` symmetrises what it is given): the kernel route forms the one
+    product ``G = D XTX`` and uses it for the loss and, as ``(XTX + XTX^T) D^T / 2``, for both gradients.
+
+    Routes: fp32 codebooks and scales (master parameters), fp32 ``XTX`` and an fp32 / fp16 / bf16 target on the MI355X, for 1x16 layers
+    (g 8 / 16) and K x 8 layers (K 1 to 8, g 8 / 16 / 32) with ``out_group_size`` 1, run ``aqlm_hip_calib_delta`` (``D = W_q - W_ref``,
+    the bits of torch's fp32 ``_dequantize_weight(...) - W_ref``), ``torch.mm(D, XTX)``, ``aqlm_hip_calib_rows`` (per row the scale
+    gradient and the row's share of the loss, from the stored ``D``) and ``aqlm_hip_calib_codebook_grad_1x16`` (through ``index``, a
+    ``hip_kernel.CodebookGradIndex`` of these codes: built here when None, which a hipGraph capture cannot do) or
+    ``aqlm_hip_calib_codebook_grad_kx8`` (a non-finite element of ``G`` or the scales makes the whole K x 8 codebook
+    gradient NaN).  No atomics, bit-reproducible, no host synchronisation.  Everything else -- host tensors, ``out_group_size > 1``,
+    other schemes, g 32 with 16-bit codes, fp16 / bf16 or fp64 parameters, ``CALIBRATED_GRAD_KERNEL = False`` -- runs ``_compute_mse``
+    restated on ``_dequantize_weight`` under autograd, in fp32 (fp64 when any input is fp64): slow, correct, never silent."""
+    if codes.dim() != 3 or codebooks.dim() != 4 or codes.shape[2] != codebooks.shape[0]:
+        raise ValueError("calibrated_loss_and_grads: codes are [out_groups, in_groups, K], codebooks [K, S, out_group_size, in_group_size]")
+    K, size, out_group_size, in_group_size = codebooks.shape
+    out_features, in_features = codes.shape[0] * out_group_size, codes.shape[1] * in_group_size
+    if tuple(reference_weight.shape) != (out_features, in_features) or tuple(XTX.shape) != (in_features, in_features):
+        raise ValueError(f"calibrated_loss_and_grads: a layer of {in_features} -> {out_features} needs a target of [{out_features}, "
+                         f"{in_features}] and XTX [{in_features}, {in_features}], got {tuple(reference_weight.shape)} and {tuple(XTX.shape)}")
+    if scales.numel() != codes.shape[0]:
+        raise ValueError(f"calibrated_loss_and_grads: scales must hold one factor per output group ({codes.shape[0]})")
+    if _calibrated_grad_route(codes, codebooks, scales, reference_weight, XTX):
+        from .inference_kernels import hip_kernel
+
+        with torch.no_grad():
+            stored = codes.detach()
+            stored = stored if stored.is_contiguous() else stored.contiguous()
+            reference = reference_weight.detach()
+            reference = reference if reference.stride(1) == 1 else reference.contiguous()
+            delta = hip_kernel.calib_delta(stored, codebooks, scales, reference)
+            product = torch.mm(delta, XTX.detach())
+            ds_raw, rowloss = hip_kernel.calib_rows(product, delta, stored, codebooks)
+            if size == 65536:
+                if index is None:
+                    index = hip_kernel.build_codebook_grad_index(stored, in_group_size)
+                d_books = hip_kernel.calib_codebook_grad_1x16(product, scales, index)
+            else:
+                d_books = hip_kernel.calib_codebook_grad_kx8(product, scales, stored, in_group_size)
+            factor = 2.0 / out_features
+            # (the rows' shares are added in fp64: the last sum of the loss adds no rounding of its own to theirs)
+            return rowloss.sum(dtype=torch.float64) / out_features, (d_books * factor).reshape(codebooks.shape), (ds_raw * factor).reshape(scales.shape)
+
+    from .utils import _dequantize_weight
+
+    wide = any(t.dtype == torch.float64 for t in (codebooks, scales, reference_weight, XTX))
+    compute = torch.float64 if wide else torch.float32
+    with torch.enable_grad():
+        books = codebooks.detach().to(compute).requires_grad_(True)
+        factors = scales.detach().to(compute).requires_grad_(True)
+        weight = _dequantize_weight(codes.detach().to(torch.int64) % size, books, factors)
+        delta = weight - reference_weight.detach().to(compute)
+        loss = (delta @ XTX.detach().to(compute)).flatten() @ delta.flatten() / out_features
+        d_books, d_factors = torch.autograd.grad(loss, (books, factors))
+    return loss.detach(), d_books, d_factors
+
+
+@torch.no_grad()
+def accumulate_xtx_(XTX: torch.Tensor, nsamples: int, inp: torch.Tensor) -> int:
+    """Add a batch of layer inputs ``inp`` ([n, in] or [batch, seq, in]) to the running mean ``XTX`` [in, in] of ``x x^T`` over the
+    ``nsamples`` rows seen so far, IN PLACE and in the accumulator's dtype -- the reference's ``AQEngine.add_batch`` (aq_engine.py:30-42):
+    ``XTX *= nsamples / (nsamples + n); XTX += (x / sqrt(nsamples + n))^T (x / sqrt(nsamples + n))``.  Returns the new ``nsamples``."""
+    if inp.dim() == 3:
+        inp = inp.reshape(-1, inp.shape[-1])
+    if inp.dim() != 2 or XTX.dim() != 2 or tuple(XTX.shape) != (inp.shape[1], inp.shape[1]):
+        raise ValueError(f"accumulate_xtx_: inputs of {tuple(inp.shape)} do not fit an accumulator of {tuple(XTX.shape)}")
+    rows = int(inp.shape[0])
+    XTX *= nsamples / (nsamples + rows)
+    nsamples = int(nsamples) + rows
+    scaled = math.sqrt(1 / nsamples) * inp.t().to(XTX.dtype)
+    XTX += scaled.matmul(scaled.t())
+    return nsamples
+
+
+def _calibrated_search_route(layer, reference_weight, XTX, beam_size: int) -> str:
+    """"kernel" or "torch": what ``find_optimal_codes_calibrated`` runs for this layer (its predicates on its conditions)."""
+    K, nbits, g = layer.num_codebooks, layer.nbits_per_codebook, layer.in_group_size
+    tensors = (XTX, reference_weight, layer.codebooks, layer.codes, layer.scales)
+    on_gpu = all(t.is_cuda for t in tensors)
+    floats_ok = (layer.codebooks.dtype in (torch.float16, torch.bfloat16) and layer.scales.dtype == layer.codebooks.dtype
+                 and XTX.dtype == torch.float32 and reference_weight.dtype in (torch.float32, torch.float16, torch.bfloat16))
+    if not (CODE_SEARCH_KERNEL and on_gpu and floats_ok and layer.out_group_size == 1):
+        return "torch"
+    from .inference_kernels import hip_kernel
+
+    if nbits == 8 and 1 <= K <= 8 and g in (8, 16, 32) and 1 <= beam_size <= 16:
+        supported = hip_kernel.code_search_kx8_xtx_supported(layer.out_features, K, g, beam_size, beam_size)
+        taken = takes_code_search_kernel_kx8_xtx(K, nbits, 1, g, beam_size, on_gpu, layer.codes.dtype == torch.int8, supported)
+    elif nbits == 16 and K == 1 and g in (8, 16) and 1 <= beam_size <= 8:
+        supported = hip_kernel.code_search_1x16_xtx_supported(layer.out_features, g, beam_size, beam_size)
+        taken = takes_code_search_kernel_1x16_xtx(nbits, K, 1, g, beam_size, on_gpu, layer.codes.dtype == torch.int16, supported)
+    else:
+        taken = False
+    return "kernel" if taken else "torch"
+
+
+def quantize_layer_(layer, reference_weight: torch.Tensor, XTX: torch.Tensor, *, lr: float = 1e-4, max_epochs: int = 1000,
+                    steps_per_epoch: int = 100, relative_mse_tolerance: Optional[float] = None, beam_size: int = 1, init: bool = True,
+                    init_max_iter: int = 100, init_max_points_per_centroid: Optional[int] = None,
+                    generator: Optional[torch.Generator] = None, seed=None, callback=None) -> dict:
+    """Turn the dense ``reference_weight`` [out, in] and the calibration statistics ``XTX`` [in, in] (``accumulate_xtx_``) into the codes,
+    codebooks and scales of ``layer`` (a ``QuantizedLinear``), IN PLACE -- the loop of the reference's ``AQEngine.quantize``
+    (aq_engine.py:44-106):
+      * ``XTX`` is made symmetric once, ``(XTX + XTX^T) / 2``: the objective does not change and the one-GEMM gradient of
+        ``calibrated_loss_and_grads`` is exact.  It is used in fp32 (fp64 when the target is fp64);
+      * unless ``init=False`` the layer is initialised by ``init_layer_kmeans_`` (``init_max_iter``, ``init_max_points_per_centroid``,
+        ``generator``);
+      * fp32 masters of the codebooks and scales (fp64 for an fp64 layer) train under ``torch.optim.Adam(lr, betas=(0.0, 0.95),
+        amsgrad=True)``: every epoch ``steps_per_epoch`` steps of ``calibrated_loss_and_grads``, with the reference's early stop on the
+        loss of an epoch's step 0 (``relative_mse_tolerance``: stop when ``loss / best so far > 1 - tolerance``; a non-finite loss
+        raises ``ValueError``);
+      * at the end of an epoch the masters are written into the layer IN ITS DTYPE and the codes are re-chosen by
+        ``update_codes_calibrated_(beam_size=..., dim_order=...)``, one order of the codebooks per input group drawn from
+        ``random.Random(seed)``.  THE SEARCH THEREFORE SEES THE CODEBOOKS AND SCALES AS INFERENCE WILL -- rounded to the layer's dtype --
+        while the masters keep training unrounded (the reference searches on its fp32 parameters and rounds once at the end).  An fp32
+        layer's masters are exact copies of its own parameters; its search takes the torch route;
+      * the inverted index of a 1x16 layer is the layer's cached one (``codebook_grad_index``): rebuilt only when a search changed codes.
+    ``callback(event, epoch, info)`` is called with ``"trained"`` (masters written, before the search; ``info["loss"]``: the loss of the
+    epoch's step 0 or None) and ``"searched"`` (``info["changed"]``).
+
+    Returns a dict: ``losses`` (per epoch, the loss at its step 0), ``changed`` (groups whose codes each search changed),
+    ``initial_error`` and ``error`` (``calibrated_error`` of the layer before the first epoch and at the end), ``epochs`` run,
+    ``stopped_early`` and ``routes`` (``{"init", "grad", "search"}``: "kernel" or "torch" each; "init" None without one).  Refusals as in
+    ``update_codes_calibrated_``: the experts of a ``QuantizedMixtralExperts`` block and ``ShardedQuantizedLinear`` raise ``TypeError``,
+    inference tensors ``RuntimeError``."""
+    import random
+
+    from .inference import QuantizedLinear
+    from .moe import QuantizedMixtralExperts
+    from .sharded import ShardedQuantizedLinear
+
+    if isinstance(layer, (QuantizedMixtralExperts, ShardedQuantizedLinear)) or getattr(layer, "_moe_expert", False):
+        raise TypeError(f"quantize_layer_: {type(layer).__name__}{' (an expert of a QuantizedMixtralExperts block)' if getattr(layer, '_moe_expert', False) else ''}"
+                        " is outside the scope of the quantization loop (as it is of make_trainable)")
+    if not isinstance(layer, QuantizedLinear):
+        raise TypeError(f"quantize_layer_: expected a QuantizedLinear, got {type(layer).__name__}")
+    if tuple(reference_weight.shape) != (layer.out_features, layer.in_features) or tuple(XTX.shape) != (layer.in_features, layer.in_features):
+        raise ValueError(f"quantize_layer_: the layer is {layer.in_features} -> {layer.out_features}, the weight {tuple(reference_weight.shape)}, "
+                         f"XTX {tuple(XTX.shape)}")
+    if max_epochs < 0 or steps_per_epoch < 0 or not lr > 0:
+        raise ValueError("quantize_layer_: max_epochs >= 0, steps_per_epoch >= 0, lr > 0")
+    with torch.no_grad():
+        layer.restore_canonical_codes()
+        if layer.codes.is_inference() or layer.codebooks.is_inference() or layer.scales.is_inference():
+            raise RuntimeError("quantize_layer_: the parameters of this layer are inference tensors (the model was built or loaded under "
+                               "torch.inference_mode()); they cannot be written in place -- build the model outside inference mode")
+        device = layer.codes.device
+        wide = reference_weight.dtype == torch.float64
+        reference = reference_weight.detach().to(device)
+        stats = XTX.detach().to(device)
+        stats = (0.5 * (stats + stats.T)).to(torch.float64 if wide else torch.float32).contiguous()
+        routes = {"init": None, "grad": None, "search": None}
+        if init:
+            routes["init"] = "kernel" if takes_kmeans_kernel(layer.codebook_size, layer.in_group_size, device.type == "cuda", torch.float32,
+                                                             layer.out_group_size) else "torch"
+            init_layer_kmeans_(layer, reference, max_iter=init_max_iter, max_points_per_centroid=init_max_points_per_centroid,
+                               generator=generator)
+        master_dtype = torch.float64 if layer.codebooks.dtype == torch.float64 else torch.float32
+        books = layer.codebooks.detach().to(master_dtype).clone()
+        factors = layer.scales.detach().to(master_dtype).clone()
+        initial_error = float(calibrated_error(layer, reference, stats))
+    optimizer = torch.optim.Adam([books, factors], lr=lr, betas=(0.0, 0.95), amsgrad=True)
+    rng = random.Random(seed)
+    takes_index = layer.num_codebooks == 1 and layer.nbits_per_codebook == 16
+    losses, changed = [], []
+    best, stopped, epochs = float("inf"), False, 0
+    for epoch in range(max_epochs):
+        first = None
+        if steps_per_epoch:
+            kernel = _calibrated_grad_route(layer.codes, books, factors, reference, stats)
+            routes["grad"] = "kernel" if kernel else "torch"
+            index = layer.codebook_grad_index() if kernel and takes_index else None
+        for step in range(steps_per_epoch):
+            loss, d_books, d_factors = calibrated_loss_and_grads(layer.codes.detach(), books, factors, reference, stats, index=index)
+            value = float(loss)
+            if not math.isfinite(value):
+                raise ValueError(f"quantize_layer_: the calibrated loss is {value}")
+            if step == 0:
+                first = value
+                if relative_mse_tolerance is not None:
+                    if value / best > 1.0 - relative_mse_tolerance:
+                        stopped = True  # (no update after the last epoch's search, as in the reference)
+                        break
+                    best = min(best, value)
+            books.grad, factors.grad = d_books.to(master_dtype), d_factors.to(master_dtype)
+            optimizer.step()
+        if stopped:
+            break
+        epochs = epoch + 1
+        if first is not None:
+            losses.append(first)
+        with torch.no_grad():
+            layer.codebooks.copy_(books)
+            layer.scales.copy_(factors)
+        if callback is not None:
+            callback("trained", epoch, {"loss": first})
+        routes["search"] = _calibrated_search_route(layer, reference, stats, beam_size)
+        K = layer.num_codebooks
+        orders = [rng.sample(range(K), K) for _ in range(layer.in_features // layer.in_group_size)]
+        moved = int(update_codes_calibrated_(layer, reference, stats, beam_size=beam_size, dim_order=orders))
+        changed.append(moved)
+        if callback is not None:
+            callback("searched", epoch, {"changed": moved})
+    return {"losses": losses, "changed": changed, "initial_error": initial_error, "error": float(calibrated_error(layer, reference, stats)),
+            "epochs": epochs, "stopped_early": stopped, "routes": routes}

@@ -862,6 +862,54 @@ int aqlm_hip_scales_grad_kx8(const void* dw, long dw_row_stride, int dw_dtype, c
                              void* stream);
 
 /*
+ * One step of the CALIBRATED training of codebooks and scales (the reference's AQEngine._compute_mse, aq_engine.py:108-131, and its
+ * backward) on fp32 master parameters.  With D = W_q - W_ref [out][in], XTX symmetric and G = D XTX (a library GEMM of the caller,
+ * between the first entry and the others):
+ *     loss = sum_o rowloss[o] / out,    d loss / d scales[o] = 2 / out * ds_raw[o],    d loss / d codebooks = 2 / out * dC
+ * No entry applies the factor 2 / out.  All parameters are fp32: codebooks [K][S][g] (16-byte aligned), scales [out]; the codes are
+ * canonical: nbits_per_codebook 16: K = 1, int16 [out][in / g], g in {8, 16}; nbits_per_codebook 8: K in 1..8, int8 [out][in / g][K]
+ * (the entry is the byte & 0xff), g in {8, 16, 32}; out_group_size 1.  Row strides are in elements.
+ * aqlm_hip_calib_delta:  d[o][j * g + t] = scales[o] * w_j[t] - w_ref[o][j * g + t], w_j[t] = ((C_0[v_0][t] + C_1[v_1][t]) + ...) in
+ * codebook order; every operation is ONE fp32 operation (a multiply, then a subtract: no fused multiply-add), which is torch's fp32
+ * `_dequantize_weight(codes, codebooks, scales) - w_ref` bit for bit.  w_ref in w_ref_dtype (fp32 / fp16 / bf16, aligned to its
+ * element, any row stride >= in_features); d fp32, 16-byte aligned, d_row_stride a multiple of 4.  Codebooks of up to 64 KiB are
+ * staged in LDS, larger ones (8x8 g32: 256 KiB; 1x16: 2 / 4 MiB) are gathered from L2.  One launch.
+ * aqlm_hip_calib_rows:  ds_raw[o] = sum over j, t of g[o][j * g + t] * w_j[t];  rowloss[o] = sum over j, t of g[o][j * g + t] *
+ * d[o][j * g + t] -- the STORED d, so nothing cancels.  g and d fp32, 16-byte aligned, row strides multiples of 4.  One wave per
+ * row: lane l adds the products of the groups l, l + 64, ... in order (fp32, fused multiply-add over t ascending), a fixed tree
+ * adds the lanes (the order of aqlm_hip_scales_grad_1x16).  Ordinary IEEE propagation: a NaN poisons its own row only.  One launch.
+ * aqlm_hip_calib_codebook_grad_1x16:  out[c][t] (fp32 [65536][g]) = the sum of scales[o] * g[o][j * g + t] over the positions of
+ * entry c -- aqlm_hip_codebook_grad_1x16 (same index, chunk size, lane order, butterfly, finish launch, workspace size) with the
+ * scales read as fp32 and dW = g in fp32.  Every output is written by every call.
+ * aqlm_hip_calib_codebook_grad_kx8:  the same sums by the fixed-point scheme of aqlm_hip_codebook_grad_kx8 (maxima launch, int64
+ * LDS sums per pass of 64 / g codebooks, finish; same workspace size) with the scales read as fp32 -- the product s * g is then
+ * exact in double as well (24 x 24 significant bits).  A non-finite element of g or scales makes EVERY output NaN.
+ * All: stream-ordered, no allocation, no synchronisation (hipGraph-capturable), no scratch, no global atomics.  Checks, in the
+ * order of the sibling entries: a null pointer, misalignment, non-positive sizes or in_features % g != 0, a row stride below
+ * in_features or a workspace that is too small (AQLM_HIP_E_INVALID); then w_ref_dtype outside fp16 / bf16 / fp32, a scheme, K or g
+ * outside the above, too many positions or fp32 rows that are not 16-byte aligned (AQLM_HIP_E_UNSUPPORTED).  Nothing is launched on
+ * bad arguments.
+ */
+int aqlm_hip_calib_delta_supported(int out_features, int in_features, int num_codebooks, int nbits_per_codebook, int in_group_size);
+int aqlm_hip_calib_delta(const void* codes, const void* codebooks, const void* scales, const void* w_ref, int w_ref_dtype,
+                         long w_ref_row_stride, int out_features, int in_features, int num_codebooks, int nbits_per_codebook,
+                         int in_group_size, void* d, long d_row_stride, void* stream);
+int aqlm_hip_calib_rows_supported(int out_features, int in_features, int num_codebooks, int nbits_per_codebook, int in_group_size);
+int aqlm_hip_calib_rows(const void* g, long g_row_stride, const void* d, long d_row_stride, const void* codes, const void* codebooks,
+                        int out_features, int in_features, int num_codebooks, int nbits_per_codebook, int in_group_size, void* ds_raw,
+                        void* rowloss, void* stream);
+int aqlm_hip_calib_codebook_grad_1x16_supported(int out_features, int in_features, int in_group_size);
+size_t aqlm_hip_calib_codebook_grad_1x16_workspace_bytes(int out_features, int in_features, int in_group_size);
+int aqlm_hip_calib_codebook_grad_1x16(const void* g, long g_row_stride, const void* scales, const void* starts, const void* order,
+                                      const void* chunks, const void* chunk_starts, int out_features, int in_features,
+                                      int in_group_size, void* out, void* workspace, size_t workspace_bytes, void* stream);
+int aqlm_hip_calib_codebook_grad_kx8_supported(int out_features, int in_features, int num_codebooks, int in_group_size);
+size_t aqlm_hip_calib_codebook_grad_kx8_workspace_bytes(int out_features, int in_features, int num_codebooks, int in_group_size);
+int aqlm_hip_calib_codebook_grad_kx8(const void* g, long g_row_stride, const void* scales, const void* codes, int out_features,
+                                     int in_features, int num_codebooks, int in_group_size, void* out, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
+/*
  * The V step of PV-tuning for the 1x16 schemes (one codebook of 65536 entries, out_group_size 1, g = 8 / 16): the nearest codeword
  * of every group of g weights -- the reference's `_greedy_find_best_codes` (src/beam_search_l2.py) without its 65536 x groups score
  * matrix.  For group n = o * (in_features / g) + j:
