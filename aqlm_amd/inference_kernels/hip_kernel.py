@@ -11,14 +11,24 @@ Differences from the reference, all deliberate:
     schemes dequantise with our kernel and call F.linear (hipBLASLt) like the reference;
   * ``*_dequant_transposed`` applies the scales for every scheme and honours in_group_size (the reference drops
     the scales for 2x8/1x8 and hard-codes g=8 for 1x16).
+
+Layout.  This module is the forward path -- the gemv ops, the packed / planar / look-up-table formats with their cell
+registries, the raw-op prepack cache and compiled front end, dequantisation and the large-batch ops -- and the one namespace
+callers and tests use.  The launch helpers live in ``_launch``; the mixture-of-experts, LoRA, gradient and search / k-means ops
+live in ``ops_moe``, ``ops_lora``, ``ops_grad`` and ``ops_search``, each registering its own ``aqlm::`` ops, and are re-exported
+at the end of this file, name by name and as the same objects.  The forward path stays here on purpose: its knobs
+(``RAW_OP_PREPACK*``, ``RAW_OP_CHECK_EVERY``, ``FUSED_MFMA_MAX_ROWS``, ``FUSED_8X8_MFMA_MAX_ROWS``, ``USE_FUSED_8X8_MFMA``) and
+``tensor_checksum`` / ``unpack_1x16`` are rebound as attributes of this module by tests and benchmarks and read here as module
+globals, so moving that code would silently disconnect a knob or a test's patch.  The family modules never import this module at
+module scope; it imports them after its own definitions.
 """
 from __future__ import annotations
 
-import contextlib
+import contextlib  # noqa: F401  (not used here since the split; still a name of this namespace, like NamedTuple below)
 import ctypes
 import os
 from types import SimpleNamespace
-from typing import NamedTuple, Optional
+from typing import NamedTuple, Optional  # noqa: F401
 
 import torch
 import torch.nn.functional as F
@@ -26,54 +36,27 @@ import torch.nn.functional as F
 from .. import _native
 from .._native import lib as _lib
 from ..derived import tensor_checksum, tensor_version
+from ._launch import (  # noqa: F401  (by name: the decode path keeps plain global look-ups)
+    _DT,
+    _GRAD_DT,
+    _GRAD_TORCH_DT,
+    _LIB,
+    _NO_GUARD,
+    _WORKSPACES,
+    _c,
+    _device_guard,
+    _dtype_id,
+    _flat_rows,
+    _ptr,
+    _stream_ptr,
+    _workspace,
+    register_op,
+)
 
 _version = tensor_version  # the name the tests reach
 
 HIP_FOLDER = os.path.dirname(os.path.abspath(_native.LIB_PATH))
 CUDA_FOLDER = HIP_FOLDER  # reference name (cuda_kernel.py:6); ROCm reports device type "cuda"
-
-_DT = {torch.float16: _native.F16, torch.bfloat16: _native.BF16}
-
-
-def _dtype_id(t: torch.Tensor) -> int:
-    try:
-        return _DT[t.dtype]
-    except KeyError:
-        # message mirrors check_use_bfloat16 (cuda_kernel.cpp:9-25)
-        raise NotImplementedError(
-            f"AQLM HIP kernels only support float16 and bfloat16. Got {t.dtype}. "
-            "Please specify the correct `torch_dtype` when loading the model."
-        ) from None
-
-
-def _stream_ptr(device=None) -> int:
-    """The current stream of ``device`` (default: the current device).  Always pass the tensor's device when the call
-    is not inside ``torch.cuda.device(...)``: with accelerate's device_map the current device is not the layer's."""
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-_NO_GUARD = contextlib.nullcontext()
-
-
-def _device_guard(device: torch.device):
-    """``torch.cuda.device(device)`` only when the tensor is not on the current device: an eager decode loop is host-bound
-    and entering / leaving the guard costs as much as a kernel launch."""
-    return _NO_GUARD if torch.cuda.current_device() == device.index else torch.cuda.device(device)
-
-
-def _c(t: torch.Tensor) -> torch.Tensor:
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _flat_rows(input: torch.Tensor) -> torch.Tensor:
-    x = input.reshape(-1, input.shape[-1])
-    if x.stride(-1) != 1 or (x.shape[0] > 1 and x.stride(0) % 8 != 0) or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
-    return x
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -328,23 +311,6 @@ def dequant_1x16_packed(packed: PackedCodes, codebooks: torch.Tensor, scales: Op
     return W
 
 
-# fp32 partial workspaces, one per (device, stream): a decode loop calls the packed op hundreds of times per token and
-# the allocator round trip is a measurable part of an eager call.  Not used while a hipGraph is being captured (the
-# capture's private pool must own what the graph touches).
-_WORKSPACES = {}
-
-
-def _workspace(device: torch.device, nbytes: int, stream: Optional[int] = None) -> torch.Tensor:
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty((nbytes // 4,), dtype=torch.float32, device=device)
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream if stream is None else stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = torch.empty((max(nbytes, 1 << 20) // 4,), dtype=torch.float32, device=device)
-        _WORKSPACES[key] = ws
-    return ws
-
-
 # Accumulator cells of the single-kernel finalize, one zero-at-rest set per (device, stream): the prepacked buffers are then
 # only read, so one layer may run on several streams at once (weight sharing, overlapped graphs) -- the reference's
 # launcher is stateless in the same way (cuda_kernel.cu:505-509).  Launches on one stream are ordered, so all layers of a
@@ -543,1364 +509,6 @@ def code1x16_matmat_multi(input, codes, codebooks, scales, bias):
         if cb.shape[0] != 1 or cb.shape[1] != 65536:
             raise NotImplementedError(f"code1x16_matmat_multi needs codebooks [1, 65536, 1, g], got {tuple(cb.shape)}")
     return _gemv_multi(input, codes, codebooks, scales, bias, "1x16")
-
-
-# ------------------------------------------------------------------------------------------------------
-# expert-routed 1x16 matvec (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed)
-# ------------------------------------------------------------------------------------------------------
-def routed_table(layers, device) -> torch.Tensor:
-    """The device-resident table of aqlm_hip_gemv_1x16_routed: ``layers[e][s] = (codes, codebooks, scales, bias or None)``
-    -> int64 [E * S * 4] of device pointers, entry [e * S + s].  The table holds raw addresses: the caller keeps the tensors
-    alive and rebuilds it when one of them moves (``aqlm_amd.moe.QuantizedMixtralExperts`` keys it on data_ptr + version).
-    A host-to-device copy: never while a hipGraph is being captured."""
-    words = []
-    for per_expert in layers:
-        for codes, codebooks, scales, bias in per_expert:
-            for t in (codes, codebooks, scales):
-                if not t.is_contiguous() or t.data_ptr() % 16:
-                    raise ValueError("routed table: codes / codebooks / scales must be contiguous and 16-byte aligned")
-            if bias is not None and not bias.is_contiguous():
-                raise ValueError("routed table: bias must be contiguous")
-            words += [codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), 0 if bias is None else bias.data_ptr()]
-    return torch.tensor(words, dtype=torch.int64).to(device)
-
-
-def routed_chunks(tokens: int, top_k: int):
-    """Token ranges [t0, t1) of the routed launches that serve ``tokens`` tokens: at most MAX_ROUTED_PAIRS (token, expert) pairs
-    per launch, whole tokens only."""
-    per = max(1, _native.MAX_ROUTED_PAIRS // max(1, top_k))
-    return [(t0, min(tokens, t0 + per)) for t0 in range(0, tokens, per)]
-
-
-def _check_routed_args(input, expert_ids, table, E, S, in_features, top_k, x_per_pair, entry_words, words) -> int:
-    """The id, input and table checks of the two routed ops (``words``: the table length the caller was told) -> tokens."""
-    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
-        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
-    T = expert_ids.shape[0]
-    rows = T * top_k if x_per_pair else T
-    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
-        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
-    if table.dtype != torch.int64 or table.numel() != words or words != E * S * entry_words or table.device != input.device:
-        raise ValueError(f"table must be int64 [{E * S * entry_words}] on {input.device}")
-    if expert_ids.device != input.device:
-        raise ValueError("expert_ids must be on the input's device")
-    return T
-
-
-def _routed_launches(x, ids, y, top_k, x_per_pair, what, launch) -> None:
-    """One ``launch(ids pointer, ids_int64, pairs, x pointer, y pointer) -> rc`` per chunk of ``routed_chunks``."""
-    esz = ids.element_size()
-    with _device_guard(x.device):
-        for t0, t1 in routed_chunks(ids.shape[0], top_k):
-            p0 = t0 * top_k
-            rc = launch(ids.data_ptr() + p0 * esz, int(esz == 8), (t1 - t0) * top_k,
-                        x.data_ptr() + (p0 if x_per_pair else t0) * x.stride(0) * 2, y.data_ptr() + p0 * y.stride(0) * 2)
-            if rc:
-                _native.check(rc, what)
-
-
-def code1x16_moe_matmat(input, expert_ids, table, geometry, x_per_pair):
-    """Every (token, expert) pair of one or two 1x16 projections of a mixture-of-experts block in one launch per 64 pairs.
-    geometry = [num_experts, num_segments, out_features, in_features, in_group_size, top_k]; ``expert_ids`` [T, top_k] int64 /
-    int32 on the device (what the router's topk returns; read on the device only, any values are safe: ids outside
-    [0, num_experts) give zero rows); ``input`` [T, in] (token rows, ``x_per_pair`` False) or [T * top_k, in] (pair rows);
-    ``table`` from ``routed_table``.  -> [T * top_k, num_segments, out_features]; row (t * top_k + j, s) is projection s of
-    expert expert_ids[t, j] applied to its x row, bit-identical to code1x16_matmat of that expert on that row."""
-    E, S, out_features, in_features, g, top_k = (int(v) for v in geometry)
-    dt = _dtype_id(input)
-    T = _check_routed_args(input, expert_ids, table, E, S, in_features, top_k, x_per_pair, _native.ROUTED_ENTRY_WORDS,
-                           E * S * _native.ROUTED_ENTRY_WORDS)
-    x = _flat_rows(input)
-    ids = _c(expert_ids)
-    y = torch.empty((T * top_k, S, out_features), dtype=input.dtype, device=input.device)
-    if T == 0:
-        return y
-    stream = _stream_ptr(input.device)
-    _routed_launches(x, ids, y, top_k, x_per_pair, "aqlm routed gemv", lambda idp, i64, npairs, xp, yp: _lib.aqlm_hip_gemv_1x16_routed(
-        table.data_ptr(), E, S, idp, i64, npairs, top_k, xp, x.stride(0), int(bool(x_per_pair)), yp, out_features, in_features, g, dt,
-        stream))
-    return y
-
-
-# ------------------------------------------------------------------------------------------------------
-# LoRA adapters per row of a decode batch (aqlm_hip_lora_bgmv; aqlm_amd/lora.py is the module-level interface)
-# ------------------------------------------------------------------------------------------------------
-def lora_table(adapters, device) -> torch.Tensor:
-    """The device-resident table of aqlm_hip_lora_bgmv: ``adapters[a] = (A [rank, in], B [out, rank], scaling)`` -> int64
-    [num_adapters * 3] holding the aqlm_hip_lora_entry structs, entry a = adapter id a.  Filled on the host and copied once, like
-    ``routed_table``: the table holds raw addresses, so the caller keeps the tensors alive and rebuilds it when one of them moves
-    or is written (``aqlm_amd.lora`` keys it on data_ptr + version).  Never while a hipGraph is being captured."""
-    entries = (_native.LoraEntry * len(adapters))()
-    for ent, (a, b, scaling) in zip(entries, adapters):
-        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.dtype != b.dtype:
-            raise ValueError(f"lora table: A must be [rank, in] and B [out, rank] of one dtype, got {tuple(a.shape)} / {tuple(b.shape)}")
-        for t in (a, b):
-            if not t.is_contiguous() or t.data_ptr() % 16:
-                raise ValueError("lora table: A and B must be contiguous and 16-byte aligned")
-        ent.a, ent.b, ent.rank, ent.scaling = a.data_ptr(), b.data_ptr(), int(a.shape[0]), float(scaling)
-    words = torch.frombuffer(bytearray(bytes(entries)), dtype=torch.int64) if len(adapters) else torch.empty(0, dtype=torch.int64)
-    return words.to(device)
-
-
-def lora_bgmv_supported(out_features: int, in_features: int, max_rank: int, rows: int) -> bool:
-    return bool(_lib.aqlm_hip_lora_bgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
-
-
-def _lora_gmv_(y, x, ids, table, geometry, entry, workspace_bytes, what, y_groups_of_4) -> None:
-    """The checks, the workspace and the call of ``lora_bgmv_`` / ``lora_sgmv_``: ``entry`` the native launch,
-    ``workspace_bytes(rows, max_rank, in_features)`` its workspace size."""
-    n, max_rank, out_features, in_features = (int(v) for v in geometry)
-    dt = _dtype_id(y)
-    if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0] or y.shape[1] != out_features or x.shape[1] != in_features:
-        raise ValueError(f"y must be [rows, {out_features}] and x [rows, {in_features}], got {tuple(y.shape)} / {tuple(x.shape)}")
-    if x.dtype != y.dtype or x.device != y.device or table.device != y.device:
-        raise ValueError("x, y and the table must share dtype and device")
-    if y.stride(1) != 1:
-        raise ValueError("y must have a unit inner stride (it is written in place)")
-    rows = y.shape[0]
-    if y_groups_of_4 and (y.data_ptr() % 8 or (rows > 1 and y.stride(0) % 4)):
-        raise ValueError("y must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written in groups of 4)")
-    if table.dtype != torch.int64 or table.numel() != n * _native.LORA_ENTRY_WORDS:
-        raise ValueError(f"table must be int64 [{n * _native.LORA_ENTRY_WORDS}]")
-    if ids is not None:
-        if ids.dim() != 1 or ids.shape[0] != rows or ids.dtype not in (torch.int64, torch.int32) or ids.device != y.device:
-            raise ValueError(f"ids must be [{rows}] int64 / int32 on {y.device}, got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
-        ids = _c(ids)
-    if rows == 0:
-        return
-    x = _flat_rows(x)
-    ws = _workspace(y.device, max(workspace_bytes(rows, max_rank, in_features), 16))
-    with _device_guard(y.device):
-        rc = entry(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8), rows, x.data_ptr(),
-                   x.stride(0) if rows > 1 else in_features, y.data_ptr(), y.stride(0) if rows > 1 else out_features, out_features,
-                   in_features, dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
-    if rc:
-        _native.check(rc, what)
-
-
-def lora_bgmv_(y, x, ids, table, geometry) -> None:
-    """``y[b] += scaling_a * B_a (A_a x[b])`` with a = ids[b], in place, for every row of a decode batch in two launches
-    (include/aqlm_hip.h, aqlm_hip_lora_bgmv: fp32 sums, the rank-sized intermediate is never rounded, y is rounded once).
-    geometry = [num_adapters, max_rank, out_features, in_features]; ``y`` [rows, out] and ``x`` [rows, in] fp16 / bf16 with unit
-    inner strides; ``ids`` [rows] int64 / int32 on the device (read there only; a row whose id lies outside [0, num_adapters) is
-    left as it is) or None = adapter 0 for every row; ``table`` from ``lora_table``.  The fp32 workspace comes from the caching
-    allocator, so the call can be captured."""
-    _lora_gmv_(y, x, ids, table, geometry, _lib.aqlm_hip_lora_bgmv,
-               lambda rows, max_rank, in_features: _lib.aqlm_hip_lora_workspace_bytes(rows, max_rank),
-               "aqlm lora bgmv", y_groups_of_4=False)
-
-
-def lora_sgmv_supported(out_features: int, in_features: int, max_rank: int, rows: int) -> bool:
-    return bool(_lib.aqlm_hip_lora_sgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
-
-
-def lora_sgmv_(y, x, ids, table, geometry) -> None:
-    """``lora_bgmv_`` at any row count (prefill, large batches): the segmented adapter GEMM on the matrix unit
-    (include/aqlm_hip.h, aqlm_hip_lora_sgmv), two launches, one pass per distinct adapter of every 16-row tile.  Same arguments
-    as ``lora_bgmv_``; in addition ``y`` must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written
-    in groups of 4 outputs).  Not bit-equal to ``lora_bgmv_``: the sums run in another order, and the rank-sized intermediate
-    enters the second product as a pair of storage-type values."""
-    _lora_gmv_(y, x, ids, table, geometry, _lib.aqlm_hip_lora_sgmv, _lib.aqlm_hip_lora_sgmv_workspace_bytes, "aqlm lora sgmv",
-               y_groups_of_4=True)
-
-
-# ------------------------------------------------------------------------------------------------------
-# LoRA adapters on the routed experts of a mixture-of-experts block (aqlm_hip_lora_bgmv_routed; aqlm_amd/lora.py
-# LoraQuantizedMixtralExperts is the module-level interface)
-# ------------------------------------------------------------------------------------------------------
-def lora_routed_table(entries, device) -> torch.Tensor:
-    """The device-resident table of aqlm_hip_lora_bgmv_routed: ``entries[a][e][s]`` is ``(A [rank, in], B [out, rank], scaling)`` or
-    ``None`` (adapter a has no weights for projection s of expert e: a zero entry, "no adapter") -> int64 [A * E * S * 3] holding
-    the aqlm_hip_lora_entry structs, entry [(a * E + e) * S + s].  Same checks, same ownership rules as ``lora_table``: raw
-    addresses, the caller keeps the tensors alive and rebuilds the table when one moves or is written.  Never while a hipGraph
-    is being captured."""
-    flat = [ent for per_adapter in entries for per_expert in per_adapter for ent in per_expert]
-    E = len(entries[0]) if entries else 0
-    S = len(entries[0][0]) if E else 0
-    if any(len(pa) != E or any(len(pe) != S for pe in pa) for pa in entries):
-        raise ValueError("lora routed table: entries must be [adapters][experts][segments]")
-    structs = (_native.LoraEntry * len(flat))()
-    for ent, item in zip(structs, flat):
-        if item is None:
-            continue  # ctypes zero-fills: rank 0, null pointers
-        a, b, scaling = item
-        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.dtype != b.dtype:
-            raise ValueError(f"lora table: A must be [rank, in] and B [out, rank] of one dtype, got {tuple(a.shape)} / {tuple(b.shape)}")
-        for t in (a, b):
-            if not t.is_contiguous() or t.data_ptr() % 16:
-                raise ValueError("lora table: A and B must be contiguous and 16-byte aligned")
-        ent.a, ent.b, ent.rank, ent.scaling = a.data_ptr(), b.data_ptr(), int(a.shape[0]), float(scaling)
-    words = torch.frombuffer(bytearray(bytes(structs)), dtype=torch.int64) if len(flat) else torch.empty(0, dtype=torch.int64)
-    return words.to(device)
-
-
-def lora_bgmv_routed_supported(out_features: int, in_features: int, max_rank: int, num_pairs: int, num_experts: int,
-                               num_segments: int) -> bool:
-    return bool(_lib.aqlm_hip_lora_bgmv_routed_supported(int(out_features), int(in_features), int(max_rank), int(num_pairs),
-                                                         int(num_experts), int(num_segments)))
-
-
-def _check_lora_routed(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair):
-    """The argument checks of ``lora_bgmv_routed_`` / ``lora_sgmv_routed_`` -> (P, rows, dtype id, contiguous adapter ids)."""
-    n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
-    dt = _dtype_id(y)
-    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
-        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
-    T = expert_ids.shape[0]
-    P = T * top_k
-    rows = P if x_per_pair else T
-    if tuple(y.shape) not in ((P, S, out_features),) + (((P, out_features),) if S == 1 else ()) or not y.is_contiguous():
-        raise ValueError(f"y must be contiguous [{P}, {S}, {out_features}], got {tuple(y.shape)} with strides {y.stride()}")
-    if x.dim() != 2 or tuple(x.shape) != (rows, in_features):
-        raise ValueError(f"x must be [{rows}, {in_features}], got {tuple(x.shape)}")
-    if x.dtype != y.dtype or x.device != y.device or table.device != y.device or expert_ids.device != y.device:
-        raise ValueError("x, y, expert_ids and the table must share a device, x and y a dtype")
-    if table.dtype != torch.int64 or table.numel() != n * E * S * _native.LORA_ENTRY_WORDS:
-        raise ValueError(f"table must be int64 [{n * E * S * _native.LORA_ENTRY_WORDS}]")
-    if adapter_ids is not None:
-        if (adapter_ids.dim() != 1 or adapter_ids.shape[0] != T or adapter_ids.dtype not in (torch.int64, torch.int32)
-                or adapter_ids.device != y.device):
-            raise ValueError(f"adapter_ids must be [{T}] int64 / int32 on {y.device}, got {tuple(adapter_ids.shape)} "
-                             f"{adapter_ids.dtype} on {adapter_ids.device}")
-        adapter_ids = _c(adapter_ids)
-    return P, rows, dt, adapter_ids
-
-
-def lora_bgmv_routed_(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair) -> None:
-    """``y[p, s] += scaling * B (A x_row(p))`` with the adapter of ``table`` entry (adapter_ids[p // top_k], expert_ids[p], s), in
-    place, for every (token, expert) pair and projection of a mixture-of-experts launch in two launches (include/aqlm_hip.h,
-    aqlm_hip_lora_bgmv_routed; bit-identical per row to ``lora_bgmv_`` with that entry as a one-slot table).
-    geometry = [num_adapters, num_experts, num_segments, max_rank, out_features, in_features, top_k]; ``y`` contiguous
-    [T * top_k, num_segments, out] (or [T * top_k, out] with one segment), the output of the routed / grouped ops; ``x`` [T, in]
-    (token rows, ``x_per_pair`` False) or [T * top_k, in] (pair rows) with a unit inner stride; ``adapter_ids`` [T] int64 / int32 on
-    the device or None = adapter 0; ``expert_ids`` [T, top_k] int64 / int32 on the device; both are read on the device only, and a
-    pair with either id out of range is left as it is.  ``table`` from ``lora_routed_table``.  At most MAX_LORA_ROWS pairs per
-    call.  The fp32 workspace comes from the caching allocator, so the call can be captured."""
-    n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
-    P, rows, dt, adapter_ids = _check_lora_routed(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair)
-    if P == 0:
-        return
-    x = _flat_rows(x)
-    eids = _c(expert_ids)
-    ws = _workspace(y.device, max(_lib.aqlm_hip_lora_bgmv_routed_workspace_bytes(P, S, max_rank), 16))
-    with _device_guard(y.device):
-        rc = _lib.aqlm_hip_lora_bgmv_routed(
-            table.data_ptr(), n, E, S, max_rank, _ptr(adapter_ids), int(adapter_ids is not None and adapter_ids.element_size() == 8),
-            eids.data_ptr(), int(eids.element_size() == 8), P, top_k, x.data_ptr(), x.stride(0) if rows > 1 else in_features,
-            int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
-    if rc:
-        _native.check(rc, "aqlm lora bgmv routed")
-
-
-SGMV_ROUTED_TILE_PAIRS = 16  # pairs per tile of the bucket aqlm_hip_lora_sgmv_routed reads: the rows of one matrix instruction
-
-
-def lora_sgmv_routed_supported(out_features: int, in_features: int, max_rank: int, num_pairs: int, num_experts: int,
-                               num_segments: int) -> bool:
-    return bool(_lib.aqlm_hip_lora_sgmv_routed_supported(int(out_features), int(in_features), int(max_rank), int(num_pairs),
-                                                         int(num_experts), int(num_segments)))
-
-
-def lora_sgmv_routed_(y, x, adapter_ids, expert_ids, bucket, table, geometry, x_per_pair, workspace=None) -> None:
-    """``lora_bgmv_routed_`` at any number of pairs (prefill, large batches): the segmented adapter GEMM on the matrix unit over
-    row tiles gathered through the expert bucket (include/aqlm_hip.h, aqlm_hip_lora_sgmv_routed; bit-identical per row to
-    ``lora_sgmv_`` with that entry as a one-slot table).  Same arguments as ``lora_bgmv_routed_`` plus ``bucket``:
-    ``moe_bucket(expert_ids, num_experts, 16)`` of the same ``expert_ids``.  ``out_features`` must be a multiple of 4 (y rows are
-    written in groups of 4 outputs).  At most MAX_LORA_SGMV_ROUTED_PAIRS pairs per call.  ``workspace``: a contiguous fp32 tensor
-    of at least ``lora_sgmv_routed_workspace_floats`` elements that the caller owns -- after the call it holds the rank-sized
-    intermediate t [P][S][splits][max_rank] of every served pair (the backward reads it) --; default: the cached workspace."""
-    n, E, S, max_rank, out_features, in_features, top_k = (int(v) for v in geometry)
-    P, rows, dt, adapter_ids = _check_lora_routed(y, x, adapter_ids, expert_ids, table, geometry, x_per_pair)
-    if P == 0:
-        return
-    if (bucket.dtype != torch.int32 or bucket.device != y.device or not bucket.is_contiguous()
-            or bucket.numel() != _bucket_words(P, E, SGMV_ROUTED_TILE_PAIRS)):
-        raise ValueError(f"bucket must come from moe_bucket(expert_ids, {E}, {SGMV_ROUTED_TILE_PAIRS}) on {y.device}")
-    x = _flat_rows(x)
-    eids = _c(expert_ids)
-    need = max(_lib.aqlm_hip_lora_sgmv_routed_workspace_bytes(P, S, max_rank, in_features), 16)
-    if workspace is None:
-        ws = _workspace(y.device, need)
-    else:
-        ws = workspace
-        if (ws.dtype != torch.float32 or ws.device != y.device or not ws.is_contiguous() or ws.numel() * 4 < need
-                or ws.data_ptr() % 16):
-            raise ValueError(f"workspace must be a contiguous, 16-byte aligned float32 tensor of at least {need // 4} elements on "
-                             f"{y.device}")
-    with _device_guard(y.device):
-        rc = _lib.aqlm_hip_lora_sgmv_routed(
-            table.data_ptr(), n, E, S, max_rank, _ptr(adapter_ids), int(adapter_ids is not None and adapter_ids.element_size() == 8),
-            eids.data_ptr(), int(eids.element_size() == 8), bucket.data_ptr(), P, top_k, x.data_ptr(),
-            x.stride(0) if rows > 1 else in_features, int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, dt,
-            ws.data_ptr(), ws.numel() * 4, _stream_ptr(y.device))
-    if rc:
-        _native.check(rc, "aqlm lora sgmv routed")
-
-
-def lora_sgmv_splits(in_features: int) -> int:
-    """K slices of the shrink launch of ``lora_sgmv_`` / ``lora_sgmv_routed_``: a function of in_features alone."""
-    return _lib.aqlm_hip_lora_sgmv_routed_workspace_bytes(1, 1, 8, int(in_features)) // 32
-
-
-def lora_sgmv_routed_workspace_floats(num_pairs: int, num_segments: int, max_rank: int, in_features: int) -> int:
-    """fp32 elements of the workspace of one ``lora_sgmv_routed_`` call: [P][S][splits][max_rank]; 0 when unsupported."""
-    return _lib.aqlm_hip_lora_sgmv_routed_workspace_bytes(int(num_pairs), int(num_segments), int(max_rank), int(in_features)) // 4
-
-
-# ------------------------------------------------------------------------------------------------------
-# the backward of the adapters on the routed experts (aqlm_hip_lora_transpose_routed, aqlm_hip_lora_grad_routed; aqlm_amd/lora.py
-# is the module-level interface)
-# ------------------------------------------------------------------------------------------------------
-def lora_routed_transposed_layout(ranks, scalings, out_features: int, in_features: int, base: int, element_size: int = 2):
-    """The transposed table of the grad_x launch and the layout of the buffer behind it, a pure function (no device):
-    ``ranks[a][e][s]`` the rank of entry (a, e, s) or 0 / None for none, ``scalings[a][e][s]`` its factor, ``base`` the address of
-    the buffer.  -> (the aqlm_hip_lora_entry structs laid out [s][a][e], offsets, elements): entry (s, a, e) is
-    ``{a: B^T [rank, out], b: A^T [in, rank], rank, scaling}``, its two copies back to back in the buffer in table order --
-    ``offsets[(a, e, s)] = (element offset of B^T, element offset of A^T)`` -- and an entry without weights or with a rank that is
-    no multiple of 8 is a zero entry that owns no part of the buffer."""
-    n = len(ranks)
-    E = len(ranks[0]) if n else 0
-    S = len(ranks[0][0]) if E else 0
-    structs = (_native.LoraEntry * (n * E * S))()
-    offsets, at = {}, 0
-    for s in range(S):
-        for a in range(n):
-            for e in range(E):
-                r = int(ranks[a][e][s] or 0)
-                if r <= 0 or r % 8:
-                    continue
-                ent = structs[(s * n + a) * E + e]
-                offsets[(a, e, s)] = (at, at + r * out_features)
-                ent.a, ent.b = base + at * element_size, base + (at + r * out_features) * element_size
-                ent.rank, ent.scaling = r, float(scalings[a][e][s])
-                at += r * (out_features + in_features)
-    return structs, offsets, at
-
-
-def lora_routed_transposed_table(entries, device):
-    """``entries[a][e][s]`` as for ``lora_routed_table`` -> (buffer, table, offsets): the storage-type buffer of the transposed
-    copies (filled by ``lora_transpose_routed_``, not here), the device table [S][A][E] of ``lora_routed_transposed_layout``
-    whose segment s is the one-segment table ``table[s * A * E * 3:(s + 1) * A * E * 3]``, and the element offsets of the copies.
-    Never while a hipGraph is being captured."""
-    live = [ent for pa in entries for pe in pa for ent in pe if ent is not None]
-    if not live:
-        raise ValueError("lora routed transposed table: no entry has weights")
-    a0, b0, _ = live[0]
-    out_features, in_features = int(b0.shape[0]), int(a0.shape[1])
-    for a, b, _ in live:
-        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.dtype != a0.dtype or b.dtype != a0.dtype \
-                or a.shape[1] != in_features or b.shape[0] != out_features:
-            raise ValueError(f"lora table: A must be [rank, {in_features}] and B [{out_features}, rank] of one dtype, got "
-                             f"{tuple(a.shape)} / {tuple(b.shape)}")
-    if out_features % 8 or in_features % 8:
-        raise NotImplementedError("lora routed transposed table: in_features and out_features must be multiples of 8")
-    ranks = [[[0 if ent is None else int(ent[0].shape[0]) for ent in pe] for pe in pa] for pa in entries]
-    scalings = [[[0.0 if ent is None else float(ent[2]) for ent in pe] for pe in pa] for pa in entries]
-    _, _, elements = lora_routed_transposed_layout(ranks, scalings, out_features, in_features, 0)
-    buffer = torch.zeros((max(elements, 8),), dtype=a0.dtype, device=device)
-    structs, offsets, _ = lora_routed_transposed_layout(ranks, scalings, out_features, in_features, buffer.data_ptr(),
-                                                        buffer.element_size())
-    words = torch.frombuffer(bytearray(bytes(structs)), dtype=torch.int64)
-    return buffer, words.to(device), offsets
-
-
-def lora_transpose_routed_supported(out_features: int, in_features: int, max_rank: int, num_experts: int, num_segments: int) -> bool:
-    return bool(_lib.aqlm_hip_lora_transpose_routed_supported(int(out_features), int(in_features), int(max_rank), int(num_experts),
-                                                              int(num_segments)))
-
-
-def lora_transpose_routed_(buffer, table, transposed, geometry) -> None:
-    """Fill ``buffer`` with B^T and A^T of every live entry of the forward ``table`` (``lora_routed_table``) at the places the
-    ``transposed`` table (``lora_routed_transposed_table``) names, in ONE launch (include/aqlm_hip.h,
-    aqlm_hip_lora_transpose_routed).  geometry = [num_adapters, num_experts, num_segments, max_rank, out_features, in_features].
-    An entry that is not live, whose transposed entry has another rank, or whose copies would not lie inside ``buffer`` leaves
-    the buffer as it is."""
-    n, E, S, max_rank, out_features, in_features = (int(v) for v in geometry)
-    words = n * E * S * _native.LORA_ENTRY_WORDS
-    for t in (table, transposed):
-        if t.dtype != torch.int64 or t.numel() != words or t.device != buffer.device or not t.is_contiguous():
-            raise ValueError(f"table and transposed must be contiguous int64 [{words}] on {buffer.device}")
-    if buffer.dtype not in _DT or not buffer.is_contiguous() or buffer.dim() != 1:
-        raise ValueError("buffer must be a contiguous 1-D float16 / bfloat16 tensor")
-    with _device_guard(buffer.device):
-        rc = _lib.aqlm_hip_lora_transpose_routed(table.data_ptr(), transposed.data_ptr(), n, E, S, max_rank, out_features, in_features,
-                                                 buffer.data_ptr(), buffer.numel() * buffer.element_size(), _stream_ptr(buffer.device))
-    if rc:
-        _native.check(rc, "aqlm lora transpose routed")
-
-
-def lora_grad_routed_supported(dim: int, max_rank: int, num_pairs: int, num_experts: int, num_segments: int) -> bool:
-    return bool(_lib.aqlm_hip_lora_grad_routed_supported(int(dim), int(max_rank), int(num_pairs), int(num_experts), int(num_segments)))
-
-
-def lora_grad_routed(v, w, adapter_ids, expert_ids, bucket, table, geometry, layout, out=None):
-    """The reduction over pairs that both weight gradients of the routed adapters are (include/aqlm_hip.h,
-    aqlm_hip_lora_grad_routed), for ONE adapter: -> fp32 ``G [E, S, max_rank, dim]``,
-    ``G[e, s, r, i] = scaling * sum over the pairs p of expert e with adapter `adapter`, ascending, of w[p, s][r] * V[p, s][i]``.
-    geometry = [num_adapters, num_experts, num_segments, max_rank, dim, top_k, adapter]; ``v`` the fp16 / bf16 tensor that holds
-    the V rows and ``w`` the fp32 tensor that holds the rank-sized rows, both addressed through
-    layout = [v_row_stride, v_seg_stride, v_per_pair, w_pair_stride, w_seg_stride, w_splits, w_split_stride] (elements; every
-    address it can form is checked against the two tensors here).  ``adapter_ids`` [T] or None = adapter 0 for every pair,
-    ``expert_ids`` [T, top_k], ``bucket`` = ``moe_bucket(expert_ids, num_experts, 16)``, ``table`` from ``lora_routed_table``.
-    Entries that are not live keep what ``out`` held (a new ``G`` is zero there)."""
-    n, E, S, max_rank, dim, top_k, adapter = (int(x) for x in geometry)
-    vrs, vss, vpp, wps, wss, wsplits, wsp = (int(x) for x in layout)
-    dt = _dtype_id(v)
-    if expert_ids.dim() != 2 or expert_ids.shape[1] != top_k or expert_ids.dtype not in (torch.int64, torch.int32):
-        raise ValueError(f"expert_ids must be [T, {top_k}] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
-    T = expert_ids.shape[0]
-    P = T * top_k
-    if P == 0:
-        raise ValueError("lora_grad_routed: no pairs")
-    if w.dtype != torch.float32 or v.stride(-1) != 1:
-        raise ValueError("w must be float32 and v must have a unit inner stride")
-    if any(t.device != v.device for t in (w, expert_ids, bucket, table)):
-        raise ValueError("v, w, expert_ids, bucket and table must share a device")
-    if table.dtype != torch.int64 or table.numel() != n * E * S * _native.LORA_ENTRY_WORDS:
-        raise ValueError(f"table must be int64 [{n * E * S * _native.LORA_ENTRY_WORDS}]")
-    if (bucket.dtype != torch.int32 or not bucket.is_contiguous() or bucket.numel() != _bucket_words(P, E, SGMV_ROUTED_TILE_PAIRS)):
-        raise ValueError(f"bucket must come from moe_bucket(expert_ids, {E}, {SGMV_ROUTED_TILE_PAIRS})")
-    if adapter_ids is not None:
-        if (adapter_ids.dim() != 1 or adapter_ids.shape[0] != T or adapter_ids.dtype not in (torch.int64, torch.int32)
-                or adapter_ids.device != v.device):
-            raise ValueError(f"adapter_ids must be [{T}] int64 / int32 on {v.device}")
-        adapter_ids = _c(adapter_ids)
-    if min(vrs, wps, wsplits) < 1 or min(vss, wss, wsp) < 0 or S < 1 or max_rank < 1 or dim < 1:
-        raise ValueError("lora_grad_routed: strides and sizes must be positive")
-    # the furthest element either operand can be asked for, against what the tensors hold (from their data_ptr on)
-    v_rows = P if vpp else T
-    v_span = v.untyped_storage().nbytes() // v.element_size() - v.storage_offset()
-    w_span = w.untyped_storage().nbytes() // 4 - w.storage_offset()
-    if (v_rows - 1) * vrs + (S - 1) * vss + dim > v_span:
-        raise ValueError(f"v holds {v_span} elements, the layout reaches {(v_rows - 1) * vrs + (S - 1) * vss + dim}")
-    if (P - 1) * wps + (S - 1) * wss + (wsplits - 1) * wsp + max_rank > w_span:
-        raise ValueError(f"w holds {w_span} elements, the layout reaches {(P - 1) * wps + (S - 1) * wss + (wsplits - 1) * wsp + max_rank}")
-    if out is None:
-        out = torch.zeros((E, S, max_rank, dim), dtype=torch.float32, device=v.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (E, S, max_rank, dim) or not out.is_contiguous() or out.device != v.device:
-        raise ValueError(f"out must be contiguous float32 [{E}, {S}, {max_rank}, {dim}] on {v.device}")
-    eids = _c(expert_ids)
-    with _device_guard(v.device):
-        rc = _lib.aqlm_hip_lora_grad_routed(
-            table.data_ptr(), n, E, S, max_rank, adapter, _ptr(adapter_ids),
-            int(adapter_ids is not None and adapter_ids.element_size() == 8), eids.data_ptr(), int(eids.element_size() == 8),
-            bucket.data_ptr(), P, top_k, v.data_ptr(), vrs, vss, int(bool(vpp)), dim, w.data_ptr(), wps, wss, wsplits, wsp,
-            out.data_ptr(), out.numel() * 4, dt, _stream_ptr(v.device))
-    if rc:
-        _native.check(rc, "aqlm lora grad routed")
-    return out
-
-
-# ------------------------------------------------------------------------------------------------------
-# gradients of the codebook and the scales of a 1x16 layer (aqlm_hip_codebook_grad_1x16, aqlm_hip_scales_grad_1x16)
-# ------------------------------------------------------------------------------------------------------
-CODEBOOK_GRAD_CHUNK = int(_lib.aqlm_hip_codebook_grad_chunk())  # positions per chunk of an entry's list (a constant of the library)
-CODEBOOK_GRAD_ENTRIES = 65536
-_GRAD_DT = {torch.float16: _native.F16, torch.bfloat16: _native.BF16, torch.float32: _native.F32}
-
-
-def codebook_grad_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
-    return bool(_lib.aqlm_hip_codebook_grad_1x16_supported(int(out_features), int(in_features), int(in_group_size))
-                and _lib.aqlm_hip_scales_grad_1x16_supported(int(out_features), int(in_features), int(in_group_size)))
-
-
-def codebook_grad_max_chunks(out_features: int, in_features: int, in_group_size: int) -> int:
-    return int(_lib.aqlm_hip_codebook_grad_1x16_max_chunks(int(out_features), int(in_features), int(in_group_size)))
-
-
-class CodebookGradIndex:
-    """The inverted index of a 1x16 layer's codes (include/aqlm_hip.h, aqlm_hip_codebook_grad_1x16): per codebook entry the
-    ascending list of the positions ``o * (in_features / g) + j`` that use it (``order`` int32 [n_codes], ``starts`` int32 [65537]),
-    every list cut into chunks of at most ``CODEBOOK_GRAD_CHUNK`` positions (``chunks`` int32 [max_chunks, 3]: entry, begin, end;
-    rows past the last chunk hold entry -1; ``chunk_starts`` int32 [65537]).  4 bytes per code plus ~0.5 MB of tables."""
-
-    __slots__ = ("order", "starts", "chunks", "chunk_starts", "out_features", "in_features", "in_group_size")
-
-    def __init__(self, order, starts, chunks, chunk_starts, out_features, in_features, in_group_size):
-        self.order, self.starts, self.chunks, self.chunk_starts = order, starts, chunks, chunk_starts
-        self.out_features, self.in_features, self.in_group_size = int(out_features), int(in_features), int(in_group_size)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.order, self.starts, self.chunks, self.chunk_starts))
-
-    def geometry(self):
-        return [self.out_features, self.in_features, self.in_group_size]
-
-
-def build_codebook_grad_index(codes: torch.Tensor, in_group_size: int) -> CodebookGradIndex:
-    """The index from canonical ``codes`` [out, in / g, 1] int16, with torch ops on the codes' device: one stable sort by the
-    unsigned code value and binary searches for the tables.  No host synchronisation (the chunk table has its upper bound
-    ``min(n_codes, 65536) + n_codes // CHUNK`` of rows, the unused ones marked -1) and no kernel of this library: it runs once per
-    layer.  Works on host tensors too (the tests model it in numpy)."""
-    if codes.dim() != 3 or codes.shape[2] != 1 or codes.dtype != torch.int16:
-        raise ValueError(f"codes must be int16 [out, in / g, 1], got {codes.dtype} {tuple(codes.shape)}")
-    out_features, nj = int(codes.shape[0]), int(codes.shape[1])
-    g, n, chunk = int(in_group_size), out_features * nj, CODEBOOK_GRAD_CHUNK
-    max_chunks = codebook_grad_max_chunks(out_features, nj * g, g)
-    if max_chunks == 0:
-        raise NotImplementedError(f"no codebook-gradient index for a layer of {out_features} x {nj * g}, g = {g}")
-    dev = codes.device
-    with torch.inference_mode(False), torch.no_grad():
-        values = codes.detach().reshape(-1).to(torch.int32) & 0xFFFF  # the unsigned index a two's-complement container holds
-        sorted_values, order = torch.sort(values, stable=True)        # stable: every entry's list ascends
-        entries = torch.arange(CODEBOOK_GRAD_ENTRIES + 1, dtype=torch.int32, device=dev)
-        starts = torch.searchsorted(sorted_values, entries)           # [65537]; starts[65536] == n
-        counts = starts[1:] - starts[:-1]
-        chunk_starts = torch.zeros_like(starts)
-        chunk_starts[1:] = torch.cumsum((counts + (chunk - 1)) // chunk, 0)
-        k = torch.arange(max_chunks, dtype=torch.int64, device=dev)
-        entry = torch.searchsorted(chunk_starts[1:], k, right=True)   # the entry whose chunk rows hold k; 65536: past the last chunk
-        valid = entry < CODEBOOK_GRAD_ENTRIES
-        e = entry.clamp(max=CODEBOOK_GRAD_ENTRIES - 1)
-        begin = starts[e] + (k - chunk_starts[e]) * chunk
-        end = torch.minimum(begin + chunk, starts[e + 1])
-        zero = torch.zeros_like(k)
-        chunks = torch.stack((torch.where(valid, entry, zero - 1), torch.where(valid, begin, zero), torch.where(valid, end, zero)), 1)
-        return CodebookGradIndex(order.to(torch.int32), starts.to(torch.int32), chunks.to(torch.int32).contiguous(),
-                                 chunk_starts.to(torch.int32), out_features, nj * g, g)
-
-
-def _check_dw(dw, out_features, in_features, what):
-    if dw.dim() != 2 or tuple(dw.shape) != (out_features, in_features) or dw.stride(1) != 1 or dw.dtype not in _GRAD_DT or not dw.is_cuda:
-        raise ValueError(f"{what}: dW must be a GPU fp16 / bf16 / fp32 [{out_features}, {in_features}] with a unit inner stride, got "
-                         f"{dw.dtype} {tuple(dw.shape)} strides {tuple(dw.stride())} on {dw.device}")
-
-
-def _codebook_grad_op(dw, scales, starts, order, chunks, chunk_starts, geometry):
-    out_features, in_features, g, out_dt = (int(x) for x in geometry)
-    _check_dw(dw, out_features, in_features, "codebook_grad_1x16")
-    n = out_features * (in_features // max(g, 1))
-    max_chunks = codebook_grad_max_chunks(out_features, in_features, g)
-    want = ((starts, (CODEBOOK_GRAD_ENTRIES + 1,)), (order, (n,)), (chunks, (max_chunks, 3)), (chunk_starts, (CODEBOOK_GRAD_ENTRIES + 1,)))
-    for t, shape in want:
-        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dw.device:
-            raise ValueError(f"codebook_grad_1x16: index tensors must be contiguous int32 {[s for _, s in want]} on {dw.device} "
-                             "(build_codebook_grad_index)")
-    dt = _native.F16
-    if scales is not None:
-        if scales.numel() != out_features or scales.device != dw.device:
-            raise ValueError(f"codebook_grad_1x16: scales must hold {out_features} elements on {dw.device}")
-        dt = _dtype_id(scales)
-        scales = _c(scales)
-    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
-    out = torch.empty((CODEBOOK_GRAD_ENTRIES, g), dtype=out_dtype, device=dw.device)
-    ws_bytes = int(_lib.aqlm_hip_codebook_grad_1x16_workspace_bytes(out_features, in_features, g))
-    ws = _workspace(dw.device, max(ws_bytes, 16))
-    with _device_guard(dw.device):
-        rc = _lib.aqlm_hip_codebook_grad_1x16(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], _ptr(scales), dt, starts.data_ptr(),
-                                              order.data_ptr(), chunks.data_ptr(), chunk_starts.data_ptr(), out_features, in_features,
-                                              g, out.data_ptr(), out_dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(dw.device))
-    if rc:
-        _native.check(rc, "aqlm codebook grad")
-    return out
-
-
-def codebook_grad_1x16(dw, scales, index: CodebookGradIndex, out_dtype: Optional[torch.dtype] = None):
-    """dC [65536, g] (``out_dtype``, default dW's dtype) = for every entry the sum of ``scales[o] * dW[o, j*g : j*g + g]`` over the
-    positions of its list, fp32, in the fixed order of the index (include/aqlm_hip.h); ``scales`` None = 1.  Every element is
-    written (+0 for unused entries).  Two launches on the current stream, the fp32 partials in the cached per-stream workspace (a
-    fresh one inside a hipGraph capture)."""
-    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
-    return _codebook_grad_op(dw, scales, index.starts, index.order, index.chunks, index.chunk_starts, index.geometry() + [out_dt])
-
-
-def _scales_grad_op(dw, codes, codebooks, geometry):
-    out_features, in_features, g, out_dt = (int(x) for x in geometry)
-    _check_dw(dw, out_features, in_features, "scales_grad_1x16")
-    if (codes.dtype != torch.int16 or codes.numel() != out_features * (in_features // max(g, 1)) or not codes.is_contiguous()
-            or codes.device != dw.device):
-        raise ValueError(f"scales_grad_1x16: codes must be contiguous int16 [{out_features}, {in_features // max(g, 1)}, 1] on {dw.device}")
-    if tuple(codebooks.shape) != (1, CODEBOOK_GRAD_ENTRIES, 1, g) or codebooks.device != dw.device:
-        raise ValueError(f"scales_grad_1x16: codebooks must be [1, 65536, 1, {g}] on {dw.device}, got {tuple(codebooks.shape)}")
-    dt = _dtype_id(codebooks)
-    codebooks = _c(codebooks)
-    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
-    out = torch.empty((out_features,), dtype=out_dtype, device=dw.device)
-    with _device_guard(dw.device):
-        rc = _lib.aqlm_hip_scales_grad_1x16(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], codes.data_ptr(), codebooks.data_ptr(), dt,
-                                            out_features, in_features, g, out.data_ptr(), out_dt, _stream_ptr(dw.device))
-    if rc:
-        _native.check(rc, "aqlm scales grad")
-    return out
-
-
-def scales_grad_1x16(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = None):
-    """ds [out] (``out_dtype``, default dW's dtype): ``sum over j, t of dW[o, j*g + t] * codebooks[0, code(o, j), 0, t]`` -- the
-    unscaled codebook, the canonical codes; fp32 in a fixed order, one rounding (include/aqlm_hip.h)."""
-    g = int(codebooks.shape[3])
-    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
-    return _scales_grad_op(dw, codes, codebooks, [int(codes.shape[0]), int(codes.shape[1]) * g, g, out_dt])
-
-
-# ------------------------------------------------------------------------------------------------------
-# the same gradients for the K x 8 schemes (aqlm_hip_codebook_grad_kx8, aqlm_hip_scales_grad_kx8): no index
-# ------------------------------------------------------------------------------------------------------
-def codebook_grad_kx8_supported(out_features: int, in_features: int, num_codebooks: int, in_group_size: int) -> bool:
-    args = (int(out_features), int(in_features), int(num_codebooks), int(in_group_size))
-    return bool(_lib.aqlm_hip_codebook_grad_kx8_supported(*args) and _lib.aqlm_hip_scales_grad_kx8_supported(*args))
-
-
-def _check_kx8_codes(codes, dw, out_features, in_features, K, g, what):
-    if (codes.dtype != torch.int8 or codes.numel() != out_features * (in_features // max(g, 1)) * K or not codes.is_contiguous()
-            or codes.device != dw.device):
-        raise ValueError(f"{what}: codes must be contiguous int8 [{out_features}, {in_features // max(g, 1)}, {K}] on {dw.device}")
-
-
-def _codebook_grad_kx8_op(dw, scales, codes, geometry):
-    out_features, in_features, K, g, out_dt = (int(x) for x in geometry)
-    _check_dw(dw, out_features, in_features, "codebook_grad_kx8")
-    _check_kx8_codes(codes, dw, out_features, in_features, K, g, "codebook_grad_kx8")
-    dt = _native.F16
-    if scales is not None:
-        if scales.numel() != out_features or scales.device != dw.device:
-            raise ValueError(f"codebook_grad_kx8: scales must hold {out_features} elements on {dw.device}")
-        dt = _dtype_id(scales)
-        scales = _c(scales)
-    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
-    out = torch.empty((K, 256, g), dtype=out_dtype, device=dw.device)
-    ws_bytes = int(_lib.aqlm_hip_codebook_grad_kx8_workspace_bytes(out_features, in_features, K, g))
-    ws = _workspace(dw.device, max(ws_bytes, 16))
-    with _device_guard(dw.device):
-        rc = _lib.aqlm_hip_codebook_grad_kx8(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], _ptr(scales), dt, codes.data_ptr(),
-                                             out_features, in_features, K, g, out.data_ptr(), out_dt, ws.data_ptr(), ws.numel() * 4,
-                                             _stream_ptr(dw.device))
-    if rc:
-        _native.check(rc, "aqlm codebook grad kx8")
-    return out
-
-
-def codebook_grad_kx8(dw, scales, codes, in_group_size: int, out_dtype: Optional[torch.dtype] = None):
-    """dC [K, 256, g] (``out_dtype``, default dW's dtype) of a K x 8 layer from ``dw`` [out, in], ``scales`` ([out] elements or None =
-    1) and the canonical ``codes`` [out, in / g, K] int8: per entry the sum of ``scales[o] * dW[o, j*g : j*g + g]`` over the positions
-    that use it, taken as fixed-point integers (include/aqlm_hip.h has the arithmetic) -- exact in the quantised terms and the same
-    bits under any schedule.  Every element is written (+0 for unused entries; NaN everywhere when dW or the scales hold a
-    non-finite value).  Three launches on the current stream, the int64 partials in the cached per-stream workspace (a fresh one
-    inside a hipGraph capture)."""
-    g = int(in_group_size)
-    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
-    return _codebook_grad_kx8_op(dw, scales, codes, [int(codes.shape[0]), int(codes.shape[1]) * g, int(codes.shape[2]), g, out_dt])
-
-
-def _scales_grad_kx8_op(dw, codes, codebooks, geometry):
-    out_features, in_features, K, g, out_dt = (int(x) for x in geometry)
-    _check_dw(dw, out_features, in_features, "scales_grad_kx8")
-    _check_kx8_codes(codes, dw, out_features, in_features, K, g, "scales_grad_kx8")
-    if tuple(codebooks.shape) != (K, 256, 1, g) or codebooks.device != dw.device:
-        raise ValueError(f"scales_grad_kx8: codebooks must be [{K}, 256, 1, {g}] on {dw.device}, got {tuple(codebooks.shape)}")
-    dt = _dtype_id(codebooks)
-    codebooks = _c(codebooks)
-    out_dtype = {v: k for k, v in _GRAD_DT.items()}[out_dt]
-    out = torch.empty((out_features,), dtype=out_dtype, device=dw.device)
-    with _device_guard(dw.device):
-        rc = _lib.aqlm_hip_scales_grad_kx8(dw.data_ptr(), dw.stride(0), _GRAD_DT[dw.dtype], codes.data_ptr(), codebooks.data_ptr(), dt,
-                                           out_features, in_features, K, g, out.data_ptr(), out_dt, _stream_ptr(dw.device))
-    if rc:
-        _native.check(rc, "aqlm scales grad kx8")
-    return out
-
-
-def scales_grad_kx8(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = None):
-    """ds [out] (``out_dtype``, default dW's dtype): ``sum over j, t of dW[o, j*g + t] * sum over c of codebooks[c, code(o, j, c), 0,
-    t]`` -- the unscaled codebooks [K, 256, 1, g], the canonical codes [out, in / g, K] int8; fp32 in a fixed order, one rounding
-    (include/aqlm_hip.h)."""
-    K, g = int(codebooks.shape[0]), int(codebooks.shape[3])
-    out_dt = _GRAD_DT[dw.dtype if out_dtype is None else out_dtype]
-    return _scales_grad_kx8_op(dw, codes, codebooks, [int(codes.shape[0]), int(codes.shape[1]) * g, K, g, out_dt])
-
-
-# ------------------------------------------------------------------------------------------------------
-# one step of the calibrated training of codebooks and scales on fp32 masters (aqlm_hip_calib_*; tuning.calibrated_loss_and_grads)
-# ------------------------------------------------------------------------------------------------------
-def calib_supported(out_features: int, in_features: int, num_codebooks: int, nbits_per_codebook: int, in_group_size: int) -> bool:
-    """All entries of the calibrated step take this layer (out_group_size 1: 1x16 with g 8 / 16, K x 8 with K 1..8 and g 8 / 16 / 32)."""
-    o, i, K, nbits, g = int(out_features), int(in_features), int(num_codebooks), int(nbits_per_codebook), int(in_group_size)
-    if not (_lib.aqlm_hip_calib_delta_supported(o, i, K, nbits, g) and _lib.aqlm_hip_calib_rows_supported(o, i, K, nbits, g)):
-        return False
-    if nbits == 16:
-        return bool(_lib.aqlm_hip_calib_codebook_grad_1x16_supported(o, i, g))
-    return bool(_lib.aqlm_hip_calib_codebook_grad_kx8_supported(o, i, K, g))
-
-
-def _calib_layer(who, codes, codebooks, scales):
-    """(codes, codebooks [K, S, g] fp32, scales [out] fp32 or None, out, in, K, nbits, g) of checked operands on one GPU."""
-    if codebooks.dim() != 4 or codebooks.shape[2] != 1 or codebooks.dtype != torch.float32 or not codebooks.is_cuda:
-        raise ValueError(f"{who}: codebooks must be GPU fp32 [K, S, 1, g], got {codebooks.dtype} {tuple(codebooks.shape)} on {codebooks.device}")
-    K, size, _, g = (int(v) for v in codebooks.shape)
-    nbits = {256: 8, 65536: 16}.get(size, 0)
-    want = torch.int16 if nbits == 16 else torch.int8
-    if codes.dim() != 3 or codes.shape[2] != K or codes.dtype != want or not codes.is_contiguous() or codes.device != codebooks.device:
-        raise ValueError(f"{who}: codes must be contiguous {want} [out, in / g, {K}] on {codebooks.device}, got {codes.dtype} {tuple(codes.shape)}")
-    out_features, in_features = int(codes.shape[0]), int(codes.shape[1]) * g
-    if scales is not None:
-        if scales.numel() != out_features or scales.dtype != torch.float32 or scales.device != codebooks.device:
-            raise ValueError(f"{who}: scales must hold {out_features} fp32 elements on {codebooks.device}")
-        scales = _c(scales.detach()).reshape(-1)
-    return codes, _c(codebooks.detach()), scales, out_features, in_features, K, nbits, g
-
-
-def _check_calib_matrix(who, name, m, out_features, in_features, device, dtypes=(torch.float32,)):
-    if m.dim() != 2 or tuple(m.shape) != (out_features, in_features) or m.stride(1) != 1 or m.dtype not in dtypes or m.device != device:
-        raise ValueError(f"{who}: {name} must be a {' / '.join(str(d) for d in dtypes)} [{out_features}, {in_features}] with a unit inner "
-                         f"stride on {device}, got {m.dtype} {tuple(m.shape)} strides {tuple(m.stride())} on {m.device}")
-
-
-def calib_delta(codes, codebooks, scales, reference_weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """D [out, in] fp32 = ``scales * sum_c codebooks[c][codes[..., c]] - reference_weight``: every operation one fp32 operation, the bits of
-    torch's fp32 ``_dequantize_weight(...) - reference_weight`` (include/aqlm_hip.h, aqlm_hip_calib_delta).  ``reference_weight`` fp32 / fp16
-    / bf16 with any row stride; ``out``: an fp32 [out, in] to write (rows 16-byte aligned), default a new one.  One launch."""
-    codes, books, scales, o, i, K, nbits, g = _calib_layer("calib_delta", codes, codebooks, scales)
-    if scales is None:
-        raise ValueError("calib_delta: scales are required")
-    _check_calib_matrix("calib_delta", "reference_weight", reference_weight, o, i, books.device, tuple(_GRAD_DT))
-    if out is None:
-        out = torch.empty((o, i), dtype=torch.float32, device=books.device)
-    _check_calib_matrix("calib_delta", "out", out, o, i, books.device)
-    with _device_guard(books.device):
-        rc = _lib.aqlm_hip_calib_delta(codes.data_ptr(), books.data_ptr(), scales.data_ptr(), reference_weight.data_ptr(),
-                                       _GRAD_DT[reference_weight.dtype], reference_weight.stride(0), o, i, K, nbits, g, out.data_ptr(),
-                                       out.stride(0), _stream_ptr(books.device))
-    if rc:
-        _native.check(rc, "aqlm calib delta")
-    return out
-
-
-def calib_rows(g_matrix, delta, codes, codebooks):
-    """``(ds_raw [out], rowloss [out])`` fp32 of ``G = D @ XTX`` and the stored ``D``: ``ds_raw[o] = sum G[o] * w[o]`` (w: the UNSCALED
-    dequantised row), ``rowloss[o] = sum G[o] * D[o]``; one wave per row in the fixed order of ``scales_grad_1x16`` (include/aqlm_hip.h,
-    aqlm_hip_calib_rows).  One launch."""
-    codes, books, _, o, i, K, nbits, g = _calib_layer("calib_rows", codes, codebooks, None)
-    _check_calib_matrix("calib_rows", "G", g_matrix, o, i, books.device)
-    _check_calib_matrix("calib_rows", "D", delta, o, i, books.device)
-    out = torch.empty((2, o), dtype=torch.float32, device=books.device)
-    with _device_guard(books.device):
-        rc = _lib.aqlm_hip_calib_rows(g_matrix.data_ptr(), g_matrix.stride(0), delta.data_ptr(), delta.stride(0), codes.data_ptr(),
-                                      books.data_ptr(), o, i, K, nbits, g, out[0].data_ptr(), out[1].data_ptr(), _stream_ptr(books.device))
-    if rc:
-        _native.check(rc, "aqlm calib rows")
-    return out[0], out[1]
-
-
-def calib_codebook_grad_1x16(g_matrix, scales, index: CodebookGradIndex) -> torch.Tensor:
-    """dC [65536, g] fp32: per entry the sum of ``scales[o] * G[o, j*g : j*g + g]`` over the positions of its list -- the launches and the
-    order of ``codebook_grad_1x16`` with fp32 scales (aqlm_hip_calib_codebook_grad_1x16).  Every element is written."""
-    o, i, g = index.geometry()
-    _check_calib_matrix("calib_codebook_grad_1x16", "G", g_matrix, o, i, index.order.device)
-    if scales.numel() != o or scales.dtype != torch.float32 or scales.device != g_matrix.device:
-        raise ValueError(f"calib_codebook_grad_1x16: scales must hold {o} fp32 elements on {g_matrix.device}")
-    scales = _c(scales.detach()).reshape(-1)
-    out = torch.empty((CODEBOOK_GRAD_ENTRIES, g), dtype=torch.float32, device=g_matrix.device)
-    ws_bytes = int(_lib.aqlm_hip_calib_codebook_grad_1x16_workspace_bytes(o, i, g))
-    ws = _workspace(g_matrix.device, max(ws_bytes, 16))
-    with _device_guard(g_matrix.device):
-        rc = _lib.aqlm_hip_calib_codebook_grad_1x16(g_matrix.data_ptr(), g_matrix.stride(0), scales.data_ptr(), index.starts.data_ptr(),
-                                                    index.order.data_ptr(), index.chunks.data_ptr(), index.chunk_starts.data_ptr(), o, i, g,
-                                                    out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(g_matrix.device))
-    if rc:
-        _native.check(rc, "aqlm calib codebook grad")
-    return out
-
-
-def calib_codebook_grad_kx8(g_matrix, scales, codes, in_group_size: int) -> torch.Tensor:
-    """dC [K, 256, g] fp32 of a K x 8 layer: the fixed-point sums of ``codebook_grad_kx8`` with fp32 scales
-    (aqlm_hip_calib_codebook_grad_kx8); NaN everywhere when ``G`` or the scales hold a non-finite value."""
-    g = int(in_group_size)
-    o, i, K = int(codes.shape[0]), int(codes.shape[1]) * g, int(codes.shape[2])
-    _check_calib_matrix("calib_codebook_grad_kx8", "G", g_matrix, o, i, codes.device)
-    _check_kx8_codes(codes, g_matrix, o, i, K, g, "calib_codebook_grad_kx8")
-    if scales.numel() != o or scales.dtype != torch.float32 or scales.device != g_matrix.device:
-        raise ValueError(f"calib_codebook_grad_kx8: scales must hold {o} fp32 elements on {g_matrix.device}")
-    scales = _c(scales.detach()).reshape(-1)
-    out = torch.empty((K, 256, g), dtype=torch.float32, device=g_matrix.device)
-    ws_bytes = int(_lib.aqlm_hip_calib_codebook_grad_kx8_workspace_bytes(o, i, K, g))
-    ws = _workspace(g_matrix.device, max(ws_bytes, 16))
-    with _device_guard(g_matrix.device):
-        rc = _lib.aqlm_hip_calib_codebook_grad_kx8(g_matrix.data_ptr(), g_matrix.stride(0), scales.data_ptr(), codes.data_ptr(), o, i, K, g,
-                                                   out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(g_matrix.device))
-    if rc:
-        _native.check(rc, "aqlm calib codebook grad kx8")
-    return out
-
-
-# ------------------------------------------------------------------------------------------------------
-# nearest-codeword search of the 1x16 schemes (the V step of PV-tuning; aqlm_hip_code_search_1x16)
-# ------------------------------------------------------------------------------------------------------
-CODE_SEARCH_EPS = _native.CODE_SEARCH_EPS  # the accuracy contract of include/aqlm_hip.h: computed scores within eps * (|r|^2 + max|C|^2)
-
-
-def code_search_1x16_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
-    return bool(_lib.aqlm_hip_code_search_1x16_supported(int(out_features), int(in_features), int(in_group_size)))
-
-
-def _code_search_1x16_impl(reference, scales, codebook, group_ids, codes_out, geometry):
-    out_features, in_features, g = (int(x) for x in geometry)
-    if (reference.dim() != 2 or tuple(reference.shape) != (out_features, in_features) or reference.dtype not in _GRAD_DT
-            or not reference.is_cuda):
-        raise ValueError(f"code_search_1x16: reference must be fp16 / bf16 / fp32 [{out_features}, {in_features}] on the GPU, got "
-                         f"{reference.dtype} {tuple(reference.shape)}")
-    if reference.stride(1) != 1 or reference.stride(0) < in_features:  # a transposed or expanded view: the kernel walks rows
-        reference = reference.contiguous()
-    if codebook.numel() != CODEBOOK_GRAD_ENTRIES * g or codebook.device != reference.device:
-        raise ValueError(f"code_search_1x16: the codebook must hold 65536 x {g} elements on {reference.device}")
-    dt = _dtype_id(codebook)
-    codebook = _c(codebook)
-    if scales is not None:
-        if scales.numel() != out_features or scales.device != reference.device or scales.dtype != codebook.dtype:
-            raise ValueError(f"code_search_1x16: scales must hold {out_features} elements of {codebook.dtype} on {reference.device}")
-        scales = _c(scales)
-    total = out_features * (in_features // max(g, 1))
-    if group_ids is not None:
-        if group_ids.dtype not in (torch.int32, torch.int64) or group_ids.dim() != 1 or group_ids.device != reference.device:
-            raise ValueError("code_search_1x16: group_ids must be a 1-d int32 / int64 tensor on the reference's device")
-        group_ids = _c(group_ids)
-        n = int(group_ids.numel())
-    else:
-        n = total
-    if codes_out is None:
-        codes_out = torch.empty((n,), dtype=torch.int16, device=reference.device)
-    elif codes_out.dtype != torch.int16 or codes_out.numel() != n or not codes_out.is_contiguous() or codes_out.device != reference.device:
-        raise ValueError(f"code_search_1x16: codes_out must be contiguous int16 [{n}] on {reference.device}")
-    if n == 0:
-        return codes_out
-    ws_bytes = int(_lib.aqlm_hip_code_search_1x16_workspace_bytes(n, g))
-    ws = _workspace(reference.device, max(ws_bytes, 16))
-    with _device_guard(reference.device):
-        rc = _lib.aqlm_hip_code_search_1x16(reference.data_ptr(), _GRAD_DT[reference.dtype], reference.stride(0), _ptr(scales),
-                                            codebook.data_ptr(), dt, out_features, in_features, g, _ptr(group_ids),
-                                            int(group_ids is not None and group_ids.dtype == torch.int64), n, codes_out.data_ptr(),
-                                            ws.data_ptr(), ws.numel() * 4, _stream_ptr(reference.device))
-    if rc:
-        _native.check(rc, "aqlm code search")
-    return codes_out
-
-
-def _code_search_1x16_op(reference, scales, codebook, group_ids, geometry):
-    return _code_search_1x16_impl(reference, scales, codebook, group_ids, None, geometry)
-
-
-def code_search_1x16(reference, scales, codebook, in_group_size: int, group_ids=None, codes_out=None):
-    """int16 codes: for every group of ``in_group_size`` weights of ``reference`` [out, in] (fp32 / fp16 / bf16, any row stride; a view
-    with another column stride is copied first) --
-    or for the flat groups ``group_ids`` (int32 / int64, ``o * (in / g) + j``), in their order -- the codeword of ``codebook`` (65536
-    x g elements, fp16 / bf16) that minimises ``|C_c|^2 - 2 <reference_group / scales[o], C_c>``; ``scales`` ([out] elements in the
-    codebook dtype) None = 1.  Equal computed scores give the smallest index; the accuracy contract is in include/aqlm_hip.h
-    (``CODE_SEARCH_EPS``).  ``codes_out`` (int16, one entry per group searched): written in place when given -- an id outside the
-    layer leaves its entry as it was.  Two launches on the current stream, |C|^2 in the cached per-stream workspace."""
-    g = int(in_group_size)
-    return _code_search_1x16_impl(reference, scales, codebook, group_ids, codes_out, [int(reference.shape[0]), int(reference.shape[1]), g])
-
-
-# ------------------------------------------------------------------------------------------------------
-# k-means initialisation: one Lloyd iteration (aqlm_hip_kmeans_assign, aqlm_hip_kmeans_update)
-# ------------------------------------------------------------------------------------------------------
-KMEANS_EPS = _native.KMEANS_EPS  # the accuracy contract of include/aqlm_hip.h: computed scores within eps * (|x|^2 + max|C|^2)
-
-
-def kmeans_supported(n: int, k: int, d: int) -> bool:
-    return bool(_lib.aqlm_hip_kmeans_supported(int(n), int(k), int(d)))
-
-
-def _kmeans_operands(who, data, centroids):
-    if data.dim() != 2 or data.dtype != torch.float32 or not data.is_cuda:
-        raise ValueError(f"{who}: data must be fp32 [n, d] on the GPU, got {data.dtype} {tuple(data.shape)} on {data.device}")
-    if centroids.dim() != 2 or centroids.dtype != torch.float32 or centroids.device != data.device or centroids.shape[1] != data.shape[1]:
-        raise ValueError(f"{who}: centroids must be fp32 [k, {data.shape[1]}] on {data.device}, got {centroids.dtype} "
-                         f"{tuple(centroids.shape)} on {centroids.device}")
-    n, d, k = int(data.shape[0]), int(data.shape[1]), int(centroids.shape[0])
-    if not kmeans_supported(n, k, d):
-        raise NotImplementedError(f"{who}: n={n} k={k} d={d} is outside the kernel (d 8 or 16, k a multiple of 128 up to 65536, "
-                                  "1 <= n < 2^31)")
-    return n, k, d
-
-
-def _aligned16(t: torch.Tensor) -> torch.Tensor:
-    t = _c(t)
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
-def _kmeans_assign_op(data, centroids, data_absmax, with_sums):
-    n, k, d = _kmeans_operands("kmeans_assign", data, centroids)
-    data, centroids = _aligned16(data), _aligned16(centroids)
-    codes = torch.empty((n,), dtype=torch.int32, device=data.device)
-    sums = torch.empty((k, d) if with_sums else (0, d), dtype=torch.int64, device=data.device)
-    counts = torch.empty((k,) if with_sums else (0,), dtype=torch.int32, device=data.device)
-    ws_bytes = int(_lib.aqlm_hip_kmeans_workspace_bytes(n, k, d))
-    ws = _workspace(data.device, ws_bytes)
-    with _device_guard(data.device):
-        rc = _lib.aqlm_hip_kmeans_assign(data.data_ptr(), n, centroids.data_ptr(), k, d, float(data_absmax), codes.data_ptr(),
-                                         sums.data_ptr() if with_sums else None, counts.data_ptr() if with_sums else None,
-                                         ws.data_ptr(), ws.numel() * 4, _stream_ptr(data.device))
-    if rc:
-        _native.check(rc, "aqlm kmeans assign")
-    return codes, sums, counts
-
-
-def kmeans_assign(data, centroids, data_absmax: float, with_sums: bool = True):
-    """-> (codes int32 [n], sums int64 [k, d], counts int32 [k]): per row of ``data`` [n, d] (fp32, d 8 / 16) the index of the row of
-    ``centroids`` [k, d] (fp32, k a multiple of 128 up to 65536) that minimises ``|C_c|^2 - 2 <x_n, C_c>`` -- equal computed scores
-    give the smallest index, the accuracy contract is in include/aqlm_hip.h (``KMEANS_EPS``) -- and the fixed-point sums and counts of
-    every cluster's points in the unit that ``data_absmax`` (>= every |element| of ``data``) and n set (tests/kmeans_model.py restates
-    it); a point with a non-finite element or one above ``data_absmax`` adds nothing.  ``with_sums=False``: the codes alone (the other two
-    tensors are empty).  Memsets and three launches on the current stream, the centroids' split image in the cached workspace."""
-    return _kmeans_assign_op(data, centroids, float(data_absmax), bool(with_sums))
-
-
-def kmeans_update_(centroids, sums, counts, n: int, data_absmax: float) -> None:
-    """``centroids[c] = sums[c] * 2^-s / counts[c]`` in place where ``counts[c] > 0`` (double arithmetic, one rounding to fp32); an empty
-    cluster keeps its centroid bit for bit.  ``n`` and ``data_absmax``: those of the ``kmeans_assign`` call that made the sums."""
-    if centroids.dim() != 2 or centroids.dtype != torch.float32 or not centroids.is_cuda or not centroids.is_contiguous():
-        raise ValueError(f"kmeans_update_: centroids must be contiguous fp32 [k, d] on the GPU, got {centroids.dtype} {tuple(centroids.shape)}")
-    k, d = int(centroids.shape[0]), int(centroids.shape[1])
-    if (sums.dtype != torch.int64 or tuple(sums.shape) != (k, d) or not sums.is_contiguous() or sums.device != centroids.device
-            or counts.dtype != torch.int32 or tuple(counts.shape) != (k,) or not counts.is_contiguous() or counts.device != centroids.device):
-        raise ValueError(f"kmeans_update_: sums must be contiguous int64 [{k}, {d}] and counts int32 [{k}] on {centroids.device}")
-    with _device_guard(centroids.device):
-        rc = _lib.aqlm_hip_kmeans_update(sums.data_ptr(), counts.data_ptr(), int(n), k, d, float(data_absmax), centroids.data_ptr(),
-                                         _stream_ptr(centroids.device))
-    if rc:
-        _native.check(rc, "aqlm kmeans update")
-
-
-def kmeans_update(centroids, sums, counts, n: int, data_absmax: float) -> torch.Tensor:
-    """``kmeans_update_`` on a copy: the new centroids."""
-    out = centroids.detach().clone(memory_format=torch.contiguous_format)
-    kmeans_update_(out, sums, counts, n, data_absmax)
-    return out
-
-
-# ------------------------------------------------------------------------------------------------------
-# beam search over the codebooks of the K x 8 schemes (the V step of PV-tuning; aqlm_hip_code_search_kx8)
-# ------------------------------------------------------------------------------------------------------
-CODE_SEARCH_KX8_MAX_BEAM = 16  # AQLM_HIP_CODE_SEARCH_KX8_MAX_BEAM
-
-
-def code_search_kx8_supported(out_features: int, in_features: int, num_codebooks: int, in_group_size: int, beam_size: int) -> bool:
-    return bool(_lib.aqlm_hip_code_search_kx8_supported(int(out_features), int(in_features), int(num_codebooks), int(in_group_size),
-                                                        int(beam_size)))
-
-
-def _dim_order(who: str, dim_order, K: int):
-    """``dim_order`` as a list of ints (None stays None); anything but a permutation of 0 .. K - 1 is a ValueError in ``who``'s name."""
-    if dim_order is None:
-        return None
-    order = [int(c) for c in dim_order]
-    if sorted(order) != list(range(K)):
-        raise ValueError(f"{who}: dim_order must be a permutation of 0 .. {K - 1}, got {order}")
-    return order
-
-
-def _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out, geometry, want_scores):
-    out_features, in_features, K, g, beam_size = (int(x) for x in geometry[:5])
-    if (reference.dim() != 2 or tuple(reference.shape) != (out_features, in_features) or reference.dtype not in _GRAD_DT
-            or not reference.is_cuda):
-        raise ValueError(f"code_search_kx8: reference must be fp16 / bf16 / fp32 [{out_features}, {in_features}] on the GPU, got "
-                         f"{reference.dtype} {tuple(reference.shape)}")
-    if reference.stride(1) != 1 or reference.stride(0) < in_features:  # a transposed or expanded view: the kernel walks rows
-        reference = reference.contiguous()
-    if codebooks.numel() != K * 256 * g or codebooks.device != reference.device:
-        raise ValueError(f"code_search_kx8: the codebooks must hold {K} x 256 x {g} elements on {reference.device}")
-    dt = _dtype_id(codebooks)
-    codebooks = _c(codebooks)
-    if scales is not None:
-        if scales.numel() != out_features or scales.device != reference.device or scales.dtype != codebooks.dtype:
-            raise ValueError(f"code_search_kx8: scales must hold {out_features} elements of {codebooks.dtype} on {reference.device}")
-        scales = _c(scales)
-    total = out_features * (in_features // max(g, 1))
-    if prev_codes.dtype != torch.int8 or prev_codes.numel() != total * K or prev_codes.device != reference.device:
-        raise ValueError(f"code_search_kx8: prev_codes must hold {total} x {K} int8 codes (the whole layer) on {reference.device}")
-    prev_codes = _c(prev_codes)
-    order = _dim_order("code_search_kx8", geometry[5:] or None, K)  # (the geometry ends after beam_size: no dim_order)
-    if group_ids is not None:
-        if group_ids.dtype not in (torch.int32, torch.int64) or group_ids.dim() != 1 or group_ids.device != reference.device:
-            raise ValueError("code_search_kx8: group_ids must be a 1-d int32 / int64 tensor on the reference's device")
-        group_ids = _c(group_ids)
-        n = int(group_ids.numel())
-    else:
-        n = total
-    if codes_out is None:
-        codes_out = torch.empty((n, K), dtype=torch.int8, device=reference.device)
-    elif codes_out.dtype != torch.int8 or codes_out.numel() != n * K or not codes_out.is_contiguous() or codes_out.device != reference.device:
-        raise ValueError(f"code_search_kx8: codes_out must be contiguous int8 [{n}, {K}] on {reference.device}")
-    scores = torch.empty((n,), dtype=torch.float32, device=reference.device) if want_scores else None
-    if n == 0:
-        return codes_out, scores
-    dim_order = (ctypes.c_int * K)(*order) if order else None
-    with _device_guard(reference.device):
-        rc = _lib.aqlm_hip_code_search_kx8(reference.data_ptr(), _GRAD_DT[reference.dtype], reference.stride(0), _ptr(scales),
-                                           codebooks.data_ptr(), dt, prev_codes.data_ptr(), out_features, in_features, K, g, beam_size,
-                                           dim_order, _ptr(group_ids), int(group_ids is not None and group_ids.dtype == torch.int64), n,
-                                           codes_out.data_ptr(), _ptr(scores), None, 0, _stream_ptr(reference.device))
-    if rc:
-        _native.check(rc, "aqlm code search kx8")
-    return codes_out, scores
-
-
-def _code_search_kx8_op(reference, scales, codebooks, prev_codes, group_ids, geometry):
-    return _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, None, geometry, True)
-
-
-def code_search_kx8(reference, scales, codebooks, prev_codes, in_group_size: int, beam_size: int, dim_order=None, group_ids=None,
-                    codes_out=None, return_scores: bool = False):
-    """int8 codes [n, K]: for every group of ``in_group_size`` weights of ``reference`` [out, in] (fp32 / fp16 / bf16, any row stride; a
-    view with another column stride is copied first) -- or for the flat groups ``group_ids`` (int32 / int64, ``o * (in / g) + j``), in
-    their order -- the codes the reference's beam search over the ``K`` codebooks (``codebooks``: K x 256 x g elements, fp16 / bf16)
-    reaches from ``prev_codes`` (int8, the WHOLE layer's [out * in / g, K], read at the group's id) with ``beam_size`` hypotheses,
-    revisiting the codebooks in ``dim_order`` (default 0 .. K - 1); ``scales`` ([out] elements in the codebook dtype) None = 1.  The
-    arithmetic is fixed operation for operation in include/aqlm_hip.h (tests/kx8_search_model.py is its numpy restatement): equal
-    scores go to the smaller flat index ``position * 256 + code``.  ``codes_out`` (int8, K entries per group searched): written in
-    place when given -- an id outside the layer leaves its entries as they were.  ``return_scores``: also the fp32 score of the
-    returned hypothesis on the last step, [n].  One launch on the current stream, no workspace."""
-    g, K = int(in_group_size), int(codebooks.shape[0])
-    order = _dim_order("code_search_kx8", dim_order, K) or []
-    codes, scores = _code_search_kx8_impl(reference, scales, codebooks, prev_codes, group_ids, codes_out,
-                                          [int(reference.shape[0]), int(reference.shape[1]), K, g, int(beam_size)] + order, return_scores)
-    return (codes, scores) if return_scores else codes
-
-
-# ------------------------------------------------------------------------------------------------------
-# the calibrated beam search of the K x 8 schemes, one input group per launch (aqlm_hip_code_search_kx8_xtx)
-# ------------------------------------------------------------------------------------------------------
-def code_search_kx8_xtx_supported(out_features: int, num_codebooks: int, in_group_size: int, beam_size: int, positions_in: int = 1) -> bool:
-    return bool(_lib.aqlm_hip_code_search_kx8_xtx_supported(int(out_features), int(num_codebooks), int(in_group_size), int(beam_size),
-                                                            int(positions_in)))
-
-
-class XtxStep(NamedTuple):
-    """What one launch of aqlm_hip_code_search_kx8_xtx returns, every tensor [beam_size, out, ...] with rank 0 the best."""
-
-    loss: torch.Tensor     # fp32 [beam, out]
-    codes: torch.Tensor    # int8 [beam, out, K]
-    source: torch.Tensor   # uint8 [beam, out]: the position at entry
-    delta: torch.Tensor    # fp32 [beam, out, g]
-    t: Optional[torch.Tensor]  # fp32 [beam, out, g] when asked for
-
-
-def code_search_kx8_xtx_step(t, loss, codes_in, H, q, codebooks, scales, beam_size: int, dim_order=None, return_t: bool = False) -> XtxStep:
-    """One launch of aqlm_hip_code_search_kx8_xtx: all K codebook steps of the calibrated beam search for ONE input group and every
-    output row (include/aqlm_hip.h has the definition and the arithmetic, tests/kx8_xtx_model.py its numpy restatement).  ``t`` fp32
-    [positions, out, g] -- the group's slice of ``T = (W_ref - W_position) XTX``, any position / row stride with g contiguous (a view
-    into a wider buffer is read in place) --, ``loss`` fp32 [positions, out], ``codes_in`` int8 [positions, out, K], ``H`` fp32 [g, g] =
-    ``XTX[group, group]``, ``q`` fp32 [K, 256] = ``C H C^T`` unscaled, ``codebooks`` K x 256 x g elements fp16 / bf16, ``scales`` [out]
-    elements in the same dtype or None.  One launch on the current stream; no workspace, no synchronisation."""
-    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
-        raise ValueError(f"code_search_kx8_xtx_step: t must be fp32 [positions, out, g] on the GPU, got {t.dtype} {tuple(t.shape)}")
-    positions, out_features, g = (int(x) for x in t.shape)
-    K, beam_size = int(codebooks.shape[0]), int(beam_size)
-    dev = t.device
-    if t.stride(2) != 1 or t.stride(1) < g or (positions > 1 and t.stride(0) < g):
-        t = t.contiguous()
-    if codebooks.numel() != K * 256 * g or codebooks.device != dev:
-        raise ValueError(f"code_search_kx8_xtx_step: the codebooks must hold {K} x 256 x {g} elements on {dev}")
-    dt = _dtype_id(codebooks)
-    codebooks = _c(codebooks)
-    for name, x, shape, dtype in (("loss", loss, (positions, out_features), torch.float32), ("codes_in", codes_in, (positions, out_features, K), torch.int8),
-                                  ("H", H, (g, g), torch.float32), ("q", q, (K, 256), torch.float32)):
-        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
-            raise ValueError(f"code_search_kx8_xtx_step: {name} must be {dtype} {list(shape)} on {dev}, got {x.dtype} {tuple(x.shape)}")
-    loss, codes_in, H, q = _c(loss), _c(codes_in), _c(H), _c(q)
-    if scales is not None:
-        if scales.numel() != out_features or scales.device != dev or scales.dtype != codebooks.dtype:
-            raise ValueError(f"code_search_kx8_xtx_step: scales must hold {out_features} elements of {codebooks.dtype} on {dev}")
-        scales = _c(scales)
-    order = _dim_order("code_search_kx8_xtx_step", dim_order, K)
-    if not code_search_kx8_xtx_supported(out_features, K, g, beam_size, positions):
-        raise NotImplementedError(f"code_search_kx8_xtx_step: K={K} g={g} beam_size={beam_size} positions={positions} is outside the kernel")
-    out = XtxStep(torch.empty((beam_size, out_features), dtype=torch.float32, device=dev),
-                  torch.empty((beam_size, out_features, K), dtype=torch.int8, device=dev),
-                  torch.empty((beam_size, out_features), dtype=torch.uint8, device=dev),
-                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev),
-                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev) if return_t else None)
-    with _device_guard(dev):
-        rc = _lib.aqlm_hip_code_search_kx8_xtx(t.data_ptr(), t.stride(0), t.stride(1), loss.data_ptr(), codes_in.data_ptr(), H.data_ptr(),
-                                               q.data_ptr(), codebooks.data_ptr(), dt, _ptr(scales), out_features, K, g, beam_size, positions,
-                                               None if order is None else (ctypes.c_int * K)(*order), out.loss.data_ptr(),
-                                               out.codes.data_ptr(), out.source.data_ptr(), out.delta.data_ptr(), _ptr(out.t), None, 0,
-                                               _stream_ptr(dev))
-    if rc:
-        _native.check(rc, "aqlm code search kx8 xtx")
-    return out
-
-
-# ------------------------------------------------------------------------------------------------------
-# the calibrated search of the 1x16 schemes, one input group per call (aqlm_hip_code_search_1x16_xtx)
-# ------------------------------------------------------------------------------------------------------
-CODE_SEARCH_1X16_XTX_MAX_BEAM = 8  # AQLM_HIP_CODE_SEARCH_1X16_XTX_MAX_BEAM
-
-
-def code_search_1x16_xtx_supported(out_features: int, in_group_size: int, beam_size: int, positions_in: int = 1) -> bool:
-    return bool(_lib.aqlm_hip_code_search_1x16_xtx_supported(int(out_features), int(in_group_size), int(beam_size), int(positions_in)))
-
-
-def code_search_1x16_xtx_step(t, loss, codes_in, H, q, codebook, scales, beam_size: int, return_t: bool = False) -> XtxStep:
-    """One call of aqlm_hip_code_search_1x16_xtx: the calibrated search of ONE input group of a 1x16 layer for every output row
-    (include/aqlm_hip.h has the definition and the arithmetic, tests/x16_xtx_model.py its numpy restatement).  ``t`` fp32 [positions, out,
-    g] -- any position / row stride with g contiguous (a view into a wider buffer is read in place) --, ``loss`` fp32 [positions, out],
-    ``codes_in`` int16 [positions, out, 1], ``H`` fp32 [g, g] = ``XTX[group, group]``, ``q`` fp32 [65536] (or [1, 65536]) = ``C H C^T``
-    unscaled, ``codebook`` 65536 x g elements fp16 / bf16, ``scales`` [out] elements in the same dtype or None.  Returns an ``XtxStep``
-    with int16 codes [beam_size, out, 1].  Three launches on the current stream through a workspace allocated on the current device;
-    no synchronisation."""
-    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
-        raise ValueError(f"code_search_1x16_xtx_step: t must be fp32 [positions, out, g] on the GPU, got {t.dtype} {tuple(t.shape)}")
-    positions, out_features, g = (int(x) for x in t.shape)
-    beam_size = int(beam_size)
-    dev = t.device
-    if t.stride(2) != 1 or t.stride(1) < g or (positions > 1 and t.stride(0) < g):
-        t = t.contiguous()
-    if codebook.numel() != 65536 * g or codebook.device != dev:
-        raise ValueError(f"code_search_1x16_xtx_step: the codebook must hold 65536 x {g} elements on {dev}")
-    dt = _dtype_id(codebook)
-    codebook = _c(codebook)
-    if q.dim() == 2 and q.shape[0] == 1:
-        q = q[0]
-    for name, x, shape, dtype in (("loss", loss, (positions, out_features), torch.float32), ("codes_in", codes_in, (positions, out_features, 1), torch.int16),
-                                  ("H", H, (g, g), torch.float32), ("q", q, (65536,), torch.float32)):
-        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
-            raise ValueError(f"code_search_1x16_xtx_step: {name} must be {dtype} {list(shape)} on {dev}, got {x.dtype} {tuple(x.shape)}")
-    loss, codes_in, H, q = _c(loss), _c(codes_in), _c(H), _c(q)
-    if scales is not None:
-        if scales.numel() != out_features or scales.device != dev or scales.dtype != codebook.dtype:
-            raise ValueError(f"code_search_1x16_xtx_step: scales must hold {out_features} elements of {codebook.dtype} on {dev}")
-        scales = _c(scales)
-    if not code_search_1x16_xtx_supported(out_features, g, beam_size, positions):
-        raise NotImplementedError(f"code_search_1x16_xtx_step: g={g} beam_size={beam_size} positions={positions} is outside the kernel")
-    out = XtxStep(torch.empty((beam_size, out_features), dtype=torch.float32, device=dev),
-                  torch.empty((beam_size, out_features, 1), dtype=torch.int16, device=dev),
-                  torch.empty((beam_size, out_features), dtype=torch.uint8, device=dev),
-                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev),
-                  torch.empty((beam_size, out_features, g), dtype=torch.float32, device=dev) if return_t else None)
-    need = int(_lib.aqlm_hip_code_search_1x16_xtx_workspace_bytes(out_features, g, beam_size, positions))
-    with _device_guard(dev):
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-        rc = _lib.aqlm_hip_code_search_1x16_xtx(t.data_ptr(), t.stride(0), t.stride(1), loss.data_ptr(), codes_in.data_ptr(), H.data_ptr(),
-                                                q.data_ptr(), codebook.data_ptr(), dt, _ptr(scales), out_features, g, beam_size, positions,
-                                                out.loss.data_ptr(), out.codes.data_ptr(), out.source.data_ptr(), out.delta.data_ptr(),
-                                                _ptr(out.t), workspace.data_ptr(), need, _stream_ptr(dev))
-    if rc:
-        _native.check(rc, "aqlm code search 1x16 xtx")
-    return out
-
-
-# ------------------------------------------------------------------------------------------------------
-# expert-routed matvec on PREPACKED experts (mixture-of-experts decode; aqlm_hip_gemv_1x16_routed_packed)
-# ------------------------------------------------------------------------------------------------------
-ROUTED_PACKED_GEOMETRY_INTS = 11  # [E, S, out, in, g, top_k] + rows_per_group, max_waves, slice_first, lds_bytes, table words
-
-
-def _desc_array(packed_list):
-    return (_native._descp * len(packed_list))(*[ctypes.pointer(p.desc) for p in packed_list])
-
-
-def routed_packed_supported(packed_list) -> bool:
-    """Will aqlm_hip_gemv_1x16_routed_packed serve a table of these ``PackedCodes`` (one shape; 4-byte entries, uniform geometry, a
-    codebook range each)?  A host query on the descriptors."""
-    if not packed_list or any(p is None or not isinstance(p, PackedCodes) for p in packed_list):
-        return False
-    return bool(_lib.aqlm_hip_gemv_1x16_routed_packed_supported(_desc_array(packed_list), len(packed_list)))
-
-
-def routed_packed_table(layers, device):
-    """The device-resident table of aqlm_hip_gemv_1x16_routed_packed and its launch geometry: ``layers[e][s] = (packed,
-    codebooks, scales, bias or None)`` with ``packed`` the layer's ``PackedCodes`` -> (int64 table on ``device``, entry [e * S + s]
-    as filled by aqlm_hip_routed_packed_entry_fill; geometry tail for ``code1x16_moe_matmat_packed``).  Every expert's codebook
-    range -- and the codebook image of a relabelled buffer -- is brought up to date first (``refresh_range``): the table bakes in
-    the bound and the image's address.  The table holds raw addresses: the caller keeps the tensors alive and rebuilds it when one
-    of them moves or is rewritten.  A host-to-device copy (and, for a stale range, a read-back): never while a hipGraph is being
-    captured.  NotImplementedError when the launch declines the table (the caller keeps the routed launch on the canonical
-    codes)."""
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("routed_packed_table: the table is built by a host-to-device copy; build it before capturing")
-    entries, packs = [], []
-    for per_expert in layers:
-        for packed, codebooks, scales, bias in per_expert:
-            for t in (codebooks, scales):
-                if not t.is_contiguous() or t.data_ptr() % 16:
-                    raise ValueError("routed packed table: codebooks / scales must be contiguous and 16-byte aligned")
-            if bias is not None and not bias.is_contiguous():
-                raise ValueError("routed packed table: bias must be contiguous")
-            refresh_range(packed, codebooks)
-            ent = _native.RoutedPackedEntry()
-            rc = _lib.aqlm_hip_routed_packed_entry_fill(ctypes.byref(packed.desc), packed.data_ptr(), codebooks.data_ptr(),
-                                                        scales.data_ptr(), _ptr(bias), ctypes.byref(ent))
-            if rc:
-                _native.check(rc, "aqlm routed_packed_entry_fill")
-            entries.append(ent)
-            packs.append(packed)
-    geom = _native.RoutedPackedGeometry()
-    rc = _lib.aqlm_hip_gemv_1x16_routed_packed_geometry(_desc_array(packs), len(packs), ctypes.byref(geom))
-    if rc:
-        _native.check(rc, "aqlm routed_packed_geometry")
-    raw = b"".join(bytes(e) for e in entries)
-    table = torch.frombuffer(bytearray(raw), dtype=torch.int64).clone().to(device)
-    tail = [int(geom.rows_per_group), int(geom.max_waves), int(geom.slice_first), int(geom.lds_bytes), int(table.numel())]
-    return table, tail
-
-
-# Accumulator cells of the routed packed launch: [pairs][segments][out_features] u64, zero at rest.  One zero-filled buffer per
-# table (= per block and projection launch) and size class, allocated at the first eager call and reused by every later call,
-# captured ones included -- a capture runs on a stream of its own, so a per-stream registry would find nothing there, and
-# nothing can be allocated for good inside a capture.  The kernel leaves every cell it touched at zero.  Like the cells inside a
-# packed buffer, a set serves one stream at a time: one block must not run on two streams at once.  A hipGraph may have captured
-# an address, so a buffer is never resized or freed behind its back: sizes are rounded up to a power of two and each size class
-# is allocated once (release_routed_packed_cells frees them when the caller knows no such graph is alive).
-_ROUTED_PACKED_CELLS = {}
-
-
-def routed_packed_cells(device: torch.device, owner: int, nbytes: int):
-    size = 1 << max(16, (int(nbytes) - 1).bit_length())
-    key = (device.index, owner, size)
-    cells = _ROUTED_PACKED_CELLS.get(key)
-    if cells is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("code1x16_moe_matmat_packed: the accumulator cells are allocated at the first eager call; run one "
-                               "eager forward of this size before capturing")
-        with torch.cuda.device(device):
-            cells = torch.zeros((size // 8,), dtype=torch.int64, device=device)
-        _ROUTED_PACKED_CELLS[key] = cells
-    return cells
-
-
-def release_routed_packed_cells() -> int:
-    """Free every cell buffer of the routed packed launch (the caller knows that no hipGraph that captured one is alive)."""
-    n = len(_ROUTED_PACKED_CELLS)
-    _ROUTED_PACKED_CELLS.clear()
-    return n
-
-
-def code1x16_moe_matmat_packed(input, expert_ids, table, geometry, x_per_pair):
-    """``code1x16_moe_matmat`` on prepacked experts: every (token, expert) pair of one or two 1x16 projections of a
-    mixture-of-experts block in one launch per 64 pairs, each pair a batch-1 pass of the packed matvec on its expert's buffer.
-    geometry = [num_experts, num_segments, out_features, in_features, in_group_size, top_k] + the tail ``routed_packed_table``
-    returned with ``table``.  ``expert_ids`` [T, top_k] int64 / int32 on the device (read there only; ids outside
-    [0, num_experts) give zero rows); ``input`` [T, in] (token rows) or [T * top_k, in] (``x_per_pair``).
-    -> [T * top_k, num_segments, out_features]; row (t * top_k + j, s) is bit-identical to ``code1x16_matmat_packed`` of expert
-    expert_ids[t, j], projection s, on that row alone."""
-    if len(geometry) != ROUTED_PACKED_GEOMETRY_INTS:
-        raise ValueError(f"geometry must hold {ROUTED_PACKED_GEOMETRY_INTS} ints (shape + the tail of routed_packed_table)")
-    E, S, out_features, in_features, g, top_k, rpg, max_waves, slice_first, lds_bytes, words = (int(v) for v in geometry)
-    dt = _dtype_id(input)
-    T = _check_routed_args(input, expert_ids, table, E, S, in_features, top_k, x_per_pair, _native.ROUTED_PACKED_ENTRY_WORDS, words)
-    x = _flat_rows(input)
-    if x.data_ptr() % 16 or (x.stride(0) * 2) % 16:
-        x = x.clone(memory_format=torch.contiguous_format)
-    ids = _c(expert_ids)
-    y = torch.empty((T * top_k, S, out_features), dtype=input.dtype, device=input.device)
-    if T == 0:
-        return y
-    geom = _native.RoutedPackedGeometry(out_features, in_features, g, rpg, max_waves, slice_first, lds_bytes, 0)
-    stream = _stream_ptr(input.device)
-    max_pairs = max(t1 - t0 for t0, t1 in routed_chunks(T, top_k)) * top_k
-    cells = routed_packed_cells(input.device, table.data_ptr(), max_pairs * S * out_features * 8)
-    _routed_launches(x, ids, y, top_k, x_per_pair, "aqlm routed packed gemv",
-                     lambda idp, i64, npairs, xp, yp: _lib.aqlm_hip_gemv_1x16_routed_packed(
-                         table.data_ptr(), ctypes.byref(geom), E, S, idp, i64, npairs, top_k, xp, x.stride(0), int(bool(x_per_pair)),
-                         yp, dt, cells.data_ptr(), cells.numel() * 8, stream))
-    return y
-
-
-# ------------------------------------------------------------------------------------------------------
-# expert-grouped 1x16 GEMM (mixture-of-experts prefill / training; aqlm_hip_moe_bucket + aqlm_hip_gemm_1x16_grouped)
-# ------------------------------------------------------------------------------------------------------
-def grouped_tile_pairs(num_pairs: int, num_experts: int) -> int:
-    """Pairs per tile of the grouped launches: the mean pairs per expert rounded up to a power of two, 16 .. 128.  A function of
-    the sizes only, never of the routing, so a captured graph serves every routing."""
-    mean = -(-int(num_pairs) // max(1, int(num_experts)))
-    t = _native.GROUPED_TILE_PAIRS[0]
-    while t < mean and t < _native.GROUPED_TILE_PAIRS[-1]:
-        t *= 2
-    return t
-
-
-def grouped_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
-    """Whether aqlm_hip_gemm_1x16_grouped takes a layer of this shape (a host query: decide before a capture)."""
-    return bool(_lib.aqlm_hip_gemm_1x16_grouped_supported(int(out_features), int(in_features), int(in_group_size)))
-
-
-def _bucket_words(num_pairs: int, num_experts: int, tile_pairs: int) -> int:
-    n = _lib.aqlm_hip_moe_bucket_bytes(int(num_pairs), int(num_experts), int(tile_pairs))
-    if n == 0:
-        raise ValueError(f"moe_bucket: {num_pairs} pairs, {num_experts} experts, tiles of {tile_pairs} are outside the entry "
-                         f"(1..{_native.MAX_GROUPED_PAIRS} pairs, 1..{_native.MAX_ROUTED_EXPERTS} experts, tiles of "
-                         f"{'/'.join(map(str, _native.GROUPED_TILE_PAIRS))})")
-    return n // 4
-
-
-def moe_bucket(expert_ids, num_experts, tile_pairs):
-    """The router's ids [T, top_k] (int64 / int32, device) grouped by expert on the device (aqlm_hip_moe_bucket): an int32
-    buffer whose size depends on T * top_k, num_experts and tile_pairs only.  No host synchronisation."""
-    if expert_ids.dim() != 2 or expert_ids.dtype not in (torch.int64, torch.int32):
-        raise ValueError(f"expert_ids must be [T, top_k] int64 / int32, got {tuple(expert_ids.shape)} {expert_ids.dtype}")
-    ids = _c(expert_ids)
-    bucket = torch.empty((_bucket_words(ids.numel(), num_experts, tile_pairs),), dtype=torch.int32, device=ids.device)
-    with _device_guard(ids.device):
-        rc = _lib.aqlm_hip_moe_bucket(ids.data_ptr(), int(ids.element_size() == 8), ids.numel(), int(num_experts), int(tile_pairs),
-                                      bucket.data_ptr(), _stream_ptr(ids.device))
-    if rc:
-        _native.check(rc, "aqlm moe bucket")
-    return bucket
-
-
-def _check_grouped_args(table, bucket, E, S, P, tile_pairs, device) -> None:
-    """The table and bucket checks of the grouped forward and its transposed op."""
-    if table.dtype != torch.int64 or table.numel() != E * S * _native.ROUTED_ENTRY_WORDS or table.device != device:
-        raise ValueError(f"table must be int64 [{E * S * _native.ROUTED_ENTRY_WORDS}] on {device}")
-    if bucket.dtype != torch.int32 or bucket.numel() != _bucket_words(P, E, tile_pairs) or bucket.device != device:
-        raise ValueError("bucket must come from moe_bucket with the same pairs, experts and tile size")
-
-
-def code1x16_moe_matmat_grouped(input, bucket, table, geometry, x_per_pair):
-    """``code1x16_moe_matmat`` for any number of pairs, on the expert-grouped 16-row MFMA kernel.  geometry = [num_experts,
-    num_segments, out_features, in_features, in_group_size, top_k, tile_pairs, num_pairs]; ``bucket`` from ``moe_bucket`` with
-    the same num_pairs / num_experts / tile_pairs; ``table`` from ``routed_table``; ``input`` [num_pairs / top_k, in] (token rows)
-    or [num_pairs, in] (``x_per_pair``).  -> [num_pairs, num_segments, out_features]; pairs whose id lies outside [0,
-    num_experts) get zero rows.  No host synchronisation."""
-    E, S, out_features, in_features, g, top_k, tile_pairs, P = (int(v) for v in geometry)
-    dt = _dtype_id(input)
-    if top_k < 1 or P % top_k != 0:
-        raise ValueError(f"{P} pairs is not a multiple of top_k {top_k}")
-    rows = P if x_per_pair else P // top_k
-    if input.dim() != 2 or tuple(input.shape) != (rows, in_features):
-        raise ValueError(f"input must be [{rows}, {in_features}], got {tuple(input.shape)}")
-    _check_grouped_args(table, bucket, E, S, P, tile_pairs, input.device)
-    y = torch.empty((P, S, out_features), dtype=input.dtype, device=input.device)
-    if P == 0:
-        return y
-    x = _flat_rows(input)
-    with _device_guard(input.device):
-        rc = _lib.aqlm_hip_gemm_1x16_grouped(table.data_ptr(), E, S, bucket.data_ptr(), tile_pairs, P, top_k, x.data_ptr(), x.stride(0),
-                                             int(bool(x_per_pair)), y.data_ptr(), out_features, in_features, g, dt,
-                                             _stream_ptr(input.device))
-    if rc:
-        _native.check(rc, "aqlm grouped gemm")
-    return y
-
-
-def grouped_transposed_supported(out_features: int, in_features: int, in_group_size: int) -> bool:
-    """Whether aqlm_hip_gemm_1x16_grouped_transposed takes a layer of this shape (a host query: decide before a capture)."""
-    return bool(_lib.aqlm_hip_gemm_1x16_grouped_transposed_supported(int(out_features), int(in_features), int(in_group_size)))
-
-
-def code1x16_moe_matmat_grouped_transposed(grad_output, bucket, table, geometry):
-    """The input gradient of ``code1x16_moe_matmat_grouped``: ``grad_output`` [num_pairs, num_segments, out_features] (fp16 / bf16),
-    ``bucket``, ``table`` and ``geometry`` those of the forward call -> fp32 [num_pairs, in_features],
-    gx[p] = sum_s (grad_output[p, s] * scales[e_p, s]) @ Wq[e_p, s]; pairs whose id lies outside [0, num_experts) get zero rows.
-    One launch, W never leaves the chip, no host synchronisation."""
-    E, S, out_features, in_features, g, top_k, tile_pairs, P = (int(v) for v in geometry)
-    dt = _dtype_id(grad_output)
-    if grad_output.dim() != 3 or tuple(grad_output.shape) != (P, S, out_features):
-        raise ValueError(f"grad_output must be [{P}, {S}, {out_features}], got {tuple(grad_output.shape)}")
-    _check_grouped_args(table, bucket, E, S, P, tile_pairs, grad_output.device)
-    gx = torch.empty((P, in_features), dtype=torch.float32, device=grad_output.device)
-    if P == 0:
-        return gx
-    gy = _c(grad_output)
-    if gy.data_ptr() % 16 != 0:
-        gy = gy.clone()
-    with _device_guard(gy.device):
-        rc = _lib.aqlm_hip_gemm_1x16_grouped_transposed(table.data_ptr(), E, S, bucket.data_ptr(), tile_pairs, P, gy.data_ptr(),
-                                                        gy.stride(0), gx.data_ptr(), out_features, in_features, g, dt,
-                                                        _stream_ptr(gy.device))
-    if rc:
-        _native.check(rc, "aqlm grouped transposed gemm")
-    return gx
 
 
 # Zero-at-rest accumulator cells of the single-kernel look-up-table matvec (aqlm_hip_gemv_8x8_lut_fused): one persistent
@@ -2772,7 +1380,6 @@ def code1x8_matmat_dequant_transposed(input, codes, codebooks, scales, bias=None
 # reference's C++ signature std::optional<torch::Tensor> actually accepts)
 # ------------------------------------------------------------------------------------------------------
 _SCHEMA = "(Tensor input, Tensor codes, Tensor codebooks, Tensor scales, Tensor? bias) -> Tensor"
-_LIB = torch.library.Library("aqlm", "DEF")
 
 
 def _fake_forward(input, codes, codebooks, scales, bias=None):
@@ -2822,154 +1429,8 @@ def _fake_multi(input, codes, codebooks, scales, bias):
 
 
 for _name, _impl in (("code1x16_matmat_multi", code1x16_matmat_multi), ("codekx8_matmat_multi", codekx8_matmat_multi)):
-    _LIB.define(f"{_name}(Tensor input, Tensor[] codes, Tensor[] codebooks, Tensor[] scales, Tensor?[] bias) -> Tensor[]")
-    _LIB.impl(_name, _impl, "CUDA")
-    torch.library.register_fake(f"aqlm::{_name}")(_fake_multi)
-
-
-# expert-routed matvec (mixture-of-experts decode; no reference counterpart)
-def _fake_moe(input, expert_ids, table, geometry, x_per_pair):
-    return input.new_empty((expert_ids.shape[0] * expert_ids.shape[1], int(geometry[1]), int(geometry[2])))
-
-
-_LIB.define("code1x16_moe_matmat(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
-_LIB.impl("code1x16_moe_matmat", code1x16_moe_matmat, "CUDA")
-torch.library.register_fake("aqlm::code1x16_moe_matmat")(_fake_moe)
-
-
-_LIB.define("code1x16_moe_matmat_packed(Tensor input, Tensor expert_ids, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
-_LIB.impl("code1x16_moe_matmat_packed", code1x16_moe_matmat_packed, "CUDA")
-torch.library.register_fake("aqlm::code1x16_moe_matmat_packed")(_fake_moe)
-
-
-# per-row LoRA adapters on top of a layer's output (no reference counterpart); mutates y, returns nothing
-def _fake_lora_bgmv(y, x, ids, table, geometry):
-    return None
-
-
-_LIB.define("lora_bgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
-_LIB.impl("lora_bgmv_", lora_bgmv_, "CUDA")
-torch.library.register_fake("aqlm::lora_bgmv_")(_fake_lora_bgmv)
-
-_LIB.define("lora_bgmv_routed_(Tensor(a!) y, Tensor x, Tensor? adapter_ids, Tensor expert_ids, Tensor table, int[] geometry, "
-            "bool x_per_pair) -> ()")
-_LIB.impl("lora_bgmv_routed_", lora_bgmv_routed_, "CUDA")
-torch.library.register_fake("aqlm::lora_bgmv_routed_")(lambda y, x, adapter_ids, expert_ids, table, geometry, x_per_pair: None)
-
-_LIB.define("lora_sgmv_(Tensor(a!) y, Tensor x, Tensor? ids, Tensor table, int[] geometry) -> ()")
-_LIB.impl("lora_sgmv_", lora_sgmv_, "CUDA")
-torch.library.register_fake("aqlm::lora_sgmv_")(_fake_lora_bgmv)
-
-_LIB.define("lora_sgmv_routed_(Tensor(a!) y, Tensor x, Tensor? adapter_ids, Tensor expert_ids, Tensor bucket, Tensor table, "
-            "int[] geometry, bool x_per_pair) -> ()")
-_LIB.impl("lora_sgmv_routed_", lora_sgmv_routed_, "CUDA")
-torch.library.register_fake("aqlm::lora_sgmv_routed_")(
-    lambda y, x, adapter_ids, expert_ids, bucket, table, geometry, x_per_pair: None)
-
-
-# the backward of the routed adapters: the transposed copies (mutates buffer) and the reduction both weight gradients are
-_LIB.define("lora_transpose_routed_(Tensor(a!) buffer, Tensor table, Tensor transposed, int[] geometry) -> ()")
-_LIB.impl("lora_transpose_routed_", lora_transpose_routed_, "CUDA")
-torch.library.register_fake("aqlm::lora_transpose_routed_")(lambda buffer, table, transposed, geometry: None)
-
-
-def _lora_grad_routed_op(v, w, adapter_ids, expert_ids, bucket, table, geometry, layout):
-    return lora_grad_routed(v, w, adapter_ids, expert_ids, bucket, table, geometry, layout)
-
-
-_LIB.define("lora_grad_routed(Tensor v, Tensor w, Tensor? adapter_ids, Tensor expert_ids, Tensor bucket, Tensor table, "
-            "int[] geometry, int[] layout) -> Tensor")
-_LIB.impl("lora_grad_routed", _lora_grad_routed_op, "CUDA")
-torch.library.register_fake("aqlm::lora_grad_routed")(
-    lambda v, w, adapter_ids, expert_ids, bucket, table, geometry, layout: v.new_empty(
-        (int(geometry[1]), int(geometry[2]), int(geometry[3]), int(geometry[4])), dtype=torch.float32))
-
-
-# gradients of the codebook and the scales of a 1x16 layer; geometry = [out_features, in_features, g, output dtype id]
-_GRAD_FAKE_DT = {_native.F16: torch.float16, _native.BF16: torch.bfloat16, _native.F32: torch.float32}
-_LIB.define("codebook_grad_1x16(Tensor dw, Tensor? scales, Tensor starts, Tensor order, Tensor chunks, Tensor chunk_starts, "
-            "int[] geometry) -> Tensor")
-_LIB.impl("codebook_grad_1x16", _codebook_grad_op, "CUDA")
-torch.library.register_fake("aqlm::codebook_grad_1x16")(
-    lambda dw, scales, starts, order, chunks, chunk_starts, geometry: dw.new_empty(
-        (CODEBOOK_GRAD_ENTRIES, int(geometry[2])), dtype=_GRAD_FAKE_DT[int(geometry[3])]))
-_LIB.define("scales_grad_1x16(Tensor dw, Tensor codes, Tensor codebooks, int[] geometry) -> Tensor")
-_LIB.impl("scales_grad_1x16", _scales_grad_op, "CUDA")
-torch.library.register_fake("aqlm::scales_grad_1x16")(
-    lambda dw, codes, codebooks, geometry: dw.new_empty((int(geometry[0]),), dtype=_GRAD_FAKE_DT[int(geometry[3])]))
-# ... of a K x 8 layer; geometry = [out_features, in_features, K, g, output dtype id]
-_LIB.define("codebook_grad_kx8(Tensor dw, Tensor? scales, Tensor codes, int[] geometry) -> Tensor")
-_LIB.impl("codebook_grad_kx8", _codebook_grad_kx8_op, "CUDA")
-torch.library.register_fake("aqlm::codebook_grad_kx8")(
-    lambda dw, scales, codes, geometry: dw.new_empty((int(geometry[2]), 256, int(geometry[3])), dtype=_GRAD_FAKE_DT[int(geometry[4])]))
-_LIB.define("scales_grad_kx8(Tensor dw, Tensor codes, Tensor codebooks, int[] geometry) -> Tensor")
-_LIB.impl("scales_grad_kx8", _scales_grad_kx8_op, "CUDA")
-torch.library.register_fake("aqlm::scales_grad_kx8")(
-    lambda dw, codes, codebooks, geometry: dw.new_empty((int(geometry[0]),), dtype=_GRAD_FAKE_DT[int(geometry[4])]))
-
-# nearest-codeword search of a 1x16 layer; geometry = [out_features, in_features, g]
-_LIB.define("code_search_1x16(Tensor reference, Tensor? scales, Tensor codebook, Tensor? group_ids, int[] geometry) -> Tensor")
-_LIB.impl("code_search_1x16", _code_search_1x16_op, "CUDA")
-torch.library.register_fake("aqlm::code_search_1x16")(
-    lambda reference, scales, codebook, group_ids, geometry: reference.new_empty(
-        (int(group_ids.numel()) if group_ids is not None else int(geometry[0]) * (int(geometry[1]) // int(geometry[2])),), dtype=torch.int16))
-# one Lloyd iteration of k-means: the assignment with the clusters' fixed-point sums, and the update of the centroids in place
-_LIB.define("kmeans_assign(Tensor data, Tensor centroids, float data_absmax, bool with_sums) -> (Tensor, Tensor, Tensor)")
-_LIB.impl("kmeans_assign", _kmeans_assign_op, "CUDA")
-
-
-def _fake_kmeans_assign(data, centroids, data_absmax, with_sums):
-    k, d = (int(centroids.shape[0]), int(centroids.shape[1])) if with_sums else (0, int(centroids.shape[1]))
-    return (data.new_empty((data.shape[0],), dtype=torch.int32), data.new_empty((k, d), dtype=torch.int64),
-            data.new_empty((k,), dtype=torch.int32))
-
-
-torch.library.register_fake("aqlm::kmeans_assign")(_fake_kmeans_assign)
-_LIB.define("kmeans_update_(Tensor(a!) centroids, Tensor sums, Tensor counts, int n, float data_absmax) -> ()")
-_LIB.impl("kmeans_update_", kmeans_update_, "CUDA")
-torch.library.register_fake("aqlm::kmeans_update_")(lambda centroids, sums, counts, n, data_absmax: None)
-
-# beam search over the codebooks of a K x 8 layer; geometry = [out_features, in_features, K, g, beam_size] + dim_order (or nothing);
-# returns the codes [n, K] int8 and the fp32 score of every returned hypothesis [n]
-_LIB.define("code_search_kx8(Tensor reference, Tensor? scales, Tensor codebooks, Tensor prev_codes, Tensor? group_ids, int[] geometry)"
-            " -> (Tensor, Tensor)")
-_LIB.impl("code_search_kx8", _code_search_kx8_op, "CUDA")
-
-
-def _fake_code_search_kx8(reference, scales, codebooks, prev_codes, group_ids, geometry):
-    n = int(group_ids.numel()) if group_ids is not None else int(geometry[0]) * (int(geometry[1]) // int(geometry[3]))
-    return reference.new_empty((n, int(geometry[2])), dtype=torch.int8), reference.new_empty((n,), dtype=torch.float32)
-
-
-torch.library.register_fake("aqlm::code_search_kx8")(_fake_code_search_kx8)
-
-
-# expert-grouped GEMM (mixture-of-experts prefill / training; no reference counterpart)
-def _fake_bucket(expert_ids, num_experts, tile_pairs):
-    return expert_ids.new_empty((_bucket_words(expert_ids.shape[0] * expert_ids.shape[1], num_experts, tile_pairs),),
-                                dtype=torch.int32)
-
-
-def _fake_grouped(input, bucket, table, geometry, x_per_pair):
-    return input.new_empty((int(geometry[7]), int(geometry[1]), int(geometry[2])))
-
-
-_LIB.define("moe_bucket(Tensor expert_ids, int num_experts, int tile_pairs) -> Tensor")
-_LIB.impl("moe_bucket", moe_bucket, "CUDA")
-torch.library.register_fake("aqlm::moe_bucket")(_fake_bucket)
-_LIB.define("code1x16_moe_matmat_grouped(Tensor input, Tensor bucket, Tensor table, int[] geometry, bool x_per_pair) -> Tensor")
-_LIB.impl("code1x16_moe_matmat_grouped", code1x16_moe_matmat_grouped, "CUDA")
-torch.library.register_fake("aqlm::code1x16_moe_matmat_grouped")(_fake_grouped)
-
-
-
-def _fake_grouped_transposed(grad_output, bucket, table, geometry):
-    return grad_output.new_empty((int(geometry[7]), int(geometry[3])), dtype=torch.float32)
-
-
-_LIB.define("code1x16_moe_matmat_grouped_transposed(Tensor grad_output, Tensor bucket, Tensor table, int[] geometry) -> Tensor")
-_LIB.impl("code1x16_moe_matmat_grouped_transposed", code1x16_moe_matmat_grouped_transposed, "CUDA")
-torch.library.register_fake("aqlm::code1x16_moe_matmat_grouped_transposed")(_fake_grouped_transposed)
+    register_op(_name, "(Tensor input, Tensor[] codes, Tensor[] codebooks, Tensor[] scales, Tensor?[] bias) -> Tensor[]", _impl,
+                _fake_multi)
 
 
 # the prepacked op as a dispatcher op, so that a QuantizedLinear on the packed path traces under torch.compile
@@ -2994,10 +1455,8 @@ def _fake_packed(input, packed, codebooks, scales, bias, desc):
     return torch.empty(input.shape[:-1] + (int(desc[2]),), device=input.device, dtype=input.dtype)
 
 
-_LIB.define("code1x16_matmat_packed(Tensor input, Tensor packed, Tensor codebooks, Tensor scales, Tensor? bias, "
-            "int[] desc) -> Tensor")
-_LIB.impl("code1x16_matmat_packed", _packed_op, "CUDA")
-torch.library.register_fake("aqlm::code1x16_matmat_packed")(_fake_packed)
+register_op("code1x16_matmat_packed", "(Tensor input, Tensor packed, Tensor codebooks, Tensor scales, Tensor? bias, "
+            "int[] desc) -> Tensor", _packed_op, _fake_packed)
 
 
 # W from a packed buffer as a dispatcher op (the packed-dequant routes of QuantizedLinear under torch.compile)
@@ -3009,9 +1468,8 @@ def _fake_packed_dequant(packed, codebooks, scales, desc):
     return torch.empty((int(desc[2]), int(desc[3])), device=codebooks.device, dtype=codebooks.dtype)
 
 
-_LIB.define("code1x16_dequant_packed(Tensor packed, Tensor codebooks, Tensor? scales, int[] desc) -> Tensor")
-_LIB.impl("code1x16_dequant_packed", _packed_dequant_op, "CUDA")
-torch.library.register_fake("aqlm::code1x16_dequant_packed")(_fake_packed_dequant)
+register_op("code1x16_dequant_packed", "(Tensor packed, Tensor codebooks, Tensor? scales, int[] desc) -> Tensor", _packed_dequant_op,
+            _fake_packed_dequant)
 
 
 # the planar 8x8 matvec as a dispatcher op (same reason; geometry = [out_features, in_features, in_group_size], the codebook bound
@@ -3027,10 +1485,8 @@ def _fake_planar(input, planar, codebooks, scales, bias, geometry, codebook_absm
     return torch.empty(input.shape[:-1] + (int(geometry[0]),), device=input.device, dtype=input.dtype)
 
 
-_LIB.define("code8x8_matmat_planar(Tensor input, Tensor planar, Tensor codebooks, Tensor scales, Tensor? bias, int[] geometry, "
-            "float codebook_absmax) -> Tensor")
-_LIB.impl("code8x8_matmat_planar", _planar_op, "CUDA")
-torch.library.register_fake("aqlm::code8x8_matmat_planar")(_fake_planar)
+register_op("code8x8_matmat_planar", "(Tensor input, Tensor planar, Tensor codebooks, Tensor scales, Tensor? bias, int[] geometry, "
+            "float codebook_absmax) -> Tensor", _planar_op, _fake_planar)
 
 
 # what benchmark/matmul_benchmark.py:6,103 reaches for: CUDA_KERNEL.code1x16_matmat etc. (pybind module in the
@@ -3061,3 +1517,41 @@ if _RAW_FAST is not None:  # the compiled functions, as in the reference's pybin
     HIP_KERNEL.code2x8_matmat = _RAW_FAST.code2x8_matmat
     HIP_KERNEL.code1x8_matmat = _RAW_FAST.code1x8_matmat
 CUDA_KERNEL = HIP_KERNEL
+
+
+# ------------------------------------------------------------------------------------------------------
+# the op families: each module registers its own aqlm:: ops on import; every name it defines is re-exported here as the same object
+# (tests/test_hip_kernel_layout_host.py holds the lists to the modules)
+# ------------------------------------------------------------------------------------------------------
+from .ops_moe import (  # noqa: E402, F401
+    _MOE_SCHEMA, _ROUTED_PACKED_CELLS, ROUTED_PACKED_GEOMETRY_INTS, _bucket_words, _check_grouped_args, _check_routed_args,
+    _desc_array, _fake_bucket, _fake_grouped, _fake_grouped_transposed, _fake_moe, _routed_launches, code1x16_moe_matmat,
+    code1x16_moe_matmat_grouped, code1x16_moe_matmat_grouped_transposed, code1x16_moe_matmat_packed, grouped_supported,
+    grouped_tile_pairs, grouped_transposed_supported, moe_bucket, release_routed_packed_cells, routed_chunks, routed_packed_cells,
+    routed_packed_supported, routed_packed_table, routed_table,
+)
+from .ops_lora import (  # noqa: E402, F401
+    _LORA_GMV_SCHEMA, SGMV_ROUTED_TILE_PAIRS, _check_lora_routed, _fake_lora_bgmv, _lora_gmv_, lora_bgmv_, lora_bgmv_routed_,
+    lora_bgmv_routed_supported, lora_bgmv_supported, lora_grad_routed, lora_grad_routed_supported, lora_routed_table,
+    lora_routed_transposed_layout, lora_routed_transposed_table, lora_sgmv_, lora_sgmv_routed_, lora_sgmv_routed_supported,
+    lora_sgmv_routed_workspace_floats, lora_sgmv_splits, lora_sgmv_supported, lora_table, lora_transpose_routed_,
+    lora_transpose_routed_supported,
+)
+from .ops_grad import (  # noqa: E402, F401
+    CODEBOOK_GRAD_CHUNK, CODEBOOK_GRAD_ENTRIES, CodebookGradIndex, _calib_layer, _calib_scales, _check_calib_matrix, _check_dw,
+    _check_kx8_codes, _check_scales, _codebook_grad_kx8_op, _codebook_grad_op, _scales_grad_kx8_op, _scales_grad_op,
+    build_codebook_grad_index, calib_codebook_grad_1x16, calib_codebook_grad_kx8, calib_delta, calib_rows, calib_supported,
+    codebook_grad_1x16, codebook_grad_kx8, codebook_grad_kx8_supported, codebook_grad_max_chunks, codebook_grad_supported,
+    scales_grad_1x16, scales_grad_kx8,
+)
+from .ops_search import (  # noqa: E402, F401
+    CODE_SEARCH_1X16_XTX_MAX_BEAM, CODE_SEARCH_EPS, CODE_SEARCH_KX8_MAX_BEAM, KMEANS_EPS, XtxStep, _aligned16,
+    _code_search_1x16_impl, _code_search_1x16_op, _code_search_kx8_impl, _code_search_kx8_op, _dim_order, _fake_code_search_kx8,
+    _fake_kmeans_assign, _kmeans_assign_op, _kmeans_operands, code_search_1x16, code_search_1x16_supported,
+    code_search_1x16_xtx_step, code_search_1x16_xtx_supported, code_search_kx8, code_search_kx8_supported,
+    code_search_kx8_xtx_step, code_search_kx8_xtx_supported, kmeans_assign, kmeans_supported, kmeans_update, kmeans_update_,
+)
+
+# two private names of the former registration block, for anything that reached them in this namespace
+_GRAD_FAKE_DT = _GRAD_TORCH_DT
+_lora_grad_routed_op = lora_grad_routed
