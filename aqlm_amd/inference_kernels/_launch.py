@@ -1,5 +1,5 @@
 """What every op module of this package launches with: dtype ids, the current stream, the device guard, operand helpers, the
-cached fp32 workspace, and the one ``aqlm`` op library with ``register_op``.  A leaf: it imports ``_native`` only, and
+shared argument checks, the row slabs and segment table of the matvec launches, the cached fp32 workspace, and the one ``aqlm`` op library with ``register_op``.  A leaf: it imports ``_native`` only, and
 ``hip_kernel`` and the ``ops_*`` family modules import its names one by one (plain global look-ups on the decode path)."""
 from __future__ import annotations
 
@@ -52,6 +52,51 @@ def _flat_rows(input: torch.Tensor) -> torch.Tensor:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def _check_dtypes(input, codebooks, scales) -> None:
+    if codebooks.dtype != input.dtype or scales.dtype != input.dtype:
+        raise NotImplementedError(f"input dtype {input.dtype} must match codebooks/scales dtype {codebooks.dtype}")
+
+
+def _check_features(input, in_features: int, layers: bool = False) -> None:
+    if input.shape[-1] != in_features:
+        raise ValueError(f"input has {input.shape[-1]} features, {'layers expect' if layers else 'layer expects'} {in_features}")
+
+
+def _shaped(y: torch.Tensor, input: torch.Tensor) -> torch.Tensor:
+    """The rows of ``y`` [rows, out_features] in the leading shape of ``input``."""
+    return y.reshape(input.shape[:-1] + (y.shape[1],))
+
+
+def _row_slabs(x: torch.Tensor):
+    """The rows of ``x`` in slabs of MAX_GEMV_BATCH, what one matvec launch takes: (first row, rows, address of the first row,
+    row offset).  The row offset is in bytes per output column: a contiguous y [rows, n] of x's dtype starts the slab at
+    ``y.data_ptr() + offset * n``.  A decode call is one slab: it gets a tuple, not a generator (an eager call is host-bound)."""
+    B, most = x.shape[0], _native.MAX_GEMV_BATCH
+    if 0 < B <= most:
+        return ((0, B, x.data_ptr(), 0),)
+    size = x.element_size()
+    base, step = x.data_ptr(), x.stride(0) * size
+    return [(b0, min(most, B - b0), base + b0 * step, b0 * size) for b0 in range(0, B, most)]
+
+
+def _segment_table(x: torch.Tensor, rows: int, layers):
+    """The ``Segment`` array of a shared-input launch on the flattened input ``x``.  ``layers`` holds one (address of the codes,
+    codebooks, scales, bias or None, out_features) per layer; whatever the codes live in stays with the caller.  Returns the
+    table, the outputs [rows, out_features] in layer order, and the contiguous parameters the table points into: hold them
+    until the launch is issued."""
+    segs = (_native.Segment * len(layers))()
+    outs, keep = [], []
+    for seg, (codes_ptr, cb, sc, bi, out_features) in zip(segs, layers):
+        cb, sc = _c(cb), _c(sc)
+        bi = None if bi is None else _c(bi)
+        y = torch.empty((rows, out_features), dtype=x.dtype, device=x.device)
+        keep += [cb, sc, bi]
+        outs.append(y)
+        seg.codes, seg.codebook, seg.scales, seg.bias = codes_ptr, cb.data_ptr(), sc.data_ptr(), _ptr(bi)
+        seg.y, seg.y_row_stride, seg.out_features = y.data_ptr(), out_features, out_features
+    return segs, outs, keep
 
 
 # fp32 partial workspaces, one per (device, stream): a decode loop calls the packed op hundreds of times per token and

@@ -44,10 +44,15 @@ from ._launch import (  # noqa: F401  (by name: the decode path keeps plain glob
     _NO_GUARD,
     _WORKSPACES,
     _c,
+    _check_dtypes,
+    _check_features,
     _device_guard,
     _dtype_id,
     _flat_rows,
     _ptr,
+    _row_slabs,
+    _segment_table,
+    _shaped,
     _stream_ptr,
     _workspace,
     register_op,
@@ -67,6 +72,8 @@ def _gemv(input, codes, codebooks, scales, bias, kind):
     num_codebooks, codebook_size, out_group_size, in_group_size = codebooks.shape
     if out_group_size != 1:
         raise NotImplementedError("AQLM HIP kernels require out_group_size == 1")
+    # the two checks and the closing reshape are written out here: this is the shim of every eager decode call, and three call
+    # frames measure on it (profiles/forward_shims.log).  They mirror _check_dtypes, _check_features and _shaped of _launch.
     if codebooks.dtype != input.dtype or scales.dtype != input.dtype:
         raise NotImplementedError(f"input dtype {input.dtype} must match codebooks/scales dtype {codebooks.dtype}")
     out_features = codes.shape[0]
@@ -87,10 +94,8 @@ def _gemv(input, codes, codebooks, scales, bias, kind):
     y = torch.empty((B, out_features), dtype=input.dtype, device=input.device)
     stream = _stream_ptr(input.device)
     with _device_guard(input.device):
-        for b0 in range(0, B, _native.MAX_GEMV_BATCH):
-            nb = min(_native.MAX_GEMV_BATCH, B - b0)
-            xp = x.data_ptr() + b0 * x.stride(0) * 2
-            yp = y.data_ptr() + b0 * out_features * 2
+        for _b0, nb, xp, offset in _row_slabs(x):
+            yp = y.data_ptr() + offset * out_features
             if kind == "1x16":
                 rc = _lib.aqlm_hip_gemv_1x16(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias),
                                              xp, yp, out_features, in_features, in_group_size, nb,
@@ -403,13 +408,23 @@ def set_fused_finalize(on: bool) -> None:
 
 def _check_packed_args(input, packed, codebooks, scales):
     dt = _dtype_id(input)
-    if codebooks.dtype != input.dtype or scales.dtype != input.dtype:
-        raise NotImplementedError(f"input dtype {input.dtype} must match codebooks/scales dtype {codebooks.dtype}")
-    if input.shape[-1] != packed.in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layer expects {packed.in_features}")
+    _check_dtypes(input, codebooks, scales)
+    _check_features(input, packed.in_features)
     if input.device != packed.device or codebooks.device != input.device:
         raise ValueError(f"input on {input.device}, layer on {packed.device}")
     return dt
+
+
+def _packed_scratch(device, stream, bounded, slices, rows, out_features):
+    """What a prepacked launch of ``rows`` x ``out_features`` outputs accumulates in, as (single kernel?, buffer, bytes): the
+    stream's fixed-point cells when the finalize is fused and every layer has a codebook bound (``bounded``), else the cached
+    fp32 workspace of the two-kernel form with one partial per codebook slice.  Without a cell set (a capture on a fresh stream,
+    more cells than a set holds) the two-kernel entry gets no buffer and uses the cells inside the packed buffer."""
+    if FUSED_FINALIZE and bounded:
+        cells = _packed_cells(device, stream, rows * out_features * 8)
+        return (True, cells, cells.numel() * 8) if cells is not None else (False, None, 0)
+    ws = _workspace(device, slices * rows * out_features * 4, stream)
+    return False, ws, ws.numel() * 4
 
 
 def code1x16_matmat_packed(input, packed: PackedCodes, codebooks, scales, bias=None):
@@ -423,32 +438,18 @@ def code1x16_matmat_packed(input, packed: PackedCodes, codebooks, scales, bias=N
         bias = _c(bias)
     B = x.shape[0]
     y = torch.empty((B, out_features), dtype=input.dtype, device=input.device)
-    nb_max = min(B, _native.MAX_GEMV_BATCH)
     stream = _stream_ptr(input.device)
     refresh_range(packed, codebooks)
-    cells = None
-    if FUSED_FINALIZE and packed.desc.codebook_absmax > 0.0:   # single kernel: fixed-point cells, per stream where possible
-        ws_ptr, ws_len = None, 0
-        cells = _packed_cells(input.device, stream, nb_max * out_features * 8)
-    else:                                   # two kernels: fp32 slice partials in a workspace
-        ws = _workspace(input.device, packed.slices * nb_max * out_features * 4, stream)
-        ws_ptr, ws_len = ws.data_ptr(), ws.numel() * 4
+    fused, scratch, nbytes = _packed_scratch(input.device, stream, packed.desc.codebook_absmax > 0.0, packed.slices,
+                                             min(B, _native.MAX_GEMV_BATCH), out_features)
+    entry = _lib.aqlm_hip_gemv_1x16_packed_cells if fused else _lib.aqlm_hip_gemv_1x16_packed
     with _device_guard(input.device):
-        for b0 in range(0, B, _native.MAX_GEMV_BATCH):
-            nb = min(_native.MAX_GEMV_BATCH, B - b0)
-            if cells is not None:
-                rc = _lib.aqlm_hip_gemv_1x16_packed_cells(ctypes.byref(packed.desc), packed.data_ptr(), codebooks.data_ptr(),
-                                                          scales.data_ptr(), _ptr(bias), x.data_ptr() + b0 * x.stride(0) * 2,
-                                                          y.data_ptr() + b0 * out_features * 2, nb, x.stride(0), out_features,
-                                                          dt, cells.data_ptr(), cells.numel() * 8, stream)
-            else:
-                rc = _lib.aqlm_hip_gemv_1x16_packed(ctypes.byref(packed.desc), packed.data_ptr(), codebooks.data_ptr(),
-                                                    scales.data_ptr(), _ptr(bias), x.data_ptr() + b0 * x.stride(0) * 2,
-                                                    y.data_ptr() + b0 * out_features * 2, nb, x.stride(0), out_features, dt,
-                                                    ws_ptr, ws_len, stream)
+        for _b0, nb, xp, offset in _row_slabs(x):
+            rc = entry(ctypes.byref(packed.desc), packed.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias), xp,
+                       y.data_ptr() + offset * out_features, nb, x.stride(0), out_features, dt, _ptr(scratch), nbytes, stream)
             if rc:
                 _native.check(rc, "aqlm gemv_1x16_packed")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _shaped(y, input)
 
 
 def _gemv_multi(input, codes, codebooks, scales, bias, kind):
@@ -460,37 +461,23 @@ def _gemv_multi(input, codes, codebooks, scales, bias, kind):
     if out_group_size != 1:
         raise NotImplementedError("AQLM HIP kernels require out_group_size == 1")
     in_features = codes[0].shape[1] * in_group_size
-    if input.shape[-1] != in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layers expect {in_features}")
-    keep = []
-    segs = (_native.Segment * n)()
+    _check_features(input, in_features, layers=True)
     x = _flat_rows(input)
-    B = x.shape[0]
-    outs = []
     for k in range(n):
-        cb = codebooks[k]
-        if tuple(cb.shape) != (num_codebooks, codebook_size, 1, in_group_size):
+        if tuple(codebooks[k].shape) != (num_codebooks, codebook_size, 1, in_group_size):
             raise NotImplementedError(f"all layers of a shared-input launch must use one scheme; got codebooks "
-                                      f"{tuple(cb.shape)} next to {tuple(codebooks[0].shape)}")
+                                      f"{tuple(codebooks[k].shape)} next to {tuple(codebooks[0].shape)}")
         if codes[k].shape[1] * in_group_size != in_features or codes[k].shape[2] != num_codebooks:
             raise ValueError("all layers of a shared-input launch must have the same in_features and num_codebooks")
-        if cb.dtype != input.dtype or scales[k].dtype != input.dtype:
-            raise NotImplementedError(f"input dtype {input.dtype} must match codebooks/scales dtype {cb.dtype}")
-        c, cb, sc = _c(codes[k]), _c(cb), _c(scales[k])
-        bi = None if bias[k] is None else _c(bias[k])
-        out_features = c.shape[0]
-        y = torch.empty((B, out_features), dtype=input.dtype, device=input.device)
-        keep += [c, cb, sc, bi]
-        outs.append(y)
-        segs[k].codes, segs[k].codebook, segs[k].scales, segs[k].bias = c.data_ptr(), cb.data_ptr(), sc.data_ptr(), _ptr(bi)
-        segs[k].y, segs[k].y_row_stride, segs[k].out_features = y.data_ptr(), out_features, out_features
+        _check_dtypes(input, codebooks[k], scales[k])
+    codes = [_c(c) for c in codes]
+    segs, outs, keep = _segment_table(x, x.shape[0], [(codes[k].data_ptr(), codebooks[k], scales[k], bias[k], codes[k].shape[0])
+                                                      for k in range(n)])
     stream = _stream_ptr(input.device)
     with _device_guard(input.device):
-        for b0 in range(0, B, _native.MAX_GEMV_BATCH):
-            nb = min(_native.MAX_GEMV_BATCH, B - b0)
+        for _b0, nb, xp, offset in _row_slabs(x):
             for k in range(n):
-                segs[k].y = outs[k].data_ptr() + b0 * outs[k].shape[1] * 2
-            xp = x.data_ptr() + b0 * x.stride(0) * 2
+                segs[k].y = outs[k].data_ptr() + offset * outs[k].shape[1]
             if kind == "1x16":
                 rc = _lib.aqlm_hip_gemv_1x16_multi(segs, n, xp, in_features, in_group_size, nb, x.stride(0), dt, stream)
             else:
@@ -498,7 +485,7 @@ def _gemv_multi(input, codes, codebooks, scales, bias, kind):
                                                   x.stride(0), dt, stream)
             if rc:
                 _native.check(rc, "aqlm shared-input gemv")
-    return [y.reshape(input.shape[:-1] + (y.shape[1],)) for y in outs]
+    return [_shaped(y, input) for y in outs]
 
 
 def code1x16_matmat_multi(input, codes, codebooks, scales, bias):
@@ -539,6 +526,17 @@ def _lut_cells(device: torch.device, stream: int, rows: int) -> Optional[torch.T
     return cells
 
 
+def _lut_scratch(device, stream, bounded, g, in_features, out_features):
+    """What a one-row look-up-table launch over layers of ``out_features`` (one entry per layer) accumulates in, as (single
+    kernel?, buffer, bytes): the stream's cells -- planar codes pass ``bounded``, whether every layer has a codebook bound;
+    canonical codes need none -- else an fp32 workspace of the two-kernel form, allocated per call (not the cached one)."""
+    cells = _lut_cells(device, stream, sum(out_features)) if bounded else None
+    if cells is not None:
+        return True, cells, cells.numel() * 8
+    ws_bytes = sum(_lib.aqlm_hip_workspace_bytes(_native.OP_GEMV_8X8_LUT, g, n, in_features) for n in out_features)
+    return False, torch.empty((ws_bytes // 4,), dtype=torch.float32, device=device), ws_bytes
+
+
 def _gemv_8x8_lut_multi(input, codes, codebooks, scales, bias):
     """Several 8-codebook layers times one single input row through per-token look-up tables in ONE launch
     (aqlm_hip_gemv_8x8_lut_multi); bit-identical to _gemv_8x8_lut per layer."""
@@ -546,40 +544,23 @@ def _gemv_8x8_lut_multi(input, codes, codebooks, scales, bias):
     dt = _dtype_id(input)
     g = codebooks[0].shape[3]
     in_features = codes[0].shape[1] * g
-    if input.shape[-1] != in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layers expect {in_features}")
+    _check_features(input, in_features, layers=True)
     x = _flat_rows(input)
-    segs = (_native.Segment * n)()
-    keep, outs = [], []
-    ws_bytes = 0
     for k in range(n):
         if tuple(codebooks[k].shape) != tuple(codebooks[0].shape) or codes[k].shape[1] * g != in_features:
             raise ValueError("all layers of a shared-input launch must have the same scheme and in_features")
-        c, cb, sc = _c(codes[k]), _c(codebooks[k]), _c(scales[k])
-        bi = None if bias[k] is None else _c(bias[k])
-        out_features = c.shape[0]
-        y = torch.empty((1, out_features), dtype=input.dtype, device=input.device)
-        keep += [c, cb, sc, bi]
-        outs.append(y)
-        segs[k].codes, segs[k].codebook, segs[k].scales, segs[k].bias = c.data_ptr(), cb.data_ptr(), sc.data_ptr(), _ptr(bi)
-        segs[k].y, segs[k].y_row_stride, segs[k].out_features = y.data_ptr(), out_features, out_features
-        ws_bytes += _lib.aqlm_hip_workspace_bytes(_native.OP_GEMV_8X8_LUT, g, out_features, in_features)
+    codes = [_c(c) for c in codes]
+    segs, outs, keep = _segment_table(x, 1, [(codes[k].data_ptr(), codebooks[k], scales[k], bias[k], codes[k].shape[0])
+                                             for k in range(n)])
     stream = _stream_ptr(input.device)
-    cells = _lut_cells(input.device, stream, sum(y.shape[1] for y in outs))
-    if cells is not None:
-        with _device_guard(input.device):
-            rc = _lib.aqlm_hip_gemv_8x8_lut_multi_fused(segs, n, x.data_ptr(), in_features, g, dt, cells.data_ptr(),
-                                                        cells.numel() * 8, stream)
-        if rc:
-            _native.check(rc, "aqlm gemv_8x8_lut_multi_fused")
-        return [y.reshape(input.shape[:-1] + (y.shape[1],)) for y in outs]
-    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=input.device)
+    fused, scratch, nbytes = _lut_scratch(input.device, stream, True, g, in_features, [y.shape[1] for y in outs])
+    entry, name = ((_lib.aqlm_hip_gemv_8x8_lut_multi_fused, "aqlm gemv_8x8_lut_multi_fused") if fused else
+                   (_lib.aqlm_hip_gemv_8x8_lut_multi, "aqlm gemv_8x8_lut_multi"))
     with _device_guard(input.device):
-        rc = _lib.aqlm_hip_gemv_8x8_lut_multi(segs, n, x.data_ptr(), in_features, g, dt, ws.data_ptr(), ws_bytes,
-                                              _stream_ptr(input.device))
+        rc = entry(segs, n, x.data_ptr(), in_features, g, dt, scratch.data_ptr(), nbytes, stream)
     if rc:
-        _native.check(rc, "aqlm gemv_8x8_lut_multi")
-    return [y.reshape(input.shape[:-1] + (y.shape[1],)) for y in outs]
+        _native.check(rc, name)
+    return [_shaped(y, input) for y in outs]
 
 
 def codekx8_matmat_multi(input, codes, codebooks, scales, bias):
@@ -608,45 +589,26 @@ def code1x16_matmat_packed_multi(input, packed, codebooks, scales, bias):
     B = x.shape[0]
     if B > _native.MAX_GEMV_BATCH:
         return [code1x16_matmat_packed(input, packed[k], codebooks[k], scales[k], bias[k]) for k in range(n)]
-    segs = (_native.Segment * n)()
-    descs = (_native._descp * n)()
-    keep, outs = [], []
-    total = sum(pk.out_features for pk in packed)
     dt = None
     for k in range(n):
         dt = _check_packed_args(input, packed[k], codebooks[k], scales[k])
         refresh_range(packed[k], codebooks[k])
-        cb, sc = _c(codebooks[k]), _c(scales[k])
-        bi = None if bias[k] is None else _c(bias[k])
-        of = packed[k].out_features
-        y = torch.empty((B, of), dtype=input.dtype, device=input.device)
-        keep += [cb, sc, bi]
-        outs.append(y)
-        segs[k].codes, segs[k].codebook, segs[k].scales, segs[k].bias = packed[k].data_ptr(), cb.data_ptr(), sc.data_ptr(), _ptr(bi)
-        segs[k].y, segs[k].y_row_stride, segs[k].out_features = y.data_ptr(), of, of
-        descs[k] = ctypes.pointer(packed[k].desc)
+    segs, outs, keep = _segment_table(x, B, [(packed[k].data_ptr(), codebooks[k], scales[k], bias[k], packed[k].out_features)
+                                             for k in range(n)])
+    descs = (_native._descp * n)(*[ctypes.pointer(pk.desc) for pk in packed])
     stream = _stream_ptr(input.device)
-    cells = None
-    if FUSED_FINALIZE and all(pk.desc.codebook_absmax > 0.0 for pk in packed):  # single kernel, no workspace
-        ws_ptr, ws_len = None, 0
-        cells = _packed_cells(input.device, stream, B * total * 8)
-    else:
-        ws = _workspace(input.device, packed[0].slices * B * total * 4, stream)
-        ws_ptr, ws_len = ws.data_ptr(), ws.numel() * 4
+    fused, scratch, nbytes = _packed_scratch(input.device, stream, all(pk.desc.codebook_absmax > 0.0 for pk in packed),
+                                             packed[0].slices, B, sum(pk.out_features for pk in packed))
+    entry = _lib.aqlm_hip_gemv_1x16_packed_multi_cells if fused else _lib.aqlm_hip_gemv_1x16_packed_multi
     with _device_guard(input.device):
-        if cells is not None:
-            rc = _lib.aqlm_hip_gemv_1x16_packed_multi_cells(segs, descs, n, x.data_ptr(), packed[0].in_features, B, x.stride(0),
-                                                            dt, cells.data_ptr(), cells.numel() * 8, stream)
-        else:
-            rc = _lib.aqlm_hip_gemv_1x16_packed_multi(segs, descs, n, x.data_ptr(), packed[0].in_features, B, x.stride(0), dt,
-                                                      ws_ptr, ws_len, stream)
+        rc = entry(segs, descs, n, x.data_ptr(), packed[0].in_features, B, x.stride(0), dt, _ptr(scratch), nbytes, stream)
     if rc == _native.E_UNSUPPORTED and B > 1:
         # the rows do not fit one LDS image next to the codebook slice (very wide inputs): per-layer launches split the
         # rows themselves; same kernels, same bits
         return [code1x16_matmat_packed(input, packed[k], codebooks[k], scales[k], bias[k]) for k in range(n)]
     if rc:
         _native.check(rc, "aqlm gemv_1x16_packed_multi")
-    return [y.reshape(input.shape[:-1] + (y.shape[1],)) for y in outs]
+    return [_shaped(y, input) for y in outs]
 
 
 # Transparent prepack for the RAW op.  `aqlm::code1x16_matmat` is stateless in the reference (cuda_kernel.cpp:148-182); here
@@ -855,45 +817,47 @@ def _gemv_8x8_lut_rows(input, x, codes_ptr, codebooks, scales, bias, out_feature
                                               float(absmax), cells.data_ptr(), cells.numel() * 8, stream)
     if rc:
         _native.check(rc, "aqlm gemv_8x8_lut_batch")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _shaped(y, input)
+
+
+def _lut_launch(input, x, codes_ptr, codebooks, scales, bias, out_features, in_features, g, dt, planar, absmax):
+    """The look-up-table matvec of 1..LUT_MAX_ROWS checked, flattened rows, on canonical codes or (``planar``, with the codebook
+    bound ``absmax``) planar ones.  2+ rows: one launch, or one per row when the stream's cells do not hold them."""
+    if x.shape[0] > 1:
+        y = _gemv_8x8_lut_rows(input, x, codes_ptr, codebooks, scales, bias, out_features, in_features, g, dt, planar, absmax)
+        if y is not None:
+            return y
+        return _shaped(torch.cat([_lut_launch(x[b:b + 1], x[b:b + 1], codes_ptr, codebooks, scales, bias, out_features, in_features,
+                                              g, dt, planar, absmax) for b in range(x.shape[0])]), input)
+    y = torch.empty((1, out_features), dtype=input.dtype, device=input.device)
+    stream = _stream_ptr(input.device)
+    fused, scratch, nbytes = _lut_scratch(input.device, stream, not planar or absmax > 0.0, g, in_features, (out_features,))
+    with _device_guard(input.device):
+        if planar:
+            name = "aqlm gemv_8x8_lut_planar"
+            rc = _lib.aqlm_hip_gemv_8x8_lut_planar(codes_ptr, codebooks.data_ptr(), scales.data_ptr(), _ptr(bias), x.data_ptr(),
+                                                   y.data_ptr(), out_features, in_features, g, dt, absmax if fused else 0.0,
+                                                   scratch.data_ptr(), nbytes, 1 if fused else 0, stream)
+        else:  # one kernel on the cells, or two through the workspace: same arguments
+            name = "aqlm gemv_8x8_lut_fused" if fused else "aqlm gemv_8x8_lut"
+            entry = _lib.aqlm_hip_gemv_8x8_lut_fused if fused else _lib.aqlm_hip_gemv_8x8_lut
+            rc = entry(codes_ptr, codebooks.data_ptr(), scales.data_ptr(), _ptr(bias), x.data_ptr(), y.data_ptr(), out_features,
+                       in_features, g, dt, scratch.data_ptr(), nbytes, stream)
+    if rc:
+        _native.check(rc, name)
+    return y.reshape(input.shape[:-1] + (out_features,))  # (_shaped, written out: the eager one-row path is host-bound)
 
 
 def _gemv_8x8_lut(input, codes, codebooks, scales, bias):
     dt = _dtype_id(input)
     g = codebooks.shape[3]
     out_features, in_features = codes.shape[0], codes.shape[1] * g
-    if input.shape[-1] != in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layer expects {in_features}")
+    _check_features(input, in_features)
     x = _flat_rows(input)
     codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales)
     if bias is not None:
         bias = _c(bias)
-    if x.shape[0] > 1:
-        y = _gemv_8x8_lut_rows(input, x, codes.data_ptr(), codebooks, scales, bias, out_features, in_features, g, dt, False, 0.0)
-        if y is not None:
-            return y
-        return torch.cat([_gemv_8x8_lut(x[b:b + 1], codes, codebooks, scales, bias) for b in range(x.shape[0])]).reshape(
-            input.shape[:-1] + (out_features,))
-    y = torch.empty((1, out_features), dtype=input.dtype, device=input.device)
-    stream = _stream_ptr(input.device)
-    cells = _lut_cells(input.device, stream, out_features)
-    if cells is not None:  # one kernel
-        with _device_guard(input.device):
-            rc = _lib.aqlm_hip_gemv_8x8_lut_fused(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias),
-                                                  x.data_ptr(), y.data_ptr(), out_features, in_features, g, dt,
-                                                  cells.data_ptr(), cells.numel() * 8, stream)
-        if rc:
-            _native.check(rc, "aqlm gemv_8x8_lut_fused")
-        return y.reshape(input.shape[:-1] + (out_features,))
-    ws_bytes = _lib.aqlm_hip_workspace_bytes(_native.OP_GEMV_8X8_LUT, g, out_features, in_features)
-    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=input.device)
-    with _device_guard(input.device):
-        rc = _lib.aqlm_hip_gemv_8x8_lut(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias),
-                                        x.data_ptr(), y.data_ptr(), out_features, in_features, g, dt, ws.data_ptr(),
-                                        ws_bytes, stream)
-    if rc:
-        _native.check(rc, "aqlm gemv_8x8_lut")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _lut_launch(input, x, codes.data_ptr(), codebooks, scales, bias, out_features, in_features, g, dt, False, 0.0)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -960,12 +924,10 @@ def planar_8x8_unpack(planar: PlanarCodes) -> torch.Tensor:
 
 
 def _check_planar_args(input, planar, codebooks, scales):
-    if codebooks.dtype != input.dtype or scales.dtype != input.dtype:
-        raise NotImplementedError(f"input dtype {input.dtype} must match codebooks/scales dtype {codebooks.dtype}")
+    _check_dtypes(input, codebooks, scales)
     if tuple(codebooks.shape) != (8, 256, 1, planar.in_group_size):
         raise NotImplementedError(f"planar codes of an 8x8 g{planar.in_group_size} layer need codebooks [8, 256, 1, {planar.in_group_size}], got {tuple(codebooks.shape)}")
-    if input.shape[-1] != planar.in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layer expects {planar.in_features}")
+    _check_features(input, planar.in_features)
     if input.device != planar.device or codebooks.device != input.device:
         raise ValueError(f"input on {input.device}, layer on {planar.device}")
     return _dtype_id(input)
@@ -978,33 +940,11 @@ def code8x8_matmat_planar(input, planar: PlanarCodes, codebooks, scales, bias=No
     codebooks, scales = _c(codebooks), _c(scales)
     if bias is not None:
         bias = _c(bias)
-    out_features, in_features, g = planar.out_features, planar.in_features, planar.in_group_size
     refresh_range(planar, codebooks)
-    if x.shape[0] > 1:
-        if x.shape[0] > LUT_MAX_ROWS:
-            raise ValueError(f"code8x8_matmat_planar takes 1..{LUT_MAX_ROWS} rows, got {x.shape[0]}")
-        y = _gemv_8x8_lut_rows(input, x, planar.data_ptr(), codebooks, scales, bias, out_features, in_features, g, dt, True,
-                               planar.codebook_absmax)
-        if y is not None:
-            return y
-        return torch.cat([code8x8_matmat_planar(x[b:b + 1], planar, codebooks, scales, bias) for b in range(x.shape[0])]).reshape(
-            input.shape[:-1] + (out_features,))
-    y = torch.empty((1, out_features), dtype=input.dtype, device=input.device)
-    stream = _stream_ptr(input.device)
-    cells = _lut_cells(input.device, stream, out_features) if planar.codebook_absmax > 0.0 else None
-    with _device_guard(input.device):
-        if cells is not None:
-            rc = _lib.aqlm_hip_gemv_8x8_lut_planar(planar.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias), x.data_ptr(),
-                                                   y.data_ptr(), out_features, in_features, g, dt, planar.codebook_absmax,
-                                                   cells.data_ptr(), cells.numel() * 8, 1, stream)
-        else:
-            ws_bytes = _lib.aqlm_hip_workspace_bytes(_native.OP_GEMV_8X8_LUT, g, out_features, in_features)
-            ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=input.device)
-            rc = _lib.aqlm_hip_gemv_8x8_lut_planar(planar.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias), x.data_ptr(),
-                                                   y.data_ptr(), out_features, in_features, g, dt, 0.0, ws.data_ptr(), ws_bytes, 0, stream)
-    if rc:
-        _native.check(rc, "aqlm gemv_8x8_lut_planar")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    if x.shape[0] > max(LUT_MAX_ROWS, 1):
+        raise ValueError(f"code8x8_matmat_planar takes 1..{LUT_MAX_ROWS} rows, got {x.shape[0]}")
+    return _lut_launch(input, x, planar.data_ptr(), codebooks, scales, bias, planar.out_features, planar.in_features,
+                       planar.in_group_size, dt, True, planar.codebook_absmax)
 
 
 def code8x8_matmat_planar_multi(input, planar, codebooks, scales, bias):
@@ -1016,39 +956,25 @@ def code8x8_matmat_planar_multi(input, planar, codebooks, scales, bias):
     if _lut_rows(input) > 1:  # the shared-input kernel takes one row of x: 2+ rows run one (multi-row) launch per layer
         return [code8x8_matmat_planar(input, planar[k], codebooks[k], scales[k], bias[k]) for k in range(n)]
     x = _flat_rows(input)
-    segs = (_native.Segment * n)()
-    absmax = (ctypes.c_float * n)()
-    keep, outs = [], []
-    dt, ws_bytes = None, 0
+    dt = None
     g, in_features = planar[0].in_group_size, planar[0].in_features
     for k in range(n):
         dt = _check_planar_args(input, planar[k], codebooks[k], scales[k])
         if planar[k].in_group_size != g or planar[k].in_features != in_features:
             raise ValueError("all layers of a shared-input launch must have the same scheme and in_features")
         refresh_range(planar[k], codebooks[k])
-        cb, sc = _c(codebooks[k]), _c(scales[k])
-        bi = None if bias[k] is None else _c(bias[k])
-        of = planar[k].out_features
-        y = torch.empty((1, of), dtype=input.dtype, device=input.device)
-        keep += [cb, sc, bi]
-        outs.append(y)
-        segs[k].codes, segs[k].codebook, segs[k].scales, segs[k].bias = planar[k].data_ptr(), cb.data_ptr(), sc.data_ptr(), _ptr(bi)
-        segs[k].y, segs[k].y_row_stride, segs[k].out_features = y.data_ptr(), of, of
-        absmax[k] = planar[k].codebook_absmax
-        ws_bytes += _lib.aqlm_hip_workspace_bytes(_native.OP_GEMV_8X8_LUT, g, of, in_features)
+    segs, outs, keep = _segment_table(x, 1, [(planar[k].data_ptr(), codebooks[k], scales[k], bias[k], planar[k].out_features)
+                                             for k in range(n)])
+    absmax = (ctypes.c_float * n)(*[pl.codebook_absmax for pl in planar])
     stream = _stream_ptr(input.device)
-    cells = _lut_cells(input.device, stream, sum(y.shape[1] for y in outs)) if all(a > 0.0 for a in absmax) else None
+    fused, scratch, nbytes = _lut_scratch(input.device, stream, all(a > 0.0 for a in absmax), g, in_features,
+                                          [pl.out_features for pl in planar])
     with _device_guard(input.device):
-        if cells is not None:
-            rc = _lib.aqlm_hip_gemv_8x8_lut_planar_multi(segs, absmax, n, x.data_ptr(), in_features, g, dt, cells.data_ptr(),
-                                                         cells.numel() * 8, 1, stream)
-        else:
-            ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=input.device)
-            rc = _lib.aqlm_hip_gemv_8x8_lut_planar_multi(segs, absmax, n, x.data_ptr(), in_features, g, dt, ws.data_ptr(), ws_bytes, 0,
-                                                         stream)
+        rc = _lib.aqlm_hip_gemv_8x8_lut_planar_multi(segs, absmax, n, x.data_ptr(), in_features, g, dt, scratch.data_ptr(), nbytes,
+                                                     1 if fused else 0, stream)
     if rc:
         _native.check(rc, "aqlm gemv_8x8_lut_planar_multi")
-    return [y.reshape(input.shape[:-1] + (y.shape[1],)) for y in outs]
+    return [_shaped(y, input) for y in outs]
 
 
 def codekx8_matmat(input, codes, codebooks, scales, bias=None):
@@ -1149,8 +1075,7 @@ def code1x16_matmat_scan(input, codes, codebooks, scales, bias=None):
     if codebooks.shape[0] != 1 or codebooks.shape[1] != 65536 or codebooks.shape[2] != 1 or codebooks.shape[3] != 8:
         return None
     out_features, in_features = codes.shape[0], codes.shape[1] * 8
-    if input.shape[-1] != in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layer expects {in_features}")
+    _check_features(input, in_features)
     x = _flat_rows(input)
     B = x.shape[0]
     if B == 0 or in_features % 256 != 0 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
@@ -1170,7 +1095,7 @@ def code1x16_matmat_scan(input, codes, codebooks, scales, bias=None):
                                           _stream_ptr(input.device))
     if rc:
         _native.check(rc, "aqlm gemm_1x16_scan")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _shaped(y, input)
 
 
 def code1x16_matmat_dequant(input, codes, codebooks, scales, bias=None):
@@ -1180,14 +1105,13 @@ def code1x16_matmat_dequant(input, codes, codebooks, scales, bias=None):
         raise NotImplementedError(f"code1x16_matmat_dequant needs codebooks [1, 65536, 1, g], got {tuple(codebooks.shape)}")
     in_group_size = codebooks.shape[3]
     out_features, in_features = codes.shape[0], codes.shape[1] * in_group_size
-    if input.shape[-1] != in_features:
-        raise ValueError(f"input has {input.shape[-1]} features, layer expects {in_features}")
+    _check_features(input, in_features)
     x = _flat_rows(input)
     B = x.shape[0]
     if not _fused_mfma_ok(x, in_features):
         # unscaled W is exact in the storage dtype (it IS the codebook entries); scaling W instead of y would round it
         W = _dequant(codes, codebooks, None, "1x16")
-        return _scale_bias_fp32(F.linear(x, W), scales, bias).reshape(input.shape[:-1] + (out_features,))
+        return _shaped(_scale_bias_fp32(F.linear(x, W), scales, bias), input)
     codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales)
     if bias is not None:
         bias = _c(bias)
@@ -1200,7 +1124,7 @@ def code1x16_matmat_dequant(input, codes, codebooks, scales, bias=None):
                                           x.stride(0), out_features, dt, ws.data_ptr(), ws.numel() * 4, _stream_ptr(input.device))
     if rc:
         _native.check(rc, "aqlm gemm_1x16_mfma")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _shaped(y, input)
 
 
 def _matmat_dequant_kx8(input, codes, codebooks, scales, bias):
@@ -1262,7 +1186,7 @@ def _fused_kx8_mfma(input, codes, codebooks, scales, bias, dt):
         return None
     if rc:
         _native.check(rc, "aqlm gemm_kx8_mfma")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _shaped(y, input)
 
 
 # 8x8 g32 beyond one row (aqlm_hip_gemm_8x8_mfma, round 5): the codebooks in LDS, one MFMA per codebook and k-step, cost independent
@@ -1323,7 +1247,7 @@ def _fused_8x8_mfma(input, codes, codebooks, scales, bias, dt):
         return None
     if rc:
         _native.check(rc, "aqlm gemm_8x8_mfma")
-    return y.reshape(input.shape[:-1] + (out_features,))
+    return _shaped(y, input)
 
 
 def code2x8_matmat_dequant(input, codes, codebooks, scales, bias=None):
