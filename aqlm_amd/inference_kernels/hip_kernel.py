@@ -1258,6 +1258,25 @@ def code1x8_matmat_dequant(input, codes, codebooks, scales, bias=None):
     return _matmat_dequant_kx8(input, codes, codebooks, scales, bias)
 
 
+# The backward of the dense K x 8 layers on the fused transposed MFMA GEMM (ops_grad.codekx8_matmat_transposed: W is built tile by
+# tile in LDS, the out x in x 2-byte transient of the route below is never allocated).  kernel_selector.get_backward_pass_kernel tries
+# it first from FUSED_KX8_TRANSPOSED_MIN_ROWS rows on -- an int, or {(num_codebooks, in_group_size): rows, None: rows of every other
+# scheme}; NEVER = opt-in only -- and falls back to the named op below where it declines.  DESIGN.md section 4.8t has the
+# measurements behind the thresholds (profiles/kx8_transposed.json, tools/kx8_transposed_benchmark.py).
+USE_FUSED_KX8_TRANSPOSED = True
+FUSED_KX8_TRANSPOSED_NEVER = 1 << 30
+FUSED_KX8_TRANSPOSED_MIN_ROWS = {(2, 8): FUSED_KX8_TRANSPOSED_NEVER, (1, 8): FUSED_KX8_TRANSPOSED_NEVER,
+                                 (8, 32): FUSED_KX8_TRANSPOSED_NEVER, None: FUSED_KX8_TRANSPOSED_NEVER}
+
+
+def fused_kx8_transposed_min_rows(num_codebooks: int, in_group_size: int) -> int:
+    """Rows from which the backward of a (num_codebooks x 8, g) layer takes the fused transposed GEMM."""
+    rule = FUSED_KX8_TRANSPOSED_MIN_ROWS
+    if isinstance(rule, dict):
+        rule = rule.get((int(num_codebooks), int(in_group_size)), rule.get(None, FUSED_KX8_TRANSPOSED_NEVER))
+    return int(rule)
+
+
 def _matmat_dequant_transposed(input, codes, codebooks, scales, bias, kind):
     """grad_input = (grad_output * scales) @ W  (+ bias): backward of the linear layer
     (cuda_kernel.cpp:303-354; generic definition kernel_selector.py:145-161)."""
@@ -1466,7 +1485,7 @@ from .ops_grad import (  # noqa: E402, F401
     _check_kx8_codes, _check_scales, _codebook_grad_kx8_op, _codebook_grad_op, _scales_grad_kx8_op, _scales_grad_op,
     build_codebook_grad_index, calib_codebook_grad_1x16, calib_codebook_grad_kx8, calib_delta, calib_rows, calib_supported,
     codebook_grad_1x16, codebook_grad_kx8, codebook_grad_kx8_supported, codebook_grad_max_chunks, codebook_grad_supported,
-    scales_grad_1x16, scales_grad_kx8,
+    codekx8_matmat_transposed, scales_grad_1x16, scales_grad_kx8,
 )
 from .ops_search import (  # noqa: E402, F401
     CODE_SEARCH_1X16_XTX_MAX_BEAM, CODE_SEARCH_EPS, CODE_SEARCH_KX8_MAX_BEAM, KMEANS_EPS, XtxStep, _aligned16,

@@ -129,7 +129,16 @@ def get_backward_pass_kernel(
     else:  # any other scheme: generic dequant + GEMM (the reference transposes the tensors and reuses its forward kernel)
         kern = ops.generic_matmat_dequant_transposed
 
+    fused_kx8 = codebook_size == 256 and num_codebooks <= 8 and in_group_size in (8, 16, 32)
+
     def _backward(grad_output, codes, codebooks, scales, bias):
+        # K x 8 from the measured row count on: the fused transposed GEMM, W never materialised (None: the launch declined the call)
+        if fused_kx8 and hip_kernel.USE_FUSED_KX8_TRANSPOSED:
+            rows = grad_output.numel() // grad_output.shape[-1] if grad_output.shape[-1] else 0
+            if rows >= hip_kernel.fused_kx8_transposed_min_rows(num_codebooks, in_group_size):
+                grad_input = hip_kernel.codekx8_matmat_transposed(grad_output, codes, codebooks, scales)
+                if grad_input is not None:
+                    return grad_input
         # the layer's bias does not enter grad_input (reference kernel_selector.py:160 passes None as well)
         return kern(grad_output, codes, codebooks, scales, None)
 

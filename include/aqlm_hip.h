@@ -1304,6 +1304,32 @@ int aqlm_hip_gemm_kx8_mfma_ws(const void* codes_i8, const void* codebooks, const
                               void* Y, int batch, int out_features, int in_features, int num_codebooks, int in_group_size,
                               long x_row_stride, long y_row_stride, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Input gradient of the dense 8-bit schemes (additive to ABI 9): gx[rows][in] = gy[rows][out] @ Wq for 1 .. 8 codebooks of 256 entries
+ * with g = 8 / 16 / 32 (1x8 g8, 2x8 g8, 4x8 g16, 8x8 g32, ...), out_group_size 1, Wq the SCALED storage weight aqlm_hip_dequant_kx8
+ * writes (fp32 sum of the entries in codebook order, times scales[o], one rounding) -- never materialised: the codebooks live in
+ * LDS, a block owns a tile of batch rows x 128 columns of gx, builds W[32 rows][128 columns] of every step in LDS with exactly those
+ * bits and reads it column-major (ds_read_b64_tr_b16) into v_mfma_f32_16x16x32 (exact products, fp32 sums over o ascending, one
+ * rounding of gx).  gy and gx are of `dtype`; a row's bits depend neither on the other rows of the call nor on their number, for
+ * given `splits`.
+ * `splits`: blocks that share the output rows of one tile (few batch rows cannot fill the device otherwise); 1 = gx is written
+ * directly, no workspace; 2 .. 16 = fp32 partial tiles in `workspace` (16-B aligned, aqlm_hip_gemm_kx8_transposed_workspace_bytes =
+ * splits * rows * in_features * 4 bytes), added in slice order by a second kernel before the one rounding (deterministic, no
+ * atomics; a slice without steps adds zeros); 0 = the entry chooses, never more than out_features / (8 rows) slices -- the
+ * workspace stays within a quarter of the W it replaces -- and _workspace_bytes(.., 0) is an upper bound for that choice.
+ * in_features a multiple of g and of 8 (a last column block narrower than 128 is masked), any out_features >= 1, 1 .. 65536 rows.
+ * Replaces: the W transient of code2x8_matmat_dequant_transposed / code1x8_matmat_dequant_transposed = Code2x8Dequant /
+ * CodeKx8Dequant + torch::matmul (cuda_kernel.cpp:486-519, 651-684) and of the generic backward (kernel_selector.py:145-161).
+ * AQLM_HIP_E_UNSUPPORTED (the caller dequantises + calls its GEMM): other schemes (_supported says which), codebooks or rows of gy /
+ * gx not 16-B aligned (row strides in elements, multiples of 8).  AQLM_HIP_E_INVALID: null pointers, a missing or too small workspace.
+ */
+int aqlm_hip_gemm_kx8_transposed_supported(int out_features, int in_features, int num_codebooks, int in_group_size);
+size_t aqlm_hip_gemm_kx8_transposed_workspace_bytes(int rows, int out_features, int in_features, int splits);
+int aqlm_hip_gemm_kx8_transposed(const void* codes_i8, const void* codebooks, const void* scales, const void* gy, void* gx,
+                                 int rows, int out_features, int in_features, int num_codebooks, int in_group_size,
+                                 long gy_row_stride, long gx_row_stride, int dtype, int splits,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 #define AQLM_HIP_OP_GEMM_1X16_MFMA 1
 #define AQLM_HIP_OP_GEMM_KX8_MFMA 6
 #define AQLM_HIP_OP_GEMV_1X16_PACKED 3
