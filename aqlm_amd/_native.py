@@ -178,6 +178,10 @@ SIGNATURES = {
     "aqlm_hip_lora_grad_routed_supported": (_ci, [_ci, _ci, _ci, _ci, _ci]),
     "aqlm_hip_lora_grad_routed": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _cl, _cl, _ci, _ci, _vp, _cl,
                                   _cl, _ci, _cl, _vp, _sz, _ci, _vp]),
+    "aqlm_hip_lora_grad_supported": (_ci, [_ci, _ci, _ci]),
+    "aqlm_hip_lora_grad_slabs": (_ci, [_ci, _ci]),
+    "aqlm_hip_lora_grad_workspace_bytes": (_sz, [_ci, _ci, _ci]),
+    "aqlm_hip_lora_grad": (_ci, [_vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _cl, _ci, _vp, _cl, _ci, _cl, _vp, _sz, _vp, _sz, _ci, _vp]),
     "aqlm_hip_codebook_grad_chunk": (_ci, []),
     "aqlm_hip_codebook_grad_1x16_supported": (_ci, [_ci, _ci, _ci]),
     "aqlm_hip_codebook_grad_1x16_max_chunks": (_ci, [_ci, _ci, _ci]),

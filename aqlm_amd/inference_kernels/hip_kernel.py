@@ -1474,11 +1474,11 @@ from .ops_moe import (  # noqa: E402, F401
     routed_packed_supported, routed_packed_table, routed_table,
 )
 from .ops_lora import (  # noqa: E402, F401
-    _LORA_GMV_SCHEMA, SGMV_ROUTED_TILE_PAIRS, _check_lora_routed, _fake_lora_bgmv, _lora_gmv_, lora_bgmv_, lora_bgmv_routed_,
-    lora_bgmv_routed_supported, lora_bgmv_supported, lora_grad_routed, lora_grad_routed_supported, lora_routed_table,
-    lora_routed_transposed_layout, lora_routed_transposed_table, lora_sgmv_, lora_sgmv_routed_, lora_sgmv_routed_supported,
-    lora_sgmv_routed_workspace_floats, lora_sgmv_splits, lora_sgmv_supported, lora_table, lora_transpose_routed_,
-    lora_transpose_routed_supported,
+    _LORA_GMV_SCHEMA, SGMV_ROUTED_TILE_PAIRS, _check_lora_routed, _fake_lora_bgmv, _lora_gmv_, _owned_workspace, lora_bgmv_,
+    lora_bgmv_routed_, lora_bgmv_routed_supported, lora_bgmv_supported, lora_grad, lora_grad_routed, lora_grad_routed_supported,
+    lora_grad_slabs, lora_grad_supported, lora_routed_table, lora_routed_transposed_layout, lora_routed_transposed_table,
+    lora_sgmv_, lora_sgmv_routed_, lora_sgmv_routed_supported, lora_sgmv_routed_workspace_floats, lora_sgmv_splits,
+    lora_sgmv_supported, lora_sgmv_workspace_floats, lora_table, lora_transpose_routed_, lora_transpose_routed_supported,
 )
 from .ops_grad import (  # noqa: E402, F401
     CODEBOOK_GRAD_CHUNK, CODEBOOK_GRAD_ENTRIES, CodebookGradIndex, _calib_layer, _calib_scales, _check_calib_matrix, _check_dw,

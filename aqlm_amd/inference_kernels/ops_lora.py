@@ -35,9 +35,17 @@ def lora_bgmv_supported(out_features: int, in_features: int, max_rank: int, rows
     return bool(_lib.aqlm_hip_lora_bgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
 
 
-def _lora_gmv_(y, x, ids, table, geometry, entry, workspace_bytes, what, y_groups_of_4) -> None:
+def _owned_workspace(ws, need: int, device) -> torch.Tensor:
+    """A workspace the caller owns, checked against the ``need`` bytes of the launch that is about to write it."""
+    if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.float32 or ws.device != device or not ws.is_contiguous()
+            or ws.numel() * 4 < need or ws.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned float32 tensor of at least {need // 4} elements on {device}")
+    return ws
+
+
+def _lora_gmv_(y, x, ids, table, geometry, entry, workspace_bytes, what, y_groups_of_4, workspace=None) -> None:
     """The checks, the workspace and the call of ``lora_bgmv_`` / ``lora_sgmv_``: ``entry`` the native launch,
-    ``workspace_bytes(rows, max_rank, in_features)`` its workspace size."""
+    ``workspace_bytes(rows, max_rank, in_features)`` its workspace size, ``workspace`` one the caller owns (default: the cached one)."""
     n, max_rank, out_features, in_features = (int(v) for v in geometry)
     dt = _dtype_id(y)
     if y.dim() != 2 or x.dim() != 2 or y.shape[0] != x.shape[0] or y.shape[1] != out_features or x.shape[1] != in_features:
@@ -58,7 +66,8 @@ def _lora_gmv_(y, x, ids, table, geometry, entry, workspace_bytes, what, y_group
     if rows == 0:
         return
     x = _flat_rows(x)
-    ws = _workspace(y.device, max(workspace_bytes(rows, max_rank, in_features), 16))
+    need = max(workspace_bytes(rows, max_rank, in_features), 16)
+    ws = _workspace(y.device, need) if workspace is None else _owned_workspace(workspace, need, y.device)
     with _device_guard(y.device):
         rc = entry(table.data_ptr(), n, max_rank, _ptr(ids), int(ids is not None and ids.element_size() == 8), rows, x.data_ptr(),
                    x.stride(0) if rows > 1 else in_features, y.data_ptr(), y.stride(0) if rows > 1 else out_features, out_features,
@@ -91,17 +100,24 @@ def lora_sgmv_supported(out_features: int, in_features: int, max_rank: int, rows
     return bool(_lib.aqlm_hip_lora_sgmv_supported(int(out_features), int(in_features), int(max_rank), int(rows)))
 
 
-def lora_sgmv_(y, x, ids, table, geometry) -> None:
+def lora_sgmv_(y, x, ids, table, geometry, workspace=None) -> None:
     """``lora_bgmv_`` at any row count (prefill, large batches): the segmented adapter GEMM on the matrix unit
     (include/aqlm_hip.h, aqlm_hip_lora_sgmv), two launches, one pass per distinct adapter of every 16-row tile.  Same arguments
     as ``lora_bgmv_``; in addition ``y`` must be 8-byte aligned with a row stride that is a multiple of 4 elements (it is written
     in groups of 4 outputs).  Not bit-equal to ``lora_bgmv_``: the sums run in another order, and the rank-sized intermediate
-    enters the second product as a pair of storage-type values."""
+    enters the second product as a pair of storage-type values.  ``workspace``: a contiguous fp32 tensor of at least
+    ``lora_sgmv_workspace_floats`` elements that the caller owns -- after the call it holds the rank-sized intermediate
+    t [rows][splits][max_rank] of every served row (the backward reads it) --; default: the cached workspace."""
     _lora_gmv_(y, x, ids, table, geometry, _lib.aqlm_hip_lora_sgmv, _lib.aqlm_hip_lora_sgmv_workspace_bytes, "aqlm lora sgmv",
-               y_groups_of_4=True)
+               y_groups_of_4=True, workspace=workspace)
 
 
 register_op("lora_sgmv_", _LORA_GMV_SCHEMA, lora_sgmv_, _fake_lora_bgmv)
+
+
+def lora_sgmv_workspace_floats(rows: int, max_rank: int, in_features: int) -> int:
+    """fp32 elements of the workspace of one ``lora_sgmv_`` call: [rows][splits][max_rank]; 0 when unsupported."""
+    return _lib.aqlm_hip_lora_sgmv_workspace_bytes(int(rows), int(max_rank), int(in_features)) // 4
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -223,14 +239,7 @@ def lora_sgmv_routed_(y, x, adapter_ids, expert_ids, bucket, table, geometry, x_
     x = _flat_rows(x)
     eids = _c(expert_ids)
     need = max(_lib.aqlm_hip_lora_sgmv_routed_workspace_bytes(P, S, max_rank, in_features), 16)
-    if workspace is None:
-        ws = _workspace(y.device, need)
-    else:
-        ws = workspace
-        if (ws.dtype != torch.float32 or ws.device != y.device or not ws.is_contiguous() or ws.numel() * 4 < need
-                or ws.data_ptr() % 16):
-            raise ValueError(f"workspace must be a contiguous, 16-byte aligned float32 tensor of at least {need // 4} elements on "
-                             f"{y.device}")
+    ws = _workspace(y.device, need) if workspace is None else _owned_workspace(workspace, need, y.device)
     with _device_guard(y.device):
         rc = _lib.aqlm_hip_lora_sgmv_routed(
             table.data_ptr(), n, E, S, max_rank, _ptr(adapter_ids), int(adapter_ids is not None and adapter_ids.element_size() == 8),
@@ -408,3 +417,62 @@ register_op("lora_grad_routed", "(Tensor v, Tensor w, Tensor? adapter_ids, Tenso
             "int[] geometry, int[] layout) -> Tensor", lora_grad_routed,
             lambda v, w, adapter_ids, expert_ids, bucket, table, geometry, layout: v.new_empty(
                 (int(geometry[1]), int(geometry[2]), int(geometry[3]), int(geometry[4])), dtype=torch.float32))
+
+
+# ------------------------------------------------------------------------------------------------------
+# the weight gradients of the adapters on a dense layer (aqlm_hip_lora_grad; aqlm_amd/lora.py _DenseAdapterFunction is the
+# module-level interface).  Plain functions, not aqlm:: ops: they run inside an autograd backward, never under torch.compile.
+# ------------------------------------------------------------------------------------------------------
+def lora_grad_supported(dim: int, max_rank: int, rows: int) -> bool:
+    return bool(_lib.aqlm_hip_lora_grad_supported(int(dim), int(max_rank), int(rows)))
+
+
+def lora_grad_slabs(rows: int, dim: int) -> int:
+    """Row slabs of one ``lora_grad`` call: a function of the two sizes alone (aqlm_amd/csrc/lora_grad.hip has the rule)."""
+    return _lib.aqlm_hip_lora_grad_slabs(int(rows), int(dim))
+
+
+def lora_grad(v, w, ids, table, geometry, out=None):
+    """The reduction over rows that both weight gradients of a dense layer's adapters are (include/aqlm_hip.h, aqlm_hip_lora_grad),
+    for ONE adapter: -> fp32 ``G [max_rank, dim]``, ``G[r, i] = scaling * sum over the rows b with ids[b] == adapter of
+    w[b, :, r].sum() * v[b, i]``, on the matrix unit, the rows split over workgroups and added in a fixed order (two calls give
+    the same bits).  geometry = [num_adapters, max_rank, dim, adapter]; ``v`` [rows, dim] fp16 / bf16 with a unit inner stride
+    and 16-byte aligned rows (x for grad_A, grad_y for grad_B^T); ``w`` fp32 [rows, splits, max_rank] with a unit inner stride,
+    the workspace of a ``lora_sgmv_`` call (u for grad_A, t for grad_B^T); ``ids`` [rows] int64 / int32 on the device or None =
+    adapter 0 for every row; ``table`` from ``lora_table``.  An entry that is not live keeps what ``out`` held (a new ``G`` is
+    zero there).  The fp32 workspace of the slabs comes from the caching allocator, so the call can be captured."""
+    n, max_rank, dim, adapter = (int(x) for x in geometry)
+    dt = _dtype_id(v)
+    if v.dim() != 2 or v.shape[1] != dim or v.stride(1) != 1 or v.shape[0] < 1:
+        raise ValueError(f"v must be [rows >= 1, {dim}] with a unit inner stride, got {tuple(v.shape)} with strides {v.stride()}")
+    rows = v.shape[0]
+    if w.dtype != torch.float32 or w.dim() != 3 or w.shape[0] != rows or w.shape[2] != max_rank or w.stride(2) != 1:
+        raise ValueError(f"w must be float32 [{rows}, splits, {max_rank}] with a unit inner stride, got {w.dtype} {tuple(w.shape)}")
+    if w.device != v.device or table.device != v.device:
+        raise ValueError("v, w and the table must share a device")
+    if table.dtype != torch.int64 or table.numel() != n * _native.LORA_ENTRY_WORDS or not table.is_contiguous():
+        raise ValueError(f"table must be contiguous int64 [{n * _native.LORA_ENTRY_WORDS}]")
+    if not 0 <= adapter < n:
+        raise ValueError(f"adapter {adapter} outside [0, {n})")
+    if ids is not None:
+        if ids.dim() != 1 or ids.shape[0] != rows or ids.dtype not in (torch.int64, torch.int32) or ids.device != v.device:
+            raise ValueError(f"ids must be [{rows}] int64 / int32 on {v.device}, got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
+        ids = _c(ids)
+    if not lora_grad_supported(dim, max_rank, rows) or not 1 <= w.shape[1] <= 8:
+        raise NotImplementedError(f"lora_grad: dim={dim} max_rank={max_rank} rows={rows} splits={w.shape[1]} outside the kernel "
+                                  "(dim % 8 == 0, max_rank a multiple of 8 in 8..128, 1..8 slices)")
+    if out is None:
+        out = torch.zeros((max_rank, dim), dtype=torch.float32, device=v.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (max_rank, dim) or not out.is_contiguous() or out.device != v.device:
+        raise ValueError(f"out must be contiguous float32 [{max_rank}, {dim}] on {v.device}")
+    need = _lib.aqlm_hip_lora_grad_workspace_bytes(rows, max_rank, dim)
+    ws = _workspace(v.device, max(need, 16))
+    with _device_guard(v.device):
+        rc = _lib.aqlm_hip_lora_grad(
+            table.data_ptr(), n, max_rank, adapter, _ptr(ids), int(ids is not None and ids.element_size() == 8), rows, v.data_ptr(),
+            v.stride(0) if rows > 1 else dim, dim, w.data_ptr(), w.stride(0) if rows > 1 else w.shape[1] * max_rank, w.shape[1],
+            w.stride(1) if w.shape[1] > 1 else max_rank, out.data_ptr(), out.numel() * 4, ws.data_ptr(), ws.numel() * 4, dt,
+            _stream_ptr(v.device))
+    if rc:
+        _native.check(rc, "aqlm lora grad")
+    return out

@@ -15,7 +15,10 @@ Decode-sized calls run ``aqlm_hip_lora_bgmv`` (aqlm_amd/csrc/lora_bgmv.hip): two
 ids read on the device only, capturable.  Larger calls -- prefill, big batches -- have ``aqlm_hip_lora_sgmv``
 (aqlm_amd/csrc/lora_sgmv.hip), the same two launches on the matrix unit, one pass per distinct adapter of every 16-row tile, for
 the row counts at which it was measured to win (``SGMV_MAX_ROWS``).  Everything else -- training, host tensors, shapes the kernels
-decline -- runs the adapters as torch ops, differentiable in x, A and B, so the same module trains.
+decline -- runs the adapters as torch ops, differentiable in x, A and B, so the same module trains.  Opt-in
+(``TRAIN_MAX_ROWS``), a call that needs a gradient runs ``aqlm_hip_lora_sgmv`` inside an autograd function whose backward is
+device launches only: the launch again on a transposed table for grad_x, ``aqlm_hip_lora_grad`` (aqlm_amd/csrc/lora_grad.hip, a
+row-split MFMA reduction) for grad_A and grad_B.
 
 Adapters on the ROUTED EXPERTS of a Mixtral block ride on whichever launches the block takes: for up to
 ``ROUTED_BGMV_MAX_PAIRS`` (token, expert) pairs ``aqlm_hip_lora_bgmv_routed`` (aqlm_amd/csrc/lora_bgmv_routed.hip) adds them in place to
@@ -107,6 +110,27 @@ ROUTED_SGMV_MAX_PAIRS = AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS
 ROUTED_TRAIN_MIN_PAIRS = 1
 ROUTED_TRAIN_MAX_PAIRS = AQLM_HIP_MAX_LORA_SGMV_ROUTED_PAIRS
 
+# Calls on a DENSE layer that NEED A GRADIENT and have TRAIN_MIN_ROWS .. TRAIN_MAX_ROWS rows run aqlm_hip_lora_sgmv inside an autograd
+# function whose backward is device launches only (_DenseAdapterFunction: the same launch on a transposed table for grad_x,
+# aqlm_hip_lora_grad -- aqlm_amd/csrc/lora_grad.hip, the row-split MFMA reduction -- for grad_A / grad_B); every
+# other call that needs a gradient keeps the torch path.  TRAIN_MAX_ROWS = 0: the route is OPT-IN
+# (`aqlm.lora.TRAIN_MAX_ROWS = aqlm.lora.AQLM_HIP_MAX_LORA_SGMV_ROWS` switches it on), the status FUSED_KX8_TRANSPOSED_MIN_ROWS has:
+# tests/test_lora_sgmv_gpu.py pins that a gradient-needing 80-row call takes the torch path at default settings.
+# Measured (profiles/lora_train.json, written by `python tools/lora_benchmark.py --train`: forward + backward of the seven-projection
+# Llama-3-8B-shaped 1x16 block, rank 16 and 64, 128 / 1024 / 4096 rows, one of four adapters trained, against the torch path of the
+# same commit; medians of 3 x 10, spreads below 45 us captured): the route WINS wherever ids mix adapters over the rows -- four
+# contiguous sequences, captured: 1191 against 2411 us at 128 rows, 2424 against 4505 us at 1024, 5947 against 10017 us at 4096
+# (rank 16; rank 64: 1330 / 2695, 2783 / 4662, 7195 / 10342); interleaved by row at rank 16: 1433 / 2405, 2879 / 4466, 7634 / 10002
+# -- and LOSES where the torch path has a single unmasked pass: one adapter selected by name (rank 16: 1143 against 1129 us at 128
+# rows, 2384 / 2362 at 1024, 5918 / 5454 at 4096; rank 64: 1283 / 1213, 2760 / 2410, 7147 / 5611), and four rank-64 adapters
+# interleaved by row over 4096 rows (11670 against 10288 us; it wins that mix at 128 and 1024 rows, 1657 / 2683 and 3974 / 4637).
+# Eager steps order the same way.  The reduction alone is not what loses: aqlm_hip_lora_grad takes 38 us for 4096 rows x 4096 wide
+# at rank 16 where aqlm_hip_lora_grad_routed driven as one expert takes 631 us.  A change that flips this default needs the
+# one-adapter case to win first (the clone of y, the two sgmv passes of the backward and the zeroed grad_x tensor are what it
+# pays there), and retires the pinned assertion with that evidence.
+TRAIN_MIN_ROWS = 1
+TRAIN_MAX_ROWS = 0
+
 _PREFIX = "base_model.model."
 _DTYPES_OK = (torch.float16, torch.bfloat16)
 
@@ -124,6 +148,15 @@ def takes_sgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling
     ``takes_bgmv_route`` with SGMV_MIN_ROWS..SGMV_MAX_ROWS rows (never more than one launch takes)."""
     return bool(is_cuda and dtype_ok and not grad_needed and not compiling
                 and SGMV_MIN_ROWS <= rows <= min(SGMV_MAX_ROWS, AQLM_HIP_MAX_LORA_SGMV_ROWS) and supported)
+
+
+def takes_train_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling: bool, rows: int, supported: bool) -> bool:
+    """Whether a call on a dense layer that needs a gradient runs the device route (aqlm_hip_lora_sgmv under autograd, backward on
+    launches only; else the torch path): tensors on the device, one fp16 / bf16 dtype throughout, a gradient needed, not being
+    traced by torch.compile, TRAIN_MIN_ROWS..TRAIN_MAX_ROWS rows (never more than one launch takes; TRAIN_MAX_ROWS = 0 switches
+    the route off), and shapes the launches accept."""
+    return bool(is_cuda and dtype_ok and grad_needed and not compiling
+                and TRAIN_MIN_ROWS <= rows <= min(TRAIN_MAX_ROWS, AQLM_HIP_MAX_LORA_SGMV_ROWS) and supported)
 
 
 def takes_routed_bgmv_route(is_cuda: bool, dtype_ok: bool, grad_needed: bool, compiling: bool, pairs: int, supported: bool) -> bool:
@@ -194,6 +227,7 @@ class LoraQuantizedLinear(nn.Module):
         self.in_features, self.out_features = base_layer.in_features, base_layer.out_features
         self._table = None       # (key, device table, ranks): rebuilt when an A / B moved or was written
         self._slot_map = None    # (key, device tensor bank id -> table slot): layers that lack some of the bank's adapters
+        self._ttable = None      # (key of _table, buffer, transposed device table): the training route's grad_x launch
 
     def add_adapter(self, name: str, a: torch.Tensor, b: torch.Tensor, scaling: float) -> None:
         """``a`` [rank, in_features], ``b`` [out_features, rank]; copied into new bias-free ``nn.Linear`` modules on the base
@@ -319,7 +353,59 @@ class LoraQuantizedLinear(nn.Module):
                 self._bgmv(y2, x.reshape(-1, self.in_features), sel if isinstance(sel, str) else self._row_ids(sel, x),
                            hip_kernel.lora_sgmv_)
                 return y
+        supported = False
+        if (x.is_cuda and dtype_ok and grad_needed and not compiling
+                and TRAIN_MIN_ROWS <= rows <= min(TRAIN_MAX_ROWS, AQLM_HIP_MAX_LORA_SGMV_ROWS)):
+            from .inference_kernels import hip_kernel
+
+            ranks = [a.shape[0] for a, _, _ in weights]
+            every = [self.lora_A[n].weight.shape[0] for _, n in self._present()]  # the transposed table covers the whole layer
+            M, K = self.out_features, self.in_features
+            supported = (all(r % 8 == 0 for r in every) and M % 8 == 0 and y.stride(-1) == 1 and y.data_ptr() % 8 == 0
+                         and hip_kernel.lora_sgmv_supported(M, K, max(ranks), rows)
+                         and hip_kernel.lora_sgmv_supported(K, M, max(ranks), rows)
+                         and hip_kernel.lora_transpose_routed_supported(M, K, max(every), 1, 1)
+                         and hip_kernel.lora_grad_supported(M, max(ranks), rows)
+                         and hip_kernel.lora_grad_supported(K, max(ranks), rows))
+        if takes_train_route(x.is_cuda, dtype_ok, grad_needed, compiling, rows, supported):
+            try:
+                y2 = y.view(-1, self.out_features)
+            except RuntimeError:
+                y2 = None
+            if y2 is not None and y2.stride(0) % 4 == 0:
+                return self._train(y, x.reshape(-1, self.in_features), sel if isinstance(sel, str) else self._row_ids(sel, x))
         return self._torch_path(y, x, sel, names)
+
+    def _transposed_table(self, device: torch.device):
+        """(buffer, transposed device table) of the grad_x launch over this layer's adapters ([1][slots][1], the routed layout with
+        one expert and one segment), cached under the key of ``_device_table``; the copies in the buffer are written by a launch
+        at the start of every backward, not here."""
+        key = self._table[0]
+        if self._ttable is None or self._ttable[0] != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LoraQuantizedLinear: the transposed adapter table is built by a host-to-device copy; run one "
+                                   "eager training step before capturing (and again after moving or rewriting an adapter)")
+            from .inference_kernels import hip_kernel
+
+            entries = [[[self._weights(n)]] for _, n in self._present()]
+            self._ttable = (key,) + tuple(hip_kernel.lora_routed_transposed_table(entries, device)[:2])
+        return self._ttable[1], self._ttable[2]
+
+    def _train(self, y: torch.Tensor, x2: torch.Tensor, sel) -> torch.Tensor:
+        """The training route: ``sel`` as for ``_bgmv``; -> ``y`` (any leading shape; its rows a regular view) as the output of
+        ``_DenseAdapterFunction``."""
+        if y._is_view():
+            y = y.clone()  # autograd lets no function write in place into a view that another function made (the base layer's output)
+        table, ranks = self._device_table(x2.device)
+        self._transposed_table(x2.device)
+        present = [n for _, n in self._present()]
+        if isinstance(sel, str):
+            slot0, ids, n, max_rank, slots = present.index(sel), None, 1, ranks[present.index(sel)], [present.index(sel)]
+        else:
+            slot0, ids, n, max_rank, slots = None, self._local_ids(sel), len(ranks), max(ranks), list(range(len(ranks)))
+        flat = [t for s in slots for t in self._weights(present[s])[:2]]  # A and B of every adapter in play, in table order
+        call = _DenseCall(self, ids, table, slot0, n, max_rank, slots, ranks)
+        return _DenseAdapterFunction.apply(y, x2, call, *flat)
 
     def _bgmv(self, y2: torch.Tensor, x2: torch.Tensor, sel, launch=None) -> None:
         """``sel``: an adapter name, or one bank id per row of ``x2``.  ``launch``: ``hip_kernel.lora_sgmv_`` for the SGMV route
@@ -749,6 +835,83 @@ class _RoutedAdapterFunction(torch.autograd.Function):
                 r = w.shape[1] if which else w.shape[0]
                 grads[i] = ga[e, s, :r].to(w.dtype) if which == 0 else gb[e, s, :r].t().to(w.dtype)
         return (gy, gx, None, *grads)
+
+
+class _DenseCall:
+    """What one training call of ``LoraQuantizedLinear`` hands to its autograd function besides the tensors autograd
+    differentiates: ``slot0`` the table slot selected by name (then ``ids`` is None and the launches see a one-slot table) or None,
+    ``slots`` the table slots whose A and B follow as arguments, ``ranks`` the rank of every slot of the layer's table."""
+
+    def __init__(self, layer, ids, table, slot0, n, max_rank, slots, ranks):
+        self.layer, self.ids, self.table, self.slot0, self.n, self.max_rank = layer, ids, table, slot0, n, max_rank
+        self.slots, self.ranks = slots, ranks
+
+
+class _DenseAdapterFunction(torch.autograd.Function):
+    """``y += adapters(x)`` on a dense layer with a backward on device launches only, the dense twin of
+    ``_RoutedAdapterFunction``.  Forward: ``aqlm_hip_lora_sgmv`` in place -- the bits of the serving route -- into a workspace this
+    call owns: it keeps t = A x of every row.  Backward, with gy the gradient of ``y``: the transposed copies of the weights as
+    they are now (one launch), the same launch on the transposed table with x := gy into a zeroed tensor (its output is
+    scaling * A^T u, the adapter term of grad_x; its workspace then holds u = B^T gy), and per TRAINED adapter one
+    ``aqlm_hip_lora_grad`` for grad_A (V = x, w = u) and one for grad_B^T (V = gy, w = t).  No host synchronisation, no atomics,
+    capturable after one eager step, bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, y, x, call, *weights):
+        from .inference_kernels import hip_kernel
+
+        y2 = y.view(-1, y.shape[-1])
+        rows, M = y2.shape
+        K = x.shape[1]
+        table = call.table
+        if call.slot0 is not None:
+            words = table.shape[0] // len(call.ranks)
+            table = table[call.slot0 * words:(call.slot0 + 1) * words]
+        t = torch.empty((hip_kernel.lora_sgmv_workspace_floats(rows, call.max_rank, K),), dtype=torch.float32, device=x.device)
+        hip_kernel.lora_sgmv_(y2, x, call.ids, table, [call.n, call.max_rank, M, K], t)
+        ctx.mark_dirty(y)
+        ctx.call = call
+        ctx.save_for_backward(x, t, table, *(() if call.ids is None else (call.ids,)))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        from .inference_kernels import hip_kernel
+
+        call = ctx.call
+        x, t, table = ctx.saved_tensors[:3]
+        ids = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        layer, n, max_rank = call.layer, call.n, call.max_rank
+        gy = grad_y.reshape(-1, grad_y.shape[-1]).contiguous()
+        rows, M = gy.shape
+        K = x.shape[1]
+        x = hip_kernel._flat_rows(x)  # rows the launches can address, as the forward's launch saw them
+        need_x = ctx.needs_input_grad[1]
+        need_w = ctx.needs_input_grad[3:]
+        gx = u = None
+        if need_x or any(need_w[0::2]):
+            buffer, ttable = layer._transposed_table(x.device)
+            hip_kernel.lora_transpose_routed_(buffer, call.table, ttable, [len(call.ranks), 1, 1, max(call.ranks), M, K])
+            words = ttable.shape[0] // len(call.ranks)
+            first = 0 if call.slot0 is None else call.slot0
+            u = torch.empty((rows, hip_kernel.lora_sgmv_splits(M), max_rank), dtype=torch.float32, device=x.device)
+            gx = torch.zeros((rows, K), dtype=gy.dtype, device=x.device)
+            hip_kernel.lora_sgmv_(gx, gy, ids, ttable[first * words:(first + n) * words], [n, max_rank, K, M], u.view(-1))
+        grads = [None] * len(need_w)
+        for j, slot in enumerate(call.slots):
+            # (every entry is live -- the route needs every rank a multiple of 8 -- and the kernel writes all of a live entry, so
+            # the outputs need no memset)
+            a_local = slot if call.slot0 is None else 0
+            r = call.ranks[slot]
+            if need_w[2 * j]:
+                ga = hip_kernel.lora_grad(x, u, ids, table, [n, max_rank, K, a_local],
+                                          out=torch.empty((max_rank, K), dtype=torch.float32, device=x.device))
+                grads[2 * j] = ga[:r].to(gy.dtype)
+            if need_w[2 * j + 1]:
+                gb = hip_kernel.lora_grad(gy, t.view(rows, -1, max_rank), ids, table, [n, max_rank, M, a_local],
+                                          out=torch.empty((max_rank, M), dtype=torch.float32, device=x.device))
+                grads[2 * j + 1] = gb[:r].t().to(gy.dtype)
+        return (grad_y, gx if need_x else None, None, *grads)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

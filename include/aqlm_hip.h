@@ -766,6 +766,39 @@ int aqlm_hip_lora_grad_routed(const aqlm_hip_lora_entry* table, int num_adapters
                               int w_splits, long w_split_stride, float* g, size_t g_bytes, int dtype, void* stream);
 
 /*
+ * The weight gradients of the adapters on a DENSE layer (training; no reference counterpart): the table [num_adapters] and the
+ * ids are aqlm_hip_lora_sgmv's.  grad_x is aqlm_hip_lora_sgmv on the transposed table -- aqlm_hip_lora_transpose_routed with one
+ * expert and one segment --, x := grad_y; its workspace then holds u = B^T grad_y, as the forward's holds t = A x, both fp32
+ * [rows][splits][max_rank].  aqlm_hip_lora_grad is the reduction over rows that grad_A and grad_B^T are: for ONE adapter index
+ * `adapter`, with scaling that of its entry,
+ *     g[r][i] = scaling * sum over the rows b < rows with id(b) == adapter of  w[b][r] * V[b][i]      r < max_rank, i < dim   (fp32)
+ * V[b] = v + b * v_row_stride: storage-type rows of `dim` elements (16-byte aligned rows; x for grad_A, grad_y for grad_B^T).
+ * w[b][r] = sum over k < w_splits, in ascending k, of w[b * w_row_stride + k * w_split_stride + r] (fp32, 16-byte aligned rows and
+ * slices; u for grad_A, t for grad_B^T).  ids: int32 / int64 per row, NULL = adapter 0 for every row; a row whose id is negative,
+ * >= num_adapters or another adapter's contributes nothing, and neither its V nor its w can reach g (both are replaced by zeros,
+ * not multiplied by them: an inf or NaN there is harmless).  A live entry (rank a multiple of 8 in 8..max_rank) has ALL its
+ * max_rank x dim elements written -- zeros for r >= rank and when no row matches --; an entry that is not live leaves g as it is.
+ * On the matrix unit (v_mfma_f32_16x16x32, k = the row index): w enters as the pair hi = round_T(w), lo = round_T(w - float(hi)),
+ * the products are exact and the sums fp32; in fp16 a |w| above 65504 has no such pair.  The rows are cut into
+ * aqlm_hip_lora_grad_slabs(rows, dim) contiguous slabs -- a function of these two sizes only, each slab a multiple of 32 rows --
+ * whose fp32 partial sums go to `workspace` [slabs][max_rank][dim] (aqlm_hip_lora_grad_workspace_bytes, 16-byte aligned) and are
+ * added in ascending slab order by a second launch: no atomics, no inter-workgroup communication, two calls give the same bits.
+ * Stream-ordered, no allocation, no synchronisation (hipGraph-capturable).
+ * Checks, in order: a null pointer (ids may be NULL), misalignment (table 8, ids their size, w 4, g and workspace 16 bytes), a size
+ * below 1 / adapter outside [0, num_adapters), strides shorter than the rows (AQLM_HIP_E_INVALID); the dtype, then max_rank no
+ * multiple of 8 in 8..128, dim no multiple of 8, rows > AQLM_HIP_MAX_LORA_SGMV_ROWS, w_splits > 8, v or w not 16-byte aligned, a V
+ * stride no multiple of 8 or a w stride no multiple of 4 (AQLM_HIP_E_UNSUPPORTED); last g_bytes < max_rank * dim * 4 and the
+ * workspace size (AQLM_HIP_E_INVALID).  aqlm_hip_lora_grad_supported answers for the three sizes beforehand.
+ */
+int aqlm_hip_lora_grad_supported(int dim, int max_rank, int rows);
+int aqlm_hip_lora_grad_slabs(int rows, int dim);                                /* 0 for sizes below 1 */
+size_t aqlm_hip_lora_grad_workspace_bytes(int rows, int max_rank, int dim);    /* 0 when unsupported */
+int aqlm_hip_lora_grad(const aqlm_hip_lora_entry* table, int num_adapters, int max_rank, int adapter, const void* ids,
+                       int ids_int64, int rows, const void* v, long v_row_stride, int dim, const float* w, long w_row_stride,
+                       int w_splits, long w_split_stride, float* g, size_t g_bytes, void* workspace, size_t workspace_bytes,
+                       int dtype, void* stream);
+
+/*
  * Gradients of the continuous parameters of a 1x16 layer (one codebook of 65536 entries, out_group_size 1, in_group_size g = 8
  * or 16) from dW = grad_y^T @ x, [out_features][in_features] with a row stride in elements, fp16 / bf16 / fp32 (dw_dtype; 16-byte
  * aligned rows).  The reference gets them from autograd through its dequantisation (an embedding_bag backward: sort or atomics);

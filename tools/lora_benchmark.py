@@ -25,6 +25,16 @@ set to (AQLM_HIP_MAX_LORA_SGMV_ROWS when it won at every count, 0 when it lost a
 launches alone, captured, per distinct projection shape.  Writes --out (default profiles/lora_sgmv.json).
 
     python tools/lora_benchmark.py --prefill [--rows 96,128,256,512,1024,2048,4096] [--iters 50] [--repeats 3]
+
+``--train`` measures forward + backward of the same block with the adapters of rank 16 and of rank 64, ``ad0`` trained (A and B
+of all seven projections) and the input requiring a gradient, at 128 / 1024 / 4096 rows in the three adapter mixes of --prefill:
+(b) torch -- the torch path, what every gradient-needing call runs at default settings -- against (d) device -- the route
+``aqlm_amd.lora.TRAIN_MAX_ROWS`` switches on (aqlm_hip_lora_sgmv under autograd, aqlm_hip_lora_grad for grad_A / grad_B) --,
+eager and captured, the two alternating; median of --iters steps, median and spread over --repeats rounds.  ``grad_op_us`` times
+``lora_grad`` alone against ``lora_grad_routed`` driven as one expert on the same operands at 4096 rows.  Writes --out (default
+profiles/lora_train.json).
+
+    python tools/lora_benchmark.py --train [--rows 128,1024,4096] [--iters 20] [--repeats 3]
 """
 import argparse
 import json
@@ -62,13 +72,13 @@ class Block(torch.nn.Module):
         return self.down_proj(self.gate_proj(h2) * self.up_proj(h2)), k, v
 
 
-def adapter(seed):
+def adapter(seed, rank=RANK):
     gen = torch.Generator().manual_seed(seed)
     state = {}
     for name, (fin, fout) in SHAPES.items():
-        state[f"base_model.model.{name}.lora_A.weight"] = (torch.randn((RANK, fin), generator=gen) / fin ** 0.5).half()
-        state[f"base_model.model.{name}.lora_B.weight"] = (torch.randn((fout, RANK), generator=gen) * 0.02).half()
-    return state, {"peft_type": "LORA", "r": RANK, "lora_alpha": 2 * RANK, "bias": "none", "target_modules": sorted(SHAPES)}
+        state[f"base_model.model.{name}.lora_A.weight"] = (torch.randn((rank, fin), generator=gen) / fin ** 0.5).half()
+        state[f"base_model.model.{name}.lora_B.weight"] = (torch.randn((fout, rank), generator=gen) * 0.02).half()
+    return state, {"peft_type": "LORA", "r": rank, "lora_alpha": 2 * rank, "bias": "none", "target_modules": sorted(SHAPES)}
 
 
 def captured(fn):
@@ -207,8 +217,107 @@ def prefill(args):
     print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
 
 
+TRAIN_ROWS = "128,1024,4096"
+
+
+def train(args):
+    """--train: forward + backward, torch path against the device route, eager and captured; writes profiles/lora_train.json."""
+    import aqlm_amd.lora as lora
+    from aqlm_amd.inference_kernels import hip_kernel
+
+    dev = torch.device("cuda:0")
+    block = Block(dev)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    row_counts = [int(r) for r in args.rows.split(",")]
+    table, ops = [], []
+    for rank in (16, 64):
+        bank = lora.attach_adapters(block, {f"ad{i}": adapter(100 + i, rank) for i in range(ADAPTERS)})
+        trained = [p for n in SHAPES for p in (getattr(block, n).lora_A["ad0"].weight, getattr(block, n).lora_B["ad0"].weight)]
+        for p in trained:
+            p.requires_grad_(True)
+        for rows in row_counts:
+            seq_ids = torch.arange(ADAPTERS, device=dev, dtype=torch.int64)
+            row_ids = (torch.arange(rows, device=dev) % ADAPTERS).to(torch.int64)
+            mixes = (("one adapter", "ad0", (rows, H)), (f"{ADAPTERS} adapters, contiguous sequences", seq_ids, (ADAPTERS, rows // ADAPTERS, H)),
+                     (f"{ADAPTERS} adapters interleaved by row", row_ids, (rows, H)))
+            for mix, selection, shape in mixes:
+                bank.select(selection)
+                x = torch.randn(shape, generator=gen, device=dev).half().requires_grad_(True)
+                gys = None
+
+                def step():
+                    nonlocal gys
+                    x.grad = None
+                    for p in trained:
+                        p.grad = None
+                    outs = block(x)
+                    if gys is None:
+                        gys = [torch.randn(o.shape, generator=gen, device=dev).half() * 0.01 for o in outs]
+                    torch.autograd.backward(outs, gys)
+
+                fns, graphs = [], []
+                for limit in (0, lora.AQLM_HIP_MAX_LORA_SGMV_ROWS):  # the route is decided when the call runs (and when it is captured)
+                    fns.append(lambda limit=limit: (setattr(lora, "TRAIN_MAX_ROWS", limit), step()))
+                row = {"rank": rank, "rows": rows, "adapters": mix}
+
+                def record(names, calls):
+                    runs = [timed_alternating(calls, args.iters, args.warmup) for _ in range(args.repeats)]
+                    for i, name in enumerate(names):
+                        vals = sorted(r[i] for r in runs)
+                        row[name] = vals[len(vals) // 2]
+                        row[name.replace("_us", "_spread_us")] = round(vals[-1] - vals[0], 2)
+
+                record(["torch_eager_us", "device_eager_us"], fns)
+                for fn in fns:
+                    graphs.append(captured(fn)[0])
+                record(["torch_graph_us", "device_graph_us"], [g.replay for g in graphs])
+                lora.TRAIN_MAX_ROWS = 0
+                del graphs
+                table.append(row)
+                print(json.dumps(row), flush=True)
+        # the reduction alone at 4096 rows: the row-split MFMA launch against the routed launch driven as one expert
+        rows = 4096
+        ids = (torch.arange(rows, device=dev) % ADAPTERS).to(torch.int64)
+        eids = torch.zeros((rows, 1), dtype=torch.int64, device=dev)
+        bucket = torch.ops.aqlm.moe_bucket(eids, 1, hip_kernel.SGMV_ROUTED_TILE_PAIRS)
+        for name in ("q_proj", "k_proj", "gate_proj"):
+            fin, fout = SHAPES[name]
+            tbl, ranks = getattr(block, name)._device_table(dev)
+            for what, dim, splits in (("grad_A", fin, hip_kernel.lora_sgmv_splits(fout)), ("grad_B", fout, hip_kernel.lora_sgmv_splits(fin))):
+                v = torch.randn((rows, dim), generator=gen, device=dev).half()
+                w = torch.randn((rows, splits, rank), generator=gen, device=dev)
+                dense = lambda: hip_kernel.lora_grad(v, w, ids, tbl, [ADAPTERS, rank, dim, 0])  # noqa: E731
+                routed = lambda: hip_kernel.lora_grad_routed(v, w, ids, eids, bucket, tbl, [ADAPTERS, 1, 1, rank, dim, 1, 0],  # noqa: E731
+                                                             [dim, 0, 1, splits * rank, 0, splits, rank])
+                diff = float((dense() - routed().view(rank, dim)).abs().max())
+                gs = [captured(dense)[0], captured(routed)[0]]
+                runs = [timed_alternating([g.replay for g in gs], args.iters, args.warmup) for _ in range(args.repeats)]
+                op = {"rank": rank, "rows": rows, "dim": dim, "what": f"{what} of {name}", "slabs": hip_kernel.lora_grad_slabs(rows, dim),
+                      "lora_grad_us": sorted(r[0] for r in runs)[len(runs) // 2], "lora_grad_routed_us": sorted(r[1] for r in runs)[len(runs) // 2],
+                      "lora_grad_spread_us": round(max(r[0] for r in runs) - min(r[0] for r in runs), 2),
+                      "lora_grad_routed_spread_us": round(max(r[1] for r in runs) - min(r[1] for r in runs), 2), "max_abs_diff": diff}
+                ops.append(op)
+                print(json.dumps(op), flush=True)
+                del gs
+        lora.detach_adapters(block)
+    result = {"block": {"hidden": H, "kv": KV, "intermediate": I, "scheme": "1x16g8", "dtype": "float16", "projections": list(SHAPES),
+                        "adapters": ADAPTERS, "trained": "ad0, A and B of every projection; the input requires a gradient"},
+              "device": torch.cuda.get_device_name(dev), "iters": args.iters, "repeats": args.repeats, "warmup": args.warmup,
+              "what": "one block forward + backward, the torch path (TRAIN_MAX_ROWS = 0, the default) against the device route, the two "
+                      "alternating; eager and captured in a hipGraph; median over the repeats of the median step (device events), spread "
+                      "= max - min over the repeats; grad_op_us: the reduction alone, captured, on the operands of one projection",
+              "rows": table, "grad_op_us": ops,
+              "command": f"python tools/lora_benchmark.py --train --rows {args.rows} --iters {args.iters} --repeats {args.repeats}"}
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true",
+                    help=f"measure forward + backward with one adapter trained ({TRAIN_ROWS} rows, rank 16 and 64): the torch path "
+                         "against the device route; writes profiles/lora_train.json")
     ap.add_argument("--prefill", action="store_true",
                     help=f"measure the segmented route at prefill row counts ({PREFILL_ROWS}) against the torch path; writes "
                          "profiles/lora_sgmv.json")
@@ -221,9 +330,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/lora_benchmark.py measures on the GPU; none found")
     if args.rows is None:
-        args.rows = PREFILL_ROWS if args.prefill else "1,2,4,8,16,32,64"
+        args.rows = TRAIN_ROWS if args.train else PREFILL_ROWS if args.prefill else "1,2,4,8,16,32,64"
     if args.out is None:
-        args.out = os.path.join("profiles", "lora_sgmv.json" if args.prefill else "lora_bgmv.json")
+        args.out = os.path.join("profiles", "lora_train.json" if args.train else "lora_sgmv.json" if args.prefill else "lora_bgmv.json")
+    if args.train:
+        return train(args)
     if args.prefill:
         return prefill(args)
 
