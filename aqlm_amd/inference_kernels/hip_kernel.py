@@ -1277,6 +1277,26 @@ def fused_kx8_transposed_min_rows(num_codebooks: int, in_group_size: int) -> int
     return int(rule)
 
 
+# The backward of the dense 1x16 layers on the fused transposed MFMA GEMM (ops_grad.code1x16_matmat_transposed: the codebook vectors
+# are gathered per row tile, W is built in LDS, the out x in x 2-byte transient of the route below is never allocated).
+# kernel_selector.get_backward_pass_kernel tries it first inside the row WINDOW of FUSED_1X16_TRANSPOSED_ROWS -- {in_group_size:
+# (min_rows, max_rows), None: the window of every other group size}, both ends inclusive; NEVER = opt-in only -- and falls back to
+# the named op below where it declines.  DESIGN.md section 4.8u has the measurements behind the windows
+# (profiles/x16_transposed.json, tools/x16_transposed_benchmark.py).
+USE_FUSED_1X16_TRANSPOSED = True
+FUSED_1X16_TRANSPOSED_NEVER = (1 << 30, 0)
+FUSED_1X16_TRANSPOSED_ROWS = {8: FUSED_1X16_TRANSPOSED_NEVER, 16: (16, 64), None: FUSED_1X16_TRANSPOSED_NEVER}
+
+
+def fused_1x16_transposed_rows(in_group_size: int):
+    """(min_rows, max_rows), inclusive, between which the backward of a 1x16 layer of this group size takes the fused transposed GEMM."""
+    rule = FUSED_1X16_TRANSPOSED_ROWS
+    if isinstance(rule, dict):
+        rule = rule.get(int(in_group_size), rule.get(None, FUSED_1X16_TRANSPOSED_NEVER))
+    lo, hi = rule
+    return int(lo), int(hi)
+
+
 def _matmat_dequant_transposed(input, codes, codebooks, scales, bias, kind):
     """grad_input = (grad_output * scales) @ W  (+ bias): backward of the linear layer
     (cuda_kernel.cpp:303-354; generic definition kernel_selector.py:145-161)."""
@@ -1484,7 +1504,7 @@ from .ops_grad import (  # noqa: E402, F401
     CODEBOOK_GRAD_CHUNK, CODEBOOK_GRAD_ENTRIES, CodebookGradIndex, _calib_layer, _calib_scales, _check_calib_matrix, _check_dw,
     _check_kx8_codes, _check_scales, _codebook_grad_kx8_op, _codebook_grad_op, _scales_grad_kx8_op, _scales_grad_op,
     build_codebook_grad_index, calib_codebook_grad_1x16, calib_codebook_grad_kx8, calib_delta, calib_rows, calib_supported,
-    codebook_grad_1x16, codebook_grad_kx8, codebook_grad_kx8_supported, codebook_grad_max_chunks, codebook_grad_supported,
+    code1x16_matmat_transposed, codebook_grad_1x16, codebook_grad_kx8, codebook_grad_kx8_supported, codebook_grad_max_chunks, codebook_grad_supported,
     codekx8_matmat_transposed, scales_grad_1x16, scales_grad_kx8,
 )
 from .ops_search import (  # noqa: E402, F401

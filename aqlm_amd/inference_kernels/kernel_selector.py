@@ -130,8 +130,17 @@ def get_backward_pass_kernel(
         kern = ops.generic_matmat_dequant_transposed
 
     fused_kx8 = codebook_size == 256 and num_codebooks <= 8 and in_group_size in (8, 16, 32)
+    fused_1x16 = (num_codebooks, codebook_size) == (1, 65536) and in_group_size in (8, 16)
 
     def _backward(grad_output, codes, codebooks, scales, bias):
+        # 1x16 inside the measured row window: the fused transposed GEMM, W never materialised (None: the launch declined the call)
+        if fused_1x16 and hip_kernel.USE_FUSED_1X16_TRANSPOSED:
+            rows = grad_output.numel() // grad_output.shape[-1] if grad_output.shape[-1] else 0
+            lo, hi = hip_kernel.fused_1x16_transposed_rows(in_group_size)
+            if lo <= rows <= hi:
+                grad_input = hip_kernel.code1x16_matmat_transposed(grad_output, codes, codebooks, scales)
+                if grad_input is not None:
+                    return grad_input
         # K x 8 from the measured row count on: the fused transposed GEMM, W never materialised (None: the launch declined the call)
         if fused_kx8 and hip_kernel.USE_FUSED_KX8_TRANSPOSED:
             rows = grad_output.numel() // grad_output.shape[-1] if grad_output.shape[-1] else 0

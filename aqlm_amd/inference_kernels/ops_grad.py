@@ -297,6 +297,51 @@ def codekx8_matmat_transposed(grad_output, codes, codebooks, scales, splits: Opt
 
 
 # ------------------------------------------------------------------------------------------------------
+# the input gradient of a dense 1x16 layer (aqlm_hip_gemm_1x16_transposed): codebook vectors gathered per row tile, W never in memory
+# ------------------------------------------------------------------------------------------------------
+@torch.compiler.disable
+def code1x16_matmat_transposed(grad_output, codes, codebooks, scales, splits: Optional[int] = None):
+    """``grad_input = grad_output @ Wq`` [..., in] of a 1x16 layer (one codebook of 65536 entries, g 8 / 16), ``Wq`` being the scaled
+    storage weight the dequantise kernel writes -- the arithmetic of ``code1x16_matmat_dequant_transposed`` up to the order of the fp32
+    sums over the output rows -- without W ever reaching memory (include/aqlm_hip.h).  ``splits``: blocks that share the output rows
+    of a tile (1 = none; None = the library chooses, its fp32 partials in the cached per-stream workspace, a fresh one inside a
+    hipGraph capture).  Returns None where the entry declines (other schemes, rows that cannot be 16-byte aligned): the caller then
+    takes the dequantise + GEMM route.  A ``grad_output`` with unaligned or non-unit-stride rows is copied once."""
+    if codebooks.dim() != 4 or codes.dim() != 3 or codes.dtype != torch.int16 or grad_output.dtype not in (torch.float16, torch.bfloat16):
+        return None
+    K, size, og, g = (int(v) for v in codebooks.shape)
+    out_features, in_features = int(codes.shape[0]), int(codes.shape[1]) * g
+    if (K != 1 or size != 65536 or og != 1 or int(codes.shape[2]) != 1 or codebooks.dtype != grad_output.dtype
+            or scales.dtype != grad_output.dtype or scales.numel() != out_features or grad_output.shape[-1] != out_features
+            or not grad_output.is_cuda or any(t.device != grad_output.device for t in (codes, codebooks, scales))
+            or not _lib.aqlm_hip_gemm_1x16_transposed_supported(out_features, in_features, g)):
+        return None
+    gy = grad_output.reshape(-1, out_features)
+    rows = gy.shape[0]
+    if rows < 1 or rows > 65536:
+        return None
+    # (out_features % 8 == 0 here: contiguous rows are 16-byte aligned)
+    if gy.stride(1) != 1 or gy.data_ptr() % 16 != 0 or (rows > 1 and (gy.stride(0) % 8 != 0 or gy.stride(0) < out_features)):
+        gy = gy.contiguous()
+    gys = gy.stride(0) if rows > 1 else out_features  # (one row has no stride)
+    codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales)
+    splits = 0 if splits is None else int(splits)
+    gx = torch.empty((rows, in_features), dtype=grad_output.dtype, device=grad_output.device)
+    stream = _stream_ptr(grad_output.device)
+    ws_bytes = int(_lib.aqlm_hip_gemm_1x16_transposed_workspace_bytes(rows, out_features, in_features, splits))
+    ws = _workspace(grad_output.device, ws_bytes, stream) if ws_bytes else None
+    with _device_guard(grad_output.device):
+        rc = _lib.aqlm_hip_gemm_1x16_transposed(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), gy.data_ptr(), gx.data_ptr(), rows,
+                                                out_features, in_features, g, gys, in_features, _native.F16 if gx.dtype == torch.float16
+                                                else _native.BF16, splits, _ptr(ws), ws_bytes, stream)
+    if rc == _native.E_UNSUPPORTED:
+        return None
+    if rc:
+        _native.check(rc, "aqlm gemm_1x16_transposed")
+    return gx.reshape(grad_output.shape[:-1] + (in_features,))
+
+
+# ------------------------------------------------------------------------------------------------------
 # one step of the calibrated training of codebooks and scales on fp32 masters (aqlm_hip_calib_*; tuning.calibrated_loss_and_grads)
 # ------------------------------------------------------------------------------------------------------
 def calib_supported(out_features: int, in_features: int, num_codebooks: int, nbits_per_codebook: int, in_group_size: int) -> bool:

@@ -1363,6 +1363,35 @@ int aqlm_hip_gemm_kx8_transposed(const void* codes_i8, const void* codebooks, co
                                  long gy_row_stride, long gx_row_stride, int dtype, int splits,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Input gradient of the dense 1x16 layers (additive to ABI 9): gx[rows][in] = gy[rows][out] @ Wq for one codebook of 65536 entries
+ * with g = 8 / 16, out_group_size 1, Wq the SCALED storage weight aqlm_hip_dequant_1x16 writes (fp32(codebook value) x
+ * fp32(scales[o]), one rounding) -- never materialised: a block owns a tile of 16 / 64 / 256 batch rows x 128 columns of gx, gathers
+ * the codebook vectors of every step of 32 output rows from global memory, builds W[32 rows][128 columns] in LDS with exactly those
+ * bits and reads it column-major (ds_read_b64_tr_b16) into v_mfma_f32_16x16x32 (exact products, fp32 sums over o ascending, one
+ * rounding of gx).  gy and gx are of `dtype`, codes int16 [out][in / g], codebook [65536][g] and scales [out] of `dtype`.  The tile
+ * height follows from `rows` and in_features alone; a row's bits depend neither on the other rows of the call nor on their number,
+ * for given `splits`.
+ * `splits`: blocks that share the output rows of one tile (few batch rows cannot fill the device otherwise); 1 = gx is written
+ * directly, no workspace; 2 .. 16 = fp32 partial tiles in `workspace` (16-B aligned, aqlm_hip_gemm_1x16_transposed_workspace_bytes =
+ * splits * rows * in_features * 4 bytes), added in slice order by a second kernel before the one rounding (deterministic, no
+ * atomics; a slice without steps adds zeros); 0 = the entry chooses, never more than out_features / (8 rows) slices -- the
+ * workspace stays within a quarter of the W it replaces -- and _workspace_bytes(.., 0) is exactly what that choice needs.
+ * _workspace_bytes answers 0 for sizes below 1, rows above 65536 and splits outside 0 .. 16.
+ * Memory contract: gy rows are 16-byte aligned (row strides in elements, multiples of 8, at least out_features / in_features);
+ * nothing is read past a row, past the codes or past the codebook; a last column block narrower than 128 is masked.
+ * out_features a multiple of 8, in_features a multiple of g, an even number of codes (a code is fetched as the aligned 4-byte word
+ * that holds it), 1 .. 65536 rows.
+ * Replaces: the W transient of code1x16_matmat_dequant_transposed = Code1x16Dequant + torch::matmul (cuda_kernel.cpp:303-354).
+ * AQLM_HIP_E_UNSUPPORTED (the caller dequantises + calls its GEMM): other shapes (_supported says which), codes or scales not 4-B aligned,
+ * codebook or rows of gy / gx not 16-B aligned.  AQLM_HIP_E_INVALID: null pointers, sizes below 1, a missing or too small workspace.
+ */
+int aqlm_hip_gemm_1x16_transposed_supported(int out_features, int in_features, int in_group_size);
+size_t aqlm_hip_gemm_1x16_transposed_workspace_bytes(int rows, int out_features, int in_features, int splits);
+int aqlm_hip_gemm_1x16_transposed(const void* codes_i16, const void* codebook, const void* scales, const void* gy, void* gx,
+                                  int rows, int out_features, int in_features, int in_group_size, long gy_row_stride,
+                                  long gx_row_stride, int dtype, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
 #define AQLM_HIP_OP_GEMM_1X16_MFMA 1
 #define AQLM_HIP_OP_GEMM_KX8_MFMA 6
 #define AQLM_HIP_OP_GEMV_1X16_PACKED 3
