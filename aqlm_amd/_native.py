@@ -270,6 +270,9 @@ SIGNATURES = {
     "aqlm_hip_gemm_1x16_transposed_supported": (_ci, [_ci, _ci, _ci]),
     "aqlm_hip_gemm_1x16_transposed_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_gemm_1x16_transposed": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _ci, _vp, _sz, _vp]),
+    "aqlm_hip_gemv_kx16": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
+    "aqlm_hip_gemm_kx16_rows_supported": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci]),
+    "aqlm_hip_gemm_kx16_rows": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_gemm_8x8_mfma": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cl, _cl, _ci, _vp]),
     "aqlm_hip_workspace_bytes": (_sz, [_ci, _ci, _ci, _ci]),
     "aqlm_hip_checksum": (_ci, [_vp, _sz, _vp, _vp]),

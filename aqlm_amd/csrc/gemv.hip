@@ -38,7 +38,8 @@ struct GemvRest {
   int cb_bytes;
 };
 
-template <class T, int CODE_BYTES, int KC, int G, int U, int NB, bool CB_LDS, int NWAVES, int AUX>
+// VARCB: KC codebooks of cb_bytes / (KC * G * 2) entries each, codes masked to them (gemv_body.h); the entry count is a power of two
+template <class T, int CODE_BYTES, int KC, int G, int U, int NB, bool CB_LDS, int NWAVES, int AUX, bool VARCB = false>
 __global__ __launch_bounds__(NWAVES * 64) void gemv_kernel(const uint8_t* codes, const uint8_t* codebooks, const uint16_t* x, int M,
                                                            int in_groups, int nunits, int iters, int pitch, int rpw, long xs,
                                                            const GemvRest rest) {
@@ -57,10 +58,12 @@ __global__ __launch_bounds__(NWAVES * 64) void gemv_kernel(const uint8_t* codes,
   p.rpw = rpw;
   p.prefetch = rest.prefetch;
   p.cb_bytes = rest.cb_bytes;
+  p.cb_entries = VARCB ? rest.cb_bytes / (KC * G * 2) : 65536;
+  p.code_mask = p.cb_entries - 1;
   p.xs = xs;
   p.ys = rest.ys;
   p.code_row_bytes = rest.code_row_bytes;
-  gemv_body<T, CODE_BYTES, KC, G, U, NB, CB_LDS, NWAVES, AUX>(p, blockIdx.x);
+  gemv_body<T, CODE_BYTES, KC, G, U, NB, CB_LDS, NWAVES, AUX, false, VARCB>(p, blockIdx.x);
 }
 
 // Several code matrices that multiply the SAME x (q/k/v, gate/up of a decoder layer) in one launch: every workgroup
@@ -162,10 +165,10 @@ __global__ __launch_bounds__(256) void gemv_generic_kernel(const GenericParams p
 // ---------------------------------------------------------------------------------------------
 static constexpr size_t kMaxXTileBytes = 64 * 1024;
 
-template <class T, int CODE_BYTES, int KC, int G, int U, int NB, bool CB_LDS, int NWAVES, int AUX>
+template <class T, int CODE_BYTES, int KC, int G, int U, int NB, bool CB_LDS, int NWAVES, int AUX, bool VARCB = false>
 static int launch_gemv(const GemvParams& p, hipStream_t stream) {
   constexpr int P = G / 8;
-  auto kern = gemv_kernel<T, CODE_BYTES, KC, G, U, NB, CB_LDS, NWAVES, AUX>;
+  auto kern = gemv_kernel<T, CODE_BYTES, KC, G, U, NB, CB_LDS, NWAVES, AUX, VARCB>;
   size_t lds = (size_t)NB * U * P * p.pitch * 16;
   if (CB_LDS) lds += (size_t)KC * 256 * G * 2;
   if (lds > 160 * 1024) {
@@ -419,6 +422,73 @@ extern "C" int aqlm_hip_gemv_1x16_multi(const aqlm_hip_segment* segments, int nu
       e = in_group_size == 8 ? dispatch_1x16_multi_nb<F16, 8>(nb, mp, stream) : dispatch_1x16_multi_nb<F16, 16>(nb, mp, stream);
     else
       e = in_group_size == 8 ? dispatch_1x16_multi_nb<BF16, 8>(nb, mp, stream) : dispatch_1x16_multi_nb<BF16, 16>(nb, mp, stream);
+    if (e) return e;
+    done += nb;
+  }
+  return 0;
+}
+
+// K x 9..16 bits -----------------------------------------------------------------------------------
+// 2 or 4 codebooks of 512 .. 65536 entries in 16-bit containers, g 8 (the 3- and 4-bit models of the AQLM paper: 2x12, 2x16; 4x16):
+// the direct kernel with a 16-byte lane-unit of U = 8 / KC groups, so that a lane still has 8 gathers of 16 bytes in flight, as the
+// 1x16 g8 instance has -- per group KC gathers instead of one, which is what the scheme costs.
+namespace aqlm {
+template <class T, int KC>
+static int dispatch_kx16_nb(int nb, const GemvParams& p, hipStream_t s) {
+  constexpr int U = 8 / KC;
+  switch (nb) {
+    case 1: return launch_gemv<T, 2, KC, 8, U, 1, false, 4, AUX_DEFAULT, true>(p, s);
+    case 2: return launch_gemv<T, 2, KC, 8, U, 2, false, 4, AUX_DEFAULT, true>(p, s);
+    case 4: return launch_gemv<T, 2, KC, 8, U, 4, false, 4, AUX_DEFAULT, true>(p, s);
+    default: return launch_gemv<T, 2, KC, 8, U, 8, false, 4, AUX_DEFAULT, true>(p, s);
+  }
+}
+}  // namespace aqlm
+
+extern "C" int aqlm_hip_gemv_kx16(const void* codes, const void* codebooks, const void* scales, const void* bias, const void* x,
+                                  void* y, int out_features, int in_features, int num_codebooks, int nbits, int in_group_size,
+                                  int batch, long xs, long ys, int dtype, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (int e = validate_common(codes, codebooks, scales, x, y, out_features, in_features, in_group_size, batch, dtype,
+                              "aqlm_hip_gemv_kx16"))
+    return e;
+  if (int e = check_x_row_stride("aqlm_hip_gemv_kx16", batch, in_features, xs)) return e;
+  if (nbits < 9 || nbits > 16 || num_codebooks < 2 || num_codebooks > 8) {
+    set_last_error("aqlm_hip_gemv_kx16: nbits %d / num_codebooks %d unsupported (9..16 bits in 16-bit containers, 2..8 codebooks)",
+                   nbits, num_codebooks);
+    return AQLM_HIP_E_UNSUPPORTED;
+  }
+  const int K = num_codebooks;
+  const int in_groups = in_features / in_group_size;
+  const size_t x_row_bytes = (size_t)in_features * 2;
+  const int U = K == 2 ? 4 : 2;
+  // (a code row of in_groups * K * 2 bytes is a whole number of 16-byte units: every row starts 16-byte aligned)
+  const bool fast = (K == 2 || K == 4) && in_group_size == 8 && !tuning().force_generic && (in_groups % U == 0) &&
+                    aligned16(codes) && aligned16(codebooks) && aligned16(x) && (xs % 8 == 0) && x_row_bytes <= kMaxXTileBytes;
+  if (!fast)
+    return run_generic(codes, codebooks, scales, bias, x, y, out_features, in_features, K, nbits, in_group_size, batch, xs,
+                       ys, dtype, stream);
+  GemvParams p{};
+  p.codes = (const uint8_t*)codes;
+  p.codebooks = (const uint8_t*)codebooks;
+  p.scales = (const uint16_t*)scales;
+  p.bias = (const uint16_t*)bias;
+  p.M = out_features;
+  p.xs = xs;
+  p.ys = ys;
+  p.code_row_bytes = (long)in_groups * K * 2;
+  p.cb_bytes = K * (1 << nbits) * 8 * 2;  // (the kernel takes the entry count and the code mask from it)
+  p.prefetch = 0;
+  if (K == 2) finish_params<4>(p, in_groups, out_features, 4 * 4096);
+  else finish_params<2>(p, in_groups, out_features, 4 * 4096);
+  int done = 0;
+  while (done < batch) {
+    const int nb = pick_nb(batch - done, x_row_bytes);
+    p.x = (const uint16_t*)x + (long)done * xs;
+    p.y = (uint16_t*)y + (long)done * ys;
+    int e;
+    if (dtype == AQLM_HIP_F16) e = K == 2 ? dispatch_kx16_nb<F16, 2>(nb, p, stream) : dispatch_kx16_nb<F16, 4>(nb, p, stream);
+    else e = K == 2 ? dispatch_kx16_nb<BF16, 2>(nb, p, stream) : dispatch_kx16_nb<BF16, 4>(nb, p, stream);
     if (e) return e;
     done += nb;
   }

@@ -20,6 +20,8 @@ struct GemvParams {
   int rpw;            // rows per wave
   int prefetch;       // 1x16 only: warm the XCD's L2 with a slice of the codebook first
   int cb_bytes;       // total codebook bytes
+  int cb_entries;     // VARCB only: entries of one codebook (a power of two, 512 .. 65536)
+  int code_mask;      // VARCB only: cb_entries - 1; every code is taken & code_mask, as the generic kernel does
   long xs, ys;        // row strides of x / y in elements
   long code_row_bytes;
 };
@@ -48,7 +50,9 @@ __device__ __forceinline__ void load_code_word(const uint8_t* p, uint32_t (&cw)[
 // CB_LDS: codebooks in LDS (Kx8) or L2 gathers (1x16); NWAVES: waves per block; AUX: gather cache policy.
 // `block` is the workgroup's index within its own code matrix (== blockIdx.x for a single-matrix launch).
 // GATHER: the batch rows come from / go to the row lists of `gather` instead of rows 0..NB-1.
-template <class T, int CODE_BYTES, int KC, int G, int U, int NB, bool CB_LDS, int NWAVES, int AUX, bool GATHER = false>
+// VARCB (gather route only): the KC codebooks hold p.cb_entries entries each instead of 65536, and a code is masked to them
+// (K x 9..16-bit schemes in 16-bit containers, gemv.hip's aqlm_hip_gemv_kx16); false: the code as it stands, the instances of before.
+template <class T, int CODE_BYTES, int KC, int G, int U, int NB, bool CB_LDS, int NWAVES, int AUX, bool GATHER = false, bool VARCB = false>
 __device__ __forceinline__ void gemv_body(const GemvParams& p, const int block, const GemvGather& gather = GemvGather{}) {
   constexpr int P = G / 8;                  // 16-B pieces per codebook vector
   constexpr int UB = U * KC * CODE_BYTES;   // code bytes per unit
@@ -56,6 +60,7 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int block, 
   static_assert(UB == 8 || UB == 16, "unit must be 8 or 16 code bytes");
   constexpr int NT = NWAVES * 64;
   constexpr int CB_SIZE = CB_LDS ? 256 : 65536;
+  static_assert(!VARCB || !CB_LDS, "codebooks of a run-time size are gathered from L2");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   u32x4* const xl = reinterpret_cast<u32x4*>(smem_raw);
@@ -181,8 +186,12 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int block, 
           for (int i = 0; i < U; ++i)
 #pragma unroll
             for (int c = 0; c < KC; ++c) {
-              const uint32_t code = code_at<CODE_BYTES>(cw, i * KC + c);
-              const uint32_t off = (uint32_t)(c * CB_SIZE + code) * (uint32_t)(G * 2);
+              uint32_t code = code_at<CODE_BYTES>(cw, i * KC + c), cb_first = (uint32_t)(c * CB_SIZE);
+              if constexpr (VARCB) {
+                code &= (uint32_t)p.code_mask;
+                cb_first = (uint32_t)c * (uint32_t)p.cb_entries;
+              }
+              const uint32_t off = (cb_first + code) * (uint32_t)(G * 2);
 #pragma unroll
               for (int pp = 0; pp < P; ++pp)
                 ent[(i * KC + c) * P + pp] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + pp * 16, 0, AUX);

@@ -106,9 +106,10 @@ def _gemv(input, codes, codebooks, scales, bias, kind):
                                             x.stride(0), out_features, dt, stream)
             else:
                 nbits = int(codebook_size).bit_length() - 1
-                rc = _lib.aqlm_hip_gemv_generic(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias),
-                                                xp, yp, out_features, in_features, num_codebooks, nbits,
-                                                in_group_size, nb, x.stride(0), out_features, dt, stream)
+                entry = _lib.aqlm_hip_gemv_kx16 if kind == "kx16" else _lib.aqlm_hip_gemv_generic  # (one signature)
+                rc = entry(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias),
+                           xp, yp, out_features, in_features, num_codebooks, nbits,
+                           in_group_size, nb, x.stride(0), out_features, dt, stream)
             if rc:
                 _native.check(rc, "aqlm gemv")
     return y.reshape(input.shape[:-1] + (out_features,))
@@ -1336,6 +1337,87 @@ def code2x8_matmat_dequant_transposed(input, codes, codebooks, scales, bias=None
 
 def code1x8_matmat_dequant_transposed(input, codes, codebooks, scales, bias=None):
     return _matmat_dequant_transposed(input, codes, codebooks, scales, bias, "kx8")
+
+
+# ------------------------------------------------------------------------------------------------------
+# K x 9..16 bits, g 8 (2x12, 2x16: the 3- and 4-bit models of the AQLM paper; 4x16): plain functions, no torch op of their own
+# ------------------------------------------------------------------------------------------------------
+# What kernel_selector.get_forward_pass_kernel returns for 2 or 4 codebooks of 512 .. 65536 entries with g 8.  Both routes are decided
+# by measurement (tools/kx16_benchmark.py -> profiles/kx16.json) and a call outside them is today's generic
+# route, bit for bit:
+#   USE_KX16_GEMV   {(num_codebooks, nbits): bool, None: every other scheme} -- True: `codekx16_matmat` runs the direct matvec kernel
+#                   (aqlm_hip_gemv_kx16); False: `generic_matmat`.
+#   FUSED_KX16_MAX_ROWS   rows up to which `codekx16_matmat_dequant` runs the fused dequantise-to-MFMA kernel (aqlm_hip_gemm_kx16_rows);
+#                   0 = never (opt-in); above it, and where the entry declines, `generic_matmat_dequant`.
+# Measured (profiles/kx16.json; eager calls, us, 4096^2 / 4096 -> 14336 / 14336 -> 4096): the matvec at 1 row 34 / 76 / 73 (2x16),
+# 27 / 60 / 59 (2x12), 50 / 138 / 137 (4x16) against 150 / 493 / 475, 89 / 376 / 276, 281 / 983 / 938 of the generic kernel; the fused
+# kernel at 64 rows 55 / 153 / 125 (2x16) against 174 / 525 / 536 of dequantise + GEMM, and level with it or behind at 256 rows (four
+# passes, each gathering again) on 4096 -> 14336.  Schemes that were not measured (2x9 .. 2x11, 4x9 .. 4x15, ...) stay generic at decode.
+# Under torch.compile both functions return the registered generic ops, which trace.
+USE_KX16_GEMV = {(2, 16): True, (2, 12): True, (4, 16): True, None: False}
+FUSED_KX16_MAX_ROWS = 64
+
+
+def _kx16_scheme(codes, codebooks):
+    """(num_codebooks, nbits) when the tensors are a K x 9..16-bit g 8 layer in the checkpoint layout, else None."""
+    K, size, og, g = codebooks.shape
+    if K not in (2, 4) or og != 1 or g != 8 or not 512 <= size <= 65536 or size & (size - 1):
+        return None
+    if codes.dtype != torch.int16 or codes.dim() != 3 or codes.shape[2] != K:
+        return None
+    return K, int(size).bit_length() - 1
+
+
+def codekx16_matmat(input, codes, codebooks, scales, bias=None):
+    """Decode forward of a K x 9..16-bit g 8 layer (any number of rows, slabs of 8): the direct kernel where USE_KX16_GEMV switches
+    the scheme on, else `generic_matmat`."""
+    scheme = _kx16_scheme(codes, codebooks)
+    rule = USE_KX16_GEMV
+    on = rule.get(scheme, rule.get(None, False)) if isinstance(rule, dict) else bool(rule)
+    if scheme is None or not on or torch.compiler.is_compiling():
+        return torch.ops.aqlm.generic_matmat(input, codes, codebooks, scales, bias)  # (the op: it traces under torch.compile)
+    return _gemv(input, codes, codebooks, scales, bias, "kx16")
+
+
+def codekx16_matmat_rows(input, codes, codebooks, scales, bias=None):
+    """The fused dequantise-to-MFMA kernel (aqlm_hip_gemm_kx16_rows) at any row count: one MFMA per codebook into one fp32
+    accumulator, W neither rounded nor materialised.  None when the call is outside the kernel."""
+    scheme = _kx16_scheme(codes, codebooks)
+    if scheme is None or input.dtype not in _DT or input.shape[-1] != codes.shape[1] * 8:
+        return None
+    if codebooks.dtype != input.dtype or scales.dtype != input.dtype or (bias is not None and bias.dtype != input.dtype):
+        return None
+    if not input.is_cuda or any(t is not None and t.device != input.device for t in (codes, codebooks, scales, bias)):
+        return None  # (the dequantise + GEMM route raises torch's own device-mismatch error)
+    K, nbits = scheme
+    x = _flat_rows(input)
+    B, out_features, in_features = x.shape[0], codes.shape[0], codes.shape[1] * 8
+    if not _lib.aqlm_hip_gemm_kx16_rows_supported(out_features, in_features, K, nbits, 8, B):
+        return None
+    codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales.reshape(-1))
+    if bias is not None:
+        bias = _c(bias)
+    y = torch.empty((B, out_features), dtype=input.dtype, device=input.device)
+    with _device_guard(input.device):
+        rc = _lib.aqlm_hip_gemm_kx16_rows(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), _ptr(bias), x.data_ptr(), y.data_ptr(),
+                                          B, out_features, in_features, K, nbits, 8, x.stride(0), out_features, _DT[input.dtype],
+                                          _stream_ptr(input.device))
+    if rc == _native.E_UNSUPPORTED:
+        return None
+    if rc:
+        _native.check(rc, "aqlm gemm_kx16_rows")
+    return _shaped(y, input)
+
+
+def codekx16_matmat_dequant(input, codes, codebooks, scales, bias=None):
+    """Batch forward of a K x 9..16-bit g 8 layer: the fused kernel up to FUSED_KX16_MAX_ROWS rows where it takes the call, else
+    `generic_matmat_dequant`."""
+    if (FUSED_KX16_MAX_ROWS > 0 and 0 < input.numel() // max(input.shape[-1], 1) <= FUSED_KX16_MAX_ROWS
+            and not torch.compiler.is_compiling()):
+        y = codekx16_matmat_rows(input, codes, codebooks, scales, bias)
+        if y is not None:
+            return y
+    return torch.ops.aqlm.generic_matmat_dequant(input, codes, codebooks, scales, bias)
 
 
 # ------------------------------------------------------------------------------------------------------

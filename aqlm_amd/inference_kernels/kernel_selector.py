@@ -9,6 +9,7 @@ MI355X ops of ``hip_kernel``:
     2x8  g8       decode -> aqlm::code2x8_matmat             batch -> aqlm::code2x8_matmat_dequant
     1x8  g8       decode -> aqlm::code1x8_matmat             batch -> aqlm::code1x8_matmat_dequant
     Kx8  any g    decode -> aqlm::codekx8_matmat (reference: Triton)     batch -> dequant + GEMM
+    2|4 x 9..16 g8  decode -> hip_kernel.codekx16_matmat (reference: Triton)   batch -> hip_kernel.codekx16_matmat_dequant
     anything else (out_group_size == 1) -> aqlm::generic_matmat (reference: Triton)
 
 ROCm reports ``device.type == "cuda"``.  Tensors on the host take the CPU branch (reference kernel_selector.py:95-102):
@@ -98,6 +99,9 @@ def get_forward_pass_kernel(
         return ops.code1x8_matmat_dequant if optimize_for_training else ops.code1x8_matmat
     if codebook_size == 256 and in_group_size % 8 == 0 and num_codebooks <= 16:
         return hip_kernel.code2x8_matmat_dequant if optimize_for_training else ops.codekx8_matmat
+    if num_codebooks in (2, 4) and 512 <= codebook_size <= 65536 and in_group_size == 8:
+        # 2x12, 2x16, 4x16: plain functions that fall back to the generic ops outside their measured routes
+        return hip_kernel.codekx16_matmat_dequant if optimize_for_training else hip_kernel.codekx16_matmat
     if optimize_for_training:
         return ops.generic_matmat_dequant  # generic dequant + library GEMM (the reference's dequantize_gemm)
     return ops.generic_matmat

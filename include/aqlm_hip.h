@@ -1392,6 +1392,37 @@ int aqlm_hip_gemm_1x16_transposed(const void* codes_i16, const void* codebook, c
                                   int rows, int out_features, int in_features, int in_group_size, long gy_row_stride,
                                   long gx_row_stride, int dtype, int splits, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * K x 9..16-bit layers (additive to ABI 9): num_codebooks codebooks of 2^nbits entries in 16-bit containers, g = 8, out_group_size 1 --
+ * 2x12 and 2x16, the schemes of the AQLM paper's 3- and 4-bit models, and 4x16.  codes int16 [out][in / 8][num_codebooks] (checkpoint
+ * layout), codebooks [num_codebooks][2^nbits][8] and scales [out] of `dtype`; every code is taken & (2^nbits - 1), as
+ * aqlm_hip_gemv_generic takes it.  y = (W x) * scales + bias, exact products, fp32 sums, one rounding.
+ *
+ * aqlm_hip_gemv_kx16: 1 .. AQLM_HIP_MAX_GEMV_BATCH rows, arguments as aqlm_hip_gemv_generic.  2 or 4 codebooks with in / 8 a multiple
+ * of 8 / num_codebooks, 16-B aligned codes, codebooks and rows of x: the direct matvec kernel with a 16-byte code word per lane (4 or
+ * 2 groups), all 8 gathers of a word in flight at once, x in LDS, the codebooks read from L2.  Anything else that is a valid layer
+ * (3, 5 .. 8 codebooks, other group sizes, misaligned tensors, the tuning key force_generic) runs the generic kernel: the entry never
+ * refuses a valid layer.  AQLM_HIP_E_UNSUPPORTED: nbits outside 9 .. 16, num_codebooks outside 2 .. 8, more than 8 rows, other dtypes.
+ *
+ * aqlm_hip_gemm_kx16_rows: any number of rows (1 .. 65536; made for 7+), 2 or 4 codebooks, in_features a multiple of 32.  A workgroup
+ * owns 16 output rows over all of in_features; a lane gathers the codebook vectors of (row, group) straight into its operand of
+ * v_mfma_f32_16x16x32 and issues one MFMA per codebook against the same fragment of x, so the sum over the codebooks happens in the
+ * fp32 accumulator and W is neither rounded nor materialised; the 8 waves of the workgroup deal the k range and add their
+ * accumulators in wave order (same bits on every call; a row's bits depend neither on the other rows nor on their number).  No
+ * workspace.  More than 64 rows run as passes of 64, each gathering again.  Codes aligned to the 4- / 8-byte word of a group,
+ * codebooks and rows of x 16-B aligned (x_row_stride in elements, a multiple of 8).  _supported says which (sizes, scheme, rows)
+ * it takes.  AQLM_HIP_E_UNSUPPORTED (the caller dequantises + calls its GEMM): everything else, and the tuning key force_generic.
+ * AQLM_HIP_E_INVALID: null pointers, sizes below 1, in_features no multiple of in_group_size.
+ * Replaces (behaviour): the Triton kernel the reference sends these schemes to (kernel_selector.py:91-94, triton_kernel.py:30-205).
+ */
+int aqlm_hip_gemv_kx16(const void* codes_i16, const void* codebooks, const void* scales, const void* bias, const void* x, void* y,
+                       int out_features, int in_features, int num_codebooks, int nbits, int in_group_size, int batch,
+                       long x_row_stride, long y_row_stride, int dtype, void* stream);
+int aqlm_hip_gemm_kx16_rows_supported(int out_features, int in_features, int num_codebooks, int nbits, int in_group_size, int rows);
+int aqlm_hip_gemm_kx16_rows(const void* codes_i16, const void* codebooks, const void* scales, const void* bias, const void* x, void* y,
+                            int rows, int out_features, int in_features, int num_codebooks, int nbits, int in_group_size,
+                            long x_row_stride, long y_row_stride, int dtype, void* stream);
+
 #define AQLM_HIP_OP_GEMM_1X16_MFMA 1
 #define AQLM_HIP_OP_GEMM_KX8_MFMA 6
 #define AQLM_HIP_OP_GEMV_1X16_PACKED 3
