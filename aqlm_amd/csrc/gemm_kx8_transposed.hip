@@ -1,27 +1,18 @@
 // Input gradient of the dense K x 8 layers (1x8 g8, 2x8 g8, 4x8 g16, 8x8 g32, ...): the TRANSPOSED product on the MFMA pipe, gfx950.
-//
-//   gx[b, :] = sum_o gy[b, o] * Wq[o, :]          gy [rows][out], gx [rows][in], fp16 / bf16
+// gemm_transposed.h has the tile, the layout of the W and gy images with its bank argument, the slices and the numerics, and says why
+// the shares, the consumer and the epilogue below are written out here as in gemm_1x16_transposed.hip; this file builds the W image
+// of a step from codebooks in LDS.
 //
 // Wq is the scaled storage weight of DESIGN.md section 4.7 -- per weight an fp32 zero plus the selected entry of every codebook in
 // codebook order, times the row's scale, one round-to-nearest-even -- i.e. the bits aqlm_hip_dequant_kx8 writes.  Here W never
 // reaches global memory:
 //   * all K codebooks (K x 256 x g x 2 bytes) are copied to LDS once per block;
-//   * a block owns a tile of TP batch rows x 128 columns of gx and walks the output rows in steps of 32, the k of one
-//     v_mfma_f32_16x16x32.  For every step it BUILDS the image W[32 rows][128 columns] in LDS: a thread takes two (row, 16-byte
-//     piece) cells, reads the cell's K code bytes (contiguous in the checkpoint layout [out][in / g][K]), gathers the K pieces from
-//     the LDS codebooks, adds them in fp32 in codebook order, multiplies by scales[o], rounds once and stores 16 bytes;
-//   * the product sums over the image's ROWS, so the waves read it column-major with ds_read_b64_tr_b16 (two reads make the 8 k
-//     values of one MFMA operand).  Rows are 256 bytes; piece ch of row r lies at slot ch ^ ((r & 3) << 2), and rows with bit 3 set
-//     hold the two 8-byte halves of every piece exchanged.  A 16-byte image write of 16 lanes covers one whole row; a transposed
-//     read of a 32-lane half (4 rows x 4 pieces, two blocks 8 rows apart, one half of each piece) meets 32 distinct 8-byte slots.
-//     (Freedom from bank conflicts is argued from these addresses, here and for the gy image: no counter run has measured it);
-//   * the gy tile of a step ([TP][32]) is staged in LDS beside it (64-byte rows, pieces XORed by (b >> 2) & 3).  Rows of gy past
-//     `rows`, output rows past `out` in the last step and columns past `in` enter as ZEROS: the transposed reads need EXEC all
-//     ones, so the data is masked, never the lanes, and every wave runs the same control flow;
+//   * for a cell of the image a thread reads the cell's K code bytes (contiguous in the checkpoint layout [out][in / g][K]), gathers
+//     the K pieces from the LDS codebooks, adds them in fp32 in codebook order, multiplies by scales[o], rounds once and stores 16
+//     bytes;
+//   * gy is masked where it is loaded: the piece that holds row `out` is read element by element, so out % 8 may be anything;
 //   * two image buffers, one barrier per step: the code bytes, scales and gy of step s + 1 are requested from global memory before
-//     the MFMAs of step s are issued and become the image of s + 1 after them;
-//   * the operands are swapped (A = W^T, B = gy^T) and the columns of a wave's two MFMA blocks are interleaved in fours, so a lane
-//     ends with 8 consecutive columns of one batch row: fp32 accumulators, one rounding, one 16-byte store.
+//     the MFMAs of step s are issued and become the image of s + 1 after them.
 //
 // Row tiles.  The cost of an image (2 cells per thread: K gathers and 8 K additions each) is paid once per tile, the MFMAs once
 // per 16 batch rows, so the tile is as tall as the call allows: TP = 16 for up to 16 rows, 64 up to 64 and where 128-row tiles
@@ -31,49 +22,24 @@
 //   2x8 g8          8 KiB      26 KiB    32 KiB    40 KiB
 //   4x8 g16        32 KiB      50 KiB    56 KiB    64 KiB
 //   8x8 g32       128 KiB     146 KiB   152 KiB   160 KiB   (dynamic-LDS attribute above 64 KiB; the launch declines above 160 KiB)
-//
-// Splitting the output rows.  With few batch rows the grid (row tiles x column blocks) cannot fill the device: the steps are
-// dealt to `splits` blocks per tile, whose fp32 tiles go to a workspace [splits][rows][in] and are added in slice order by a second
-// kernel before the one rounding -- deterministic, no atomics; a slice without steps writes zeros.  splits == 1 writes gx directly.
-//
-// Numerics: exact products of storage-type operands, fp32 accumulation over o ascending (per slice).  An MFMA output column
-// depends on its own gy row only: a row's bits depend neither on the other rows of the call nor on their number, for given splits.
-#include <algorithm>
-
-#include "gemm_rows16.h"
+#include "gemm_transposed.h"
 
 namespace aqlm {
 namespace {
 
-constexpr int kTCols = 128;     // columns of gx per block
-constexpr int kTRows = 32;      // output rows of W per step (the k of one MFMA)
-constexpr int kTThreads = 256;  // 4 waves, 32 columns each
-constexpr uint32_t kTWBytes = kTRows * kTCols * 2;
 constexpr size_t kTMaxLds = 160u * 1024u;
-constexpr int kTMaxSplits = 16;
 
 struct KtArgs {
   const uint8_t* codes;      // [M][in_groups][K]
   const uint8_t* codebooks;  // [K][256][G] storage type
   const uint16_t* scales;    // [M]
-  const uint16_t* gy;        // [rows][gys]
-  uint16_t* gx;              // [rows][gxs]
-  float* partial;            // [splits][rows][N], splits > 1
+  // TArgs, spelled out: K keeps the place it had among the arguments, and with it every kernel the argument loads it had
+  const uint16_t* gy;
+  uint16_t* gx;
+  float* partial;
   long gys, gxs;
   int rows, M, N, K, in_groups, nsteps, steps_per_slice, splits;
 };
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* glds_s16x4_ptr;
-
-// byte offset of 16-byte piece ch (8 columns) of row `row` in the W image (the header has the bank argument)
-__device__ __forceinline__ uint32_t timg(int row, int ch) { return 256u * row + 16u * (ch ^ ((row & 3) << 2)); }
-// ... and of piece c (8 rows of W) of batch row b in the gy image: rows are 64 bytes, so rows b, b + 4, b + 8, b + 12 share a
-// quarter of the banks and (b >> 2) & 3 tells them apart for the 16 lanes (16 batch rows, one piece) of a consumer's 16-byte read
-__device__ __forceinline__ uint32_t tgy(int b, int c) { return 64u * b + 16u * (c ^ ((b >> 2) & 3)); }
-
-template <class T>
-__device__ __forceinline__ uint32_t pack2(float a, float b) { return (uint32_t)T::from_float(a) | ((uint32_t)T::from_float(b) << 16); }
 
 // KC > 0: that many codebooks, the codes of a cell fetched as one aligned word; KC == 0: a.K (1..8) codebooks, byte loads
 template <class T, int KC, int G, int NPT>
@@ -258,22 +224,6 @@ __global__ __launch_bounds__(kTThreads) void gemm_kx8_transposed_kernel(const Kt
   }
 }
 
-// the slices meet: fp32 sums in slice order, one rounding; a thread owns 8 columns of a row
-template <class T>
-__global__ __launch_bounds__(256) void gemm_kx8_transposed_finalize_kernel(const float* partial, uint16_t* gx, long gxs, int rows, int N, int splits) {
-  const size_t n8 = (size_t)N / 8, total = (size_t)rows * n8, plane = (size_t)rows * N;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const size_t b = i / n8, c = (i - b * n8) * 8;
-    const float* src = partial + b * N + c;
-    f32x4 x = *reinterpret_cast<const f32x4*>(src), y = *reinterpret_cast<const f32x4*>(src + 4);
-    for (int z = 1; z < splits; ++z) {
-      x += *reinterpret_cast<const f32x4*>(src + z * plane);
-      y += *reinterpret_cast<const f32x4*>(src + z * plane + 4);
-    }
-    *reinterpret_cast<u32x4*>(gx + b * gxs + c) = u32x4{pack2<T>(x[0], x[1]), pack2<T>(x[2], x[3]), pack2<T>(y[0], y[1]), pack2<T>(y[2], y[3])};
-  }
-}
-
 size_t lds_bytes(int K, int G, int tp) { return (size_t)K * 256 * G * 2 + 2 * kTWBytes + 2 * (size_t)tp * 64; }
 
 bool kt_supported(int M, int N, int K, int G) {
@@ -283,18 +233,9 @@ bool kt_supported(int M, int N, int K, int G) {
 // batch rows of a tile: as tall as the rows allow and the LDS holds; 64 where tiles of 128 would leave CUs without a block
 int tile_rows(int rows, int N, int K, int G) {
   const long col_blocks = (N + kTCols - 1) / kTCols;
-  int tp = rows <= 16 ? 16 : (rows <= 64 || (long)((rows + 127) / 128) * col_blocks < 256 ? 64 : 128);
+  int tp = rows <= 16 ? 16 : (rows <= 64 || (long)((rows + 127) / 128) * col_blocks < kTFullGrid ? 64 : 128);
   while (tp > 16 && lds_bytes(K, G, tp) > kTMaxLds) tp = tp == 128 ? 64 : 16;
   return tp;
-}
-
-// splits == 0: enough slices to give every CU a block, while the workspace stays within a quarter of the W it replaces
-// (splits * rows * in * 4 <= out * in * 2 / 4) and every slice has steps
-int choose_splits(int rows, int M, int N, int tp) {
-  const long blocks = (long)((rows + tp - 1) / tp) * ((N + kTCols - 1) / kTCols);
-  const long nsteps = (M + kTRows - 1) / kTRows;
-  long s = std::min<long>({(256 + blocks - 1) / blocks, nsteps, (long)M / (8L * rows), (long)kTMaxSplits});
-  return s < 2 ? 1 : (int)s;
 }
 
 template <class T, int KC, int G, int NPT>
@@ -336,10 +277,11 @@ extern "C" int aqlm_hip_gemm_kx8_transposed_supported(int out_features, int in_f
   return kt_supported(out_features, in_features, num_codebooks, in_group_size) ? 1 : 0;
 }
 
+// (any number of rows; splits == 0 is sized without the scheme: the most slices any tile of the call gets)
 extern "C" size_t aqlm_hip_gemm_kx8_transposed_workspace_bytes(int rows, int out_features, int in_features, int splits) {
   if (rows < 1 || out_features < 1 || in_features < 1 || splits < 0 || splits > kTMaxSplits) return 0;
-  if (splits == 0) splits = choose_splits(rows, out_features, in_features, rows <= 16 ? 16 : 64);  // (the most slices any tile of the call gets)
-  return splits <= 1 ? 0 : (size_t)splits * rows * in_features * sizeof(float);
+  if (splits == 0) splits = choose_splits(rows, out_features, in_features, rows <= 16 ? 16 : 64);
+  return transposed_workspace_bytes(rows, in_features, splits);
 }
 
 extern "C" int aqlm_hip_gemm_kx8_transposed(const void* codes, const void* codebooks, const void* scales, const void* gy, void* gx, int rows,
@@ -350,9 +292,8 @@ extern "C" int aqlm_hip_gemm_kx8_transposed(const void* codes, const void* codeb
   if (int e = check_not_null(who, codes && codebooks && scales && gy && gx)) return e;
   if (int e = check_positive(who, rows, out_features, in_features)) return e;
   if (int e = check_dtype(who, dtype)) return e;
-  if (!kt_supported(out_features, in_features, num_codebooks, in_group_size) || rows > 65536 || splits < 0 || splits > kTMaxSplits ||
-      !aligned16(codebooks) || !aligned2(scales) || !aligned16(gy) || !aligned16(gx) || gy_row_stride % 8 != 0 || gx_row_stride % 8 != 0 ||
-      gy_row_stride < out_features || gx_row_stride < in_features) {
+  if (!kt_supported(out_features, in_features, num_codebooks, in_group_size) || !aligned16(codebooks) || !aligned2(scales) ||
+      !transposed_call_ok(rows, out_features, in_features, splits, gy, gx, gy_row_stride, gx_row_stride)) {
     set_last_error("%s: outside the transposed kernel (%d rows, out=%d in=%d, %d codebooks, g=%d, splits %d, row strides %ld / %ld; 1..8 "
                    "codebooks of 256, g 8 / 16 / 32, in %% g == 0, in %% 8 == 0, 16-B aligned codebooks and rows)",
                    who, rows, out_features, in_features, num_codebooks, in_group_size, splits, gy_row_stride, gx_row_stride);
@@ -360,36 +301,12 @@ extern "C" int aqlm_hip_gemm_kx8_transposed(const void* codes, const void* codeb
   }
   const int tp = tile_rows(rows, in_features, num_codebooks, in_group_size);
   if (splits == 0) splits = choose_splits(rows, out_features, in_features, tp);
-  if (splits > 1 && (!workspace || !aligned16(workspace) || workspace_bytes < (size_t)splits * rows * in_features * sizeof(float))) {
-    set_last_error("%s: %d slices need a 16-B aligned workspace of %zu bytes, got %zu", who, splits,
-                   (size_t)splits * rows * in_features * sizeof(float), workspace ? workspace_bytes : (size_t)0);
-    return AQLM_HIP_E_INVALID;
-  }
-  KtArgs a{};
-  a.codes = (const uint8_t*)codes;
-  a.codebooks = (const uint8_t*)codebooks;
-  a.scales = (const uint16_t*)scales;
-  a.gy = (const uint16_t*)gy;
-  a.gx = (uint16_t*)gx;
-  a.partial = (float*)workspace;
-  a.gys = gy_row_stride;
-  a.gxs = gx_row_stride;
-  a.rows = rows;
-  a.M = out_features;
-  a.N = in_features;
-  a.K = num_codebooks;
-  a.in_groups = in_features / in_group_size;
-  a.nsteps = (out_features + kTRows - 1) / kTRows;
-  a.splits = splits;
-  a.steps_per_slice = (a.nsteps + splits - 1) / splits;
+  if (int e = check_transposed_workspace(who, rows, in_features, splits, workspace, workspace_bytes)) return e;
+  const TArgs t = transposed_args(gy, gx, workspace, gy_row_stride, gx_row_stride, rows, out_features, in_features, in_group_size, splits);
+  const KtArgs a{(const uint8_t*)codes, (const uint8_t*)codebooks, (const uint16_t*)scales, t.gy, t.gx, t.partial, t.gys, t.gxs,
+                 t.rows, t.M, t.N, num_codebooks, t.in_groups, t.nsteps, t.steps_per_slice, t.splits};
   hipStream_t stream = (hipStream_t)stream_;
   const int e = dtype == AQLM_HIP_F16 ? launch_kt_scheme<F16>(a, in_group_size, tp, stream) : launch_kt_scheme<BF16>(a, in_group_size, tp, stream);
   if (e || splits == 1) return e;
-  const size_t items = (size_t)rows * (in_features / 8);
-  const unsigned blocks = (unsigned)std::min<size_t>((items + 255) / 256, 256u * 16u);
-  if (dtype == AQLM_HIP_F16)
-    hipLaunchKernelGGL(gemm_kx8_transposed_finalize_kernel<F16>, dim3(blocks), dim3(256), 0, stream, a.partial, a.gx, a.gxs, rows, in_features, splits);
-  else
-    hipLaunchKernelGGL(gemm_kx8_transposed_finalize_kernel<BF16>, dim3(blocks), dim3(256), 0, stream, a.partial, a.gx, a.gxs, rows, in_features, splits);
-  return check_hip(hipGetLastError(), "gemm_kx8_transposed finalize launch");
+  return launch_finalize(dtype, t, stream, "gemm_kx8_transposed finalize launch");
 }

@@ -1584,7 +1584,7 @@ from .ops_lora import (  # noqa: E402, F401
 )
 from .ops_grad import (  # noqa: E402, F401
     CODEBOOK_GRAD_CHUNK, CODEBOOK_GRAD_ENTRIES, CodebookGradIndex, _calib_layer, _calib_scales, _check_calib_matrix, _check_dw,
-    _check_kx8_codes, _check_scales, _codebook_grad_kx8_op, _codebook_grad_op, _scales_grad_kx8_op, _scales_grad_op,
+    _check_kx8_codes, _check_scales, _codebook_grad_kx8_op, _codebook_grad_op, _matmat_transposed, _scales_grad_kx8_op, _scales_grad_op,
     build_codebook_grad_index, calib_codebook_grad_1x16, calib_codebook_grad_kx8, calib_delta, calib_rows, calib_supported,
     code1x16_matmat_transposed, codebook_grad_1x16, codebook_grad_kx8, codebook_grad_kx8_supported, codebook_grad_max_chunks, codebook_grad_supported,
     codekx8_matmat_transposed, scales_grad_1x16, scales_grad_kx8,

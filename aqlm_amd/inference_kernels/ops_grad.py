@@ -249,7 +249,40 @@ def scales_grad_kx8(dw, codes, codebooks, out_dtype: Optional[torch.dtype] = Non
 
 
 # ------------------------------------------------------------------------------------------------------
-# the input gradient of a dense K x 8 layer (aqlm_hip_gemm_kx8_transposed): W is built tile by tile in LDS, never in memory
+# the input gradient of a dense layer on a fused transposed MFMA GEMM: W is built tile by tile in LDS, never in memory
+# ------------------------------------------------------------------------------------------------------
+def _matmat_transposed(grad_output, codes, codebooks, scales, splits, entry, workspace_bytes, geometry, what):
+    """The call both transposed wrappers end in, once their scheme is checked: ``entry`` / ``workspace_bytes`` are the scheme's library
+    entries, ``geometry`` what ``entry`` takes between in_features and the row strides.  None where the rows cannot be 16-byte aligned
+    or the entry declines."""
+    out_features, in_features = int(codes.shape[0]), int(codes.shape[1]) * int(codebooks.shape[3])
+    gy = grad_output.reshape(-1, out_features)
+    rows = gy.shape[0]
+    if rows < 1 or rows > 65536:
+        return None
+    if gy.stride(1) != 1 or gy.data_ptr() % 16 != 0 or (rows > 1 and (gy.stride(0) % 8 != 0 or gy.stride(0) < out_features)):
+        gy = gy.contiguous()
+    gys = gy.stride(0) if rows > 1 else (out_features + 7) // 8 * 8  # (one row has no stride)
+    if gys % 8 != 0:
+        return None  # out_features % 8 != 0 and no padded rows: the rows cannot be 16-byte aligned
+    codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales)
+    splits = 0 if splits is None else int(splits)
+    gx = torch.empty((rows, in_features), dtype=grad_output.dtype, device=grad_output.device)
+    stream = _stream_ptr(grad_output.device)
+    ws_bytes = int(workspace_bytes(rows, out_features, in_features, splits))
+    ws = _workspace(grad_output.device, ws_bytes, stream) if ws_bytes else None
+    with _device_guard(grad_output.device):
+        rc = entry(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), gy.data_ptr(), gx.data_ptr(), rows, out_features, in_features,
+                   *geometry, gys, in_features, _native.F16 if gx.dtype == torch.float16 else _native.BF16, splits, _ptr(ws), ws_bytes, stream)
+    if rc == _native.E_UNSUPPORTED:
+        return None
+    if rc:
+        _native.check(rc, what)
+    return gx.reshape(grad_output.shape[:-1] + (in_features,))
+
+
+# ------------------------------------------------------------------------------------------------------
+# ... of a dense K x 8 layer (aqlm_hip_gemm_kx8_transposed): codebooks in LDS
 # ------------------------------------------------------------------------------------------------------
 # (torch.compiler.disable: a plain function, not a registered op, that hands raw pointers to the library through ctypes -- Dynamo and
 # compiled autograd must call it, not trace it)
@@ -270,34 +303,12 @@ def codekx8_matmat_transposed(grad_output, codes, codebooks, scales, splits: Opt
             or any(t.device != grad_output.device for t in (codes, codebooks, scales))
             or not _lib.aqlm_hip_gemm_kx8_transposed_supported(out_features, in_features, K, g)):
         return None
-    gy = grad_output.reshape(-1, out_features)
-    rows = gy.shape[0]
-    if rows < 1 or rows > 65536:
-        return None
-    if gy.stride(1) != 1 or gy.data_ptr() % 16 != 0 or (rows > 1 and (gy.stride(0) % 8 != 0 or gy.stride(0) < out_features)):
-        gy = gy.contiguous()
-    gys = gy.stride(0) if rows > 1 else (out_features + 7) // 8 * 8  # (one row has no stride)
-    if gys % 8 != 0:
-        return None  # out_features % 8 != 0 and no padded rows: the rows cannot be 16-byte aligned
-    codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales)
-    splits = 0 if splits is None else int(splits)
-    gx = torch.empty((rows, in_features), dtype=grad_output.dtype, device=grad_output.device)
-    stream = _stream_ptr(grad_output.device)
-    ws_bytes = int(_lib.aqlm_hip_gemm_kx8_transposed_workspace_bytes(rows, out_features, in_features, splits))
-    ws = _workspace(grad_output.device, ws_bytes, stream) if ws_bytes else None
-    with _device_guard(grad_output.device):
-        rc = _lib.aqlm_hip_gemm_kx8_transposed(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), gy.data_ptr(), gx.data_ptr(), rows,
-                                               out_features, in_features, K, g, gys, in_features, _native.F16 if gx.dtype == torch.float16
-                                               else _native.BF16, splits, _ptr(ws), ws_bytes, stream)
-    if rc == _native.E_UNSUPPORTED:
-        return None
-    if rc:
-        _native.check(rc, "aqlm gemm_kx8_transposed")
-    return gx.reshape(grad_output.shape[:-1] + (in_features,))
+    return _matmat_transposed(grad_output, codes, codebooks, scales, splits, _lib.aqlm_hip_gemm_kx8_transposed,
+                              _lib.aqlm_hip_gemm_kx8_transposed_workspace_bytes, (K, g), "aqlm gemm_kx8_transposed")
 
 
 # ------------------------------------------------------------------------------------------------------
-# the input gradient of a dense 1x16 layer (aqlm_hip_gemm_1x16_transposed): codebook vectors gathered per row tile, W never in memory
+# ... of a dense 1x16 layer (aqlm_hip_gemm_1x16_transposed): codebook vectors gathered per row tile (out_features % 8 == 0 there)
 # ------------------------------------------------------------------------------------------------------
 @torch.compiler.disable
 def code1x16_matmat_transposed(grad_output, codes, codebooks, scales, splits: Optional[int] = None):
@@ -316,29 +327,8 @@ def code1x16_matmat_transposed(grad_output, codes, codebooks, scales, splits: Op
             or not grad_output.is_cuda or any(t.device != grad_output.device for t in (codes, codebooks, scales))
             or not _lib.aqlm_hip_gemm_1x16_transposed_supported(out_features, in_features, g)):
         return None
-    gy = grad_output.reshape(-1, out_features)
-    rows = gy.shape[0]
-    if rows < 1 or rows > 65536:
-        return None
-    # (out_features % 8 == 0 here: contiguous rows are 16-byte aligned)
-    if gy.stride(1) != 1 or gy.data_ptr() % 16 != 0 or (rows > 1 and (gy.stride(0) % 8 != 0 or gy.stride(0) < out_features)):
-        gy = gy.contiguous()
-    gys = gy.stride(0) if rows > 1 else out_features  # (one row has no stride)
-    codes, codebooks, scales = _c(codes), _c(codebooks), _c(scales)
-    splits = 0 if splits is None else int(splits)
-    gx = torch.empty((rows, in_features), dtype=grad_output.dtype, device=grad_output.device)
-    stream = _stream_ptr(grad_output.device)
-    ws_bytes = int(_lib.aqlm_hip_gemm_1x16_transposed_workspace_bytes(rows, out_features, in_features, splits))
-    ws = _workspace(grad_output.device, ws_bytes, stream) if ws_bytes else None
-    with _device_guard(grad_output.device):
-        rc = _lib.aqlm_hip_gemm_1x16_transposed(codes.data_ptr(), codebooks.data_ptr(), scales.data_ptr(), gy.data_ptr(), gx.data_ptr(), rows,
-                                                out_features, in_features, g, gys, in_features, _native.F16 if gx.dtype == torch.float16
-                                                else _native.BF16, splits, _ptr(ws), ws_bytes, stream)
-    if rc == _native.E_UNSUPPORTED:
-        return None
-    if rc:
-        _native.check(rc, "aqlm gemm_1x16_transposed")
-    return gx.reshape(grad_output.shape[:-1] + (in_features,))
+    return _matmat_transposed(grad_output, codes, codebooks, scales, splits, _lib.aqlm_hip_gemm_1x16_transposed,
+                              _lib.aqlm_hip_gemm_1x16_transposed_workspace_bytes, (g,), "aqlm gemm_1x16_transposed")
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -85,6 +85,27 @@ def test_exact_on_integers(hk, K, g, dtype, out, fin, rows, splits):
 
 
 @pytest.mark.parametrize("splits", SPLITS)
+@pytest.mark.parametrize("rows", [1, 17])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_exact_on_integers_runtime_k_and_gy_tail(hk, dtype, rows, splits):
+    """K = 3 has no fixed-K instance (the kernel reads K at run time, codes byte by byte) and out = 44 is no multiple of 8: the last
+    piece of a gy row (columns 40 .. 47) is read element by element.  gy is a view of 48-element rows, so it is neither copied nor
+    declined."""
+    K, g, out, fin = 3, 8, 44, 192
+    codes, books, scales, gy = _integer_case(K, g, out, fin, rows, dtype, 10 * K + g + out + rows)
+    assert bool((gy[:, 40:] != 0).any())
+    ref = gy.double().numpy() @ _w64(codes, books, scales, dtype)
+    assert np.abs(ref).max() > 0 and np.array_equal(torch.from_numpy(ref).to(dtype).double().numpy(), ref), "the reference is not exact in the storage type"
+    wide = torch.zeros(rows, 48, dtype=dtype, device=DEV)
+    view = wide[:, :out]
+    view.copy_(gy)
+    assert view.stride(0) == 48 and view.data_ptr() % 16 == 0
+    got = hk.codekx8_matmat_transposed(view, codes.to(DEV), books.to(DEV), scales.to(DEV), splits=splits)
+    assert got is not None and got.dtype == dtype and got.shape == (rows, fin)
+    assert np.array_equal(got.double().cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("splits", SPLITS)
 @pytest.mark.parametrize("rows", ROWS + [TALL[2]])
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("K,g", SCHEMES)
